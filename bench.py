@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - frames/sec of the 4-layer 2160p composite hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One step = one output frame of the headline pipeline (BASELINE.json / SURVEY.md 8d):
 4 x 2160p v210 layers -> unpack -> YCbCr->RGB (BT.709 matrix, gamma LUT, 709->2020 gamut) ->
@@ -11,8 +11,11 @@ distinct frame sets (> 256 MiB in total) defeats the Infinity Cache.  Channels a
 (SURVEY.md 8e): with N GPUs every rank runs its own channel, no collective on the data path,
 scaling = weak, value = total frames/sec over all ranks.
 
-Prints ONE JSON line (rank 0).  The CPU baseline leg (rank 0, N = 1) times the oracle's
-restatement of the same pipeline on the host cores - a reported baseline, never the product.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes its outputs
+(--dump-outputs) and prints the line.  Everything else the line can carry takes runs of its own and
+comes only with --full: the CPU baseline leg (rank 0, N = 1: the oracle's restatement of the same
+pipeline on the host cores - a reported baseline, never the product), the rocprofv3 counter passes,
+the picture-content figure, the secondary configs, config 5 (N > 1) and the shader clock.
 """
 import argparse
 import json
@@ -54,6 +57,11 @@ def parse():
                     help="do not measure roofline.traffic in this run (two short rocprofv3 --pmc child runs); report the recorded figure")
     ap.add_argument("--plan", action="store_true",
                     help="print how --gpus N would be launched (one JSON line) and exit; needs no GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the frames the last step composited to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: cpu_baseline, rocprofv3 counters, content_picture, "
+                         "secondary, route (N > 1), shader_clock; --no-* and --cpu-seconds select among these")
     return ap.parse_args()
 
 
@@ -93,6 +101,11 @@ def launch_plan(args, argv):
     return {"mode": "spawn", "world": args.gpus, "ranks": list(range(args.gpus)), "cmd": cmd}
 
 
+def layer_seed(job, slot, layer):
+    """seed of synth_v210 for one layer of one job (channel, or frame of a launch; numbered over all ranks) in one ring slot"""
+    return 0x5EED0000 + 16 * (job * 64 + slot) + layer
+
+
 def synth_v210(torch, width, height, seed, device, content="noise"):
     """Legal-range v210 frame generated on the GPU (Y 64..940, C 64..960): uniform noise, or a picture-like frame
     (diagonal luma gradient, chroma drifting down the frame, +-6 code values of noise)."""
@@ -121,6 +134,26 @@ def synth_v210(torch, width, height, seed, device, content="noise"):
     w[:, 2] = (cb[:, 2] << 20) | (y[:, 3] << 10) | cr[:, 1]
     w[:, 3] = (y[:, 5] << 20) | (cr[:, 2] << 10) | y[:, 4]
     return w.reshape(-1).contiguous()
+
+
+DUMP_BYTES = 48 << 20  # code values in all, npy headers on top: within the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, outs, width, height, rank, world):
+    """What the timed path hands its caller after its last step - each job's composited v210 frame - as the 10-bit code
+    values a reader of the frame sees (frames.v210_unpack_codes, line padding left out), in float32:
+    DIR/frame<g>_{y,cb,cr}.npy with g = rank * jobs per rank + job.  One 2160p frame is 66 MB of them: where all frames
+    together would exceed DUMP_BYTES, every frame keeps the same seeded sample of its lines (in order), the same in every run."""
+    import numpy as np
+    import frames
+    per_line = 4 * (width + 2 * ((width + 1) // 2))
+    lines = max(1, min(height, DUMP_BYTES // (world * len(outs) * per_line)))
+    rows = np.arange(height) if lines == height else np.sort(np.random.default_rng(0x5EED).choice(height, lines, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for c, out in enumerate(outs):
+        planes = frames.v210_unpack_codes(out.cpu().numpy().view(np.uint32), width, height)
+        for name, codes in zip(("y", "cb", "cr"), planes):
+            np.save(os.path.join(out_dir, "frame%d_%s.npy" % (rank * len(outs) + c, name)), codes[rows].astype(np.float32))
 
 
 def cpu_baseline(args, budget_s):
@@ -434,7 +467,7 @@ def main():
     C = max(1, args.channels) if K == 1 else K  # jobs of one launch: C channels' frames, or K successive frames of one channel
     ring = []  # per slot: C channels' layer lists and outputs
     for r in range(args.ring):
-        ins = [[synth_v210(torch, w, h, 0x5EED0000 + 16 * ((rank * C + c) * 64 + r) + l, device, args.content) for l in range(n)]
+        ins = [[synth_v210(torch, w, h, layer_seed(rank * C + c, r, l), device, args.content) for l in range(n)]
                for c in range(C)]
         ring.append((ins, [torch.empty(frame_words, dtype=torch.int32, device=device) for _ in range(C)]))
     torch.cuda.synchronize()
@@ -474,8 +507,9 @@ def main():
         if i == args.warmup + args.steps - 1:
             ev1.record(stream)
 
-    clock = ClockSampler(torch, local_rank)
-    clock.start()
+    clock = ClockSampler(torch, local_rank) if args.full else None
+    if clock:
+        clock.start()
     clock_since = time.perf_counter()
     for i in range(FIXED_WARMUP):  # clocks, caches and the allocator settle before the contract's own warm-up
         step(i)
@@ -485,7 +519,9 @@ def main():
     timed_local = {}
     elapsed = multigpu.timed_steps(timed_step, args.steps, args.warmup, sync, dist, reduce_device, local=timed_local)
     kernel_ms = ev0.elapsed_time(ev1) / max(args.steps, 1)  # average launch duration on the kernel's stream
-    shader_clock = clock.finish(clock_since)
+    shader_clock = clock.finish(clock_since) if clock else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ring[(args.warmup + args.steps - 1) % args.ring][1], w, h, rank, world)
     # frames every rank really composited in the timed region, summed over ranks (not assumed equal)
     frames_done = C * args.steps
     per_rank = None
@@ -505,6 +541,7 @@ def main():
 
     def report(route_rec, minimal=False):
         """rank 0 prints the one JSON line; `minimal` (the route watchdog's call) leaves out everything that takes time"""
+        extras = args.full and not minimal
         if rank == 0:
             fps = frames_done / elapsed
             algo_bytes = C * (n + 1) * frame_words * 4  # each input byte once + each output byte once
@@ -536,7 +573,8 @@ def main():
             line["roofline"]["frac_by_value"] = round(by_value / HBM_PEAK_GBS, 4)
             line["roofline"]["clocks"] = ("frac: HIP events around the timed launches on the kernel's stream (avg_launch_ms); "
                                           "frac_by_value: algorithmic bytes x value / n_gpus (host wall clock, barrier + sync on both sides)")
-            line["roofline"]["shader_clock"] = shader_clock
+            if shader_clock is not None:
+                line["roofline"]["shader_clock"] = shader_clock
             line["roofline"]["sync_overhead_us_per_step"] = round(1e3 * (1e3 * elapsed / max(args.steps, 1) - kernel_ms), 3)
             if args.steps < 200:
                 line["roofline"]["sync_overhead_note"] = ("%d timed steps: the closing sync (a few hundred microseconds of host time, once) is "
@@ -581,7 +619,7 @@ def main():
             insts, src = recorded_valu_instructions()
             if insts and headline:
                 put_valu(insts, "recorded: profiles/" + src)
-            if not minimal and world == 1 and headline and not args.no_traffic and os.environ.get("PH_BENCH_TRAFFIC", "1") != "0":
+            if extras and world == 1 and headline and not args.no_traffic and os.environ.get("PH_BENCH_TRAFFIC", "1") != "0":
                 got, detail = measured_traffic()
                 if got is not None:
                     line["roofline"]["traffic"] = got
@@ -593,7 +631,7 @@ def main():
                         put_valu(detail["SQ_INSTS_VALU_mean"], "measured in this run: rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU (child pass of this script)")
                 else:
                     line["roofline"]["traffic_not_measured"] = detail
-            if not minimal and world == 1 and headline and args.content == "noise" and not args.no_picture:
+            if extras and world == 1 and headline and args.content == "noise" and not args.no_picture:
                 # `value` is measured on independent uniform code values per sample - the worst case for tables in LDS (the 64 lanes of a wave hit
                 # random banks: two thirds of the LDS cycles are bank conflicts).  The same kernel on picture-like frames (gradients + a few codes
                 # of noise: neighbouring pixels look up neighbouring entries), measured here after the timed region, beside it:
@@ -621,7 +659,7 @@ def main():
                     del pring
                 except Exception as e:
                     line["content_picture"] = {"error": "%s: %s" % (type(e).__name__, e)}
-            if not minimal and world == 1 and not args.no_secondary and C == 1 and (w, h, n) == (WIDTH, HEIGHT, LAYERS):
+            if extras and world == 1 and not args.no_secondary and C == 1 and (w, h, n) == (WIDTH, HEIGHT, LAYERS):
                 # BASELINE configs 2 and 3 (the compositing configs: real alpha, transforms, de-interlace), fastest route of each,
                 # measured after the timed region; tools/config_bench.py prints every route
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -640,7 +678,7 @@ def main():
                             line["secondary_counters_not_measured"] = why
                 except Exception as e:  # the headline figure must not depend on the secondary workloads
                     line["secondary"] = [{"error": "%s: %s" % (type(e).__name__, e)}]
-            if not minimal and world == 1 and args.cpu_seconds > 0:
+            if extras and world == 1 and args.cpu_seconds > 0:
                 try:
                     line["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
                 except Exception as e:  # report rather than lose the line
@@ -649,10 +687,10 @@ def main():
                 line["cpu_baseline"] = None
             print(json.dumps(line), flush=True)
 
-    # N > 1 (or the forced distributed path of the tests): BASELINE config 5 in the same command - 2 channels per rank,
+    # --full, N > 1 (or the forced distributed path of the tests): BASELINE config 5 in the same command - 2 channels per rank,
     # every channel's fourth layer routed from channel k + N (ph_route_*: RCCL on its own stream), fingerprint-checked
     route_rec = None
-    if dist is not None and not args.no_route and C == 1 and (w, h, n) == (WIDTH, HEIGHT, LAYERS):
+    if args.full and dist is not None and not args.no_route and C == 1 and (w, h, n) == (WIDTH, HEIGHT, LAYERS):
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import route_bench
         del ring[:]

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -56,8 +57,8 @@ def check_per_rank(line, n_ranks):
 
 
 def test_default_line_as_the_driver_runs_it():
-    """python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's command): roofline, secondary, cpu_baseline present"""
-    line = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2"])
+    """python bench.py --gpus 1 --steps 20 --warmup 5 --full (the driver's command with --full): roofline, secondary, cpu_baseline present"""
+    line = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2", "--full"])
     check_line(line, 1, 20, 5)
     assert line["roofline"]["valu"]["frac"] > 0.2
     # config 2 alone and four such channels per launch (round 5), 720p50 (the reference's third format) fused / through the channel kernel /
@@ -94,10 +95,47 @@ def test_default_line_as_the_driver_runs_it():
         assert rf["traffic_source"].startswith("recorded")
 
 
+def test_plain_line_times_the_headline_alone(tmp_path):
+    """python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's command): the headline and its roofline from the timed steps,
+    nothing that takes runs of its own (that is --full); the last step's frame under --dump-outputs, within 64 MB"""
+    out = str(tmp_path / "dump")
+    line = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", out])
+    check_line(line, 1, 20, 5)
+    assert line["cpu_baseline"] is None and not {"secondary", "content_picture", "route"} & set(line)
+    assert line["roofline"]["traffic_source"].startswith("recorded") and "shader_clock" not in line["roofline"]
+    files = sorted(os.listdir(out))
+    assert files == ["frame0_cb.npy", "frame0_cr.npy", "frame0_y.npy"]
+    assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64e6
+    y, cb, cr = (np.load(os.path.join(out, f)) for f in ("frame0_y.npy", "frame0_cb.npy", "frame0_cr.npy"))
+    assert y.dtype == cb.dtype == cr.dtype == np.float32
+    assert 1000 < y.shape[0] < 2160 and y.shape[1] == 3840 and cb.shape == cr.shape == (y.shape[0], 1920)  # a sample of the lines
+    for a in (y, cb, cr):
+        assert np.array_equal(a, np.round(a)) and a.min() >= 0 and a.max() <= 1023
+
+
+def test_dumped_outputs_are_the_oracle_frame(tmp_path):
+    """--dump-outputs at a size it keeps whole, one ring slot: the frame the last timed step composited is, code value for code
+    value, the oracle's pipeline on the same seeded inputs"""
+    import torch
+    import bench
+    import frames
+    from oracle import orc
+    w, h, n = 1920, 64, 4
+    out = str(tmp_path / "dump")
+    run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--ring", "1", "--width", str(w), "--height", str(h),
+         "--dump-outputs", out], {"PH_BENCH_FIXED_WARMUP": "10"})
+    layers = [bench.synth_v210(torch, w, h, bench.layer_seed(0, 0, l), torch.device("cuda")).cpu().numpy().view(np.uint32) for l in range(n)]
+    want = orc.pipeline_v210_combine(layers, w, h, orc.ycbcr2rgb_matrix("709"), orc.gamma2linear_lut("709"),
+                                     orc.rgb2rgb_matrix("709", "2020"), orc.rgb2ycbcr_matrix("2020"), orc.linear2gamma_lut("2020"))
+    for name, codes in zip(("y", "cb", "cr"), frames.v210_unpack_codes(want, w, h)):
+        got = np.load(os.path.join(out, "frame0_%s.npy" % name))
+        assert got.dtype == np.float32 and np.array_equal(got, codes), name
+
+
 def test_rank_path_under_torchrun_with_rccl_on_one_gpu():
     """one rank started the way the driver starts N: the RCCL process group, barrier and all-reduce run for real"""
     line = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                "--master-port", "29571", "bench.py", "--gpus", "1", "--steps", "30", "--warmup", "5", "--cpu-seconds", "0", "--no-secondary"],
+                "--master-port", "29571", "bench.py", "--gpus", "1", "--steps", "30", "--warmup", "5", "--cpu-seconds", "0", "--no-secondary", "--full"],
                {"PH_BENCH_FORCE_DIST": "1", "PH_BENCH_ROUTE_HEIGHT": "540"})
     check_line(line, 1, 30, 5)
     check_per_rank(line, 1)
@@ -111,22 +149,28 @@ def test_rank_path_under_torchrun_with_rccl_on_one_gpu():
     assert rt["hop_ms_unoverlapped"] > 0 and rt["frames_per_sec"] > 0 and rt["path"].startswith("ph_route")
 
 
-def test_two_ranks_sum_their_frames():
-    """two ranks on the one GPU (gloo): value is the whole job's rate, one line from rank 0, no cpu_baseline / secondary at N > 1"""
+def test_two_ranks_sum_their_frames(tmp_path):
+    """two ranks on the one GPU (gloo): value is the whole job's rate, one line from rank 0, no cpu_baseline / secondary at N > 1;
+    each rank dumps its own channel's frame"""
+    out = str(tmp_path / "dump")
     line = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                "--master-port", "29572", "bench.py", "--gpus", "2", "--steps", "30", "--warmup", "5", "--width", "1920", "--height", "1080"],
+                "--master-port", "29572", "bench.py", "--gpus", "2", "--steps", "30", "--warmup", "5", "--width", "1920", "--height", "1080",
+                "--dump-outputs", out],
                {"PH_BENCH_SHARE_GPU": "1"})
     check_line(line, 2, 30, 5)
     check_per_rank(line, 2)
     assert line["cpu_baseline"] is None and "secondary" not in line
     assert line["config"]["channels"] == 2
+    assert sorted(os.listdir(out)) == ["frame%d_%s.npy" % (g, p) for g in (0, 1) for p in ("cb", "cr", "y")]
+    y0, y1 = np.load(os.path.join(out, "frame0_y.npy")), np.load(os.path.join(out, "frame1_y.npy"))
+    assert y0.shape == y1.shape == (1080, 1920) and not np.array_equal(y0, y1)
 
 
 def test_a_stalled_route_does_not_cost_the_line():
     """config 5 abandoned by the watchdog (limit set to nothing): rank 0 still prints the headline line, the failure recorded in
     it - and the job ends with a non-zero exit code, so a hung RCCL group is not mistaken for a clean run"""
     line = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                "--master-port", "29573", "bench.py", "--gpus", "1", "--steps", "30", "--warmup", "5", "--cpu-seconds", "0", "--no-secondary"],
+                "--master-port", "29573", "bench.py", "--gpus", "1", "--steps", "30", "--warmup", "5", "--cpu-seconds", "0", "--no-secondary", "--full"],
                {"PH_BENCH_FORCE_DIST": "1", "PH_BENCH_ROUTE_HEIGHT": "540", "PH_BENCH_ROUTE_TIMEOUT": "0.001"}, rc=3)
     check_line(line, 1, 30, 5)
     assert "abandoned by the watchdog" in line["route"]["error"]

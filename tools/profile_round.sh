@@ -12,12 +12,12 @@ for t in microbench opbench3 opbench4; do
   [ -x $ROOT/tools/$t ] || hipcc --offload-arch=gfx950 -O2 -o $ROOT/tools/$t $ROOT/tools/$t.hip > /dev/null 2>&1
 done
 
-# 1. the bench line exactly as the driver runs it
-$BENCH > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+# 1. the bench line as the driver runs it, with every leg a plain run leaves out (--full)
+$BENCH --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err
 tail -1 $OUT/${TAG}_bench.json
 
 # 2. rocprofv3 kernel stats of the same command (shorter K)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH --cpu-seconds 0 > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH --full --cpu-seconds 0 > $OUT/stats.log 2>&1
 f=$(find $OUT/stats -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && (head -1 "$f"; grep "ph::" "$f") > $OUT/${TAG}_bench_kernel_stats.csv
 
@@ -144,6 +144,6 @@ node $ROOT/node/test/soak_run.js 100000 2>/dev/null | grep '^{' > $OUT/${TAG}_no
 # the recording context (node/defer.js) against the launch-as-posted one: scenarios, frames compared byte for byte, launch counters
 (node $ROOT/node/test/defer_run.js; node $ROOT/node/test/defer_run.js 1920 64) 2>/dev/null | grep '^{' > $OUT/${TAG}_defer_run.jsonl
 node $ROOT/node/test/defer_fuzz.js 100 400 120 2>/dev/null | grep '^{' > $OUT/${TAG}_defer_fuzz.jsonl
-(for v in "--no-secondary" "--no-secondary --content picture" "--width 1920 --height 1080" "--width 1920 --height 1080 --channels 2" "--width 1920 --height 1080 --channels 4" "--width 1920 --height 1080 --frames-per-launch 2" "--width 1920 --height 1080 --frames-per-launch 4" "--channels 2 --ring 4"; do $BENCH $v --steps 1500 --cpu-seconds 0; done) 2>/dev/null | grep '^{' > $OUT/${TAG}_bench_variants.jsonl
+(for v in "--no-secondary" "--no-secondary --content picture" "--width 1920 --height 1080" "--width 1920 --height 1080 --channels 2" "--width 1920 --height 1080 --channels 4" "--width 1920 --height 1080 --frames-per-launch 2" "--width 1920 --height 1080 --frames-per-launch 4" "--channels 2 --ring 4"; do $BENCH $v --steps 1500 --cpu-seconds 0 --full; done) 2>/dev/null | grep '^{' > $OUT/${TAG}_bench_variants.jsonl
 rm -rf $OUT/stats $OUT/pmc_bench_* $OUT/pmc_micro_*
 ls -la $OUT
