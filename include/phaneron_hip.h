@@ -38,7 +38,9 @@ extern "C" {
  * 7: additive over 6 - ph_chan_compose_batch (ph_chan_job): several channels' frames in one launch; ph_run_programs; ph_compose_up_write_v210_batch; ph_pack_read_batch;
  *    ph_event_record_timed / ph_event_elapsed_us; ph_ctx_host_pool_stats; "host_pool_mb" defaults to 4096 again and never
  *    keeps less than the working set
- * 8: additive over 7 - ph_trace_begin / ph_trace_end (which kernels made a frame; dry runs); ph_run_programs_progress; ph_buf_reuse; ph_image_unpack_rgb (program "rgb_unpack") */
+ * 8: additive over 7 - ph_trace_begin / ph_trace_end (which kernels made a frame; dry runs); ph_run_programs_progress; ph_buf_reuse; ph_image_unpack_rgb (program "rgb_unpack").
+ *    Later additive within 8: the 10-bit 4:2:0 formats PH_FMT_YUV420P10 / PH_FMT_P010 and PH_SRC_YUV420P10 / PH_SRC_P010 - new enum
+ *    values an older binding never passes; no signature or struct changed */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -351,7 +353,12 @@ enum {
   PH_FMT_YUV420P = 3,
   PH_FMT_NV12 = 4,
   PH_FMT_RGBA8 = 5,
-  PH_FMT_BGRA8 = 6
+  PH_FMT_BGRA8 = 6,
+  /* 10-bit 4:2:0 decoder frames (no reference kernel; defined through the yuv422p10 Reader / Writer: DESIGN.md 2).  Even widths and
+   * heights; P = the width rounded up to 8 samples; 16-bit little-endian samples; Loader / Saver recipe the 10-bit one (v210, yuv422p10).
+   * read: chroma line r >> 1 serves line r; write: chroma from the upper line of a line pair (the lower one in field mode 3) */
+  PH_FMT_YUV420P10 = 7, /* yuv420p10le: Y [h][P], Cb / Cr [h/2][P/2], LSB-aligned (the whole word is the sample, as yuv422p10) */
+  PH_FMT_P010 = 8       /* p010le: Y [h][P], CbCr [h/2][P] interleaved, Cb first, MSB-aligned (read: word >> 6; write: code << 6) */
 };
 int ph_pack_plane_bytes(int format, uint32_t width, uint32_t height, size_t bytes[3]);
 int ph_pack_read(ph_ctx *ctx, int queue, int format, const void *const planes[3], void *out,
@@ -477,6 +484,10 @@ int ph_compose_up_write_v210_batch(ph_ctx *ctx, int queue, int jobs, int n, cons
  * r g b through its gamut matrix (rgba8.ts:49-62); no YCbCr matrix, no planes */
 #define PH_SRC_RGBA8 7
 #define PH_SRC_BGRA8 8
+/* 10-bit 4:2:0 (PH_FMT_YUV420P10 / PH_FMT_P010): unpacked with the call's Loader recipe, like PH_SRC_YUV422P10 (p010: data_u = the
+ * interleaved CbCr plane, data_v unused) */
+#define PH_SRC_YUV420P10 9
+#define PH_SRC_P010 10
 typedef struct ph_chan_source {
   const void *data;          /* device: v210 words (pitch ph_v210_pitch_bytes(width)), float RGBA, or the Y plane; width x height */
   int format;                /* PH_SRC_V210 | PH_SRC_RGBA_F32 | a planar PH_SRC_* | PH_SRC_RGBA8 | PH_SRC_BGRA8 (PH_SRC_NONE: absent) */

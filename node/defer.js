@@ -501,7 +501,7 @@ class Deferral {
 	static _isV210(program, which) { return program.name === which && program.format === 'v210' }
 	static _frameOf(node) { // a `read` / `write` job's frame: packer.ts:58-66 geometry (a 4:2:0 work group handles a line pair: yuv420p.ts:381)
 		const wipg = node.program.workItemsPerGroup
-		const pairs = node.program.format === 'yuv420p' || node.program.format === 'nv12' ? 2 : 1
+		const pairs = ['yuv420p', 'nv12', 'yuv420p10', 'p010'].includes(node.program.format) ? 2 : 1
 		const lines = wipg ? pairs * node.program.globalWorkItems[0] / wipg : 0
 		return { width: node.params.width, lines }
 	}
@@ -713,7 +713,8 @@ class Deferral {
 		// formats' code ranges: `cm` on the source, compared with the call's when the launch is put together)
 		let reader = null
 		let packedCm = null
-		const PLANAR = { yuv422p10: 1, yuv422p8: 2, yuv420p: 3, nv12: 4 } // PH_FMT_*
+		const PLANAR = { yuv422p10: 1, yuv422p8: 2, yuv420p: 3, nv12: 4, yuv420p10: 7, p010: 8 } // PH_FMT_* (yuv420p10 planes as yuv420p, p010 as nv12)
+		const CBCR = { nv12: true, p010: true } // one interleaved chroma plane: inputC
 		const RGB8 = { rgba8: 5, bgra8: 6 } // stills and graphics: no YCbCr matrix, alpha in the data
 		const used = new Set() // pending nodes the fused launch stands in for
 		const sameSize = (img) => img.imageDims && img.imageDims.width === width && img.imageDims.height === height
@@ -743,7 +744,7 @@ class Deferral {
 				const f = Deferral._frameOf(p)
 				const q = p.params
 				const planes = fmt === 'v210' ? q.input && f.width % 2 === 0 // (a line with a tail - 1280 - is the channel kernel's general instantiation)
-					: q.inputY && (fmt === 'nv12' ? q.inputC : q.inputU && q.inputV) && f.width % 2 === 0 && (fmt === 'yuv422p10' || fmt === 'yuv422p8' || f.lines % 2 === 0)
+					: q.inputY && (CBCR[fmt] ? q.inputC : q.inputU && q.inputV) && f.width % 2 === 0 && (fmt === 'yuv422p10' || fmt === 'yuv422p8' || f.lines % 2 === 0)
 				const ok = r.colMatrix && r.gammaLut && r.gamutMatrix && planes && img.imageDims && f.width === img.imageDims.width && f.lines === img.imageDims.height &&
 					(!reader || (Deferral.same(reader.gammaLut, r.gammaLut) && Deferral.same(reader.gamutMatrix, r.gamutMatrix))) &&
 					(fmt !== 'v210' || !packedCm || Deferral.same(packedCm, r.colMatrix))
@@ -754,7 +755,7 @@ class Deferral {
 					if (fmt === 'v210') packedCm = packedCm || r.colMatrix
 					used.add(p)
 					return fmt === 'v210' ? { source: q.input, width: f.width, height: f.lines, v210: true }
-						: { source: q.inputY, u: fmt === 'nv12' ? q.inputC : q.inputU, v: fmt === 'nv12' ? null : q.inputV, cm: r.colMatrix, packing: PLANAR[fmt], width: f.width, height: f.lines, v210: true, planar: true }
+						: { source: q.inputY, u: CBCR[fmt] ? q.inputC : q.inputU, v: CBCR[fmt] ? null : q.inputV, cm: r.colMatrix, packing: PLANAR[fmt], width: f.width, height: f.lines, v210: true, planar: true }
 				}
 			}
 			return materialised(img)

@@ -15,7 +15,8 @@ const { JobBoard } = require('./jobs.js')
 // corresponding constants of the other Readers / Writers); null = RGB formats, no YCbCr matrix
 const RANGE = {
 	v210: [10, 64, 940, 896], yuv422p10: [10, 64, 940, 896], yuv422p8: [8, 16, 235, 224],
-	yuv420p: [8, 16, 235, 224], nv12: [8, 16, 235, 224], rgba8: null, bgra8: null
+	yuv420p: [8, 16, 235, 224], nv12: [8, 16, 235, 224], rgba8: null, bgra8: null,
+	yuv420p10: [10, 64, 940, 896], p010: [10, 64, 940, 896]
 }
 const PLANE_ARGS = { 1: [''], 2: ['Y', 'C'], 3: ['Y', 'U', 'V'] }
 const ceilTo = (v, m) => Math.ceil(v / m) * m
@@ -25,7 +26,7 @@ const ceilTo = (v, m) => Math.ceil(v / m) * m
 function packGeometry(format, width, height, writer, interlaced) {
 	const wipg = format === 'v210' ? ceilTo(width, 48) / 48
 		: Math.ceil((format === 'rgba8' || format === 'bgra8' ? width : ceilTo(width, 8)) / 64)
-	const v420 = format === 'yuv420p' || format === 'nv12'
+	const v420 = format === 'yuv420p' || format === 'nv12' || format === 'yuv420p10' || format === 'p010'
 	const groups = v420 ? height / 2 : (writer && interlaced ? height / 2 : height)
 	return { workItemsPerGroup: wipg, globalWorkItems: wipg * groups }
 }

@@ -146,5 +146,8 @@ export const colour: {
 	rgb2rgbMatrix(srcColSpec: string, dstColSpec: string): Float32Array
 	transformMatrix(width: number, height: number, params?: { flipH?: boolean; flipV?: boolean; anchorX?: number; anchorY?: number; scaleX?: number; scaleY?: number; offsetX?: number; offsetY?: number; rotate?: number }): Float32Array
 }
+/** the pack formats, indexed as PH_FMT_*: 'v210', 'yuv422p10', 'yuv422p8', 'yuv420p', 'nv12', 'rgba8', 'bgra8', 'yuv420p10', 'p010'
+ * (the last two: 10-bit 4:2:0 decoder frames, yuv420p10le and p010le; their programs resolve by the tags 'phaneron:yuv420p10' / 'phaneron:p010') */
 export const FORMATS: string[]
+/** bytes per plane of a frame in `format` (yuv420p10: [2Ph, Ph/2, Ph/2]; p010: [2Ph, Ph] with P the width rounded up to 8) */
 export function planeBytes(format: string, width: number, height: number): number[]

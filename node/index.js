@@ -450,7 +450,8 @@ const colour = {
 		p.offsetX || 0, p.offsetY || 0, p.rotate || 0)
 }
 
-const FORMATS = ['v210', 'yuv422p10', 'yuv422p8', 'yuv420p', 'nv12', 'rgba8', 'bgra8']
+// (index = PH_FMT_*; yuv420p10 / p010: the 10-bit 4:2:0 decoder frames yuv420p10le / p010le, programs by tag only: INTEGRATION.md)
+const FORMATS = ['v210', 'yuv422p10', 'yuv422p8', 'yuv420p', 'nv12', 'rgba8', 'bgra8', 'yuv420p10', 'p010']
 // bytes per plane of a frame in `format`: the numBytes of the reference's Readers / Writers
 function planeBytes(format, width, height) {
 	const f = FORMATS.indexOf(format)

@@ -716,7 +716,7 @@ static napi_value ResolveProgram(napi_env env, napi_callback_info info) {
   char *src = NULL;
   int fmt = -1, how = 0;
   static const char *hows[] = {"tag", "name", "text", "signature"};
-  static const char *fmts[] = {"v210", "yuv422p10", "yuv422p8", "yuv420p", "nv12", "rgba8", "bgra8"};
+  static const char *fmts[] = {"v210", "yuv422p10", "yuv422p8", "yuv420p", "nv12", "rgba8", "bgra8", "yuv420p10", "p010"};
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < 2 || !get_str(env, argv[1], name, sizeof name)) return throw_ph(env, "resolveProgram(kernelSrc, name)");
   if (napi_get_value_string_utf8(env, argv[0], NULL, 0, &srclen) == napi_ok) {
@@ -728,7 +728,7 @@ static napi_value ResolveProgram(napi_env env, napi_callback_info info) {
   if (rc != PH_OK) return throw_ph(env, "resolveProgram");
   NAPI_OK(napi_create_object(env, &out));
   napi_create_string_utf8(env, kernel, NAPI_AUTO_LENGTH, &v), napi_set_named_property(env, out, "kernel", v);
-  if (fmt >= 0 && fmt < 7) napi_create_string_utf8(env, fmts[fmt], NAPI_AUTO_LENGTH, &v);
+  if (fmt >= 0 && fmt < (int)(sizeof fmts / sizeof fmts[0])) napi_create_string_utf8(env, fmts[fmt], NAPI_AUTO_LENGTH, &v);
   else napi_get_null(env, &v);
   napi_set_named_property(env, out, "format", v);
   napi_create_string_utf8(env, hows[how & 3], NAPI_AUTO_LENGTH, &v), napi_set_named_property(env, out, "how", v);
@@ -790,7 +790,7 @@ static napi_value TransformMatrix(napi_env env, napi_callback_info info) {
   return f32_array(env, m, 9);
 }
 
-/* planeBytes(format 0..6, width, height) -> [bytes per plane] (the Readers' / Writers' numBytes) */
+/* planeBytes(format 0..8, width, height) -> [bytes per plane] (the Readers' / Writers' numBytes) */
 static napi_value PlaneBytes(napi_env env, napi_callback_info info) {
   size_t argc = 3, pb[3] = {0, 0, 0};
   napi_value argv[3], out, v;

@@ -82,7 +82,9 @@ class PhImageLayer(C.Structure):
 
 IMG_RGBA_F32, IMG_RGB_F32 = 0, 1
 SRC_V210, SRC_RGBA_F32, SRC_YUV422P10, SRC_YUV422P8, SRC_YUV420P, SRC_NV12, SRC_RGBA8, SRC_BGRA8 = 1, 2, 3, 4, 5, 6, 7, 8
-SRC_PLANAR = {"yuv422p10": SRC_YUV422P10, "yuv422p8": SRC_YUV422P8, "yuv420p": SRC_YUV420P, "nv12": SRC_NV12}
+SRC_YUV420P10, SRC_P010 = 9, 10  # the 10-bit 4:2:0 decoder frames (yuv420p10le, p010le)
+SRC_PLANAR = {"yuv422p10": SRC_YUV422P10, "yuv422p8": SRC_YUV422P8, "yuv420p": SRC_YUV420P, "nv12": SRC_NV12,
+              "yuv420p10": SRC_YUV420P10, "p010": SRC_P010}
 TRANSITION_CUT, TRANSITION_DISSOLVE, TRANSITION_WIPE = 0, 1, 2
 
 
@@ -328,10 +330,11 @@ def v210_pitch_bytes(width):
     return int(lib().ph_v210_pitch_bytes(width))
 
 
-FORMATS = {"v210": 0, "yuv422p10": 1, "yuv422p8": 2, "yuv420p": 3, "nv12": 4, "rgba8": 5, "bgra8": 6}
+FORMATS = {"v210": 0, "yuv422p10": 1, "yuv422p8": 2, "yuv420p": 3, "nv12": 4, "rgba8": 5, "bgra8": 6, "yuv420p10": 7, "p010": 8}
 # (numBits, lumaBlack, lumaWhite, chromaRange) of each format's Reader/Writer; None = RGB (no YCbCr matrix)
 FORMAT_RANGE = {"v210": (10, 64, 940, 896), "yuv422p10": (10, 64, 940, 896), "yuv422p8": (8, 16, 235, 224),
-                "yuv420p": (8, 16, 235, 224), "nv12": (8, 16, 235, 224), "rgba8": None, "bgra8": None}
+                "yuv420p": (8, 16, 235, 224), "nv12": (8, 16, 235, 224), "rgba8": None, "bgra8": None,
+                "yuv420p10": (10, 64, 940, 896), "p010": (10, 64, 940, 896)}
 
 
 def pack_plane_bytes(fmt, width, height):

@@ -42,6 +42,19 @@ int fail(int code, const char *fmt, ...) {
     if (e_ != hipSuccess) return fail(PH_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
   } while (0)
 
+// the pack formats and chan sources by kind (the 10-bit 4:2:0 values come after the packed-RGB ones: no range covers a kind)
+bool fmt_rgb8(int f) { return f == PH_FMT_RGBA8 || f == PH_FMT_BGRA8; }
+bool fmt_v420(int f) { return f == PH_FMT_YUV420P || f == PH_FMT_NV12 || f == PH_FMT_YUV420P10 || f == PH_FMT_P010; }
+bool src_planar(int f) { return (f >= PH_SRC_YUV422P10 && f <= PH_SRC_NV12) || f == PH_SRC_YUV420P10 || f == PH_SRC_P010; }
+bool src_420(int f) { return f == PH_SRC_YUV420P || f == PH_SRC_NV12 || f == PH_SRC_YUV420P10 || f == PH_SRC_P010; }
+bool src_wide(int f) { return f == PH_SRC_YUV422P10 || f == PH_SRC_YUV420P10 || f == PH_SRC_P010; }  // 16-bit samples
+// the 10-bit 4:2:0 frames are defined for even widths and heights only (a line pair per chroma line, a sample pair per chroma sample)
+int fmt10_dims(const char *fn, int f, uint32_t w, uint32_t h) {
+  if ((f == PH_FMT_YUV420P10 || f == PH_FMT_P010) && ((w & 1) || (h & 1)))
+    return fail(PH_E_INVALID, "%s: a %s frame needs an even width and height (%ux%u)", fn, f == PH_FMT_P010 ? "p010" : "yuv420p10", w, h);
+  return PH_OK;
+}
+
 }  // namespace
 
 // ---- route trace: which kernels made it ------------------------------------------------------------------------------------------
@@ -1205,13 +1218,14 @@ static int chan_call_parse(ph_ctx *ctx, ph_program *prog, const ph_arg *args, in
         } else {
           s->format = PH_SRC_V210;
           s->data_u = s->data_v = nullptr, s->col_matrix12 = nullptr;
-          // another wire format: l<i>Packing = its PH_FMT_* (1 yuv422p10, 2 yuv422p8, 3 yuv420p, 4 nv12: l<i>In the Y plane, l<i>InU /
-          // l<i>InV the chroma planes (nv12: l<i>InU the CbCr plane), l<i>ColMatrix (optional) its own Loader matrix; 5 rgba8, 6 bgra8: l<i>In the frame)
+          // another wire format: l<i>Packing = its PH_FMT_* (1 yuv422p10, 2 yuv422p8, 3 yuv420p, 4 nv12, 7 yuv420p10, 8 p010: l<i>In the Y plane,
+          // l<i>InU / l<i>InV the chroma planes (nv12, p010: l<i>InU the CbCr plane), l<i>ColMatrix (optional) its own Loader matrix; 5 rgba8,
+          // 6 bgra8: l<i>In the frame)
           double packing = 0;
           snprintf(nm, sizeof nm, "l%d%sPacking", i, role);
           if (find_arg(args, n, nm)) TRY(need_num(args, n, nm, &packing));
           if (packing != 0) {
-            if (packing < PH_FMT_YUV422P10 || packing > PH_FMT_BGRA8) return fail(PH_E_INVALID, "kernel argument '%s': %g is not a pack format other than v210", nm, packing);
+            if (packing < PH_FMT_YUV422P10 || packing > PH_FMT_P010) return fail(PH_E_INVALID, "kernel argument '%s': %g is not a pack format other than v210", nm, packing);
             s->format = PH_SRC_YUV422P10 + ((int)packing - PH_FMT_YUV422P10);  // PH_SRC_* follow PH_FMT_* from here on
           }
           snprintf(nm, sizeof nm, "l%d%sWidth", i, role);
@@ -1229,7 +1243,7 @@ static int chan_call_parse(ph_ctx *ctx, ph_program *prog, const ph_arg *args, in
             snprintf(nu, sizeof nu, "l%d%sInU", i, role);
             TRY(need_buf(args, n, nu, pb[1], &pu));
             s->data_u = pu->dptr;
-            if (fmt != PH_FMT_NV12) {
+            if (fmt != PH_FMT_NV12 && fmt != PH_FMT_P010) {
               snprintf(nu, sizeof nu, "l%d%sInV", i, role);
               TRY(need_buf(args, n, nu, pb[2], &pv));
               s->data_v = pv->dptr;
@@ -1429,7 +1443,7 @@ static int dispatch_wire(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int 
     case K_PACK_WRITE: {
       const bool rd = prog->id == K_PACK_READ;
       const int fmt = prog->format;
-      const bool rgb = fmt >= PH_FMT_RGBA8, v420 = (fmt == PH_FMT_YUV420P || fmt == PH_FMT_NV12);
+      const bool rgb = fmt_rgb8(fmt), v420 = fmt_v420(fmt);
       double il = 0;
       TRY(need_num(args, n, "width", &num));
       if (!rd) TRY(need_num(args, n, "interlace", &il));
@@ -2072,6 +2086,7 @@ int ph_fused_v210_combine(ph_ctx *ctx, int queue, int n, const void *const *laye
 
 int ph_pack_plane_bytes(int format, uint32_t width, uint32_t height, size_t bytes[3]) {
   if (!bytes || !width) return fail(PH_E_INVALID, "ph_pack_plane_bytes: NULL/zero argument");
+  if (const int rc = fmt10_dims("ph_pack_plane_bytes", format, width, height)) return rc;
   const int n = ph::pack_plane_bytes(format, width, height, bytes);
   return n < 0 ? fail(PH_E_INVALID, "ph_pack_plane_bytes: unknown format %d", format) : n;
 }
@@ -2119,12 +2134,13 @@ int ph_pack_read(ph_ctx *ctx, int queue, int format, const void *const planes[3]
                  uint32_t height, const void *cm, const void *lut, const void *gm) {
   if (!ctx || !planes || !out || !lut || !gm || !width) return fail(PH_E_INVALID, "ph_pack_read: NULL/zero argument");
   if (format == PH_FMT_V210) return ph_v210_read(ctx, queue, planes[0], out, width, height, cm, lut, gm);
+  if (const int rc = fmt10_dims("ph_pack_read", format, width, height)) return rc;
   size_t pb[3];
   const int np = ph::pack_plane_bytes(format, width, height, pb);
   if (np < 0) return fail(PH_E_INVALID, "ph_pack_read: unknown format %d", format);
   for (int i = 0; i < np; ++i)
     if (!planes[i]) return fail(PH_E_INVALID, "ph_pack_read: plane %d is NULL", i);
-  if (format < PH_FMT_RGBA8 && !cm) return fail(PH_E_INVALID, "ph_pack_read: YCbCr formats need a colMatrix");
+  if (!fmt_rgb8(format) && !cm) return fail(PH_E_INVALID, "ph_pack_read: YCbCr formats need a colMatrix");
   if (!height) return PH_OK;
   PH_LAUNCH(ph::launch_pack_read(stream_of(ctx, queue), format, planes, out, width, height, cm, lut, gm, lds_view(ctx, lut).get(),
                                  (uint32_t)ctx->props.multiProcessorCount));
@@ -2134,6 +2150,7 @@ int ph_pack_read_batch(ph_ctx *ctx, int queue, int format, int n, const void *co
                        const void *cm, const void *lut, const void *gm) {
   if (!ctx || !planes || !outs || !lut || !gm || !width) return fail(PH_E_INVALID, "ph_pack_read_batch: NULL/zero argument");
   if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "ph_pack_read_batch: 1..%d frames", ph::kMaxLayers);
+  if (const int rc = fmt10_dims("ph_pack_read_batch", format, width, height)) return rc;
   const LutRef lref = lds_view(ctx, lut);
   const ph::LutView *v = format == PH_FMT_V210 ? nullptr : lref.get();
   if (n == 1 || !v) {  // one frame, v210 (its own batch call), or no LDS form of the table: frame by frame
@@ -2156,7 +2173,7 @@ int ph_pack_read_batch(ph_ctx *ctx, int queue, int format, int n, const void *co
     for (int k = 0; k < np; ++k)
       if (!planes[i][k]) return fail(PH_E_INVALID, "ph_pack_read_batch: frame %d: plane %d is NULL", i, k);
   }
-  if (format < PH_FMT_RGBA8 && !cm) return fail(PH_E_INVALID, "ph_pack_read_batch: YCbCr formats need a colMatrix");
+  if (!fmt_rgb8(format) && !cm) return fail(PH_E_INVALID, "ph_pack_read_batch: YCbCr formats need a colMatrix");
   if (!height) return PH_OK;
   PH_LAUNCH(ph::launch_pack_read_batch(stream_of(ctx, queue), format, n, planes, outs, width, height, cm, gm, *v, (uint32_t)ctx->props.multiProcessorCount));
 }
@@ -2166,12 +2183,13 @@ int ph_pack_write(ph_ctx *ctx, int queue, int format, const void *in, void *cons
   if (!ctx || !planes || !in || !lut || !width) return fail(PH_E_INVALID, "ph_pack_write: NULL/zero argument");
   if (interlace != 0 && interlace != 1 && interlace != 3) return fail(PH_E_INVALID, "ph_pack_write: interlace must be 0, 1 or 3");
   if (format == PH_FMT_V210) return ph_v210_write(ctx, queue, in, planes[0], width, height, interlace, cm, lut);
+  if (const int rc = fmt10_dims("ph_pack_write", format, width, height)) return rc;
   size_t pb[3];
   const int np = ph::pack_plane_bytes(format, width, height, pb);
   if (np < 0) return fail(PH_E_INVALID, "ph_pack_write: unknown format %d", format);
   for (int i = 0; i < np; ++i)
     if (!planes[i]) return fail(PH_E_INVALID, "ph_pack_write: plane %d is NULL", i);
-  if (format < PH_FMT_RGBA8 && !cm) return fail(PH_E_INVALID, "ph_pack_write: YCbCr formats need a colMatrix");
+  if (!fmt_rgb8(format) && !cm) return fail(PH_E_INVALID, "ph_pack_write: YCbCr formats need a colMatrix");
   if (!height) return PH_OK;
   PH_LAUNCH(ph::launch_pack_write(stream_of(ctx, queue), format, in, planes, width, height, interlace, cm, lut,
                                   lds_view(ctx, lut).get(), (uint32_t)ctx->props.multiProcessorCount));
@@ -2236,13 +2254,13 @@ static int chan_source(const ph_chan_source &s, const char *what, int layer, uin
                        const void **pv, const float **cm, uint32_t *planar) {
   if (!s.data || s.width <= 0 || s.height <= 0)
     return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s is empty", layer, what);
-  const bool is_planar = s.format >= PH_SRC_YUV422P10 && s.format <= PH_SRC_NV12, is_rgb8 = s.format == PH_SRC_RGBA8 || s.format == PH_SRC_BGRA8;
+  const bool is_planar = src_planar(s.format), is_rgb8 = s.format == PH_SRC_RGBA8 || s.format == PH_SRC_BGRA8;
   if (s.format != PH_SRC_V210 && s.format != PH_SRC_RGBA_F32 && !is_planar && !is_rgb8)
     return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s has format %d (not a PH_SRC_*)", layer, what, s.format);
   *pu = *pv = nullptr, *cm = nullptr;
   if (is_rgb8) *planar = 2;  // (served by the kernel's wire-format instantiation)
   if (is_planar) {
-    if (!s.data_u || (s.format != PH_SRC_NV12 && !s.data_v) || (s.width & 1) || ((s.format == PH_SRC_YUV420P || s.format == PH_SRC_NV12) && (s.height & 1)))
+    if (!s.data_u || (s.format != PH_SRC_NV12 && s.format != PH_SRC_P010 && !s.data_v) || (s.width & 1) || (src_420(s.format) && (s.height & 1)))
       return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s is planar: it needs its chroma plane(s), an even width and, for 4:2:0, an even height", layer, what);
     *pu = s.data_u, *pv = s.data_v, *cm = (const float *)s.col_matrix12, *planar = 2;
   }
@@ -2253,11 +2271,12 @@ static int chan_source(const ph_chan_source &s, const char *what, int layer, uin
   if (!s.matrix9_host && ((uint32_t)s.width != out_w || (uint32_t)s.height != out_h))
     return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s has no transform but is %dx%d, not the output size", layer, what, s.width, s.height);
   o->ptr = s.data, o->w = (uint32_t)s.width, o->h = (uint32_t)s.height;
-  static const uint32_t kinds[] = {ph::kChanNone, ph::kChanV210, ph::kChanRgba, ph::kChanP10, ph::kChanP8x422, ph::kChanP8x420, ph::kChanNv12, ph::kChanRgba8, ph::kChanBgra8};
+  static const uint32_t kinds[] = {ph::kChanNone, ph::kChanV210,  ph::kChanRgba,  ph::kChanP10,     ph::kChanP8x422, ph::kChanP8x420,
+                                   ph::kChanNv12, ph::kChanRgba8, ph::kChanBgra8, ph::kChanP10x420, ph::kChanP010};  // [PH_SRC_*]
   o->kind = kinds[s.format];
   // planar: the luma line pitch in samples is the width rounded up to 8 (yuv422p10.ts:221), one or two bytes each
   o->pitch = s.format == PH_SRC_V210 ? ph_v210_pitch_bytes((uint32_t)s.width)
-             : is_planar ? (((uint32_t)s.width + 7u) & ~7u) * (s.format == PH_SRC_YUV422P10 ? 2u : 1u)
+             : is_planar ? (((uint32_t)s.width + 7u) & ~7u) * (src_wide(s.format) ? 2u : 1u)
              : is_rgb8 ? (uint32_t)s.width * 4u : (uint32_t)s.width * 16u;  // rgba8.ts:103-105: no line padding
   if ((uint64_t)o->pitch * o->h >= (1ull << 30))
     return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s is 1 GiB or larger; run the separate kernels", layer, what);
@@ -2352,7 +2371,7 @@ static bool chan_layers_enlarged(int n, const ph_chan_layer *layers, uint32_t ou
     const float *m = L.src.matrix9_host;
     // (v210 frames, a file decoder's planar frames, packed 8-bit RGB: whatever has a reader of its own - ph_v210_read, ph_pack_read)
     // - and finished f32 images, which the compositor takes as they are
-    if (L.transition != PH_TRANSITION_CUT || L.src.format < PH_SRC_V210 || L.src.format > PH_SRC_BGRA8 || !m || L.src.width <= 0 ||
+    if (L.transition != PH_TRANSITION_CUT || L.src.format < PH_SRC_V210 || L.src.format > PH_SRC_P010 || !m || L.src.width <= 0 ||
         L.src.height <= 0 || ((L.src.width & 1) && L.src.format != PH_SRC_RGBA8 && L.src.format != PH_SRC_BGRA8 && L.src.format != PH_SRC_RGBA_F32))
       return false;
     if (m[1] != 0.0f || m[3] != 0.0f || !(m[0] > 0.0f) || !(m[4] > 0.0f)) return false;                      // (ph_kernels_up.hip compose_up_eligible)
@@ -2389,7 +2408,7 @@ static int chan_compose_enlarged(ph_ctx *ctx, int queue, int jobs, int n, const 
     bool wire = true, alpha = false;
     for (int j = 0; j < jobs && wire; ++j) {
       const ph_chan_source &S = layers[j][0].src;
-      wire = S.format != PH_SRC_RGBA_F32 && S.format != PH_SRC_V210 && !(((S.format == PH_SRC_YUV420P || S.format == PH_SRC_NV12) && (S.height & 1)));
+      wire = S.format != PH_SRC_RGBA_F32 && S.format != PH_SRC_V210 && !(src_420(S.format) && (S.height & 1));
       alpha = alpha || S.format == PH_SRC_RGBA8 || S.format == PH_SRC_BGRA8;
     }
     const LutRef rref = lds_view(ctx, rd_lut), wref = lds_view(ctx, wr_lut);
@@ -2846,7 +2865,8 @@ int ph_yadif_pair_packed(ph_ctx *ctx, int queue, int n, const ph_deint_source *s
                          int skip, int out_format, const void *cm, const void *lut, const void *gm) {
   if (!ctx || !src || !cm || !lut || !gm) return fail(PH_E_INVALID, "ph_v210_yadif_pair: NULL argument");
   if (packing != PH_FMT_V210 && packing != PH_FMT_YUV422P10 && packing != PH_FMT_YUV422P8 && packing != PH_FMT_YUV420P && packing != PH_FMT_NV12)
-    return fail(PH_E_INVALID, "ph_v210_yadif_pair: packing %d (v210 or a planar YCbCr format; run the separate kernels for the others)", packing);
+    return fail(PH_E_INVALID, "ph_v210_yadif_pair: packing %d (v210, yuv422p10, yuv422p8, yuv420p or nv12; for the others - the 10-bit 4:2:0 "
+                              "yuv420p10 / p010 among them - run the separate kernels: the format's reader, then yadif)", packing);
   if ((packing == PH_FMT_YUV420P || packing == PH_FMT_NV12) && (height & 1))
     return fail(PH_E_INVALID, "ph_v210_yadif_pair: a 4:2:0 frame needs an even height (%u)", height);
   const bool planar = packing != PH_FMT_V210;

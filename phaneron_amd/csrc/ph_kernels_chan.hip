@@ -146,6 +146,8 @@ __device__ __forceinline__ float4 rgba_load(__amdgpu_buffer_rsrc_t img, uint32_t
 //   kChanP8x422 yuv422p8     the same with 8-bit samples                             yuv422p8.ts
 //   kChanP8x420 yuv420p      Cb / Cr [row / 2][x / 2], 8-bit                          yuv420p.ts
 //   kChanNv12   nv12         Cb, Cr interleaved in one plane [row / 2][x / 2]         nv12.ts:61-74
+//   kChanP10x420 yuv420p10le 4:2:0 planes of 16-bit samples                          (no reference kernel: DESIGN.md 2)
+//   kChanP010   p010le       4:2:0, CbCr interleaved, 16-bit words with the sample in bits 6..15
 // The reader's arithmetic from the three samples on is ToRGBA's own (read_px_issue), the sample taken as it is (the reference
 // converts the whole 8- or 16-bit word).  A tap is three 1- or 2-byte buffer loads; taps outside the frame get offsets beyond
 // every plane and load 0.  Everything that depends on the kind is uniform.
@@ -154,11 +156,13 @@ struct Planes {
   uint32_t pitch_y, pitch_c;  // bytes per line of the Y plane / of a chroma plane
   uint32_t wide;              // 1: 16-bit samples
   uint32_t vshift;            // 1: a chroma line serves two luma lines
-  uint32_t nv12;              // 1: u holds CbCr pairs (v is u)
+  uint32_t nv12;              // 1: u holds CbCr pairs (v is u); with wide: p010, the sample in bits 6..15 of its word
 };
 __device__ __forceinline__ Planes planes_of(const ChanSrc &s, const void *pu, const void *pv) {
   Planes pl;
-  pl.wide = s.kind == kChanP10 ? 1u : 0u, pl.vshift = (s.kind == kChanP8x420 || s.kind == kChanNv12) ? 1u : 0u, pl.nv12 = s.kind == kChanNv12 ? 1u : 0u;
+  pl.wide = (s.kind == kChanP10 || s.kind == kChanP10x420 || s.kind == kChanP010) ? 1u : 0u;
+  pl.vshift = (s.kind == kChanP8x420 || s.kind == kChanNv12 || s.kind == kChanP10x420 || s.kind == kChanP010) ? 1u : 0u;
+  pl.nv12 = (s.kind == kChanNv12 || s.kind == kChanP010) ? 1u : 0u;
   pl.pitch_y = s.pitch, pl.pitch_c = pl.nv12 ? s.pitch : s.pitch >> 1;
   const uint32_t crows = (s.h + pl.vshift) >> pl.vshift;
   pl.y = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(s.ptr), 0, (int)(pl.pitch_y * s.h), 0x00020000);
@@ -170,10 +174,15 @@ __device__ __forceinline__ V210Words planar_load(const Planes &pl, uint32_t row,
   const uint32_t oy = __umul24(row, pl.pitch_y) + (col << pl.wide);
   // the pair's chroma sample: planar [x / 2] samples of 1 or 2 bytes, nv12 [x / 2] pairs of bytes (Cb first)
   const uint32_t ocb = __umul24(row >> pl.vshift, pl.pitch_c) + (pl.nv12 ? (col & ~1u) : ((col >> 1) << pl.wide)), ocr = ocb + pl.nv12;
-  if (pl.wide)
+  if (pl.wide) {
+    if (pl.nv12) {  // p010 (uniform): the pair's Cb, Cr words in one dword at twice nv12's column offset, every sample in bits 6..15
+      const uint32_t c = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(pl.u, (int)(ocb + (col & ~1u)), 0, 0);
+      return V210Words{(uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(pl.y, (int)oy, 0, 0) >> 6, (c & 0xFFFFu) >> 6, c >> 22};
+    }
     return V210Words{(uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(pl.y, (int)oy, 0, 0),
                      (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(pl.u, (int)ocb, 0, 0),
                      (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(pl.v, (int)ocr, 0, 0)};
+  }
   return V210Words{(uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(pl.y, (int)oy, 0, 0),
                    (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(pl.u, (int)ocb, 0, 0),
                    (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(pl.v, (int)ocr, 0, 0)};
@@ -1373,7 +1382,7 @@ hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t n
   uint32_t own_scale = 0;
   for (int k = 0; k < b.n_ops; ++k) {
     const ChanSrc &s = b.op[k].src;
-    const bool clip = s.kind >= kChanP10 && s.kind <= kChanNv12;
+    const bool clip = s.kind >= kChanP10 && s.kind <= kChanPlanarLast;
     clips_only = clips_only && (clip || s.kind == kChanRgba);
     if (clip && s.sampled && s.m[1] == 0.0f && s.m[3] == 0.0f) {
       const float sx = s.m[0] * (float)s.w / (float)a.out_w, sy = s.m[4] * (float)s.h / (float)(a.out_h) * (float)a.line_step;
@@ -1408,7 +1417,7 @@ hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t n
     for (int k = 0; k < b.n_ops && steps; ++k) {
       const ChanSrc &s = b.op[k].src;
       const bool rgb8 = graphics && s.kind >= kChanRgba8;  // (two slots: its alpha has one of its own)
-      if ((s.kind != kChanV210 && !rgb8 && !(planar_share && s.kind >= kChanP10 && s.kind <= kChanNv12)) || !s.sampled || s.m[1] != 0.0f || s.m[3] != 0.0f) continue;  // v210 clips; planar ones and graphics in their instantiations
+      if ((s.kind != kChanV210 && !rgb8 && !(planar_share && s.kind >= kChanP10 && s.kind <= kChanPlanarLast)) || !s.sampled || s.m[1] != 0.0f || s.m[3] != 0.0f) continue;  // v210 clips; planar ones and graphics in their instantiations
       const float sx = s.m[0] * (float)s.w / (float)a.out_w, sy = s.m[4] * (float)s.h / (float)(a.out_h) * (float)a.line_step;
       if (!(sx > 0.9999f && sx < 1.0001f && sy > 0.9999f && sy < 1.0001f)) continue;
       const uint32_t slots_needed = rgb8 ? 2u : 1u;

@@ -1,6 +1,8 @@
 // ph_kernels_fmt.hip - the reference's other packed formats:
 //   yuv422p10le (yuv422p10.ts), yuv422p8 (yuv422p8.ts), yuv420p (yuv420p.ts), nv12 (nv12.ts),
-//   rgba8 (rgba8.ts), bgra8 (bgra8.ts) - read (-> linear f32 RGBA) and write (<- f32 RGBA).
+//   rgba8 (rgba8.ts), bgra8 (bgra8.ts) - read (-> linear f32 RGBA) and write (<- f32 RGBA) - and the 10-bit 4:2:0 decoder frames
+//   yuv420p10le and p010le, which the reference has no kernel for: defined as its yuv422p10 Reader / Writer on the 4:2:2 frame whose
+//   chroma line r is the 4:2:0 frame's line r >> 1 (read), whose upper line of a pair gives the chroma (write) - DESIGN.md 2.
 //
 // Readers: one PIXEL per lane (coalesced float4 stores; the sample loads of a wave are 64-128
 // contiguous bytes).  Writers: one group of 8 pixels per lane (8-16 byte plane stores), the
@@ -18,7 +20,9 @@ namespace ph {
 constexpr int kFmtBlock = 256;
 
 // formats (same numbering as PH_FMT_* in include/phaneron_hip.h)
-enum { F_V210 = 0, F_YUV422P10 = 1, F_YUV422P8 = 2, F_YUV420P = 3, F_NV12 = 4, F_RGBA8 = 5, F_BGRA8 = 6 };
+enum { F_V210 = 0, F_YUV422P10 = 1, F_YUV422P8 = 2, F_YUV420P = 3, F_NV12 = 4, F_RGBA8 = 5, F_BGRA8 = 6, F_YUV420P10 = 7, F_P010 = 8 };
+constexpr bool fmt_rgb8(int f) { return f == F_RGBA8 || f == F_BGRA8; }
+constexpr bool fmt_v420(int f) { return f == F_YUV420P || f == F_NV12 || f == F_YUV420P10 || f == F_P010; }
 
 template <typename LUT>
 __device__ __forceinline__ float4 yuv_to_rgba(float y, float u, float v, const ReadK &k, const LUT &lut) {
@@ -41,7 +45,7 @@ struct FmtReadArgs {
 template <int FMT, typename LUT, bool PERSISTENT>
 __device__ __forceinline__ void fmt_read_body(const FmtReadArgs &a, const LUT &lut, uint32_t block = blockIdx.x, uint32_t blocks = gridDim.x) {
   ReadK k;
-  if (FMT >= F_RGBA8) {  // the RGB formats carry no YCbCr matrix: gamut only (9 floats, never more)
+  if (fmt_rgb8(FMT)) {  // the RGB formats carry no YCbCr matrix: gamut only (9 floats, never more)
 #pragma unroll
     for (int i = 0; i < 9; ++i) k.gm[i] = a.gm[i];
   } else {
@@ -59,12 +63,16 @@ __device__ __forceinline__ void fmt_read_body(const FmtReadArgs &a, const LUT &l
       o = make_float4(dot3(r, g, b, k.gm[0], k.gm[1], k.gm[2]), dot3(r, g, b, k.gm[3], k.gm[4], k.gm[5]),
                       dot3(r, g, b, k.gm[6], k.gm[7], k.gm[8]), lut.at((float)px.w * 65535.0f / 255.0f));
     } else {
-      const uint32_t cl = (FMT == F_YUV420P || FMT == F_NV12) ? line >> 1 : line;
+      const uint32_t cl = fmt_v420(FMT) ? line >> 1 : line;
       float y, u, v;
-      if (FMT == F_YUV422P10) {
+      if (FMT == F_YUV422P10 || FMT == F_YUV420P10) {
         y = (float)reinterpret_cast<const uint16_t *>(a.p0)[(size_t)line * a.pitch + x];
         u = (float)reinterpret_cast<const uint16_t *>(a.p1)[(size_t)cl * (a.pitch >> 1) + (x >> 1)];
         v = (float)reinterpret_cast<const uint16_t *>(a.p2)[(size_t)cl * (a.pitch >> 1) + (x >> 1)];
+      } else if (FMT == F_P010) {  // MSB-aligned: the low 6 bits dropped; the pair's Cb, Cr words in one dword load
+        y = (float)(reinterpret_cast<const uint16_t *>(a.p0)[(size_t)line * a.pitch + x] >> 6);
+        const uint32_t c = reinterpret_cast<const uint32_t *>(a.p1)[(size_t)cl * (a.pitch >> 1) + (x >> 1)];
+        u = (float)((c & 0xffffu) >> 6), v = (float)(c >> 22);
       } else if (FMT == F_NV12) {  // nv12.ts:61-74
         y = (float)reinterpret_cast<const uint8_t *>(a.p0)[(size_t)line * a.pitch + x];
         const uint8_t *c = reinterpret_cast<const uint8_t *>(a.p1) + (size_t)cl * a.pitch + (x & ~1u);  // the pair's Cb, Cr bytes (two byte loads: a 2-byte vector load measured twice as slow here)
@@ -151,8 +159,9 @@ __device__ __forceinline__ void fmt_write_body(const FmtWriteArgs &a, const LUT 
     }
     return;
   }
-  constexpr bool V420 = (FMT == F_YUV420P || FMT == F_NV12);
-  constexpr bool WIDE = (FMT == F_YUV422P10);
+  constexpr bool V420 = fmt_v420(FMT);
+  constexpr bool WIDE = (FMT == F_YUV422P10 || FMT == F_YUV420P10 || FMT == F_P010);
+  constexpr uint32_t MSB = FMT == F_P010 ? 6u : 0u;  // p010: the code in the word's upper bits
   const WriteK k = load_write_k(a.cm);
   const uint32_t full = a.width / 8, remain = a.width % 8, octets = full + (remain ? 1 : 0);
   const uint32_t total = octets * a.groups;
@@ -192,15 +201,15 @@ __device__ __forceinline__ void fmt_write_body(const FmtWriteArgs &a, const LUT 
           y[2] = cy[2], y[3] = cy[3], u[1] = cu[2], v[1] = cv[2];
           if (remain > 4) {
             y[4] = cy[4], y[5] = cy[5];
-            if (V420) u[2] = cu[4], v[2] = cv[4];
-            else u[1] = cu[4], v[1] = cv[4];  // the 4:2:2 writers overwrite slot 1 (yuv422p10.ts:209-210)
+            if (V420 && !WIDE) u[2] = cu[4], v[2] = cv[4];
+            else u[1] = cu[4], v[1] = cv[4];  // the 4:2:2 writers overwrite slot 1 (yuv422p10.ts:209-210) - so do the 10-bit 4:2:0 ones defined by them
           }
         }
       }
       if (WIDE) {
         uint4 w;
-        w.x = (y[0] & 0xffff) | y[1] << 16, w.y = (y[2] & 0xffff) | y[3] << 16;
-        w.z = (y[4] & 0xffff) | y[5] << 16, w.w = (y[6] & 0xffff) | y[7] << 16;
+        w.x = ((y[0] << MSB) & 0xffff) | y[1] << (16 + MSB), w.y = ((y[2] << MSB) & 0xffff) | y[3] << (16 + MSB);
+        w.z = ((y[4] << MSB) & 0xffff) | y[5] << (16 + MSB), w.w = ((y[6] << MSB) & 0xffff) | y[7] << (16 + MSB);
         reinterpret_cast<uint4 *>(a.p0)[((size_t)line * a.pitch >> 3) + o8] = w;
       } else {  // uchar = (uchar)ushort keeps the low 8 bits (yuv422p8.ts:166-168)
         uint2 w;
@@ -214,6 +223,11 @@ __device__ __forceinline__ void fmt_write_body(const FmtWriteArgs &a, const LUT 
           w.x = (u[0] & 0xff) | (v[0] & 0xff) << 8 | (u[1] & 0xff) << 16 | v[1] << 24;
           w.y = (u[2] & 0xff) | (v[2] & 0xff) << 8 | (u[3] & 0xff) << 16 | v[3] << 24;
           reinterpret_cast<uint2 *>(a.p1)[((size_t)crow * a.pitch >> 3) + o8] = w;
+        } else if (FMT == F_P010) {  // Cb, Cr words interleaved: 16 bytes per group, the luma line's pitch
+          uint4 w;
+          w.x = ((u[0] << MSB) & 0xffff) | v[0] << (16 + MSB), w.y = ((u[1] << MSB) & 0xffff) | v[1] << (16 + MSB);
+          w.z = ((u[2] << MSB) & 0xffff) | v[2] << (16 + MSB), w.w = ((u[3] << MSB) & 0xffff) | v[3] << (16 + MSB);
+          reinterpret_cast<uint4 *>(a.p1)[((size_t)crow * a.pitch >> 3) + o8] = w;
         } else if (WIDE) {
           uint2 wu, wv;
           wu.x = (u[0] & 0xffff) | u[1] << 16, wu.y = (u[2] & 0xffff) | u[3] << 16;
@@ -248,7 +262,7 @@ __global__ __launch_bounds__(kFmtBlock) void fmt_write_gather_kernel(FmtWriteArg
 // geometry + launchers
 // ------------------------------------------------------------------------------------------
 uint32_t pack_pitch(int fmt, uint32_t width) {
-  if (fmt == F_RGBA8 || fmt == F_BGRA8) return width;                 // rgba8.ts:103-105
+  if (fmt_rgb8(fmt)) return width;                                    // rgba8.ts:103-105
   if (fmt == F_V210) return width + 47 - ((width - 1) % 48);
   return width + 7 - ((width - 1) % 8);                              // yuv422p10.ts:221
 }
@@ -262,6 +276,8 @@ int pack_plane_bytes(int fmt, uint32_t width, uint32_t height, size_t bytes[3]) 
     case F_YUV422P8: bytes[0] = p * height, bytes[1] = bytes[2] = bytes[0] / 2; return 3;
     case F_YUV420P: bytes[0] = p * height, bytes[1] = bytes[2] = bytes[0] / 4; return 3;
     case F_NV12: bytes[0] = p * height, bytes[1] = bytes[0] / 2; return 2;
+    case F_YUV420P10: bytes[0] = p * 2 * height, bytes[1] = bytes[2] = bytes[0] / 4; return 3;
+    case F_P010: bytes[0] = p * 2 * height, bytes[1] = bytes[0] / 2; return 2;
     case F_RGBA8:
     case F_BGRA8: bytes[0] = p * 4 * height; return 1;
   }
@@ -288,7 +304,7 @@ static hipError_t launch_read_fmt(hipStream_t s, const FmtReadArgs &a, const flo
 hipError_t launch_pack_read(hipStream_t s, int fmt, const void *const planes[3], void *out, uint32_t width,
                             uint32_t height, const void *cm, const void *table, const void *gm, const LutView *lv,
                             uint32_t num_cus) {
-  const bool v420 = (fmt == F_YUV420P || fmt == F_NV12);
+  const bool v420 = fmt_v420(fmt);
   FmtReadArgs a{planes[0], planes[1], planes[2], (float4 *)out, width, v420 ? (height / 2) * 2 : height,
                 pack_pitch(fmt, width), (const float *)cm, (const float *)gm, image_nt((size_t)width * height * 16)};
   switch (fmt) {
@@ -298,6 +314,8 @@ hipError_t launch_pack_read(hipStream_t s, int fmt, const void *const planes[3],
     case F_NV12: return launch_read_fmt<F_NV12>(s, a, (const float *)table, lv, num_cus);
     case F_RGBA8: return launch_read_fmt<F_RGBA8>(s, a, (const float *)table, lv, num_cus);
     case F_BGRA8: return launch_read_fmt<F_BGRA8>(s, a, (const float *)table, lv, num_cus);
+    case F_YUV420P10: return launch_read_fmt<F_YUV420P10>(s, a, (const float *)table, lv, num_cus);
+    case F_P010: return launch_read_fmt<F_P010>(s, a, (const float *)table, lv, num_cus);
     default: return hipErrorInvalidValue;
   }
 }
@@ -315,7 +333,7 @@ static hipError_t launch_read_batch_fmt(hipStream_t s, const FmtReadBatchArgs &b
 // n frames (1 .. kMaxLayers) of one format, size and Loader recipe; the table in its LDS form
 hipError_t launch_pack_read_batch(hipStream_t s, int fmt, int n, const void *const (*planes)[3], void *const *outs, uint32_t width, uint32_t height,
                                   const void *cm, const void *gm, const LutView &lv, uint32_t num_cus) {
-  const bool v420 = (fmt == F_YUV420P || fmt == F_NV12);
+  const bool v420 = fmt_v420(fmt);
   FmtReadBatchArgs b{};
   for (int i = 0; i < n; ++i) b.p0[i] = planes[i][0], b.p1[i] = planes[i][1], b.p2[i] = planes[i][2], b.out[i] = (float4 *)outs[i];
   b.jobs = (uint32_t)n, b.width = width, b.lines = v420 ? (height / 2) * 2 : height, b.pitch = pack_pitch(fmt, width);
@@ -327,6 +345,8 @@ hipError_t launch_pack_read_batch(hipStream_t s, int fmt, int n, const void *con
     case F_NV12: return launch_read_batch_fmt<F_NV12>(s, b, lv, num_cus);
     case F_RGBA8: return launch_read_batch_fmt<F_RGBA8>(s, b, lv, num_cus);
     case F_BGRA8: return launch_read_batch_fmt<F_BGRA8>(s, b, lv, num_cus);
+    case F_YUV420P10: return launch_read_batch_fmt<F_YUV420P10>(s, b, lv, num_cus);
+    case F_P010: return launch_read_batch_fmt<F_P010>(s, b, lv, num_cus);
     default: return hipErrorInvalidValue;
   }
 }
@@ -334,7 +354,7 @@ hipError_t launch_pack_read_batch(hipStream_t s, int fmt, int n, const void *con
 template <int FMT>
 static hipError_t launch_write_fmt(hipStream_t s, const FmtWriteArgs &a, const float *table, const LutView *lv,
                                    uint32_t num_cus) {
-  const bool rgb = (FMT == F_RGBA8 || FMT == F_BGRA8);
+  const bool rgb = fmt_rgb8(FMT);
   const uint32_t total = rgb ? a.width * a.groups : ((a.width + 7) / 8) * a.groups;
   if (!total) return hipSuccess;
   if (lv) {
@@ -352,7 +372,7 @@ static hipError_t launch_write_fmt(hipStream_t s, const FmtWriteArgs &a, const f
 hipError_t launch_pack_write(hipStream_t s, int fmt, const void *in, void *const planes[3], uint32_t width,
                              uint32_t height, uint32_t interlace, const void *cm, const void *table, const LutView *lv,
                              uint32_t num_cus) {
-  const bool v420 = (fmt == F_YUV420P || fmt == F_NV12);
+  const bool v420 = fmt_v420(fmt);
   const uint32_t groups = v420 ? height / 2 : (interlace ? height / 2 : height);  // e.g. yuv422p10.ts:328, yuv420p.ts:381
   FmtWriteArgs a{(const float4 *)in, planes[0], planes[1], planes[2], width, pack_pitch(fmt, width), groups, interlace,
                  (const float *)cm};
@@ -363,6 +383,8 @@ hipError_t launch_pack_write(hipStream_t s, int fmt, const void *in, void *const
     case F_NV12: return launch_write_fmt<F_NV12>(s, a, (const float *)table, lv, num_cus);
     case F_RGBA8: return launch_write_fmt<F_RGBA8>(s, a, (const float *)table, lv, num_cus);
     case F_BGRA8: return launch_write_fmt<F_BGRA8>(s, a, (const float *)table, lv, num_cus);
+    case F_YUV420P10: return launch_write_fmt<F_YUV420P10>(s, a, (const float *)table, lv, num_cus);
+    case F_P010: return launch_write_fmt<F_P010>(s, a, (const float *)table, lv, num_cus);
     default: return hipErrorInvalidValue;
   }
 }

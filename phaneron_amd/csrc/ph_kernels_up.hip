@@ -415,7 +415,7 @@ __global__ __launch_bounds__(kUpBlock) void compose_up_write_v210_kernel(UpArgs 
 #ifndef PH_CLIP_ABLATE
 #define PH_CLIP_ABLATE 0
 #endif
-enum { CF_V210 = 0, CF_YUV422P10 = 1, CF_YUV422P8 = 2, CF_YUV420P = 3, CF_NV12 = 4, CF_RGBA8 = 5, CF_BGRA8 = 6 };  // = PH_FMT_*
+enum { CF_V210 = 0, CF_YUV422P10 = 1, CF_YUV422P8 = 2, CF_YUV420P = 3, CF_NV12 = 4, CF_RGBA8 = 5, CF_BGRA8 = 6, CF_YUV420P10 = 7, CF_P010 = 8 };  // = PH_FMT_*
 
 // one source pixel as the reader of its format makes it (ph_kernels_fmt.hip fmt_read_body, ph_kernels_lds.hip v210_read_lds_kernel), in two
 // halves: its samples requested, then converted - a lane requests the samples of all its pixels of a round before it converts the first
@@ -432,11 +432,15 @@ __device__ __forceinline__ ClipRaw clip_fetch(const ClipSrc &S, uint32_t x, uint
   } else if (FMT == CF_RGBA8 || FMT == CF_BGRA8) {
     r.w.x = reinterpret_cast<const uint32_t *>(S.p0)[(size_t)line * S.pitch + x];
   } else {
-    const uint32_t cl = (FMT == CF_YUV420P || FMT == CF_NV12) ? line >> 1 : line;
-    if (FMT == CF_YUV422P10) {
+    const uint32_t cl = (FMT == CF_YUV420P || FMT == CF_NV12 || FMT == CF_YUV420P10 || FMT == CF_P010) ? line >> 1 : line;
+    if (FMT == CF_YUV422P10 || FMT == CF_YUV420P10) {
       r.w.x = reinterpret_cast<const uint16_t *>(S.p0)[(size_t)line * S.pitch + x];
       r.w.y = reinterpret_cast<const uint16_t *>(S.p1)[(size_t)cl * (S.pitch >> 1) + (x >> 1)];
       r.w.z = reinterpret_cast<const uint16_t *>(S.p2)[(size_t)cl * (S.pitch >> 1) + (x >> 1)];
+    } else if (FMT == CF_P010) {  // as fmt_read_body: the sample in bits 6..15, the pair's Cb, Cr words in one dword
+      r.w.x = reinterpret_cast<const uint16_t *>(S.p0)[(size_t)line * S.pitch + x] >> 6;
+      const uint32_t c = reinterpret_cast<const uint32_t *>(S.p1)[(size_t)cl * (S.pitch >> 1) + (x >> 1)];
+      r.w.y = (c & 0xffffu) >> 6, r.w.z = c >> 22;
     } else if (FMT == CF_NV12) {  // nv12.ts:61-74
       r.w.x = reinterpret_cast<const uint8_t *>(S.p0)[(size_t)line * S.pitch + x];
       const uint8_t *c = reinterpret_cast<const uint8_t *>(S.p1) + (size_t)cl * S.pitch + (x & ~1u);
@@ -522,7 +526,7 @@ __device__ __forceinline__ void clip_convert(const ClipSrc &S, const UpLayer &L,
     __syncthreads();
   }
   ReadK k;
-  if (FMT >= CF_RGBA8) {
+  if (FMT == CF_RGBA8 || FMT == CF_BGRA8) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) k.gm[i] = rd_gm[i];
   } else {
@@ -609,6 +613,8 @@ __global__ __launch_bounds__(kUpBlock) void clip_up_write_v210_kernel(ClipUpArgs
       PH_CLIP_CASE(CF_YUV422P8)
       PH_CLIP_CASE(CF_YUV420P)
       PH_CLIP_CASE(CF_NV12)
+      PH_CLIP_CASE(CF_YUV420P10)
+      PH_CLIP_CASE(CF_P010)
       PH_CLIP_CASE(CF_RGBA8)
       default:
         if (l == 0) clip_convert<CF_BGRA8, RGB12, true>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);

@@ -10,6 +10,7 @@
 //      reference v0.0.15 - exact, no guessing (refbuild/kernel_hashes.py prints the table in the build container),
 //   3. the argument list of the named kernel, plus - only where two formats share an argument list
 //      (yuv422p8 / yuv420p, rgba8 / bgra8) - one structural probe of that kernel's BODY, comments removed.
+// The 10-bit 4:2:0 formats (yuv420p10, p010) have no reference text: their programs resolve by tag only.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,7 +24,7 @@ namespace ph {
 
 namespace {
 
-const char *const kFmtNames[7] = {"v210", "yuv422p10", "yuv422p8", "yuv420p", "nv12", "rgba8", "bgra8"};
+const char *const kFmtNames[9] = {"v210", "yuv422p10", "yuv422p8", "yuv420p", "nv12", "rgba8", "bgra8", "yuv420p10", "p010"};  // = PH_FMT_*
 
 struct KnownSource {
   unsigned long long fingerprint;
@@ -150,7 +151,7 @@ int resolve_program(const char *src, const char *name, ProgramChoice &c, std::st
     const bool is_read = name[0] == 'r';
     int fmt = -1, how = PH_RESOLVED_BY_TAG;
     if (tagged) {
-      for (int i = 0; i < 7; ++i)
+      for (int i = 0; i < (int)(sizeof kFmtNames / sizeof kFmtNames[0]); ++i)
         if (0 == strcmp(src + 9, kFmtNames[i])) fmt = i;
     } else if (src) {
       const unsigned long long fp = fingerprint(src);
