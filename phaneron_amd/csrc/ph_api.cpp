@@ -42,16 +42,10 @@ int fail(int code, const char *fmt, ...) {
     if (e_ != hipSuccess) return fail(PH_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
   } while (0)
 
-// the pack formats and chan sources by kind (the 10-bit 4:2:0 values come after the packed-RGB ones: no range covers a kind)
-bool fmt_rgb8(int f) { return f == PH_FMT_RGBA8 || f == PH_FMT_BGRA8; }
-bool fmt_v420(int f) { return f == PH_FMT_YUV420P || f == PH_FMT_NV12 || f == PH_FMT_YUV420P10 || f == PH_FMT_P010; }
-bool src_planar(int f) { return (f >= PH_SRC_YUV422P10 && f <= PH_SRC_NV12) || f == PH_SRC_YUV420P10 || f == PH_SRC_P010; }
-bool src_420(int f) { return f == PH_SRC_YUV420P || f == PH_SRC_NV12 || f == PH_SRC_YUV420P10 || f == PH_SRC_P010; }
-bool src_wide(int f) { return f == PH_SRC_YUV422P10 || f == PH_SRC_YUV420P10 || f == PH_SRC_P010; }  // 16-bit samples
-// the 10-bit 4:2:0 frames are defined for even widths and heights only (a line pair per chroma line, a sample pair per chroma sample)
-int fmt10_dims(const char *fn, int f, uint32_t w, uint32_t h) {
-  if ((f == PH_FMT_YUV420P10 || f == PH_FMT_P010) && ((w & 1) || (h & 1)))
-    return fail(PH_E_INVALID, "%s: a %s frame needs an even width and height (%ux%u)", fn, f == PH_FMT_P010 ? "p010" : "yuv420p10", w, h);
+// the formats defined for even sizes only (fmt_even_size: a line pair per chroma line, a sample pair per chroma sample)
+int even_dims(const char *fn, int f, uint32_t w, uint32_t h) {
+  if (fmt_even_size(f) && ((w & 1) || (h & 1)))
+    return fail(PH_E_INVALID, "%s: a %s frame needs an even width and height (%ux%u)", fn, fmt_name(f), w, h);
   return PH_OK;
 }
 
@@ -1225,17 +1219,17 @@ static int chan_call_parse(ph_ctx *ctx, ph_program *prog, const ph_arg *args, in
           snprintf(nm, sizeof nm, "l%d%sPacking", i, role);
           if (find_arg(args, n, nm)) TRY(need_num(args, n, nm, &packing));
           if (packing != 0) {
-            if (packing < PH_FMT_YUV422P10 || packing > PH_FMT_P010) return fail(PH_E_INVALID, "kernel argument '%s': %g is not a pack format other than v210", nm, packing);
-            s->format = PH_SRC_YUV422P10 + ((int)packing - PH_FMT_YUV422P10);  // PH_SRC_* follow PH_FMT_* from here on
+            if (packing < PH_FMT_YUV422P10 || packing >= kFmtCount) return fail(PH_E_INVALID, "kernel argument '%s': %g is not a pack format other than v210", nm, packing);
+            s->format = src_of_fmt((int)packing);  // (PH_FMT_V210 is 0: every value from 1 on is another format)
           }
           snprintf(nm, sizeof nm, "l%d%sWidth", i, role);
           if (find_arg(args, n, nm)) TRY(need_num(args, n, nm, &sw));
           snprintf(nm, sizeof nm, "l%d%sHeight", i, role);
           if (find_arg(args, n, nm)) TRY(need_num(args, n, nm, &sh));
-          if (s->format == PH_SRC_RGBA8 || s->format == PH_SRC_BGRA8) {
+          const int fmt = fmt_of_src(s->format);
+          if (fmt_rgb8(fmt)) {
             if (sw > 0 && sh > 0 && x->bytes < (size_t)sw * (size_t)sh * 4) return fail(PH_E_RANGE, "kernel argument 'l%d%sIn': buffer of %zu bytes is smaller than a %gx%g frame of 4 bytes per pixel", i, role, x->bytes, sw, sh);
-          } else if (s->format != PH_SRC_V210) {
-            const int fmt = PH_FMT_YUV422P10 + (s->format - PH_SRC_YUV422P10);
+          } else if (fmt_planar(fmt)) {
             size_t pb[3] = {0, 0, 0};
             if (sw > 0 && sh > 0) ph_pack_plane_bytes(fmt, (uint32_t)sw, (uint32_t)sh, pb);
             char nu[40];
@@ -1243,7 +1237,7 @@ static int chan_call_parse(ph_ctx *ctx, ph_program *prog, const ph_arg *args, in
             snprintf(nu, sizeof nu, "l%d%sInU", i, role);
             TRY(need_buf(args, n, nu, pb[1], &pu));
             s->data_u = pu->dptr;
-            if (fmt != PH_FMT_NV12 && fmt != PH_FMT_P010) {
+            if (fmt_planes(fmt) == 3) {
               snprintf(nu, sizeof nu, "l%d%sInV", i, role);
               TRY(need_buf(args, n, nu, pb[2], &pv));
               s->data_v = pv->dptr;
@@ -1288,16 +1282,16 @@ static int chan_call_parse(ph_ctx *ctx, ph_program *prog, const ph_arg *args, in
       size_t opb[3] = {0, 0, 0};
       if (ph_pack_plane_bytes(ofmt, width, height, opb) < 0) return fail(PH_E_INVALID, "kernel argument 'outPacking': %g is not a pack format", out_packing);
       TRY(need_buf(args, n, "output", opb[0], &o));
-      if (ofmt == PH_FMT_YUV422P10 || ofmt == PH_FMT_YUV422P8 || ofmt == PH_FMT_YUV420P) {
+      if (fmt_chan_out(ofmt) && fmt_planes(ofmt) == 3) {  // (ph_chan_compose refuses the formats the kernel does not write)
         TRY(need_buf(args, n, "outputU", opb[1], &ou));
         TRY(need_buf(args, n, "outputV", opb[2], &ov));
-      } else if (ofmt == PH_FMT_NV12) {  // nv12.ts:374: the interleaved CbCr plane is `outputC`
+      } else if (fmt_chan_out(ofmt) && fmt_planes(ofmt) == 2) {  // nv12.ts:374: the interleaved CbCr plane is `outputC`
         TRY(need_buf(args, n, "outputC", opb[1], &ou));
       }
       TRY(need_buf(args, n, "colMatrix", 48, &b));
       TRY(need_buf(args, n, "gammaLut", 65536 * 4, &c));
       TRY(need_buf(args, n, "gamutMatrix", 36, &d));
-      if (ofmt != PH_FMT_RGBA8 && ofmt != PH_FMT_BGRA8) TRY(need_buf(args, n, "outColMatrix", 48, &wcm));
+      if (!fmt_rgb8(ofmt)) TRY(need_buf(args, n, "outColMatrix", 48, &wcm));
       TRY(need_buf(args, n, "outGammaLut", 65536 * 4, &wl));
       if (find_arg(args, n, "interlace")) TRY(need_num(args, n, "interlace", &interlace));
       if (!check_only) refresh_buf_lut(ctx, c);
@@ -1573,7 +1567,7 @@ static int dispatch_deint(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int
       if (find_arg(args, n, "packing")) TRY(need_num(args, n, "packing", &packing));
       const int pfmt = (int)packing;
       size_t pb[3] = {0, 0, 0};
-      if (pfmt != PH_FMT_V210 && pfmt != PH_FMT_YUV422P10 && pfmt != PH_FMT_YUV422P8 && pfmt != PH_FMT_YUV420P && pfmt != PH_FMT_NV12)
+      if (!fmt_deint(pfmt))
         return fail(PH_E_INVALID, "kernel argument 'packing': %g (0 v210, 1 yuv422p10, 2 yuv422p8, 3 yuv420p, 4 nv12)", packing);
       ph_pack_plane_bytes(pfmt, width, height, pb);
       const size_t vb = pb[0], img = (size_t)width * height * (rgb != 0 ? 12 : 16);
@@ -1586,7 +1580,7 @@ static int dispatch_deint(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int
           static const char *const which[3] = {"Prev", "Cur", "Next"};
           const void **slots[3][2] = {{&src[i].prev_u, &src[i].prev_v}, {&src[i].cur_u, &src[i].cur_v}, {&src[i].next_u, &src[i].next_v}};
           for (int f = 0; f < 3; ++f)
-            for (int c = 0; c < (pfmt == PH_FMT_NV12 ? 1 : 2); ++c) {  // (nv12: l<i>PrevU ... are the interleaved CbCr planes)
+            for (int c = 0; c < fmt_planes(pfmt) - 1; ++c) {  // (nv12: l<i>PrevU ... are the interleaved CbCr planes)
               snprintf(nm, sizeof nm, "l%d%s%c", i, which[f], c ? 'V' : 'U');
               TRY(need_buf(args, n, nm, pb[1 + c], &x));
               *slots[f][c] = x->dptr;
@@ -2086,7 +2080,7 @@ int ph_fused_v210_combine(ph_ctx *ctx, int queue, int n, const void *const *laye
 
 int ph_pack_plane_bytes(int format, uint32_t width, uint32_t height, size_t bytes[3]) {
   if (!bytes || !width) return fail(PH_E_INVALID, "ph_pack_plane_bytes: NULL/zero argument");
-  if (const int rc = fmt10_dims("ph_pack_plane_bytes", format, width, height)) return rc;
+  if (const int rc = even_dims("ph_pack_plane_bytes", format, width, height)) return rc;
   const int n = ph::pack_plane_bytes(format, width, height, bytes);
   return n < 0 ? fail(PH_E_INVALID, "ph_pack_plane_bytes: unknown format %d", format) : n;
 }
@@ -2134,7 +2128,7 @@ int ph_pack_read(ph_ctx *ctx, int queue, int format, const void *const planes[3]
                  uint32_t height, const void *cm, const void *lut, const void *gm) {
   if (!ctx || !planes || !out || !lut || !gm || !width) return fail(PH_E_INVALID, "ph_pack_read: NULL/zero argument");
   if (format == PH_FMT_V210) return ph_v210_read(ctx, queue, planes[0], out, width, height, cm, lut, gm);
-  if (const int rc = fmt10_dims("ph_pack_read", format, width, height)) return rc;
+  if (const int rc = even_dims("ph_pack_read", format, width, height)) return rc;
   size_t pb[3];
   const int np = ph::pack_plane_bytes(format, width, height, pb);
   if (np < 0) return fail(PH_E_INVALID, "ph_pack_read: unknown format %d", format);
@@ -2150,7 +2144,7 @@ int ph_pack_read_batch(ph_ctx *ctx, int queue, int format, int n, const void *co
                        const void *cm, const void *lut, const void *gm) {
   if (!ctx || !planes || !outs || !lut || !gm || !width) return fail(PH_E_INVALID, "ph_pack_read_batch: NULL/zero argument");
   if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "ph_pack_read_batch: 1..%d frames", ph::kMaxLayers);
-  if (const int rc = fmt10_dims("ph_pack_read_batch", format, width, height)) return rc;
+  if (const int rc = even_dims("ph_pack_read_batch", format, width, height)) return rc;
   const LutRef lref = lds_view(ctx, lut);
   const ph::LutView *v = format == PH_FMT_V210 ? nullptr : lref.get();
   if (n == 1 || !v) {  // one frame, v210 (its own batch call), or no LDS form of the table: frame by frame
@@ -2183,7 +2177,7 @@ int ph_pack_write(ph_ctx *ctx, int queue, int format, const void *in, void *cons
   if (!ctx || !planes || !in || !lut || !width) return fail(PH_E_INVALID, "ph_pack_write: NULL/zero argument");
   if (interlace != 0 && interlace != 1 && interlace != 3) return fail(PH_E_INVALID, "ph_pack_write: interlace must be 0, 1 or 3");
   if (format == PH_FMT_V210) return ph_v210_write(ctx, queue, in, planes[0], width, height, interlace, cm, lut);
-  if (const int rc = fmt10_dims("ph_pack_write", format, width, height)) return rc;
+  if (const int rc = even_dims("ph_pack_write", format, width, height)) return rc;
   size_t pb[3];
   const int np = ph::pack_plane_bytes(format, width, height, pb);
   if (np < 0) return fail(PH_E_INVALID, "ph_pack_write: unknown format %d", format);
@@ -2254,13 +2248,14 @@ static int chan_source(const ph_chan_source &s, const char *what, int layer, uin
                        const void **pv, const float **cm, uint32_t *planar) {
   if (!s.data || s.width <= 0 || s.height <= 0)
     return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s is empty", layer, what);
-  const bool is_planar = src_planar(s.format), is_rgb8 = s.format == PH_SRC_RGBA8 || s.format == PH_SRC_BGRA8;
-  if (s.format != PH_SRC_V210 && s.format != PH_SRC_RGBA_F32 && !is_planar && !is_rgb8)
+  const int fmt = fmt_of_src(s.format);
+  const bool is_planar = fmt_planar(fmt), is_rgb8 = fmt_rgb8(fmt);
+  if (fmt < 0 && s.format != PH_SRC_RGBA_F32)
     return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s has format %d (not a PH_SRC_*)", layer, what, s.format);
   *pu = *pv = nullptr, *cm = nullptr;
   if (is_rgb8) *planar = 2;  // (served by the kernel's wire-format instantiation)
   if (is_planar) {
-    if (!s.data_u || (s.format != PH_SRC_NV12 && s.format != PH_SRC_P010 && !s.data_v) || (s.width & 1) || (src_420(s.format) && (s.height & 1)))
+    if (!s.data_u || (fmt_planes(fmt) == 3 && !s.data_v) || (s.width & 1) || (fmt_v420(fmt) && (s.height & 1)))
       return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s is planar: it needs its chroma plane(s), an even width and, for 4:2:0, an even height", layer, what);
     *pu = s.data_u, *pv = s.data_v, *cm = (const float *)s.col_matrix12, *planar = 2;
   }
@@ -2274,10 +2269,9 @@ static int chan_source(const ph_chan_source &s, const char *what, int layer, uin
   static const uint32_t kinds[] = {ph::kChanNone, ph::kChanV210,  ph::kChanRgba,  ph::kChanP10,     ph::kChanP8x422, ph::kChanP8x420,
                                    ph::kChanNv12, ph::kChanRgba8, ph::kChanBgra8, ph::kChanP10x420, ph::kChanP010};  // [PH_SRC_*]
   o->kind = kinds[s.format];
-  // planar: the luma line pitch in samples is the width rounded up to 8 (yuv422p10.ts:221), one or two bytes each
+  // the line of the frame's first plane (planar: the Y plane), or of an f32 image
   o->pitch = s.format == PH_SRC_V210 ? ph_v210_pitch_bytes((uint32_t)s.width)
-             : is_planar ? (((uint32_t)s.width + 7u) & ~7u) * (src_wide(s.format) ? 2u : 1u)
-             : is_rgb8 ? (uint32_t)s.width * 4u : (uint32_t)s.width * 16u;  // rgba8.ts:103-105: no line padding
+             : fmt >= 0 ? pack_pitch(fmt, (uint32_t)s.width) * fmt_sample_bytes(fmt) : (uint32_t)s.width * 16u;
   if ((uint64_t)o->pitch * o->h >= (1ull << 30))
     return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s is 1 GiB or larger; run the separate kernels", layer, what);
   o->sampled = s.matrix9_host ? 1u : 0u;
@@ -2371,8 +2365,9 @@ static bool chan_layers_enlarged(int n, const ph_chan_layer *layers, uint32_t ou
     const float *m = L.src.matrix9_host;
     // (v210 frames, a file decoder's planar frames, packed 8-bit RGB: whatever has a reader of its own - ph_v210_read, ph_pack_read)
     // - and finished f32 images, which the compositor takes as they are
-    if (L.transition != PH_TRANSITION_CUT || L.src.format < PH_SRC_V210 || L.src.format > PH_SRC_P010 || !m || L.src.width <= 0 ||
-        L.src.height <= 0 || ((L.src.width & 1) && L.src.format != PH_SRC_RGBA8 && L.src.format != PH_SRC_BGRA8 && L.src.format != PH_SRC_RGBA_F32))
+    const int fmt = fmt_of_src(L.src.format);
+    if (L.transition != PH_TRANSITION_CUT || (fmt < 0 && L.src.format != PH_SRC_RGBA_F32) || !m || L.src.width <= 0 || L.src.height <= 0 ||
+        ((L.src.width & 1) && !fmt_rgb8(fmt) && L.src.format != PH_SRC_RGBA_F32))
       return false;
     if (m[1] != 0.0f || m[3] != 0.0f || !(m[0] > 0.0f) || !(m[4] > 0.0f)) return false;                      // (ph_kernels_up.hip compose_up_eligible)
     // ... or a decoder's frame of the channel's size under the Mixer's default fill (the compositor takes exactly that placement beside the
@@ -2408,8 +2403,9 @@ static int chan_compose_enlarged(ph_ctx *ctx, int queue, int jobs, int n, const 
     bool wire = true, alpha = false;
     for (int j = 0; j < jobs && wire; ++j) {
       const ph_chan_source &S = layers[j][0].src;
-      wire = S.format != PH_SRC_RGBA_F32 && S.format != PH_SRC_V210 && !(src_420(S.format) && (S.height & 1));
-      alpha = alpha || S.format == PH_SRC_RGBA8 || S.format == PH_SRC_BGRA8;
+      const int fmt = fmt_of_src(S.format);
+      wire = fmt >= 0 && fmt != PH_FMT_V210 && !(fmt_v420(fmt) && (S.height & 1));
+      alpha = alpha || fmt_rgb8(fmt);
     }
     const LutRef rref = lds_view(ctx, rd_lut), wref = lds_view(ctx, wr_lut);
     if (wire && rref.found && wref.found) {
@@ -2427,7 +2423,7 @@ static int chan_compose_enlarged(ph_ctx *ctx, int queue, int jobs, int n, const 
       }
       for (int j = 0; j < jobs; ++j) {
         const ph_chan_source &S = layers[j][0].src;
-        const int fmt = PH_FMT_YUV422P10 + (S.format - PH_SRC_YUV422P10);
+        const int fmt = fmt_of_src(S.format);
         c.src[j] = ph::ClipSrc{S.data, S.data_u, S.data_v, (const float *)(S.col_matrix12 ? S.col_matrix12 : rd_cm), (uint32_t)fmt, ph::pack_pitch(fmt, (uint32_t)S.width)};
       }
       if (a.lines && ph::compose_up_eligible(a)) {
@@ -2488,7 +2484,7 @@ static int chan_compose_enlarged(ph_ctx *ctx, int queue, int jobs, int n, const 
   bool one_reader = !all_v210 && one_size && frames > 1;  // every frame a decoder's frame of ONE format, size and Loader matrix: one launch reads them all
   for (int f = 0; f < frames && one_reader; ++f) {
     const ph_chan_source &S = layers[f / n][f % n].src, &S0 = layers[0][0].src;
-    one_reader = S.format == S0.format && S.format > PH_SRC_RGBA_F32 && S.col_matrix12 == S0.col_matrix12;
+    one_reader = S.format == S0.format && fmt_of_src(S.format) > PH_FMT_V210 && S.col_matrix12 == S0.col_matrix12;
   }
   if (one_reader) {
     const void *planes[ph::kMaxUpJobs * ph::kMaxLayers][3];
@@ -2498,7 +2494,7 @@ static int chan_compose_enlarged(ph_ctx *ctx, int queue, int jobs, int n, const 
     }
     const ph_chan_source &S0 = layers[0][0].src;
     for (int f = 0; f < frames && rc == PH_OK; f += ph::kMaxLayers)
-      rc = ph_pack_read_batch(ctx, queue, PH_FMT_YUV422P10 + (S0.format - PH_SRC_YUV422P10), frames - f < ph::kMaxLayers ? frames - f : ph::kMaxLayers, planes + f, imgs + f,
+      rc = ph_pack_read_batch(ctx, queue, fmt_of_src(S0.format), frames - f < ph::kMaxLayers ? frames - f : ph::kMaxLayers, planes + f, imgs + f,
                               (uint32_t)S0.width, (uint32_t)S0.height, S0.col_matrix12 ? S0.col_matrix12 : rd_cm, rd_lut, rd_gm);
   } else if (!all_v210) {  // each clip through the reader of its format (a source with code ranges of its own brings its Loader matrix)
     for (int f = 0; f < frames && rc == PH_OK; ++f) {
@@ -2508,7 +2504,7 @@ static int chan_compose_enlarged(ph_ctx *ctx, int queue, int jobs, int n, const 
         rc = ph_v210_read(ctx, queue, S.data, imgs[f], (uint32_t)S.width, (uint32_t)S.height, rd_cm, rd_lut, rd_gm);
       } else {
         const void *planes[3] = {S.data, S.data_u, S.data_v};
-        rc = ph_pack_read(ctx, queue, PH_FMT_YUV422P10 + (S.format - PH_SRC_YUV422P10), planes, imgs[f], (uint32_t)S.width, (uint32_t)S.height,
+        rc = ph_pack_read(ctx, queue, fmt_of_src(S.format), planes, imgs[f], (uint32_t)S.width, (uint32_t)S.height,
                           S.col_matrix12 ? S.col_matrix12 : rd_cm, rd_lut, rd_gm);
       }
     }
@@ -2536,14 +2532,12 @@ int ph_chan_compose(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, 
                     const void *wr_lut) {
   if (!ctx || !layers || !out_planes || !out_planes[0] || !rd_cm || !rd_lut || !rd_gm || !wr_lut) return fail(PH_E_INVALID, "ph_chan_compose_v210: NULL argument");
   void *const out = out_planes[0];
-  const bool out_rgb8 = out_format == PH_FMT_RGBA8 || out_format == PH_FMT_BGRA8, out_420 = out_format == PH_FMT_YUV420P || out_format == PH_FMT_NV12;
-  const bool out_planar = out_format == PH_FMT_YUV422P10 || out_format == PH_FMT_YUV422P8 || out_420;
-  if (out_format != PH_FMT_V210 && !out_rgb8 && !out_planar)
-    return fail(PH_E_INVALID, "ph_chan_compose_v210: output format %d is not a PH_FMT_*", out_format);
-  if (!out_rgb8 && !wr_cm) return fail(PH_E_INVALID, "ph_chan_compose_v210: the writer's RGB -> YCbCr matrix is missing");
-  if (out_planar && (!out_planes[1] || (out_format != PH_FMT_NV12 && !out_planes[2])))
+  if (!fmt_chan_out(out_format)) return fail(PH_E_INVALID, "ph_chan_compose_v210: output format %d is not a PH_FMT_*", out_format);
+  const bool out_planar = fmt_planar(out_format);
+  if (!fmt_rgb8(out_format) && !wr_cm) return fail(PH_E_INVALID, "ph_chan_compose_v210: the writer's RGB -> YCbCr matrix is missing");
+  if (out_planar && (!out_planes[1] || (fmt_planes(out_format) == 3 && !out_planes[2])))
     return fail(PH_E_INVALID, "ph_chan_compose_v210: a planar output needs its three planes (nv12: Y and the interleaved CbCr plane)");
-  if (out_420 && (out_h & 1)) return fail(PH_E_INVALID, "ph_chan_compose_v210: a 4:2:0 frame needs an even height (%u)", out_h);
+  if (fmt_v420(out_format) && (out_h & 1)) return fail(PH_E_INVALID, "ph_chan_compose_v210: a 4:2:0 frame needs an even height (%u)", out_h);
   PH_QUEUE("ph_chan_compose_v210", queue);
   if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "ph_chan_compose_v210: 1..%d layers", ph::kMaxLayers);
   // A v210 line of a width that is not a multiple of 48 (1280 x 720, src/config.ts:43-54) ends in a padded block: whole quads, the
@@ -2864,10 +2858,10 @@ int ph_v210_yadif_pair_fmt(ph_ctx *ctx, int queue, int n, const ph_deint_source 
 int ph_yadif_pair_packed(ph_ctx *ctx, int queue, int n, const ph_deint_source *src, int packing, uint32_t width, uint32_t height, int tff,
                          int skip, int out_format, const void *cm, const void *lut, const void *gm) {
   if (!ctx || !src || !cm || !lut || !gm) return fail(PH_E_INVALID, "ph_v210_yadif_pair: NULL argument");
-  if (packing != PH_FMT_V210 && packing != PH_FMT_YUV422P10 && packing != PH_FMT_YUV422P8 && packing != PH_FMT_YUV420P && packing != PH_FMT_NV12)
+  if (!fmt_deint(packing))
     return fail(PH_E_INVALID, "ph_v210_yadif_pair: packing %d (v210, yuv422p10, yuv422p8, yuv420p or nv12; for the others - the 10-bit 4:2:0 "
                               "yuv420p10 / p010 among them - run the separate kernels: the format's reader, then yadif)", packing);
-  if ((packing == PH_FMT_YUV420P || packing == PH_FMT_NV12) && (height & 1))
+  if (fmt_v420(packing) && (height & 1))
     return fail(PH_E_INVALID, "ph_v210_yadif_pair: a 4:2:0 frame needs an even height (%u)", height);
   const bool planar = packing != PH_FMT_V210;
   if (out_format != PH_IMG_RGBA_F32 && out_format != PH_IMG_RGB_F32) return fail(PH_E_INVALID, "ph_v210_yadif_pair: output format %d", out_format);
@@ -2886,13 +2880,13 @@ int ph_yadif_pair_packed(ph_ctx *ctx, int queue, int n, const ph_deint_source *s
     a.prev[i] = (const uint4 *)s.prev, a.cur[i] = (const uint4 *)s.cur, a.next[i] = (const uint4 *)s.next;
     a.out0[i] = (float4 *)s.out_parity0, a.out1[i] = (float4 *)s.out_parity1;
     if (planar) {
-      if (!s.prev_u || !s.cur_u || !s.next_u || (packing != PH_FMT_NV12 && (!s.prev_v || !s.cur_v || !s.next_v)))
+      if (!s.prev_u || !s.cur_u || !s.next_u || (fmt_planes(packing) == 3 && (!s.prev_v || !s.cur_v || !s.next_v)))
         return fail(PH_E_INVALID, "ph_v210_yadif_pair: source %d: a planar window needs its chroma planes", i);
       a.prev_u[i] = s.prev_u, a.prev_v[i] = s.prev_v, a.cur_u[i] = s.cur_u, a.cur_v[i] = s.cur_v, a.next_u[i] = s.next_u, a.next_v[i] = s.next_v;
     }
   }
   if (!height) return PH_OK;
-  a.pack = packing == PH_FMT_V210 ? 0u : packing == PH_FMT_YUV422P10 ? 1u : packing == PH_FMT_YUV422P8 ? 2u : packing == PH_FMT_YUV420P ? 3u : 4u;
+  a.pack = (uint32_t)packing;
   // quads_pitch: a v210 line in 16-byte quads, or (planar) the luma samples per line: the width rounded up to 8 (yuv422p10.ts:221)
   a.n = n, a.skip = skip ? 1 : 0, a.width = width, a.height = height, a.quads_pitch = planar ? ((width + 7u) & ~7u) : ph_v210_pitch_bytes(width) / 16;
   a.rgb12 = out_format == PH_IMG_RGB_F32 ? 1u : 0u;

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ph_formats.h"
+
 #pragma clang fp contract(off)
 
 namespace ph {
@@ -185,6 +187,49 @@ __device__ __forceinline__ void store_stream(uint4 *p, const uint4 v) {
 #endif
 }
 
+// ------------------------------------------------------------------------------------------
+// the pack formats other than v210 (ph_formats.h), as their readers load them
+// ------------------------------------------------------------------------------------------
+// The codes of pixel (x, line): .x .y .z = Y, Cb, Cr (shifted down to the sample where it is MSB-aligned), or .x = the packed RGB
+// word.  V = uint4: the codes as they are; float4: converted as they arrive.  Planes as ph_pack_plane_bytes sizes them; pitch =
+// pack_pitch(FMT, width).
+template <int FMT, typename V = uint4>
+__device__ __forceinline__ V fmt_fetch(const void *p0, const void *p1, const void *p2, uint32_t pitch, uint32_t x, uint32_t line) {
+  using T = typename V::value_type;
+  constexpr uint32_t MSB = fmt_msb(FMT);
+  V c;
+  c.x = c.y = c.z = c.w = T(0);
+  if (fmt_rgb8(FMT)) {  // rgba8.ts:49-62
+    c.x = reinterpret_cast<const uint32_t *>(p0)[(size_t)line * pitch + x];
+    return c;
+  }
+  const uint32_t cl = fmt_v420(FMT) ? line >> 1 : line;
+  if (fmt_wide(FMT) && fmt_cbcr(FMT)) {  // p010: the pair's Cb, Cr words in one dword load
+    c.x = T(reinterpret_cast<const uint16_t *>(p0)[(size_t)line * pitch + x] >> MSB);
+    const uint32_t w = reinterpret_cast<const uint32_t *>(p1)[(size_t)cl * (pitch >> 1) + (x >> 1)];
+    c.y = T((w & 0xffffu) >> MSB), c.z = T(w >> (16 + MSB));
+  } else if (fmt_wide(FMT)) {
+    c.x = T(reinterpret_cast<const uint16_t *>(p0)[(size_t)line * pitch + x] >> MSB);
+    c.y = T(reinterpret_cast<const uint16_t *>(p1)[(size_t)cl * (pitch >> 1) + (x >> 1)] >> MSB);
+    c.z = T(reinterpret_cast<const uint16_t *>(p2)[(size_t)cl * (pitch >> 1) + (x >> 1)] >> MSB);
+  } else if (fmt_cbcr(FMT)) {  // nv12.ts:61-74
+    c.x = T(reinterpret_cast<const uint8_t *>(p0)[(size_t)line * pitch + x]);
+    const uint8_t *cc = reinterpret_cast<const uint8_t *>(p1) + (size_t)cl * pitch + (x & ~1u);  // the pair's Cb, Cr bytes (two byte loads: a 2-byte vector load measured twice as slow here)
+    c.y = T(cc[0]), c.z = T(cc[1]);
+  } else {
+    c.x = T(reinterpret_cast<const uint8_t *>(p0)[(size_t)line * pitch + x]);
+    c.y = T(reinterpret_cast<const uint8_t *>(p1)[(size_t)cl * (pitch >> 1) + (x >> 1)]);
+    c.z = T(reinterpret_cast<const uint8_t *>(p2)[(size_t)cl * (pitch >> 1) + (x >> 1)]);
+  }
+  return c;
+}
+// a packed 8-bit RGB pixel's bytes: every byte through the reader's table, r g b through its gamut matrix (rgba8.ts:49-62)
+template <typename LUT>
+__device__ __forceinline__ float4 rgb8_to_rgba(float rf, float gf, float bf, float af, const ReadK &k, const LUT &lut) {
+  const float r = lut.at(rf * 65535.0f / 255.0f), g = lut.at(gf * 65535.0f / 255.0f), b = lut.at(bf * 65535.0f / 255.0f);
+  return make_float4(dot3(r, g, b, k.gm[0], k.gm[1], k.gm[2]), dot3(r, g, b, k.gm[3], k.gm[4], k.gm[5]), dot3(r, g, b, k.gm[6], k.gm[7], k.gm[8]),
+                     lut.at(af * 65535.0f / 255.0f));
+}
 // ------------------------------------------------------------------------------------------
 // bilinear sampler (OpenCL 1.2 s8.2: NORMALIZED | CLAMP (border 0) | LINEAR).  The f32
 // evaluation order is fixed: weights first, then ((w00*t00 + w10*t10) + w01*t01) + w11*t11,

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "ph_formats.h"
 #include "ph_lut.h"
 
 namespace ph {
@@ -226,8 +227,8 @@ struct DeintArgs {  // ph_kernels_deint.hip
   uint32_t rgb12;  // 1: the outputs are packed f32 RGB (12 bytes per pixel, the reader's alpha == 1 left out)
   const float *cm, *gm;
   LutView lut;
-  // windows of planar 4:2:2 frames (pack 1: yuv422p10le, 2: yuv422p8; 0: v210): prev / cur / next are the Y planes, these the
-  // chroma planes; read by the planar instantiations only
+  // the windows' PH_FMT_* (one the fused reader takes: fmt_deint); planar frames: prev / cur / next are the Y planes, these the
+  // chroma planes (read by the planar instantiations only)
   uint32_t pack;
   const void *prev_u[kMaxLayers], *prev_v[kMaxLayers], *cur_u[kMaxLayers], *cur_v[kMaxLayers], *next_u[kMaxLayers], *next_v[kMaxLayers];
 };
@@ -238,8 +239,6 @@ struct CombineArgs {
   size_t npx;
   uint32_t nt;  // filled in by the launcher
 };
-
-uint32_t v210_pitch_bytes(uint32_t width);
 
 hipError_t launch_v210_read(hipStream_t s, const void *in, void *out, uint32_t width, uint32_t height,
                             const void *cm, const void *lut, const void *gm);
@@ -256,8 +255,6 @@ hipError_t launch_v210_read_lds_batch(hipStream_t s, int n, const void *const *i
 hipError_t launch_v210_write_lds(hipStream_t s, const void *in, void *out, uint32_t width, uint32_t height,
                                  uint32_t interlace, const void *cm, const LutView &lut, uint32_t num_cus);
 // the other pack formats (ph_kernels_fmt.hip); lv == NULL selects the global-gather form
-uint32_t pack_pitch(int fmt, uint32_t width);
-int pack_plane_bytes(int fmt, uint32_t width, uint32_t height, size_t bytes[3]);
 hipError_t launch_pack_read(hipStream_t s, int fmt, const void *const planes[3], void *out, uint32_t width,
                             uint32_t height, const void *cm, const void *table, const void *gm, const LutView *lv,
                             uint32_t num_cus);

@@ -460,8 +460,6 @@ static inline uint32_t stream_grid(size_t n) {  // memory-bound element-wise: <=
   return (uint32_t)(want < 2048 ? (want ? want : 1) : 2048);
 }
 
-uint32_t v210_pitch_bytes(uint32_t width) { return (width + 47 - ((width - 1) % 48)) * 8 / 3; }
-
 hipError_t launch_v210_read(hipStream_t s, const void *in, void *out, uint32_t width, uint32_t height,
                             const void *cm, const void *lut, const void *gm) {
   const uint32_t qpl = v210_pitch_bytes(width) / 16;

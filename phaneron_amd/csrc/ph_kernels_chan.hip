@@ -847,7 +847,7 @@ template <int OUT>
 __device__ __forceinline__ void chan_phase2_other(const ChanArgs &a, const ChanShare &sh, const WriteK &wk, const LutK &wlut) {
   const uint2 *const index = reinterpret_cast<const uint2 *>(a.index);
   auto idx = [](uint32_t bits) __attribute__((always_inline)) { return __uint_as_float((bits & 0xFFFFu) | 0x4B400000u); };  // M + idx (ph_ldslut.h)
-  if (OUT == 5 || OUT == 6) {  // rgba8.ts:69-101: one pixel per lane, alpha 255
+  if (fmt_rgb8(OUT)) {  // rgba8.ts:69-101: one pixel per lane, alpha 255
     for (uint32_t t = threadIdx.x; t < 2u * kChanChunk * sh.slots; t += kLdsBlock) {
       const uint32_t slot = t / (2u * kChanChunk), within = t - slot * (2u * kChanChunk);
       const uint32_t chunk = chan_chunk(a, sh, slot);
@@ -861,7 +861,7 @@ __device__ __forceinline__ void chan_phase2_other(const ChanArgs &a, const ChanS
       const float r = lds_lut_finish(pend.r), g = lds_lut_finish(pend.g), b = lds_lut_finish(pend.b);
       const uint32_t r8 = sat_u8_rte(r * 255.0f), g8 = sat_u8_rte(g * 255.0f), b8 = sat_u8_rte(b * 255.0f);
       const uint32_t line = a.first_line + li * a.line_step;
-      reinterpret_cast<uint32_t *>(a.out)[(size_t)line * a.out_pitch + x] = OUT == 5 ? (r8 | g8 << 8 | b8 << 16 | 0xff000000u) : (b8 | g8 << 8 | r8 << 16 | 0xff000000u);
+      reinterpret_cast<uint32_t *>(a.out)[(size_t)line * a.out_pitch + x] = OUT == PH_FMT_RGBA8 ? (r8 | g8 << 8 | b8 << 16 | 0xff000000u) : (b8 | g8 << 8 | r8 << 16 | 0xff000000u);
     }
     return;
   }
@@ -870,7 +870,7 @@ __device__ __forceinline__ void chan_phase2_other(const ChanArgs &a, const ChanS
   // 4:2:0 (yuv420p.ts:150-216, nv12.ts:139-196): the same luma; a chroma line serves a line PAIR and is taken from the pair's upper
   // line only (`if (l == 0)`) - a field write makes one line per pair, which then is the one that gives the chroma; nv12 keeps Cb and
   // Cr interleaved in one plane (out_u).
-  constexpr bool WIDE = OUT == 1, V420 = OUT == 3 || OUT == 4, NV12 = OUT == 4;
+  constexpr bool WIDE = fmt_wide(OUT), V420 = fmt_v420(OUT), NV12 = fmt_cbcr(OUT);
   constexpr uint32_t kGroups = kChanChunk / 8u;  // per chunk row
   for (uint32_t t = threadIdx.x; t < 2u * kGroups * sh.slots; t += kLdsBlock) {
     const uint32_t slot = t / (2u * kGroups), within = t - slot * (2u * kGroups);
@@ -944,8 +944,8 @@ __device__ __forceinline__ void chan_phase2_other(const ChanArgs &a, const ChanS
 // clips, packed-RGB graphics and f32 images, the graphics' taps shared too (a logo or a lower third over a live source).  An
 // instantiation carries the scalar state of every path it contains, whether a launch takes it or not - the channel kernel's op loop
 // spills scalars to VGPR lanes (6 in mode 0, 76 in mode 2) - so 1280-wide v210 channels get one of their own.
-// OUT: the packed frame's format (PH_FMT_*: 0 v210; 2 yuv422p8 and 5 rgba8 - the other consumers' - with the lean modes too; the rest only with MODE 2)
-template <int MODE, int OUT = 0>
+// OUT: the packed frame's format (PH_FMT_*: v210; yuv422p8 and rgba8 - the other consumers' - with the lean modes too; the rest only with MODE 2)
+template <int MODE, int OUT = PH_FMT_V210>
 __global__ __launch_bounds__(kLdsBlock) void chan_compose_v210_kernel(ChanArgs a) {
   constexpr int SRC = MODE == 2 ? 1 : MODE == 5 ? 3 : MODE >= 3 ? 2 : 0;
   constexpr bool TAILS = MODE >= 1, PSHARE = MODE == 4;
@@ -973,7 +973,7 @@ __global__ __launch_bounds__(kLdsBlock) void chan_compose_v210_kernel(ChanArgs a
   // VGPR lanes as it is - does not have to keep alive)
   const WriteK wk = load_write_k(a.wr_cm);
   const LutK wlut = make_lut_k(a.wr);
-  if (OUT != 0) {
+  if (OUT != PH_FMT_V210) {
     chan_phase2_other<OUT>(a, sh, wk, wlut);
     return;
   }
@@ -1377,7 +1377,7 @@ hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t n
   // Planar YCbCr clips share their taps in an instantiation of its own (mode 4): taken when the program has nothing but such clips and
   // f32 images, makes a v210 frame, and at least half of its ops are clips at their own scale (a full-frame clip; not config 2's one
   // background under three insets and a wipe: there the plain loop's better register allocation is worth more, 61.5 against 68.7 us)
-  const bool lean_out = a.out_fmt == 0 || a.out_fmt == 2 || a.out_fmt == 5;  // v210 (SDI), yuv422p8 (an encoder), rgba8 (the screen): the reference's three consumers
+  const bool lean_out = a.out_fmt == PH_FMT_V210 || a.out_fmt == PH_FMT_YUV422P8 || a.out_fmt == PH_FMT_RGBA8;  // SDI, an encoder, the screen: the reference's three consumers
   bool clips_only = a.planar == 2 && lean_out;
   uint32_t own_scale = 0;
   for (int k = 0; k < b.n_ops; ++k) {
@@ -1445,17 +1445,17 @@ hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t n
     constexpr int O = decltype(out_tag)::value;
     if (a.planar == 2)
       return planar_share ? PH_CHAN_GO(4, O) : clips_only ? PH_CHAN_GO(3, O) : graphics ? PH_CHAN_GO(5, O) : PH_CHAN_GO(2, O);
-    if (a.planar == 1) return O == 0 ? PH_CHAN_GO(1, 0) : PH_CHAN_GO(2, O);
+    if (a.planar == 1) return O == PH_FMT_V210 ? PH_CHAN_GO(1, PH_FMT_V210) : PH_CHAN_GO(2, O);
     return PH_CHAN_GO(0, O);
   };
-  switch (a.out_fmt) {
-    case 0: return lean(std::integral_constant<int, 0>{});
-    case 1: return PH_CHAN_GO(2, 1);
-    case 2: return lean(std::integral_constant<int, 2>{});
-    case 3: return PH_CHAN_GO(2, 3);
-    case 4: return PH_CHAN_GO(2, 4);
-    case 5: return lean(std::integral_constant<int, 5>{});
-    case 6: return PH_CHAN_GO(2, 6);
+  switch (a.out_fmt) {  // (the formats of fmt_chan_out)
+    case PH_FMT_V210: return lean(std::integral_constant<int, PH_FMT_V210>{});
+    case PH_FMT_YUV422P10: return PH_CHAN_GO(2, PH_FMT_YUV422P10);
+    case PH_FMT_YUV422P8: return lean(std::integral_constant<int, PH_FMT_YUV422P8>{});
+    case PH_FMT_YUV420P: return PH_CHAN_GO(2, PH_FMT_YUV420P);
+    case PH_FMT_NV12: return PH_CHAN_GO(2, PH_FMT_NV12);
+    case PH_FMT_RGBA8: return lean(std::integral_constant<int, PH_FMT_RGBA8>{});
+    case PH_FMT_BGRA8: return PH_CHAN_GO(2, PH_FMT_BGRA8);
   }
 #undef PH_CHAN_GO
   return hipErrorInvalidValue;

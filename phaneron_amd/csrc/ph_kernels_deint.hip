@@ -79,13 +79,13 @@ __device__ __forceinline__ RawPx load_row_px(__amdgpu_buffer_rsrc_t frame, uint3
                (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(frame, (int)p.off_cb, row, 0),
                (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(frame, (int)p.off_cr, row, 0)};
 }
-// PACK: 1 yuv422p10 (16-bit samples), 2 yuv422p8, 3 yuv420p (a chroma line serves two luma lines: yuv420p.ts), 4 nv12 (the same with Cb and Cr
-// interleaved in one plane: nv12.ts:61-74; FramePlanes::v is u, the lane's offsets the pair's two bytes)
+// PACK: the PH_FMT_* of a planar window (fmt_deint) - 4:2:0: a chroma line serves two luma lines (yuv420p.ts); interleaved Cb and Cr
+// (nv12.ts:61-74): FramePlanes::v is u, the lane's offsets the pair's two bytes
 template <int PACK>
 __device__ __forceinline__ RawPx load_row_planar(const FramePlanes &f, uint32_t pitch_y, int line, const LanePick &p) {
   const int row_y = (int)((uint32_t)line * pitch_y);  // uniform
-  const int row_c = PACK >= 3 ? (int)(((uint32_t)line >> 1) * (PACK == 4 ? pitch_y : pitch_y >> 1)) : (int)((uint32_t)line * (pitch_y >> 1));
-  if (PACK == 1)
+  const int row_c = fmt_v420(PACK) ? (int)(((uint32_t)line >> 1) * (fmt_cbcr(PACK) ? pitch_y : pitch_y >> 1)) : (int)((uint32_t)line * (pitch_y >> 1));
+  if (fmt_wide(PACK))
     return RawPx{(uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(f.y, (int)p.off_y, row_y, 0),
                  (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(f.u, (int)p.off_cb, row_c, 0),
                  (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(f.v, (int)p.off_cr, row_c, 0)};
@@ -93,12 +93,13 @@ __device__ __forceinline__ RawPx load_row_planar(const FramePlanes &f, uint32_t 
                (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(f.u, (int)p.off_cb, row_c, 0),
                (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(f.v, (int)p.off_cr, row_c, 0)};
 }
-template <bool STD, int PACK = 0>
+template <bool STD, int PACK = PH_FMT_V210>
 __device__ __forceinline__ Rgb unpack_px(const RawPx &r, const LanePick &p, const ReadK &k, const LutK &lk) {
   // (a planar sample is converted whole, as the reference does: yuv422p10.ts:66-68)
-  const float yf = PACK ? (float)r.wy : (float)((r.wy >> p.sy) & 0x3ff);
-  const float cbf = PACK ? (float)r.wcb : (float)((r.wcb >> p.scb) & 0x3ff);
-  const float crf = PACK ? (float)r.wcr : (float)((r.wcr >> p.scr) & 0x3ff);
+  constexpr bool V210 = PACK == PH_FMT_V210;
+  const float yf = !V210 ? (float)r.wy : (float)((r.wy >> p.sy) & 0x3ff);
+  const float cbf = !V210 ? (float)r.wcb : (float)((r.wcb >> p.scb) & 0x3ff);
+  const float crf = !V210 ? (float)r.wcr : (float)((r.wcr >> p.scr) & 0x3ff);
   const float4 v = read_px_lds<STD>(yf, cbf, crf, k, lk);
   return Rgb{v.x, v.y, v.z};
 }
@@ -114,7 +115,7 @@ __device__ __forceinline__ float lane_tap(float v, uint32_t lane, int d) {
 #define PH_DEINT_PRICE_INDEX 0
 #endif
 
-template <int TFF, bool STD, int PACK = 0>
+template <int TFF, bool STD, int PACK = PH_FMT_V210>
 __device__ __forceinline__ void v210_yadif_pair_body(const DeintArgs &a, const ReadK &k, const LutK &lk) {
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int w = (int)a.width, h = (int)a.height;
@@ -122,15 +123,16 @@ __device__ __forceinline__ void v210_yadif_pair_body(const DeintArgs &a, const R
   for (uint32_t t = blockIdx.x * (kDeintBlock / 64) + wave; t < tasks; t += gridDim.x * (kDeintBlock / 64)) {
     const uint32_t cb = t % a.col_blocks, rest = t / a.col_blocks, strip = rest % a.strips, l = rest / a.strips;
     // bytes per line: a v210 line of quads_pitch quads, or (planar) quads_pitch luma samples of 1 or 2 bytes
-    const uint32_t line_bytes = PACK == 0 ? a.quads_pitch * 16u : a.quads_pitch * (PACK == 1 ? 2u : 1u);
+    constexpr bool V210 = PACK == PH_FMT_V210;
+    const uint32_t line_bytes = V210 ? a.quads_pitch * 16u : a.quads_pitch * (fmt_wide(PACK) ? 2u : 1u);
     const int frame_bytes = (int)(line_bytes * a.height);
     auto planes = [&](const uint4 *y, const void *u, const void *v) __attribute__((always_inline)) {
       FramePlanes f;
       f.y = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(y), 0, frame_bytes, 0x00020000);
-      if (PACK == 4) {  // nv12: (height + 1) / 2 lines of CbCr pairs, a luma line's bytes each
+      if (fmt_cbcr(PACK)) {  // nv12: (height + 1) / 2 lines of CbCr pairs, a luma line's bytes each
         f.u = f.v = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(u), 0, (int)(line_bytes * ((a.height + 1u) >> 1)), 0x00020000);
-      } else if (PACK) {  // 4:2:2: half a luma line per line; 4:2:0: that for every other line
-        const int chroma_bytes = PACK == 3 ? (int)((line_bytes >> 1) * ((a.height + 1u) >> 1)) : frame_bytes / 2;
+      } else if (!V210) {  // 4:2:2: half a luma line per line; 4:2:0: that for every other line
+        const int chroma_bytes = fmt_v420(PACK) ? (int)((line_bytes >> 1) * ((a.height + 1u) >> 1)) : frame_bytes / 2;
         f.u = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(u), 0, chroma_bytes, 0x00020000);
         f.v = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(v), 0, chroma_bytes, 0x00020000);
       } else {
@@ -138,17 +140,17 @@ __device__ __forceinline__ void v210_yadif_pair_body(const DeintArgs &a, const R
       }
       return f;
     };
-    const FramePlanes prev = planes(a.prev[l], PACK ? a.prev_u[l] : nullptr, PACK ? a.prev_v[l] : nullptr);
-    const FramePlanes cur = planes(a.cur[l], PACK ? a.cur_u[l] : nullptr, PACK ? a.cur_v[l] : nullptr);
-    const FramePlanes next = planes(a.next[l], PACK ? a.next_u[l] : nullptr, PACK ? a.next_v[l] : nullptr);
+    const FramePlanes prev = planes(a.prev[l], !V210 ? a.prev_u[l] : nullptr, !V210 ? a.prev_v[l] : nullptr);
+    const FramePlanes cur = planes(a.cur[l], !V210 ? a.cur_u[l] : nullptr, !V210 ? a.cur_v[l] : nullptr);
+    const FramePlanes next = planes(a.next[l], !V210 ? a.next_u[l] : nullptr, !V210 ? a.next_v[l] : nullptr);
     float4 *__restrict__ out0 = a.out0[l], *__restrict__ out1 = a.out1[l];
     const int xr = (int)(cb * kDeintCols) - 3 + (int)lane, x = clampi(xr, 0, w - 1);  // CLAMP_TO_EDGE
     const bool emit = lane >= 3 && lane < 64 - 3 && xr < w;
-    LanePick pick = PACK == 0 ? lane_pick((uint32_t)x) : PACK == 1 ? lane_pick_planar<2>((uint32_t)x) : lane_pick_planar<1>((uint32_t)x);
-    if (PACK == 4) pick.off_cb = (uint32_t)x & ~1u, pick.off_cr = pick.off_cb + 1u;
+    LanePick pick = V210 ? lane_pick((uint32_t)x) : fmt_wide(PACK) ? lane_pick_planar<2>((uint32_t)x) : lane_pick_planar<1>((uint32_t)x);
+    if (fmt_cbcr(PACK)) pick.off_cb = (uint32_t)x & ~1u, pick.off_cr = pick.off_cb + 1u;
     const int y0 = (int)(strip * a.rows_per_strip), y_end = (y0 + (int)a.rows_per_strip < h) ? y0 + (int)a.rows_per_strip : h;
     auto raw = [&](const FramePlanes &frame, int y) {
-      return PACK == 0 ? load_row_px(frame.y, line_bytes, clampi(y, 0, h - 1), pick) : load_row_planar<PACK>(frame, line_bytes, clampi(y, 0, h - 1), pick);
+      return V210 ? load_row_px(frame.y, line_bytes, clampi(y, 0, h - 1), pick) : load_row_planar<PACK>(frame, line_bytes, clampi(y, 0, h - 1), pick);
     };
     auto row = [&](const FramePlanes &frame, int y) { return unpack_px<STD, PACK>(raw(frame, y), pick, k, lk); };
     // rows y - 2 .. y + 2 of each frame live in a RING of five registers: the step with rotation R finds row y - 2 + i
@@ -221,7 +223,7 @@ __device__ __forceinline__ void v210_yadif_pair_body(const DeintArgs &a, const R
   }
 }
 
-template <int TFF, int PACK = 0>
+template <int TFF, int PACK = PH_FMT_V210>
 __global__ __launch_bounds__(kDeintBlock) void v210_yadif_pair_kernel(DeintArgs a) {
   const ReadK k = load_read_k(a.cm, a.gm);
   const LutK lk = make_lut_k(a.lut);
@@ -257,12 +259,12 @@ hipError_t launch_v210_yadif_pair(hipStream_t s, DeintArgs a, int tff, uint32_t 
     kernel<<<grid, kDeintBlock, a.lut.bytes, s>>>(a);
     return hipGetLastError();
   };
-  switch (a.pack) {
-    case 0: return tff ? go(v210_yadif_pair_kernel<1, 0>) : go(v210_yadif_pair_kernel<0, 0>);
-    case 1: return tff ? go(v210_yadif_pair_kernel<1, 1>) : go(v210_yadif_pair_kernel<0, 1>);
-    case 2: return tff ? go(v210_yadif_pair_kernel<1, 2>) : go(v210_yadif_pair_kernel<0, 2>);
-    case 3: return tff ? go(v210_yadif_pair_kernel<1, 3>) : go(v210_yadif_pair_kernel<0, 3>);
-    case 4: return tff ? go(v210_yadif_pair_kernel<1, 4>) : go(v210_yadif_pair_kernel<0, 4>);
+  switch (a.pack) {  // (the formats of fmt_deint)
+    case PH_FMT_V210: return tff ? go(v210_yadif_pair_kernel<1, PH_FMT_V210>) : go(v210_yadif_pair_kernel<0, PH_FMT_V210>);
+    case PH_FMT_YUV422P10: return tff ? go(v210_yadif_pair_kernel<1, PH_FMT_YUV422P10>) : go(v210_yadif_pair_kernel<0, PH_FMT_YUV422P10>);
+    case PH_FMT_YUV422P8: return tff ? go(v210_yadif_pair_kernel<1, PH_FMT_YUV422P8>) : go(v210_yadif_pair_kernel<0, PH_FMT_YUV422P8>);
+    case PH_FMT_YUV420P: return tff ? go(v210_yadif_pair_kernel<1, PH_FMT_YUV420P>) : go(v210_yadif_pair_kernel<0, PH_FMT_YUV420P>);
+    case PH_FMT_NV12: return tff ? go(v210_yadif_pair_kernel<1, PH_FMT_NV12>) : go(v210_yadif_pair_kernel<0, PH_FMT_NV12>);
   }
   return hipErrorInvalidValue;
 }

@@ -9,6 +9,7 @@
 // 4:2:0 writers handle the line pair of their group.  Every kernel exists in two forms chosen at
 // launch: gamma LUT in LDS (persistent 1024-lane workgroups) or plain table in global memory.
 #include <cstdlib>
+#include <type_traits>
 
 #include "ph_kernels.h"
 #include "ph_ldslut.h"
@@ -18,11 +19,6 @@
 namespace ph {
 
 constexpr int kFmtBlock = 256;
-
-// formats (same numbering as PH_FMT_* in include/phaneron_hip.h)
-enum { F_V210 = 0, F_YUV422P10 = 1, F_YUV422P8 = 2, F_YUV420P = 3, F_NV12 = 4, F_RGBA8 = 5, F_BGRA8 = 6, F_YUV420P10 = 7, F_P010 = 8 };
-constexpr bool fmt_rgb8(int f) { return f == F_RGBA8 || f == F_BGRA8; }
-constexpr bool fmt_v420(int f) { return f == F_YUV420P || f == F_NV12 || f == F_YUV420P10 || f == F_P010; }
 
 template <typename LUT>
 __device__ __forceinline__ float4 yuv_to_rgba(float y, float u, float v, const ReadK &k, const LUT &lut) {
@@ -56,33 +52,13 @@ __device__ __forceinline__ void fmt_read_body(const FmtReadArgs &a, const LUT &l
   for (uint32_t p = block * blockDim.x + threadIdx.x; p < total; p += stride) {
     const uint32_t line = p / a.width, x = p - line * a.width;
     float4 o;
-    if (FMT == F_RGBA8 || FMT == F_BGRA8) {  // rgba8.ts:49-62
-      const uchar4 px = reinterpret_cast<const uchar4 *>(a.p0)[(size_t)line * a.pitch + x];
-      const float rf = (float)(FMT == F_RGBA8 ? px.x : px.z), gf = (float)px.y, bf = (float)(FMT == F_RGBA8 ? px.z : px.x);
-      const float r = lut.at(rf * 65535.0f / 255.0f), g = lut.at(gf * 65535.0f / 255.0f), b = lut.at(bf * 65535.0f / 255.0f);
-      o = make_float4(dot3(r, g, b, k.gm[0], k.gm[1], k.gm[2]), dot3(r, g, b, k.gm[3], k.gm[4], k.gm[5]),
-                      dot3(r, g, b, k.gm[6], k.gm[7], k.gm[8]), lut.at((float)px.w * 65535.0f / 255.0f));
+    if (fmt_rgb8(FMT)) {
+      const uchar4 px = __builtin_bit_cast(uchar4, fmt_fetch<FMT>(a.p0, a.p1, a.p2, a.pitch, x, line).x);
+      constexpr bool RGBA = FMT == PH_FMT_RGBA8;
+      o = rgb8_to_rgba((float)(RGBA ? px.x : px.z), (float)px.y, (float)(RGBA ? px.z : px.x), (float)px.w, k, lut);
     } else {
-      const uint32_t cl = fmt_v420(FMT) ? line >> 1 : line;
-      float y, u, v;
-      if (FMT == F_YUV422P10 || FMT == F_YUV420P10) {
-        y = (float)reinterpret_cast<const uint16_t *>(a.p0)[(size_t)line * a.pitch + x];
-        u = (float)reinterpret_cast<const uint16_t *>(a.p1)[(size_t)cl * (a.pitch >> 1) + (x >> 1)];
-        v = (float)reinterpret_cast<const uint16_t *>(a.p2)[(size_t)cl * (a.pitch >> 1) + (x >> 1)];
-      } else if (FMT == F_P010) {  // MSB-aligned: the low 6 bits dropped; the pair's Cb, Cr words in one dword load
-        y = (float)(reinterpret_cast<const uint16_t *>(a.p0)[(size_t)line * a.pitch + x] >> 6);
-        const uint32_t c = reinterpret_cast<const uint32_t *>(a.p1)[(size_t)cl * (a.pitch >> 1) + (x >> 1)];
-        u = (float)((c & 0xffffu) >> 6), v = (float)(c >> 22);
-      } else if (FMT == F_NV12) {  // nv12.ts:61-74
-        y = (float)reinterpret_cast<const uint8_t *>(a.p0)[(size_t)line * a.pitch + x];
-        const uint8_t *c = reinterpret_cast<const uint8_t *>(a.p1) + (size_t)cl * a.pitch + (x & ~1u);  // the pair's Cb, Cr bytes (two byte loads: a 2-byte vector load measured twice as slow here)
-        u = (float)c[0], v = (float)c[1];
-      } else {
-        y = (float)reinterpret_cast<const uint8_t *>(a.p0)[(size_t)line * a.pitch + x];
-        u = (float)reinterpret_cast<const uint8_t *>(a.p1)[(size_t)cl * (a.pitch >> 1) + (x >> 1)];
-        v = (float)reinterpret_cast<const uint8_t *>(a.p2)[(size_t)cl * (a.pitch >> 1) + (x >> 1)];
-      }
-      o = yuv_to_rgba(y, u, v, k, lut);
+      const float4 c = fmt_fetch<FMT, float4>(a.p0, a.p1, a.p2, a.pitch, x, line);
+      o = yuv_to_rgba(c.x, c.y, c.z, k, lut);
     }
     store_image(a.out + p, o, a.nt);
   }
@@ -143,7 +119,7 @@ __device__ __forceinline__ void px_codes(const float4 px, const WriteK &k, const
 
 template <int FMT, typename LUT, bool PERSISTENT>
 __device__ __forceinline__ void fmt_write_body(const FmtWriteArgs &a, const LUT &lut) {
-  if (FMT == F_RGBA8 || FMT == F_BGRA8) {  // rgba8.ts:69-101: one pixel per lane
+  if (fmt_rgb8(FMT)) {  // rgba8.ts:69-101: one pixel per lane
     const uint32_t total = a.width * a.groups;
     const uint32_t stride = PERSISTENT ? gridDim.x * blockDim.x : total;
     for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < total; p += stride) {
@@ -154,14 +130,13 @@ __device__ __forceinline__ void fmt_write_body(const FmtWriteArgs &a, const LUT 
       const uint32_t r8 = sat_u8_rte(r * 255.0f);
       const uint32_t g8 = sat_u8_rte(gg * 255.0f);
       const uint32_t b8 = sat_u8_rte(b * 255.0f);
-      const uint32_t w = FMT == F_RGBA8 ? (r8 | g8 << 8 | b8 << 16 | 0xff000000u) : (b8 | g8 << 8 | r8 << 16 | 0xff000000u);
+      const uint32_t w = FMT == PH_FMT_RGBA8 ? (r8 | g8 << 8 | b8 << 16 | 0xff000000u) : (b8 | g8 << 8 | r8 << 16 | 0xff000000u);
       reinterpret_cast<uint32_t *>(a.p0)[(size_t)line * a.pitch + x] = w;
     }
     return;
   }
-  constexpr bool V420 = fmt_v420(FMT);
-  constexpr bool WIDE = (FMT == F_YUV422P10 || FMT == F_YUV420P10 || FMT == F_P010);
-  constexpr uint32_t MSB = FMT == F_P010 ? 6u : 0u;  // p010: the code in the word's upper bits
+  constexpr bool V420 = fmt_v420(FMT), WIDE = fmt_wide(FMT);
+  constexpr uint32_t MSB = fmt_msb(FMT);  // p010: the code in the word's upper bits
   const WriteK k = load_write_k(a.cm);
   const uint32_t full = a.width / 8, remain = a.width % 8, octets = full + (remain ? 1 : 0);
   const uint32_t total = octets * a.groups;
@@ -218,12 +193,12 @@ __device__ __forceinline__ void fmt_write_body(const FmtWriteArgs &a, const LUT 
         reinterpret_cast<uint2 *>(a.p0)[((size_t)line * a.pitch >> 3) + o8] = w;
       }
       if (l == 0) {
-        if (FMT == F_NV12) {
+        if (fmt_cbcr(FMT) && !WIDE) {  // nv12
           uint2 w;
           w.x = (u[0] & 0xff) | (v[0] & 0xff) << 8 | (u[1] & 0xff) << 16 | v[1] << 24;
           w.y = (u[2] & 0xff) | (v[2] & 0xff) << 8 | (u[3] & 0xff) << 16 | v[3] << 24;
           reinterpret_cast<uint2 *>(a.p1)[((size_t)crow * a.pitch >> 3) + o8] = w;
-        } else if (FMT == F_P010) {  // Cb, Cr words interleaved: 16 bytes per group, the luma line's pitch
+        } else if (fmt_cbcr(FMT)) {  // p010: Cb, Cr words interleaved - 16 bytes per group, the luma line's pitch
           uint4 w;
           w.x = ((u[0] << MSB) & 0xffff) | v[0] << (16 + MSB), w.y = ((u[1] << MSB) & 0xffff) | v[1] << (16 + MSB);
           w.z = ((u[2] << MSB) & 0xffff) | v[2] << (16 + MSB), w.w = ((u[3] << MSB) & 0xffff) | v[3] << (16 + MSB);
@@ -259,29 +234,22 @@ __global__ __launch_bounds__(kFmtBlock) void fmt_write_gather_kernel(FmtWriteArg
 }
 
 // ------------------------------------------------------------------------------------------
-// geometry + launchers
+// launchers
 // ------------------------------------------------------------------------------------------
-uint32_t pack_pitch(int fmt, uint32_t width) {
-  if (fmt_rgb8(fmt)) return width;                                    // rgba8.ts:103-105
-  if (fmt == F_V210) return width + 47 - ((width - 1) % 48);
-  return width + 7 - ((width - 1) % 8);                              // yuv422p10.ts:221
-}
-
-int pack_plane_bytes(int fmt, uint32_t width, uint32_t height, size_t bytes[3]) {
-  const size_t p = pack_pitch(fmt, width);
-  bytes[0] = bytes[1] = bytes[2] = 0;
+// f(std::integral_constant<int, FMT>{}) for the pack format fmt (v210 has kernels of its own: ph_kernels_lds.hip)
+template <typename F>
+static hipError_t for_fmt(int fmt, F &&f) {
   switch (fmt) {
-    case F_V210: bytes[0] = (size_t)v210_pitch_bytes(width) * height; return 1;
-    case F_YUV422P10: bytes[0] = p * 2 * height, bytes[1] = bytes[2] = bytes[0] / 2; return 3;
-    case F_YUV422P8: bytes[0] = p * height, bytes[1] = bytes[2] = bytes[0] / 2; return 3;
-    case F_YUV420P: bytes[0] = p * height, bytes[1] = bytes[2] = bytes[0] / 4; return 3;
-    case F_NV12: bytes[0] = p * height, bytes[1] = bytes[0] / 2; return 2;
-    case F_YUV420P10: bytes[0] = p * 2 * height, bytes[1] = bytes[2] = bytes[0] / 4; return 3;
-    case F_P010: bytes[0] = p * 2 * height, bytes[1] = bytes[0] / 2; return 2;
-    case F_RGBA8:
-    case F_BGRA8: bytes[0] = p * 4 * height; return 1;
+    case PH_FMT_YUV422P10: return f(std::integral_constant<int, PH_FMT_YUV422P10>{});
+    case PH_FMT_YUV422P8: return f(std::integral_constant<int, PH_FMT_YUV422P8>{});
+    case PH_FMT_YUV420P: return f(std::integral_constant<int, PH_FMT_YUV420P>{});
+    case PH_FMT_NV12: return f(std::integral_constant<int, PH_FMT_NV12>{});
+    case PH_FMT_RGBA8: return f(std::integral_constant<int, PH_FMT_RGBA8>{});
+    case PH_FMT_BGRA8: return f(std::integral_constant<int, PH_FMT_BGRA8>{});
+    case PH_FMT_YUV420P10: return f(std::integral_constant<int, PH_FMT_YUV420P10>{});
+    case PH_FMT_P010: return f(std::integral_constant<int, PH_FMT_P010>{});
   }
-  return -1;
+  return hipErrorInvalidValue;
 }
 
 template <int FMT>
@@ -307,17 +275,7 @@ hipError_t launch_pack_read(hipStream_t s, int fmt, const void *const planes[3],
   const bool v420 = fmt_v420(fmt);
   FmtReadArgs a{planes[0], planes[1], planes[2], (float4 *)out, width, v420 ? (height / 2) * 2 : height,
                 pack_pitch(fmt, width), (const float *)cm, (const float *)gm, image_nt((size_t)width * height * 16)};
-  switch (fmt) {
-    case F_YUV422P10: return launch_read_fmt<F_YUV422P10>(s, a, (const float *)table, lv, num_cus);
-    case F_YUV422P8: return launch_read_fmt<F_YUV422P8>(s, a, (const float *)table, lv, num_cus);
-    case F_YUV420P: return launch_read_fmt<F_YUV420P>(s, a, (const float *)table, lv, num_cus);
-    case F_NV12: return launch_read_fmt<F_NV12>(s, a, (const float *)table, lv, num_cus);
-    case F_RGBA8: return launch_read_fmt<F_RGBA8>(s, a, (const float *)table, lv, num_cus);
-    case F_BGRA8: return launch_read_fmt<F_BGRA8>(s, a, (const float *)table, lv, num_cus);
-    case F_YUV420P10: return launch_read_fmt<F_YUV420P10>(s, a, (const float *)table, lv, num_cus);
-    case F_P010: return launch_read_fmt<F_P010>(s, a, (const float *)table, lv, num_cus);
-    default: return hipErrorInvalidValue;
-  }
+  return for_fmt(fmt, [&](auto f) { return launch_read_fmt<decltype(f)::value>(s, a, (const float *)table, lv, num_cus); });
 }
 
 template <int FMT>
@@ -338,17 +296,7 @@ hipError_t launch_pack_read_batch(hipStream_t s, int fmt, int n, const void *con
   for (int i = 0; i < n; ++i) b.p0[i] = planes[i][0], b.p1[i] = planes[i][1], b.p2[i] = planes[i][2], b.out[i] = (float4 *)outs[i];
   b.jobs = (uint32_t)n, b.width = width, b.lines = v420 ? (height / 2) * 2 : height, b.pitch = pack_pitch(fmt, width);
   b.cm = (const float *)cm, b.gm = (const float *)gm, b.nt = image_nt((size_t)width * height * 16);
-  switch (fmt) {
-    case F_YUV422P10: return launch_read_batch_fmt<F_YUV422P10>(s, b, lv, num_cus);
-    case F_YUV422P8: return launch_read_batch_fmt<F_YUV422P8>(s, b, lv, num_cus);
-    case F_YUV420P: return launch_read_batch_fmt<F_YUV420P>(s, b, lv, num_cus);
-    case F_NV12: return launch_read_batch_fmt<F_NV12>(s, b, lv, num_cus);
-    case F_RGBA8: return launch_read_batch_fmt<F_RGBA8>(s, b, lv, num_cus);
-    case F_BGRA8: return launch_read_batch_fmt<F_BGRA8>(s, b, lv, num_cus);
-    case F_YUV420P10: return launch_read_batch_fmt<F_YUV420P10>(s, b, lv, num_cus);
-    case F_P010: return launch_read_batch_fmt<F_P010>(s, b, lv, num_cus);
-    default: return hipErrorInvalidValue;
-  }
+  return for_fmt(fmt, [&](auto f) { return launch_read_batch_fmt<decltype(f)::value>(s, b, lv, num_cus); });
 }
 
 template <int FMT>
@@ -376,17 +324,7 @@ hipError_t launch_pack_write(hipStream_t s, int fmt, const void *in, void *const
   const uint32_t groups = v420 ? height / 2 : (interlace ? height / 2 : height);  // e.g. yuv422p10.ts:328, yuv420p.ts:381
   FmtWriteArgs a{(const float4 *)in, planes[0], planes[1], planes[2], width, pack_pitch(fmt, width), groups, interlace,
                  (const float *)cm};
-  switch (fmt) {
-    case F_YUV422P10: return launch_write_fmt<F_YUV422P10>(s, a, (const float *)table, lv, num_cus);
-    case F_YUV422P8: return launch_write_fmt<F_YUV422P8>(s, a, (const float *)table, lv, num_cus);
-    case F_YUV420P: return launch_write_fmt<F_YUV420P>(s, a, (const float *)table, lv, num_cus);
-    case F_NV12: return launch_write_fmt<F_NV12>(s, a, (const float *)table, lv, num_cus);
-    case F_RGBA8: return launch_write_fmt<F_RGBA8>(s, a, (const float *)table, lv, num_cus);
-    case F_BGRA8: return launch_write_fmt<F_BGRA8>(s, a, (const float *)table, lv, num_cus);
-    case F_YUV420P10: return launch_write_fmt<F_YUV420P10>(s, a, (const float *)table, lv, num_cus);
-    case F_P010: return launch_write_fmt<F_P010>(s, a, (const float *)table, lv, num_cus);
-    default: return hipErrorInvalidValue;
-  }
+  return for_fmt(fmt, [&](auto f) { return launch_write_fmt<decltype(f)::value>(s, a, (const float *)table, lv, num_cus); });
 }
 
 }  // namespace ph

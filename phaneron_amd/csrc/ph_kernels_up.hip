@@ -415,47 +415,22 @@ __global__ __launch_bounds__(kUpBlock) void compose_up_write_v210_kernel(UpArgs 
 #ifndef PH_CLIP_ABLATE
 #define PH_CLIP_ABLATE 0
 #endif
-enum { CF_V210 = 0, CF_YUV422P10 = 1, CF_YUV422P8 = 2, CF_YUV420P = 3, CF_NV12 = 4, CF_RGBA8 = 5, CF_BGRA8 = 6, CF_YUV420P10 = 7, CF_P010 = 8 };  // = PH_FMT_*
-
 // one source pixel as the reader of its format makes it (ph_kernels_fmt.hip fmt_read_body, ph_kernels_lds.hip v210_read_lds_kernel), in two
 // halves: its samples requested, then converted - a lane requests the samples of all its pixels of a round before it converts the first
 // (a rectangle is a handful of pixels per lane: one at a time, every pixel would wait out its own trip to HBM)
 struct ClipRaw {
-  uint4 w;  // v210: the pixel's word quad; planar: .x .y .z = Y, Cb, Cr; packed RGB: .x = the pixel
+  uint4 w;  // v210: the pixel's word quad; the other formats: fmt_fetch's codes
 };
 template <int FMT>
 __device__ __forceinline__ ClipRaw clip_fetch(const ClipSrc &S, uint32_t x, uint32_t line) {
   ClipRaw r;
-  r.w = make_uint4(0u, 0u, 0u, 0u);
-  if (FMT == CF_V210) {
-    r.w = reinterpret_cast<const uint4 *>(S.p0)[(size_t)line * S.pitch + x / 6u];
-  } else if (FMT == CF_RGBA8 || FMT == CF_BGRA8) {
-    r.w.x = reinterpret_cast<const uint32_t *>(S.p0)[(size_t)line * S.pitch + x];
-  } else {
-    const uint32_t cl = (FMT == CF_YUV420P || FMT == CF_NV12 || FMT == CF_YUV420P10 || FMT == CF_P010) ? line >> 1 : line;
-    if (FMT == CF_YUV422P10 || FMT == CF_YUV420P10) {
-      r.w.x = reinterpret_cast<const uint16_t *>(S.p0)[(size_t)line * S.pitch + x];
-      r.w.y = reinterpret_cast<const uint16_t *>(S.p1)[(size_t)cl * (S.pitch >> 1) + (x >> 1)];
-      r.w.z = reinterpret_cast<const uint16_t *>(S.p2)[(size_t)cl * (S.pitch >> 1) + (x >> 1)];
-    } else if (FMT == CF_P010) {  // as fmt_read_body: the sample in bits 6..15, the pair's Cb, Cr words in one dword
-      r.w.x = reinterpret_cast<const uint16_t *>(S.p0)[(size_t)line * S.pitch + x] >> 6;
-      const uint32_t c = reinterpret_cast<const uint32_t *>(S.p1)[(size_t)cl * (S.pitch >> 1) + (x >> 1)];
-      r.w.y = (c & 0xffffu) >> 6, r.w.z = c >> 22;
-    } else if (FMT == CF_NV12) {  // nv12.ts:61-74
-      r.w.x = reinterpret_cast<const uint8_t *>(S.p0)[(size_t)line * S.pitch + x];
-      const uint8_t *c = reinterpret_cast<const uint8_t *>(S.p1) + (size_t)cl * S.pitch + (x & ~1u);
-      r.w.y = c[0], r.w.z = c[1];
-    } else {
-      r.w.x = reinterpret_cast<const uint8_t *>(S.p0)[(size_t)line * S.pitch + x];
-      r.w.y = reinterpret_cast<const uint8_t *>(S.p1)[(size_t)cl * (S.pitch >> 1) + (x >> 1)];
-      r.w.z = reinterpret_cast<const uint8_t *>(S.p2)[(size_t)cl * (S.pitch >> 1) + (x >> 1)];
-    }
-  }
+  if (FMT == PH_FMT_V210) r.w = reinterpret_cast<const uint4 *>(S.p0)[(size_t)line * S.pitch + x / 6u];
+  else r.w = fmt_fetch<FMT>(S.p0, S.p1, S.p2, S.pitch, x, line);
   return r;
 }
 template <int FMT>
 __device__ __forceinline__ float4 clip_finish(const ClipRaw &raw, uint32_t width, uint32_t x, const ReadK &k, const LutK &lk) {
-  if (FMT == CF_V210) {
+  if (FMT == PH_FMT_V210) {
     const uint4 w = raw.w;
     const uint32_t g = x / 6u, j = x - 6u * g, pr = j >> 1;
     const uint32_t wy = (j == 0) ? w.x : (j < 3) ? w.y : (j == 3) ? w.z : w.w;  // v210.ts:58-63, as v210_read_lds_kernel
@@ -466,13 +441,10 @@ __device__ __forceinline__ float4 clip_finish(const ClipRaw &raw, uint32_t width
     const float yf = (float)((wy >> sy) & 0x3ff), cbf = (float)((wcb >> (10u * pr)) & 0x3ff), crf = (float)((wcr >> scr) & 0x3ff);
     return read_px_lds(yf, cbf, crf, k, lk, x < width - width % 6u ? 1.0f : 0.0f);  // (a line's tail: v210.ts:88-93)
   }
-  if (FMT == CF_RGBA8 || FMT == CF_BGRA8) {  // rgba8.ts:49-62
+  if (fmt_rgb8(FMT)) {
     const uint32_t p = raw.w.x;
     const float c0 = (float)(p & 0xffu), gf = (float)((p >> 8) & 0xffu), c2 = (float)((p >> 16) & 0xffu), af = (float)(p >> 24);
-    const float rf = FMT == CF_RGBA8 ? c0 : c2, bf = FMT == CF_RGBA8 ? c2 : c0;
-    const float r = lds_lut_at(lk, rf * 65535.0f / 255.0f), g = lds_lut_at(lk, gf * 65535.0f / 255.0f), b = lds_lut_at(lk, bf * 65535.0f / 255.0f);
-    return make_float4(dot3(r, g, b, k.gm[0], k.gm[1], k.gm[2]), dot3(r, g, b, k.gm[3], k.gm[4], k.gm[5]), dot3(r, g, b, k.gm[6], k.gm[7], k.gm[8]),
-                       lds_lut_at(lk, af * 65535.0f / 255.0f));
+    return rgb8_to_rgba(FMT == PH_FMT_RGBA8 ? c0 : c2, gf, FMT == PH_FMT_RGBA8 ? c2 : c0, af, k, LutInLds{lk});
   }
   // (yuv422p10.ts:74-78: dot4 with the offset column, table, gamut - the v210 reader's arithmetic)
   return read_px_lds((float)raw.w.x, (float)raw.w.y, (float)raw.w.z, k, lk, 1.0f);
@@ -501,7 +473,7 @@ template <int FMT, bool RGB12, bool FIRST>
 __device__ __forceinline__ void clip_convert(const ClipSrc &S, const UpLayer &L, const ClipRect &R, char *dst, uint32_t ppitch, const float *rd_gm, const LutK &rlk,
                                              const LutView &rd_view) {
   // the rectangle's pixels row by row over all the workgroup's lanes, kClipRound of them per lane and round
-  constexpr int kClipRound = FMT == CF_V210 ? 4 : 6;  // (a 720p clip on a 1080p channel: 4.3 K pixels per workgroup - one round)
+  constexpr int kClipRound = FMT == PH_FMT_V210 ? 4 : 6;  // (a 720p clip on a 1080p channel: 4.3 K pixels per workgroup - one round)
   const uint32_t total = R.w * R.h;  // (< 2^24: exact as a float)
   const float inv_w = 1.0f / (float)(R.w ? R.w : 1u);
   struct Round {
@@ -526,7 +498,7 @@ __device__ __forceinline__ void clip_convert(const ClipSrc &S, const UpLayer &L,
     __syncthreads();
   }
   ReadK k;
-  if (FMT == CF_RGBA8 || FMT == CF_BGRA8) {
+  if (fmt_rgb8(FMT)) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) k.gm[i] = rd_gm[i];
   } else {
@@ -608,17 +580,17 @@ __global__ __launch_bounds__(kUpBlock) void clip_up_write_v210_kernel(ClipUpArgs
     else clip_convert<F, RGB12, false>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);                          \
     break;
     switch (S.fmt) {  // uniform
-      PH_CLIP_CASE(CF_V210)
-      PH_CLIP_CASE(CF_YUV422P10)
-      PH_CLIP_CASE(CF_YUV422P8)
-      PH_CLIP_CASE(CF_YUV420P)
-      PH_CLIP_CASE(CF_NV12)
-      PH_CLIP_CASE(CF_YUV420P10)
-      PH_CLIP_CASE(CF_P010)
-      PH_CLIP_CASE(CF_RGBA8)
+      PH_CLIP_CASE(PH_FMT_V210)
+      PH_CLIP_CASE(PH_FMT_YUV422P10)
+      PH_CLIP_CASE(PH_FMT_YUV422P8)
+      PH_CLIP_CASE(PH_FMT_YUV420P)
+      PH_CLIP_CASE(PH_FMT_NV12)
+      PH_CLIP_CASE(PH_FMT_YUV420P10)
+      PH_CLIP_CASE(PH_FMT_P010)
+      PH_CLIP_CASE(PH_FMT_RGBA8)
       default:
-        if (l == 0) clip_convert<CF_BGRA8, RGB12, true>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);
-        else clip_convert<CF_BGRA8, RGB12, false>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);
+        if (l == 0) clip_convert<PH_FMT_BGRA8, RGB12, true>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);
+        else clip_convert<PH_FMT_BGRA8, RGB12, false>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);
         break;
     }
 #undef PH_CLIP_CASE

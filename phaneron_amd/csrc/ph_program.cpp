@@ -24,8 +24,6 @@ namespace ph {
 
 namespace {
 
-const char *const kFmtNames[9] = {"v210", "yuv422p10", "yuv422p8", "yuv420p", "nv12", "rgba8", "bgra8", "yuv420p10", "p010"};  // = PH_FMT_*
-
 struct KnownSource {
   unsigned long long fingerprint;
   int format;
@@ -151,8 +149,8 @@ int resolve_program(const char *src, const char *name, ProgramChoice &c, std::st
     const bool is_read = name[0] == 'r';
     int fmt = -1, how = PH_RESOLVED_BY_TAG;
     if (tagged) {
-      for (int i = 0; i < (int)(sizeof kFmtNames / sizeof kFmtNames[0]); ++i)
-        if (0 == strcmp(src + 9, kFmtNames[i])) fmt = i;
+      for (int i = 0; i < kFmtCount; ++i)
+        if (0 == strcmp(src + 9, fmt_name(i))) fmt = i;
     } else if (src) {
       const unsigned long long fp = fingerprint(src);
       how = PH_RESOLVED_BY_TEXT;
@@ -166,7 +164,7 @@ int resolve_program(const char *src, const char *name, ProgramChoice &c, std::st
     }
     c.format = fmt;
     if (fmt == PH_FMT_V210) return set(c, is_read ? K_V210_READ : K_V210_WRITE, is_read ? "v210_read" : "v210_write", how);
-    return set(c, is_read ? K_PACK_READ : K_PACK_WRITE, std::string(kFmtNames[fmt]) + (is_read ? "_read" : "_write"), how);
+    return set(c, is_read ? K_PACK_READ : K_PACK_WRITE, std::string(fmt_name(fmt)) + (is_read ? "_read" : "_write"), how);
   }
   const int how = tagged ? PH_RESOLVED_BY_TAG : PH_RESOLVED_BY_NAME;
   auto layers = [&](const char *prefix, int lo, KernelId id) {
