@@ -1176,6 +1176,12 @@ static int flush_dirty_args(ph_ctx *ctx, const ph_arg *args, int n, int queue) {
   return PH_OK;
 }
 
+// a format the channel kernel does not write (fmt_chan_out): the same answer from ph_chan_compose and from a program's outPacking
+static int chan_out_refused(const char *fn, int fmt) {
+  return fail(PH_E_INVALID, "%s: the channel kernel does not write %s frames - run the separate kernels: the channel's frame as an image, then the format's writer (ph_pack_write)", fn,
+              fmt_name(fmt));
+}
+
 // A channel's frame as the by-name program chan_compose_v210_<n> describes it (dispatch K_CHAN_COMPOSE; ph_run_programs puts several
 // such calls into one launch): the arguments checked and turned into ph_chan_compose's own.
 struct ChanCall {
@@ -1280,6 +1286,8 @@ static int chan_call_parse(ph_ctx *ctx, ph_program *prog, const ph_arg *args, in
       if (find_arg(args, n, "outPacking")) TRY(need_num(args, n, "outPacking", &out_packing));
       const int ofmt = (int)out_packing;
       size_t opb[3] = {0, 0, 0};
+      if (!fmt_known(ofmt)) return fail(PH_E_INVALID, "kernel argument 'outPacking': %g is not a pack format", out_packing);
+      if (!fmt_chan_out(ofmt)) return chan_out_refused("kernel argument 'outPacking'", ofmt);
       if (ph_pack_plane_bytes(ofmt, width, height, opb) < 0) return fail(PH_E_INVALID, "kernel argument 'outPacking': %g is not a pack format", out_packing);
       TRY(need_buf(args, n, "output", opb[0], &o));
       if (fmt_chan_out(ofmt) && fmt_planes(ofmt) == 3) {  // (ph_chan_compose refuses the formats the kernel does not write)
@@ -2256,7 +2264,8 @@ static int chan_source(const ph_chan_source &s, const char *what, int layer, uin
   if (is_rgb8) *planar = 2;  // (served by the kernel's wire-format instantiation)
   if (is_planar) {
     if (!s.data_u || (fmt_planes(fmt) == 3 && !s.data_v) || (s.width & 1) || (fmt_v420(fmt) && (s.height & 1)))
-      return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s is planar: it needs its chroma plane(s), an even width and, for 4:2:0, an even height", layer, what);
+      return fail(PH_E_INVALID, "ph_chan_compose_v210: layer %d: the %s is a %s frame (planar): it needs its chroma plane(s), an even width and, for 4:2:0, an even height (%dx%d)", layer,
+                  what, fmt_name(fmt), s.width, s.height);
     *pu = s.data_u, *pv = s.data_v, *cm = (const float *)s.col_matrix12, *planar = 2;
   }
   // (the reference's v210 reader serves tails of 2 or 4 pixels: v210.ts:84-110)
@@ -2532,7 +2541,8 @@ int ph_chan_compose(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, 
                     const void *wr_lut) {
   if (!ctx || !layers || !out_planes || !out_planes[0] || !rd_cm || !rd_lut || !rd_gm || !wr_lut) return fail(PH_E_INVALID, "ph_chan_compose_v210: NULL argument");
   void *const out = out_planes[0];
-  if (!fmt_chan_out(out_format)) return fail(PH_E_INVALID, "ph_chan_compose_v210: output format %d is not a PH_FMT_*", out_format);
+  if (!fmt_known(out_format)) return fail(PH_E_INVALID, "ph_chan_compose_v210: output format %d is not a PH_FMT_*", out_format);
+  if (!fmt_chan_out(out_format)) return chan_out_refused("ph_chan_compose_v210", out_format);
   const bool out_planar = fmt_planar(out_format);
   if (!fmt_rgb8(out_format) && !wr_cm) return fail(PH_E_INVALID, "ph_chan_compose_v210: the writer's RGB -> YCbCr matrix is missing");
   if (out_planar && (!out_planes[1] || (fmt_planes(out_format) == 3 && !out_planes[2])))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import frames
+import packfmt
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
@@ -21,16 +22,37 @@ def colour(rspec, wspec):
 
 
 class Src:
-    """one source on both sides: the oracle's RGBA (read, then placed) and the tuple the binding takes"""
+    """one source on both sides: the oracle's RGBA (read, then placed) and the tuple the binding takes.  fmt: a pack format
+    (tests/packfmt.py: data = its planes, v210: its words) or "rgba" (data = an f32 image)"""
 
     def __init__(self, data, w, h, matrix=None, fmt="v210", spec="709"):
+        self.call_matrix = False
         self.data, self.w, self.h, self.matrix, self.fmt, self.spec = data, w, h, matrix, fmt, spec  # spec: the reader's colour space (8-bit planar sources make their own matrix for it)
 
+    @classmethod
+    def random(cls, fmt, w, h, seed, matrix=None, spec="709", legal=True):
+        """a random frame of any pack format, or a random f32 image ("rgba")"""
+        if fmt == "rgba":
+            return cls(frames.rgba_random(w, h, seed, -0.05, 1.05), w, h, matrix, fmt, spec)
+        planes = packfmt.get(fmt).random_planes(w, h, seed, legal=legal)
+        return cls(planes[0] if fmt == "v210" else planes, w, h, matrix, fmt, spec)
+
+    def like(self, fmt, seed=1):
+        """a source of this one's size and placement in another format (the route comparisons)"""
+        s = Src.random(fmt, self.w, self.h, seed, self.matrix, self.spec)
+        s.call_matrix = True  # (read by the call's Loader matrix, as this one is: sources with matrices of their own do not share a batched read)
+        return s
+
+    def own_matrix(self):
+        """True: the format's code range is not the call's 10-bit one, so the source brings its own Loader matrix (col_matrix12)"""
+        rng = packfmt.get(self.fmt).code_range
+        return rng is not None and rng != packfmt.get("v210").code_range and not self.call_matrix
+
     def oracle(self, rd_o, ow, oh):
-        if self.fmt in orc.FORMATS and self.fmt != "v210":  # data: the planes; a 10-bit 4:2:2 source shares the v210 Loader matrix, 8-bit ones have their own, RGB ones none
-            rng = orc.FORMAT_RANGE[self.fmt]
-            cm = rd_o[0] if self.fmt == "yuv422p10" else None if rng is None else orc.ycbcr2rgb_matrix(self.spec, *rng)
-            img = orc.pack_read(self.fmt, [np.ascontiguousarray(p).view(np.uint8) for p in self.data], self.w, self.h, cm, rd_o[1], rd_o[2])
+        if self.fmt in packfmt.BY_NAME and self.fmt != "v210":  # data: the planes; a 10-bit source shares the v210 Loader matrix, 8-bit ones have their own, RGB ones none
+            f = packfmt.get(self.fmt)
+            cm = f.reader_matrix(self.spec) if self.own_matrix() else None if f.code_range is None else rd_o[0]
+            img = f.oracle_read(self.data, self.w, self.h, cm, rd_o[1], rd_o[2])
         else:
             img = orc.v210_read(self.data, self.w, self.h, *rd_o) if self.fmt == "v210" else self.data.reshape(self.h, self.w, 4)
         if self.matrix is None:
@@ -40,11 +62,12 @@ class Src:
 
     def device(self):
         import hip_harness as hh
-        if self.fmt in orc.FORMATS and self.fmt != "v210":
+        if self.fmt in packfmt.BY_NAME and self.fmt != "v210":
             from phaneron_amd import capi
-            if orc.FORMAT_RANGE[self.fmt] is None:  # rgba8 / bgra8: one packed plane
+            f = packfmt.get(self.fmt)
+            if f.code_range is None:  # rgba8 / bgra8: one packed plane
                 return (hh.dev(np.ascontiguousarray(self.data[0]).reshape(-1)), self.w, self.h, self.matrix, self.fmt)
-            own = None if self.fmt == "yuv422p10" else hh.dev(capi.ycbcr2rgb_matrix(self.spec, *orc.FORMAT_RANGE[self.fmt]))
+            own = hh.dev(capi.ycbcr2rgb_matrix(self.spec, *f.code_range)) if self.own_matrix() else None
             return (tuple(hh.dev(np.ascontiguousarray(p).reshape(-1)) for p in self.data), self.w, self.h, self.matrix, self.fmt, own)
         t = hh.dev(self.data.reshape(-1))
         return (t, self.w, self.h, self.matrix) + (("rgba",) if self.fmt == "rgba" else ())
@@ -91,6 +114,11 @@ def check(layers, ow, oh, what, interlace=0, specs=("709", "709"), poison_dst=Fa
     bad = np.flatnonzero(got != np.asarray(want).reshape(-1))
     assert bad.size == 0, "%s: %d of %d words differ, first at word %d (line %d)" % (
         what, bad.size, got.size, bad[0], bad[0] // (frames.v210_pitch_bytes(ow) // 4))
+
+
+def pack_random(fmt, w, h, seed):
+    """random planes of any pack format but v210 (tests/packfmt.py)"""
+    return packfmt.get(fmt).random_planes(w, h, seed)
 
 
 def m(ow, oh, **kw):
@@ -243,8 +271,12 @@ def test_refusals():
         k.chan_compose_v210([ok], out, w, h, 0, *rd_d, wr_d[0], plain)
 
 
-def random_layers(r, ow, oh, n_layers, with_planar=False):
-    """n_layers random layers for an ow x oh channel: source sizes and formats, placements, transitions (see test_random_channel_programs)"""
+RANDOM_FORMATS = ("yuv422p10", "yuv422p8", "yuv420p", "nv12", "rgba8", "bgra8")  # what the campaigns of the first seven formats draw from: their cases stay as they are
+
+
+def random_layers(r, ow, oh, n_layers, with_planar=False, formats=RANDOM_FORMATS):
+    """n_layers random layers for an ow x oh channel: source sizes and formats, placements, transitions (see test_random_channel_programs);
+    formats: what a decoder's frame or graphic is drawn from (a longer list is another campaign: every draw after it changes)"""
     def source(must_fill=False):
         rgba = r.random() < 0.25
         one_to_one = r.random() < 0.3
@@ -253,13 +285,15 @@ def random_layers(r, ow, oh, n_layers, with_planar=False):
         else:
             w, h = int(r.choice([48, 96, 192, 288, 384])), int(r.integers(2, 40))
         seed = int(r.integers(1, 1 << 30))
-        planar = None if rgba or not with_planar or r.random() < 0.6 else str(r.choice(["yuv422p10", "yuv422p8", "yuv420p", "nv12", "rgba8", "bgra8"]))
+        planar = None if rgba or not with_planar or r.random() < 0.6 else str(r.choice(list(formats)))
         if planar:
             if not one_to_one:
                 h += h & 1  # (4:2:0: an even height)
             elif oh & 1 and planar in ("yuv420p", "nv12"):
                 planar = "yuv422p8"
-        data = frames.rgba_random(w, h, seed, -0.05, 1.05) if rgba else frames.pack_random(planar, w, h, seed) if planar else frames.v210_random(w, h, seed, legal=bool(r.random() < 0.7))
+            elif (ow | oh) & 1 and packfmt.get(planar).even_size:
+                planar = "yuv422p10"
+        data = frames.rgba_random(w, h, seed, -0.05, 1.05) if rgba else packfmt.get(planar).random_planes(w, h, seed) if planar else frames.v210_random(w, h, seed, legal=bool(r.random() < 0.7))
         mat = None
         if not one_to_one or r.random() < 0.5:
             kw = dict(scale_x=float(r.choice([0.3, 0.5, 1.0, 1.0, 1.7, 2.0])), scale_y=float(r.choice([0.3, 0.5, 1.0, 1.0, 1.7, 2.0])),
@@ -352,32 +386,42 @@ def test_planar_ten_bit_sources():
     """yuv422p10le frames (what a ProRes / DNxHD decoder hands over: ffmpegProducer.ts:410-412) as sources of the channel kernel:
     pixel for pixel, placed, enlarged from a smaller frame, as the incoming side of a dissolve and as a wipe's mask, beside v210
     and image layers - against the oracle's yuv422p10 reader (every 16-bit code, legal or not) followed by the chain of operators"""
-    w, h = 384, 54
-    p = [frames.pack_random("yuv422p10", w, h, 300 + i) for i in range(4)]
-    small = frames.pack_random("yuv422p10", 200, 30, 310)  # (a width that is not a multiple of 8: the planes' lines are padded)
+    small = pack_random("yuv422p10", 200, 30, 310)  # (a width that is not a multiple of 8: the planes' lines are padded)
     small = [(frames.splitmix64(311 + i, x.size // 2) % np.uint64(65536)).astype(np.uint16).view(np.uint8) for i, x in enumerate(small)]  # every 16-bit word
+    ten_bit_sources("yuv422p10", small)
+
+
+def ten_bit_sources(fmt, small):
+    """the body of test_planar_ten_bit_sources for a 10-bit planar format; small: a 200 x 30 frame of it"""
+    w, h = 384, 54
+    p = [pack_random(fmt, w, h, 300 + i) for i in range(4)]
     v = frames.v210_random(w, h, frames.layer_seed(98, 0))
-    check([dict(src=Src(p[0], w, h, fmt="yuv422p10"))], w, h, "one planar layer, pixel for pixel")
-    check([dict(src=Src(p[0], w, h, fmt="yuv422p10")), dict(src=Src(p[1], w, h, m(w, h, **PIP[1]), fmt="yuv422p10")),
-           dict(src=Src(v, w, h, m(w, h, **PIP[2]))), dict(src=Src(small, 200, 30, m(w, h, scale_x=0.6, scale_y=0.6, rotate=0.05, offset_x=0.2), fmt="yuv422p10"))],
+    check([dict(src=Src(p[0], w, h, fmt=fmt))], w, h, "one planar layer, pixel for pixel")
+    check([dict(src=Src(p[0], w, h, fmt=fmt)), dict(src=Src(p[1], w, h, m(w, h, **PIP[1]), fmt=fmt)),
+           dict(src=Src(v, w, h, m(w, h, **PIP[2]))), dict(src=Src(small, 200, 30, m(w, h, scale_x=0.6, scale_y=0.6, rotate=0.05, offset_x=0.2), fmt=fmt))],
           w, h, "planar and v210 layers, placed", specs=("709", "2020"))
     rgba = frames.rgba_random(w, h, 320, -0.05, 1.05)
     layers = [dict(src=Src(v, w, h)),
-              dict(src=Src(p[2], w, h, m(w, h), fmt="yuv422p10"), transition="dissolve", mix=0.4, incoming=Src(small, 200, 30, m(w, h, scale_x=1.5, scale_y=1.5), fmt="yuv422p10")),
-              dict(src=Src(rgba, w, h, fmt="rgba"), transition="wipe", incoming=Src(p[3], w, h, fmt="yuv422p10"), mask=Src(p[0], w, h, m(w, h, scale_x=2.0, scale_y=2.0), fmt="yuv422p10"))]
+              dict(src=Src(p[2], w, h, m(w, h), fmt=fmt), transition="dissolve", mix=0.4, incoming=Src(small, 200, 30, m(w, h, scale_x=1.5, scale_y=1.5), fmt=fmt)),
+              dict(src=Src(rgba, w, h, fmt="rgba"), transition="wipe", incoming=Src(p[3], w, h, fmt=fmt), mask=Src(p[0], w, h, m(w, h, scale_x=2.0, scale_y=2.0), fmt=fmt))]
     check(layers, w, h, "planar sources inside transitions")
     check(layers, w, h, "planar sources inside transitions, field 3", interlace=3, poison_dst=True)
 
 
-@pytest.mark.parametrize("fmt", ["yuv422p8", "yuv420p", "nv12"])
+@pytest.mark.parametrize("fmt", packfmt.PLANAR_8)
 def test_planar_eight_bit_sources(fmt):
     """the 8-bit planar formats of file decoders (ffmpegProducer.ts:398-408) as sources: their code ranges are not the 10-bit ones, so
     each brings its own Loader matrix (col_matrix12) while the gamma table and the gamut matrix are the call's - pixel for pixel,
     placed (4:2:0: a chroma line serves two luma lines, also across the bilinear taps), odd sizes' padded lines, beside v210 and
     planar 10-bit layers, inside a dissolve; against the oracle's reader of that format followed by the chain"""
+    planar_sources_beside_others(fmt)
+
+
+def planar_sources_beside_others(fmt):
+    """the body of test_planar_eight_bit_sources for any planar format"""
     w, h = 384, 54
-    a = frames.pack_random(fmt, w, h, 400)
-    b = frames.pack_random(fmt, 204, 38, 401)  # lines padded to a multiple of 8 samples
+    a = pack_random(fmt, w, h, 400)
+    b = pack_random(fmt, 204, 38, 401)  # lines padded to a multiple of 8 samples
     v = frames.v210_random(w, h, frames.layer_seed(99, 0))
     p10 = frames.pack_random("yuv422p10", w, h, 402)
     check([dict(src=Src(a, w, h, fmt=fmt))], w, h, "%s pixel for pixel" % fmt)
@@ -421,7 +465,7 @@ def placed_and_combined(layers, ow, oh, rd_o):
     return placed[0] if len(placed) == 1 else orc.combine(placed)
 
 
-@pytest.mark.parametrize("fmt", ["rgba8", "bgra8", "yuv422p8", "yuv422p10", "yuv420p", "nv12"])
+@pytest.mark.parametrize("fmt", packfmt.CHAN_OUT)
 @pytest.mark.parametrize("interlace", [0, 1, 3])
 def test_other_output_formats(fmt, interlace):
     """the channel's packed frame in the formats of the reference's other consumers - rgba8 / bgra8 for the screen
@@ -498,7 +542,7 @@ def test_ragged_sources_on_regular_outputs_and_the_other_way_round():
     check(layers, ow, oh, "HD sources, an image, a wipe and a dissolve on a 1280 channel", specs=("709", "2020"), poison_dst=True)
 
 
-@pytest.mark.parametrize("fmt", ["rgba8", "bgra8", "yuv422p8", "yuv422p10", "yuv420p", "nv12"])
+@pytest.mark.parametrize("fmt", packfmt.CHAN_OUT)
 def test_other_output_formats_at_1280(fmt):
     """the screen's and an encoder's frames of a 1280-wide channel (widths in multiples of 8 for the planar writers)"""
     w, h = 1280, 12
@@ -698,14 +742,14 @@ def test_channels_of_enlarged_clips_share_their_launches():
     both_routes(lambda route: check_batch(jobs, ow, oh, "channels of enlarged clips in one call, by the %s" % route))
 
 
-@pytest.mark.parametrize("fmt", ["yuv422p10", "yuv422p8", "yuv420p", "nv12"])
+@pytest.mark.parametrize("fmt", packfmt.PLANAR)
 def test_planar_clips_at_their_own_scale(fmt):
     """a file decoder's frame on a channel of its format under the Mixer's default fill (ffmpegProducer.ts:398-412, mixer.ts:189-228) - the
     everyday case - shares its taps between the pixels of a pair and between neighbouring lanes as v210 clips do: alone, two such clips
     (the upper one moved by whole and by fractional pixels), under an inset, in both fields, on frames that do not fill the chip and
     on a 1280-wide channel (lines with tails on the output side)"""
     for w, h in ((384, 54), (720, 60), (1280, 18)):
-        a, b = frames.pack_random(fmt, w, h, 600 + w), frames.pack_random(fmt, w, h, 601 + w)
+        a, b = pack_random(fmt, w, h, 600 + w), pack_random(fmt, w, h, 601 + w)
         v = frames.v210_random(w // 2 // 6 * 6, h // 2 // 2 * 2, frames.layer_seed(97, w))
         fill = dict(src=Src(a, w, h, m(w, h), fmt=fmt))
         # (a frame of nothing but decoders' frames under the default fill is made by read + 2 x 2-block compositor unless the option is off)
@@ -718,7 +762,7 @@ def test_planar_clips_at_their_own_scale(fmt):
             check([fill], w, h, "%s %dx%d under the default fill, field %d" % (fmt, w, h, interlace), interlace=interlace, poison_dst=True)
         # a graphic with alpha over the clip, both of the channel's size; an enlarged clip under such a graphic
         g = frames.pack_random("bgra8", w, h, 610 + w)
-        small = frames.pack_random(fmt, w // 2 // 2 * 2, h // 2 // 2 * 2, 611 + w)
+        small = pack_random(fmt, w // 2 // 2 * 2, h // 2 // 2 * 2, 611 + w)
         both_routes(lambda route: check([fill, dict(src=Src(g, w, h, m(w, h), fmt="bgra8"))], w, h, "%s clip under a bgra8 graphic by the %s" % (fmt, route)))
         both_routes(lambda route: check([dict(src=Src(small, w // 2 // 2 * 2, h // 2 // 2 * 2, m(w, h), fmt=fmt)), dict(src=Src(g, w, h, m(w, h), fmt="bgra8"))], w, h,
                                         "an enlarged %s clip under a bgra8 graphic by the %s" % (fmt, route)))
@@ -748,12 +792,12 @@ def test_random_channel_programs_with_planar_clips():
               specs=[("709", "709"), ("709", "2020")][case % 2], poison_dst=bool(interlace))
 
 
-@pytest.mark.parametrize("fmt", ["yuv422p10", "yuv422p8", "yuv420p", "nv12", "rgba8", "bgra8"])
+@pytest.mark.parametrize("fmt", packfmt.CLIPS)
 def test_enlarged_decoder_frames_on_both_routes(fmt):
     """a file smaller than its channel - a 720p H.264 clip (yuv420p) on a 1080 channel - by the reader of its format (ph_pack_read) + the
     2 x 2-block compositor and by the channel kernel: one clip, two clips, a clip beside a v210 clip, fields, a 1280-wide channel"""
     for (sw, sh, ow, oh) in ((128, 36, 192, 54), (200, 30, 384, 54), (96, 24, 1280, 30)):
-        a, b = frames.pack_random(fmt, sw, sh, 800 + sw), frames.pack_random(fmt, sw, sh, 801 + sw)
+        a, b = pack_random(fmt, sw, sh, 800 + sw), pack_random(fmt, sw, sh, 801 + sw)
         v = frames.v210_random(sw // 6 * 6, sh, frames.layer_seed(95, sw))
         one = [dict(src=Src(a, sw, sh, m(ow, oh), fmt=fmt))]
         two = one + [dict(src=Src(b, sw, sh, m(ow, oh, scale_x=0.8, scale_y=0.8, offset_x=0.1), fmt=fmt))]
@@ -764,14 +808,14 @@ def test_enlarged_decoder_frames_on_both_routes(fmt):
 
 
 @pytest.mark.parametrize("out", ["yuv422p8", "rgba8", "yuv422p10"])
-@pytest.mark.parametrize("src", ["v210", "yuv420p", "yuv422p10"])
+@pytest.mark.parametrize("src", ["v210", "yuv420p", "yuv422p10"] + packfmt.PLANAR_10_420)
 def test_other_consumers_frames_from_every_kind_of_program(src, out):
     """the encoder's and the screen's frames (ffmpegConsumer.ts:144 yuv422p8, screenConsumer.ts:131 rgba8; yuv422p10 for comparison: the
     "everything" instantiation) from programs of v210 clips, of planar clips under the default fill (shared taps) and of placed planar
     clips: the kernel's lean instantiations with another writer behind them"""
     w, h = 384, 54
     def clip(seed, ww, hh_, **kw):
-        data = frames.v210_random(ww, hh_, frames.layer_seed(seed, 0)) if src == "v210" else frames.pack_random(src, ww, hh_, seed)
+        data = frames.v210_random(ww, hh_, frames.layer_seed(seed, 0)) if src == "v210" else pack_random(src, ww, hh_, seed)
         return dict(src=Src(data, ww, hh_, m(w, h, **kw), fmt=src))
     for interlace in (0, 3):
         check_format([clip(900, w, h)], w, h, out, "%s clip under the default fill -> %s il %d" % (src, out, interlace), interlace=interlace)
@@ -841,3 +885,209 @@ def test_chan_batch_keeps_its_tables_across_the_jobs_it_hands_on():
     v = channel_variants(w, h, 991)
     jobs = [([img], 1, 0), (v[2], 3, 0), (v[1], 0, 1), (v[0], 1, 2), (v[3], 3, 2), ([img], 0, 3), (v[0], 0, 4), (v[1], 0, 5)]
     both_routes(lambda route: check_batch(jobs, w, h, "jobs handed on between launches, images by the %s" % route, specs=("709", "2020")))
+
+
+# ---- the 10-bit 4:2:0 decoder frames (yuv420p10 / p010) under what hardens the older planar formats ----------------------------------
+# (test_planar_clips_at_their_own_scale, test_enlarged_decoder_frames_on_both_routes and test_other_consumers_frames_from_every_kind_of_program
+# take them through their format lists; the tests below are the siblings of those that spell out one format)
+
+def siblings(layers):
+    """the same program with every yuv420p10 / p010 frame replaced by a frame of its 8-bit sibling (yuv420p / nv12)"""
+    def sib(s):
+        f = packfmt.BY_NAME.get(s.fmt)
+        return s.like(f.sibling8) if f is not None and f.sibling8 else s
+    return [dict(L, **{role: sib(L[role]) for role in ("src", "incoming", "mask") if L.get(role) is not None}) for L in layers]
+
+
+def dry_route(layers, ow, oh, interlace=0, specs=("709", "709")):
+    """the kernels ph_chan_compose_v210 would launch for this frame (nothing is enqueued)"""
+    import torch
+    import hip_harness as hh
+    from phaneron_amd import capi
+    _, _, rd_d, wr_d = colour(*specs)
+    out = torch.zeros(frames.v210_pitch_bytes(ow) * oh // 4, dtype=torch.int32, device="cuda")
+    dl = device_layers(layers)
+    with capi.trace(dry_run=True) as t:
+        hh.ctx().chan_compose_v210(dl, out, ow, oh, interlace, *rd_d, *wr_d)
+    return t.route
+
+
+def check10(layers, ow, oh, what, interlace=0, specs=("709", "709"), poison_dst=False):
+    """check(), and the frame goes the way the same program of 8-bit 4:2:0 frames goes"""
+    check(layers, ow, oh, what, interlace=interlace, specs=specs, poison_dst=poison_dst)
+    route, route8 = dry_route(layers, ow, oh, interlace, specs), dry_route(siblings(layers), ow, oh, interlace, specs)
+    assert route and route == route8, "%s: route %r, with the 8-bit siblings %r" % (what, route, route8)
+
+
+@pytest.mark.parametrize("fmt", packfmt.PLANAR_10_420)
+def test_ten_bit_420_sources(fmt):
+    """yuv420p10le / p010le frames (HEVC Main10, hardware decoders) where test_planar_ten_bit_sources and test_planar_eight_bit_sources
+    put the older formats: pixel for pixel, placed, enlarged from a ragged smaller frame, inside a dissolve and a wipe (outgoing side,
+    incoming side and mask), field outputs over a poisoned frame - words of all 16 bits, against the oracle's yuv422p10 Reader on F'"""
+    ten_bit_sources(fmt, pack_random(fmt, 200, 30, 310))
+    planar_sources_beside_others(fmt)
+
+
+@pytest.mark.parametrize("fmt", packfmt.PLANAR_10_420)
+def test_ten_bit_420_clips_take_the_routes_of_their_eight_bit_siblings(fmt):
+    """the shapes of test_planar_clips_at_their_own_scale and test_enlarged_decoder_frames_on_both_routes once more, each frame compared with
+    the oracle AND its route (capi.trace, dry run) with the route of the same program made of yuv420p / nv12 frames - on all three
+    chan_enlarged settings"""
+    def run(route):
+        for w, h in ((384, 54), (720, 60), (1280, 18)):
+            fill = dict(src=Src.random(fmt, w, h, 620 + w, m(w, h)))
+            up = dict(src=Src.random(fmt, w, h, 621 + w, m(w, h, offset_x=8.0 / w, offset_y=-4.0 / h)))
+            frac = dict(src=Src.random(fmt, w, h, 622 + w, m(w, h, offset_x=0.3 / w + 0.25, offset_y=0.4 / h)))
+            inset = dict(src=Src.random("v210", w // 2 // 6 * 6, h // 2 // 2 * 2, frames.layer_seed(96, w), m(w, h, **PIP[2])))
+            g = dict(src=Src.random("bgra8", w, h, 623 + w, m(w, h)))
+            small = dict(src=Src.random(fmt, w // 2 // 2 * 2, h // 2 // 2 * 2, 624 + w, m(w, h)))
+            for what, layers in (("alone", [fill]), ("two clips", [fill, dict(src=fill["src"].like(fmt, 625 + w))]), ("the second moved by whole pixels", [fill, up]),
+                                 ("moved by a fraction, a v210 inset on top", [fill, frac, inset]), ("under a bgra8 graphic", [fill, g]),
+                                 ("enlarged, under a bgra8 graphic", [small, g])):
+                check10(layers, w, h, "%s %dx%d %s by the %s" % (fmt, w, h, what, route), specs=("709", "2020"))
+            for interlace in (1, 3):
+                check10([fill], w, h, "%s %dx%d alone, field %d, by the %s" % (fmt, w, h, interlace, route), interlace=interlace, poison_dst=True)
+        for (sw, sh, ow, oh) in ((128, 36, 192, 54), (200, 30, 384, 54), (96, 24, 1280, 30)):
+            one = [dict(src=Src.random(fmt, sw, sh, 630 + sw, m(ow, oh)))]
+            two = one + [dict(src=Src.random(fmt, sw, sh, 631 + sw, m(ow, oh, scale_x=0.8, scale_y=0.8, offset_x=0.1)))]
+            mixed = one + [dict(src=Src.random("v210", sw // 6 * 6, sh, frames.layer_seed(94, sw), m(ow, oh, scale_x=0.7, scale_y=0.7, offset_y=-0.1)))]
+            for what, layers in (("one", one), ("two", two), ("beside a v210 clip", mixed)):
+                check10(layers, ow, oh, "%s enlarged %s clip(s) %dx%d on %dx%d by the %s" % (what, fmt, sw, sh, ow, oh, route))
+            check10(two, ow, oh, "two enlarged %s clips, field 3, by the %s" % (fmt, route), interlace=3, poison_dst=True, specs=("709", "2020"))
+    both_routes(run)
+
+
+RAGGED_CLIPS = [(10, 6), (14, 2), (66, 10), (250, 6)]
+
+
+@pytest.mark.parametrize("fmt", packfmt.PLANAR_10_420)
+@pytest.mark.parametrize("ow,oh", [(192, 10), (100, 8)])
+def test_small_ragged_ten_bit_420_clips_whose_taps_leave_the_frame(fmt, ow, oh):
+    """clips of a few pixels with padded lines (10 x 6, 14 x 2, 66 x 10, 250 x 6: every tail shape, a single chroma line, h % 4 == 2), scaled
+    0.3 - 2.0 and pushed partly off screen, one rotated: bilinear taps beyond the clip's last column pair (p010: the dword chroma load
+    there) and last chroma line answer the border colour - frames and both fields, over a v210 background and alone"""
+    place = [dict(scale_x=2.0, scale_y=2.0, offset_x=0.45, offset_y=-0.3), dict(scale_x=0.3, scale_y=0.5, offset_x=-0.5, offset_y=0.45),
+             dict(scale_x=1.3, scale_y=0.7, offset_x=0.5, offset_y=0.4, rotate=0.2), dict(scale_x=1.0, scale_y=1.7, offset_x=-0.55, offset_y=-0.2)]
+    bg = dict(src=Src.random("v210", ow, oh, frames.layer_seed(93, ow)))
+    clips = [dict(src=Src.random(fmt, w, h, 640 + w, m(ow, oh, **place[i]))) for i, (w, h) in enumerate(RAGGED_CLIPS)]
+    for i, c in enumerate(clips):
+        check10([c], ow, oh, "%s %dx%d clip alone, %r" % ((fmt,) + RAGGED_CLIPS[i] + (place[i],)), poison_dst=True)
+        check10([dict(src=Src(c["src"].data, c["src"].w, c["src"].h, m(ow, oh), fmt))], ow, oh, "%s %dx%d clip filling the frame" % ((fmt,) + RAGGED_CLIPS[i]), specs=("2020", "709"))
+    check10([bg] + clips, ow, oh, "four ragged %s clips over v210" % fmt, specs=("709", "2020"))
+    for interlace in (1, 3):
+        check10([bg] + clips[1:], ow, oh, "ragged %s clips over v210, field %d" % (fmt, interlace), interlace=interlace, poison_dst=True)
+        check10(clips[:2], ow, oh, "two ragged %s clips, field %d" % (fmt, interlace), interlace=interlace, poison_dst=True, specs=("2020", "2020"))
+
+
+@pytest.mark.parametrize("fmt", packfmt.PLANAR_10_420)
+def test_transitions_between_ten_bit_420_frames(fmt):
+    """a dissolve and a wipe whose outgoing side, incoming side and mask are yuv420p10 / p010 frames, mixed with v210: at the channel's size
+    (pixel for pixel and under the default fill) and placed, frames and fields"""
+    w, h = 384, 54
+    other = packfmt.PLANAR_10_420[1 - packfmt.PLANAR_10_420.index(fmt)]
+    S = lambda f, seed, ww=w, hh_=h, **kw: Src.random(f, ww, hh_, seed, m(w, h, **kw) if kw or (ww, hh_) != (w, h) else None)
+    at_size = [dict(src=S(fmt, 650), transition="dissolve", mix=0.3, incoming=S(fmt, 651)),
+               dict(src=S("v210", frames.layer_seed(92, 0), scale_x=0.6, scale_y=0.6, offset_x=-0.2), transition="wipe", incoming=S(fmt, 652), mask=S(other, 653))]
+    placed = [dict(src=S("v210", frames.layer_seed(92, 1))),
+              dict(src=S(fmt, 654, scale_x=1.0, scale_y=1.0), transition="dissolve", mix=1.0 / 3.0, incoming=S(other, 655, 202, 38, scale_x=1.4, scale_y=1.4, rotate=0.05)),
+              dict(src=S(fmt, 656, 100, 26, scale_x=0.5, scale_y=0.5, offset_x=0.25, offset_y=0.2), transition="wipe", incoming=S("v210", frames.layer_seed(92, 2), scale_x=0.5, scale_y=0.5, offset_x=0.25, offset_y=0.2),
+                   mask=S(fmt, 657, 66, 10, scale_x=2.0, scale_y=2.0))]
+    for what, layers in (("at the channel's size", at_size), ("placed", placed)):
+        check10(layers, w, h, "%s in transitions %s" % (fmt, what))
+        check10(layers, w, h, "%s in transitions %s, 2020 -> 709" % (fmt, what), specs=("2020", "709"))
+        for interlace in (1, 3):
+            check10(layers, w, h, "%s in transitions %s, field %d" % (fmt, what, interlace), interlace=interlace, poison_dst=True)
+    for mix in (0.0, 1.0):
+        at_size[0]["mix"] = mix
+        check10(at_size[:1], w, h, "%s dissolve at its ends (mix %g)" % (fmt, mix))
+
+
+NEW_FORMATS_SHARE = 3  # (of RANDOM_FORMATS_10: each of the two new formats three times among 12 entries - half of the decoders' frames)
+RANDOM_FORMATS_10 = RANDOM_FORMATS + tuple(packfmt.PLANAR_10_420) * NEW_FORMATS_SHARE
+
+
+def test_random_channel_programs_with_ten_bit_420_clips():
+    """test_random_channel_programs_with_planar_clips with yuv420p10 / p010 among the decoders' frames (a campaign of its own: the older one
+    keeps its cases): random sizes, placements, rotations, off-screen layers, transitions with such frames on either side and as masks, fields.
+    At least a third of all sources are in the two formats (counted below)"""
+    r = np.random.default_rng(int(os.environ.get("PH_FUZZ_SEED", "20261016")))
+    sizes = [(192, 2), (192, 10), (384, 33), (576, 18), (768, 6), (960, 20), (100, 8)]
+    count = {"new": 0, "all": 0}
+    for case in range(int(os.environ.get("PH_FUZZ_CASES", "24"))):
+        ow, oh = sizes[case % len(sizes)]
+        interlace = int(r.choice([0, 0, 1, 3]))
+        layers = random_layers(r, ow, oh, int(r.integers(1, 6)), with_planar=True, formats=RANDOM_FORMATS_10)
+        if case % 3 != 1:  # programs of the new formats' clips: at their own scale (the tap-sharing instantiation), moved, or placed anywhere
+            h2 = oh + (oh & 1)
+            layers = []
+            for i, f in enumerate(r.choice(packfmt.PLANAR_10_420 + ["yuv420p"], int(r.integers(1, 4)), p=[0.4, 0.4, 0.2])):
+                kw = dict(offset_x=float(i) / ow, offset_y=0.5 * i / oh)
+                cw, ch = ow, h2
+                if case % 3 == 2 and i:
+                    cw, ch = 2 * int(r.integers(1, 130)), 2 * int(r.integers(1, 20))
+                    kw = dict(scale_x=float(r.choice([0.3, 0.5, 1.0, 1.7, 2.0])), scale_y=float(r.choice([0.3, 0.5, 1.0, 1.7, 2.0])), offset_x=float(r.uniform(-0.6, 0.6)),
+                              offset_y=float(r.uniform(-0.6, 0.6)), rotate=float(r.choice([0.0, 0.0, 0.3])))
+                layers.append(dict(src=Src.random(str(f), cw, ch, 7300 + 10 * case + i, m(ow, oh, **kw))))
+        for L in layers:
+            for role in ("src", "incoming", "mask"):
+                if L.get(role) is not None:
+                    count["all"] += 1
+                    count["new"] += L[role].fmt in packfmt.PLANAR_10_420
+        check10(layers, ow, oh, "random channel with 10-bit 4:2:0 clips %d: %dx%d il %d, %d layers" % (case, ow, oh, interlace, len(layers)), interlace=interlace,
+                specs=[("709", "709"), ("709", "2020"), ("2020", "709")][case % 3], poison_dst=bool(interlace))
+    if "PH_FUZZ_SEED" not in os.environ and "PH_FUZZ_CASES" not in os.environ:
+        assert 3 * count["new"] >= count["all"], count
+
+
+@pytest.mark.parametrize("fmt", packfmt.PLANAR_10_420)
+def test_chan_batch_with_ten_bit_420_jobs(fmt):
+    """ph_chan_compose_batch: a yuv420p10 / p010 job between v210 jobs (it runs in its turn), four such jobs at ragged sizes on a 1280-wide
+    channel, fields of one frame from such jobs - every frame against the oracle's chain and against the same job posted alone"""
+    w, h = 384, 32
+    v = channel_variants(w, h, 380)
+    job = [dict(src=Src.random(fmt, w, h, 381)), v[3][0]]
+    both_routes(lambda route: check_batch([(v[0], 0, 0), (job, 0, 1), (v[1], 0, 2), (v[2], 0, 3)], w, h, "%s job between batched ones, by the %s" % (fmt, route)))
+    w, h = 1280, 24
+    other = packfmt.PLANAR_10_420[1 - packfmt.PLANAR_10_420.index(fmt)]
+    ragged = [[dict(src=Src.random(f, cw, ch, 382 + cw, m(w, h, **kw)))] for f, (cw, ch), kw in
+              zip((fmt, other, fmt, fmt), RAGGED_CLIPS, (dict(), dict(), dict(scale_x=0.8, scale_y=0.8, offset_x=0.3), dict()))]
+    both_routes(lambda route: check_batch([(x, 0, i) for i, x in enumerate(ragged)], w, h, "four ragged %s / %s jobs, by the %s" % (fmt, other, route), specs=("709", "2020")))
+    both_routes(lambda route: check_batch([(ragged[2], 1, 0), (ragged[3], 3, 0), (ragged[0], 0, 1)], w, h, "fields of one frame from %s jobs, by the %s" % (fmt, route)))
+
+
+@pytest.mark.parametrize("fmt", packfmt.NOT_CHAN_OUT)
+def test_refusals_of_the_formats_the_kernel_does_not_write(fmt):
+    """ph_chan_compose asked to WRITE yuv420p10 / p010: PH_E_INVALID, the message names the format and the way out (the channel's frame by
+    the separate kernels, then the format's standalone writer); as a source with an odd width, an odd height or a missing chroma plane:
+    PH_E_INVALID naming the format.  The outputs stay as they were"""
+    import hip_harness as hh
+    from phaneron_amd import capi
+    k = hh.ctx()
+    f = packfmt.get(fmt)
+    rd_d, wr_d = hh.ColourParams.reader("709", "709"), hh.ColourParams.writer("709")
+    w, h = 384, 8
+    ok = dict(src=Src.random("v210", w, h, 1).device())
+    planes = [hh.dev(p) for p in f.poisoned(w, h)]
+    with pytest.raises(capi.PhaneronError, match=r"error -1: .*%s.*run the separate kernels.*ph_pack_write" % fmt):  # PH_E_INVALID
+        k.chan_compose_v210([ok], planes, w, h, 0, *rd_d, wr_d[0], wr_d[1], out_fmt=fmt)
+    assert all((hh.host(p) == packfmt.POISON).all() for p in planes)
+    prog, vin = k.create_program("phaneron:chan", "chan_compose_v210_1", [w, h]), k.create_buffer(frames.v210_pitch_bytes(w) * h)
+    for check_only in (True, False):  # the same answer to a program's outPacking argument, where the job is posted and where it is run
+        with pytest.raises(capi.PhaneronError, match=r"error -1: kernel argument 'outPacking': .*%s.*run the separate kernels.*ph_pack_write" % fmt):
+            k.run_program(prog, {"l0In": vin, "outPacking": capi.FORMATS[fmt]}, check_only=check_only)
+    vin.release(), prog.destroy()
+    out = hh.dev(np.full(frames.v210_pitch_bytes(w) * h // 4, 0x2AAAAAAA, np.uint32))
+    src = tuple(hh.dev(p) for p in f.random_planes(w, h, 2))
+    for sw, sh in ((w - 1, h), (w, h - 1), (w - 1, h - 1)):
+        with pytest.raises(capi.PhaneronError, match=r"error -1: .*source is a %s frame.*even width.*even height" % fmt):
+            k.chan_compose_v210([dict(src=(src, sw, sh, capi.transform_matrix(w, h), fmt, None))], out, w, h, 0, *rd_d, *wr_d)
+    for role in ("incoming", "mask"):
+        with pytest.raises(capi.PhaneronError, match=r"error -1: .*%s is a %s frame.*even width" % ("incoming source" if role == "incoming" else "mask", fmt)):
+            L = dict(ok, transition="wipe", incoming=ok["src"], mask=ok["src"])
+            L[role] = (src, w - 1, h, capi.transform_matrix(w, h), fmt, None)
+            k.chan_compose_v210([L], out, w, h, 0, *rd_d, *wr_d)
+    missing = [(src[0], 0) + src[2:]] + ([(src[0], src[1], 0)] if len(src) == 3 else [])  # (0: a NULL plane)
+    for broken in missing:
+        with pytest.raises(capi.PhaneronError, match=r"error -1: .*source is a %s frame.*chroma plane" % fmt):
+            k.chan_compose_v210([dict(src=(broken, w, h, None, fmt, None))], out, w, h, 0, *rd_d, *wr_d)
+    assert (hh.host(out, np.uint32) == 0x2AAAAAAA).all()

@@ -8,6 +8,7 @@ import pytest
 
 import cases
 import frames
+import packfmt
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
@@ -217,31 +218,28 @@ def test_compose_with_wipes_inside():
         hh.ctx().compose_wipe_write_v210([(t, 96, 4, None)], [(t, t)], hh.dev(np.zeros(96 * 4, np.uint32)), 96, 4, 0, wcm, wlut)
 
 
-@pytest.mark.parametrize("fmt", ["yuv422p10", "yuv422p8", "yuv420p", "nv12", "rgba8", "bgra8"])
+@pytest.mark.parametrize("fmt", packfmt.STANDALONE)
 def test_pack_formats_random_sizes(fmt):
     import torch
     import hip_harness as hh
     r = rng_for("pack" + fmt)
-    rgb = fmt in ("rgba8", "bgra8")
+    f = packfmt.get(fmt)  # (planes and the oracle's read / write of any format: the 10-bit 4:2:0 ones through the yuv422p10 Reader / Writer)
+    rgb = fmt in packfmt.RGB8
     widths = [64, 128, 192] if rgb else [8, 16, 64, 70, 72, 74, 76, 78, 250, 256, 258, 1920]
     for w in widths:
         h = 2 * int(r.integers(1, 6))
-        planes = frames.pack_random(fmt, w, h, 9000 + w)
+        planes = f.random_planes(w, h, 9000 + w)
         cm, lut, gm = hh.ColourParams.fmt_reader(fmt, "709", "2020")
         out = torch.zeros(w * h * 4, dtype=torch.float32, device="cuda")
         hh.ctx().pack_read(fmt, [hh.dev(p) for p in planes], out, w, h, cm, lut, gm)
-        rng = orc.FORMAT_RANGE[fmt]
-        ocm = None if rng is None else orc.ycbcr2rgb_matrix("709", *rng)
-        bits_eq(hh.host(out), orc.pack_read(fmt, planes, w, h, ocm, orc.gamma2linear_lut("709"),
-                                            orc.rgb2rgb_matrix("709", "2020")), "%s read %dx%d" % (fmt, w, h))
+        bits_eq(hh.host(out), f.oracle_read(planes, w, h, *f.oracle_reader("709", "2020")), "%s read %dx%d" % (fmt, w, h))
         for il in (0, 1, 3):
             rgba = frames.rgba_random(w, h, 9500 + w + il, -0.1, 1.1)
             wcm, wlut = hh.ColourParams.fmt_writer(fmt, "2020")
-            dst = [np.full(nb, 0xA5, np.uint8) for nb in frames.pack_plane_bytes(fmt, w, h)]
+            dst = f.poisoned(w, h, 0xA5)
             dplanes = [hh.dev(d) for d in dst]
             hh.ctx().pack_write(fmt, hh.dev(rgba), dplanes, w, h, il, wcm, wlut)
-            owcm = None if rng is None else orc.rgb2ycbcr_matrix("2020", *rng)
-            want = orc.pack_write(fmt, rgba, w, h, il, owcm, orc.linear2gamma_lut("2020"), planes=[d.copy() for d in dst])
+            want = f.oracle_write(rgba, w, h, il, *f.oracle_writer("2020"), dst)
             for i, (gp, wp) in enumerate(zip(dplanes, want)):
                 bits_eq(hh.host(gp), wp, "%s write %dx%d il%d plane %d" % (fmt, w, h, il, i))
 
@@ -266,14 +264,13 @@ def test_special_float_values_in_write_paths():
         hh.ctx().v210_write(hh.dev(rgba), o, w, h, il, wcm, wlut)
         bits_eq(hh.host(o, np.uint32), orc.v210_write(rgba, w, h, il, orc.rgb2ycbcr_matrix("709"), orc.linear2gamma_lut("709"),
                                                        out=dst.copy()), "v210_write specials il%d" % il)
-    for fmt in ("yuv422p10", "nv12", "rgba8"):
-        rng = orc.FORMAT_RANGE[fmt]
+    for fmt in ["yuv422p10", "nv12", "rgba8"] + packfmt.PLANAR_10_420:
+        f = packfmt.get(fmt)
         wcm, wlut = hh.ColourParams.fmt_writer(fmt, "709")
-        dst = [np.full(nb, 0xA5, np.uint8) for nb in frames.pack_plane_bytes(fmt, w, h)]
+        dst = f.poisoned(w, h, 0xA5)
         dplanes = [hh.dev(d) for d in dst]
         hh.ctx().pack_write(fmt, hh.dev(rgba), dplanes, w, h, 0, wcm, wlut)
-        want = orc.pack_write(fmt, rgba, w, h, 0, None if rng is None else orc.rgb2ycbcr_matrix("709", *rng),
-                              orc.linear2gamma_lut("709"), planes=[d.copy() for d in dst])
+        want = f.oracle_write(rgba, w, h, 0, *f.oracle_writer("709"), dst)
         for i, (gp, wp) in enumerate(zip(dplanes, want)):
             bits_eq(hh.host(gp), wp, "%s write specials plane %d" % (fmt, i))
     # float kernels: same values, NaN positions must agree and every non-NaN word must be identical
