@@ -21,7 +21,7 @@ const RANGE = {
 const PLANE_ARGS = { 1: [''], 2: ['Y', 'C'], 3: ['Y', 'U', 'V'] }
 const ceilTo = (v, m) => Math.ceil(v / m) * m
 
-// work-group geometry the library derives the frame height from (ph_api.cpp dispatch: height = global / local,
+// work-group geometry the library derives the frame height from (ph_run.cpp dispatch_wire: height = global / local,
 // doubled for 4:2:0 line pairs and for interlaced writers)
 function packGeometry(format, width, height, writer, interlaced) {
 	const wipg = format === 'v210' ? ceilTo(width, 48) / 48

@@ -56,7 +56,7 @@ static void buf_finalize(napi_env env, void *data, void *hint) {
   (void)env, (void)hint;
   buf_box *b = (buf_box *)data;
   /* references leaked by JS die with the JS object; the library keeps the context alive until the last
-   * buffer is gone (ph_api.cpp "Lifetime"), so the order in which the collector finalises things is free */
+   * buffer is gone (ph_internal.h "Lifetime"), so the order in which the collector finalises things is free */
   for (; b->buf && b->js_refs > 0; --b->js_refs) ph_buf_release(b->buf);
   free(b);
 }
@@ -501,7 +501,7 @@ static napi_value CreateProgram(napi_env env, napi_callback_info info) {
  * values[i] is a buffer handle (external) or a number; float-valued kernel arguments are the
  * ones named in FLOAT_ARGS and any value that is not a whole number (per-layer arguments such as l<i>Mix of
  * chan_compose_v210_<n>); everything else numeric is passed as a 32-bit integer.  The library reads a
- * numeric argument of either kind as a number (ph_api.cpp need_num). */
+ * numeric argument of either kind as a number (ph_run.cpp Args::need_num). */
 static const char *FLOAT_ARGS[] = {"scale", "offsetX", "offsetY", "mix", "wipe", NULL};
 
 /* names[] / values[] of one job -> ph_arg array (caller frees *args and *names); 0 = a JS exception is pending */

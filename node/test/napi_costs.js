@@ -29,6 +29,17 @@ async function main() {
 	const fnames = Object.keys(fj.params)
 	const fvalues = fnames.map((k) => (Buffer.isBuffer(fj.params[k]) ? fj.params[k]._handle : fj.params[k]))
 	out.checkProgram_fused4 = await us(50000, () => native.runProgram(rig.ctx._ctx, fj.program._handle, fnames, fvalues, 1, false, true))
+	// the config-2 channel program: four v210 layers, three of them insets, the top one in mid-wipe (the longest argument list in use)
+	const chan = await rig.channelCompose(4, w, h, '709', '2020')
+	const xf = await rig.transform(w, h)
+	const insets = [null, { scaleX: 0.5, scaleY: 0.5, offsetX: -0.25, offsetY: -0.25 }, { scaleX: 0.5, scaleY: 0.5, offsetX: 0.25, offsetY: -0.25 }, { scaleX: 0.5, scaleY: 0.5, offsetX: 0.25, offsetY: 0.25 }]
+	const clayers = []
+	for (let l = 0; l < 4; ++l) clayers.push(Object.assign({ source: srcs[l], width: w, height: h }, insets[l] ? { matrix: await xf.matrix(insets[l]) } : {}))
+	clayers[3].transition = { type: 'wipe', incoming: { source: srcs[0], width: w, height: h }, mask: { source: b } }
+	const cj = chan(clayers, o, 0)
+	const cnames = Object.keys(cj.params)
+	const cvalues = cnames.map((k) => (Buffer.isBuffer(cj.params[k]) ? cj.params[k]._handle : cj.params[k]))
+	out.checkProgram_chan4 = await us(50000, () => native.runProgram(rig.ctx._ctx, cj.program._handle, cnames, cvalues, 1, false, true))
 	await rig.ctx.drain()
 	out.launch_fused4_async = await us(300, () => native.runProgram(rig.ctx._ctx, fj.program._handle, fnames, fvalues, 1, false))
 	await rig.ctx.drain()

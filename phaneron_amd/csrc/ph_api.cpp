@@ -1,6 +1,6 @@
 // ph_api.cpp - the C ABI of libphaneron_hip.so (include/phaneron_hip.h): context, ref-counted
-// pooled device buffers, program lookup by kernel name, named-argument dispatch (the nodencl
-// `runProgram` contract the reference's clJobQueue drives) and the typed entry points.
+// pooled device buffers, queues and the typed entry points.  Programs and their by-name jobs (the nodencl
+// `runProgram` contract the reference's clJobQueue drives) are ph_run.cpp, which calls the typed entry points.
 //
 // No CPU path exists here: every entry point that does work needs a HIP device.
 #include <atomic>
@@ -15,16 +15,16 @@
 #include <vector>
 
 #include "../../include/phaneron_hip.h"
+#include "ph_internal.h"
 #include "ph_kernels.h"
 #include "ph_lut_host.h"
-#include "ph_program.h"
 
 using ph::KernelId;
 using namespace ph;  // K_* kernel ids
 
 namespace {
-
 thread_local std::string g_err;
+}  // namespace
 
 int fail(int code, const char *fmt, ...) {
   char buf[512];
@@ -36,11 +36,7 @@ int fail(int code, const char *fmt, ...) {
   return code;
 }
 
-#define PH_HIP(call)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (call);                                                                   \
-    if (e_ != hipSuccess) return fail(PH_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-  } while (0)
+namespace {
 
 // the formats defined for even sizes only (fmt_even_size: a line pair per chroma line, a sample pair per chroma sample)
 int even_dims(const char *fn, int f, uint32_t w, uint32_t h) {
@@ -69,91 +65,6 @@ bool trace_launch(const char *name) {
 }
 }  // namespace ph
 
-struct LutEntry {
-  ph::LutView view{};  // bytes == 0: a plain table
-  void *blob_dev = nullptr;
-};
-
-// Lifetime: buffers, programs, events and graphs each hold a reference on their context, so the storage a
-// handle points into outlives the handle whatever order a garbage collector finalises them in.
-// ph_ctx_destroy drains the queues, marks the context closed (new work is refused) and drops the creator's
-// reference; the last handle released tears the device state down.
-// Threading: `mu` guards the pool, the LUT registry and the counters (the node addon calls hostAccess and
-// timed runProgram from libuv pool threads while the JS thread creates and releases buffers).
-struct ph_ctx {
-  int device = 0;
-  std::map<const void *, LutEntry> luts;  // device f32 table -> compressed LDS form
-  bool use_lds_lut = true;
-  int stream_images = 0;        // f32 image outputs: 0 through the caches, 1 streamed past them, 2 by size (ph_device.h store_image)
-  int stream_threshold_mb = 64;  // policy 2: images larger than this stream
-  hipStream_t streams[3] = {nullptr, nullptr, nullptr};
-  hipDeviceProp_t props;
-  std::multimap<size_t, void *> pool;  // free device blocks by exact size
-  size_t pooled_bytes = 0, live_buffers = 0, live_bytes = 0;
-  // Pinned host mirrors by exact size.  The reference makes a fresh destination per job and frame (io.ts:64-72, mixer.ts:196,
-  // combiner.ts:230) and the node binding gives every buffer its mirror at once (an OpenCLBuffer IS a node Buffer): a
-  // hipHostMalloc / hipHostFree pair of a 2160p image is ~40 ms, a pool hit nothing
-  // (a block carries the event recorded behind the last asynchronous copy that touched it: the next owner waits for it -
-  // normally long complete - before it writes the mirror; blocks are evicted oldest first when the budget is exceeded)
-  struct HostBlock {
-    void *p;
-    hipEvent_t busy;  // may be null
-    uint64_t seq;
-  };
-  std::multimap<size_t, HostBlock> host_pool;
-  size_t host_pooled_bytes = 0;
-  uint64_t host_pool_seq = 0;
-  // what the pool may keep pinned: this many MiB, or - if that is more - as much as was ever in use at once (host_peak_bytes): a
-  // pool smaller than the working set frees and pins a block per buffer again, 40 ms each (four 1080p channels create 36 images of
-  // 33 MB per tick: round 5 measured 40 ms per tick under the fixed 1 GiB of round 4)
-  // option "chan_enlarged" (default 1; PH_CHAN_ENLARGED=0 in the environment makes it 0): frames of enlarged clips by read + 2 x 2-block compositor
-  int chan_enlarged = !(getenv("PH_CHAN_ENLARGED") && getenv("PH_CHAN_ENLARGED")[0] == '0');
-  std::atomic<int> fail_launches{0};  // option "fail_launches" (a TEST hook): > 0 every launch through ph_run_program(s) fails; -k: the next k go through, then every one fails
-  int host_pool_mb = 4096;
-  size_t host_live_bytes = 0, host_peak_bytes = 0;  // mirrors attached to buffers now / at most
-  uint64_t host_pins = 0;                           // hipHostMalloc calls so far (ph_ctx_host_pool_stats)
-  void *chan_index[3] = {nullptr, nullptr, nullptr};  // index frame of the channel compositor, one per queue (ph_chan_compose_v210)
-  size_t chan_index_bytes[3] = {0, 0, 0};
-  // who is between taking a piece of a queue's area and enqueueing the last launch that uses it (callers on several threads: the launches of
-  // two calls on one queue must not interleave around the shared scratch); taken before ctx->mu, never the other way round
-  std::mutex chan_scratch_mu[3];
-  unsigned chan_scratch_turn[3] = {0, 0, 0};  // which third of the area the next frame of enlarged clips puts its images in (chan_compose_enlarged)
-  std::vector<struct ph_route *> routes;  // open ROUTEs: a recycled block must not be handed out under a transfer in flight
-  std::mutex mu;
-  std::atomic<int> refs{1};
-  std::atomic<bool> closed{false};
-  std::atomic<bool> lds_base_checked{false};  // ph_lut_register: the kernels' dynamic shared array starts at LDS address 0
-};
-
-struct ph_buf {
-  ph_ctx *ctx;
-  void *dptr;
-  void *hptr;  // pinned host mirror, lazily allocated
-  size_t bytes;
-  int width, height;
-  std::atomic<int> refs;
-  bool owned;
-  // written by libuv pool threads (hostAccess) and read by the launching thread (flush_dirty_args)
-  std::atomic<bool> host_dirty;
-  std::atomic<bool> lut_dirty;  // host data went into a table-sized buffer since its LDS form was last built
-  std::string owner;
-  hipEvent_t mirror_busy = nullptr;  // recorded behind the last asynchronous copy into or out of the mirror (travels with it into the pool)
-  hipStream_t mirror_stream = nullptr;  // the stream that copy was enqueued on
-};
-
-
-struct ph_program {
-  ph_ctx *ctx;
-  KernelId id;
-  int n_layers;  // combine_N
-  int format;    // PH_FMT_* of a read/write program
-  std::string kernel;
-  uint32_t global[2];
-  uint32_t local;
-};
-
-namespace {
-
 int set_device(ph_ctx *ctx) {
   if (ctx->closed.load()) return fail(PH_E_INVALID, "the context has been destroyed");
   PH_HIP(hipSetDevice(ctx->device));
@@ -162,22 +73,7 @@ int set_device(ph_ctx *ctx) {
   return PH_OK;
 }
 
-bool queue_ok(int queue) { return queue >= 0 && queue < 3; }
-int bad_queue(const char *fn, int queue) {
-  return fail(PH_E_INVALID, "%s: queue %d is not PH_QUEUE_LOAD (0), PH_QUEUE_PROCESS (1) or PH_QUEUE_UNLOAD (2)", fn, queue);
-}
-// The stream behind a queue index.  There is no unchecked accessor: an out-of-range index makes the ENCLOSING entry point
-// return PH_E_INVALID here, whether or not it remembered PH_QUEUE() at its top - never a silent alias of the process queue.
-#define stream_of(ctx, queue)                                  \
-  ({                                                           \
-    const int ph_q_ = (queue);                                 \
-    if (!queue_ok(ph_q_)) return bad_queue(__func__, ph_q_);   \
-    (ctx)->streams[ph_q_];                                     \
-  })
-#define PH_QUEUE(fn, queue)                        \
-  do {                                             \
-    if (!queue_ok(queue)) return bad_queue(fn, queue); \
-  } while (0)
+namespace {
 
 void order_queues_after_routes(ph_ctx *ctx);  // below, with ph_route
 
@@ -209,7 +105,11 @@ void pool_free(ph_ctx *ctx, size_t bytes, void *p) {
   ctx->pooled_bytes += bytes;
 }
 
+}  // namespace
+
 void ctx_ref(ph_ctx *ctx) { ctx->refs.fetch_add(1); }
+
+namespace {
 
 // contexts that exist: ph_ctx_destroy on a pointer that is no longer (or never was) a context is refused instead of
 // touching freed storage (a second destroy after the last handle went)
@@ -221,6 +121,8 @@ bool ctx_is_live(ph_ctx *ctx) {
     if (c == ctx) return true;
   return false;
 }
+
+}  // namespace
 
 // drops one reference; the last one frees the device state (streams, pool, LUT blobs)
 void ctx_unref(ph_ctx *ctx) {
@@ -252,38 +154,6 @@ void ctx_unref(ph_ctx *ctx) {
 }
 
 int closed_error(const char *fn) { return fail(PH_E_INVALID, "%s: the context has been destroyed", fn); }
-
-const ph_arg *find_arg(const ph_arg *args, int n, const char *name) {
-  for (int i = 0; i < n; ++i)
-    if (args[i].name && 0 == strcmp(args[i].name, name)) return &args[i];
-  return nullptr;
-}
-
-int need_buf(const ph_arg *args, int n, const char *name, size_t min_bytes, ph_buf **out) {
-  const ph_arg *a = find_arg(args, n, name);
-  if (!a || a->kind != PH_ARG_BUF || !a->v.buf) return fail(PH_E_INVALID, "kernel argument '%s' (buffer) missing", name);
-  if (a->v.buf->bytes < min_bytes)
-    return fail(PH_E_RANGE, "kernel argument '%s': buffer of %zu bytes, %zu needed", name, a->v.buf->bytes, min_bytes);
-  *out = a->v.buf;
-  return PH_OK;
-}
-
-int need_num(const ph_arg *args, int n, const char *name, double *out) {
-  const ph_arg *a = find_arg(args, n, name);
-  if (!a || a->kind == PH_ARG_BUF) return fail(PH_E_INVALID, "kernel argument '%s' (number) missing", name);
-  *out = a->kind == PH_ARG_F32 ? (double)a->v.f32 : a->kind == PH_ARG_I32 ? (double)a->v.i32 : (double)a->v.u32;
-  return PH_OK;
-}
-
-int need_image(ph_buf *b, const char *name, int *w, int *h) {
-  if (b->width <= 0 || b->height <= 0) return fail(PH_E_INVALID, "kernel argument '%s' is not an image buffer", name);
-  if (b->bytes < (size_t)b->width * b->height * 16) return fail(PH_E_RANGE, "image '%s' smaller than its dims", name);
-  *w = b->width;
-  *h = b->height;
-  return PH_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -457,7 +327,7 @@ int ph_buf_dims(const ph_buf *b, int *w, int *h) {
 }
 
 // an asynchronous copy into or out of b's mirror has just been enqueued on `s`
-static void mirror_mark(ph_buf *b, hipStream_t s) {
+extern "C++" void mirror_mark(ph_buf *b, hipStream_t s) {
   if (!b->mirror_busy && hipEventCreateWithFlags(&b->mirror_busy, hipEventDisableTiming) != hipSuccess) {
     b->mirror_busy = nullptr;
     hipStreamSynchronize(s);  // no event to carry: wait here rather than let the mirror go back to the pool under the copy
@@ -1114,7 +984,7 @@ static LutRef lds_view(ph_ctx *ctx, const void *dev) {
 }
 
 // a ph_buf used as `gammaLut`: (re)compress from its host mirror if new data went in
-static void refresh_buf_lut(ph_ctx *ctx, ph_buf *b) {
+extern "C++" void refresh_buf_lut(ph_ctx *ctx, ph_buf *b) {
   if (b->lut_dirty && b->hptr && b->bytes >= 65536 * 4) {
     hipStreamSynchronize(ctx->streams[PH_QUEUE_LOAD]);  // the mirror must be stable
     ph_lut_register(ctx, b->dptr, (const float *)b->hptr);
@@ -1122,870 +992,18 @@ static void refresh_buf_lut(ph_ctx *ctx, ph_buf *b) {
   }
 }
 
-// ---- programs ---------------------------------------------------------------------------------
-int ph_program_resolve(const char *src, const char *name, char *kernel_id, size_t kernel_id_len, int *format, int *how) {
-  ph::ProgramChoice c;
-  std::string err;
-  const int rc = ph::resolve_program(src, name, c, err);
-  if (rc != PH_OK) return fail(rc, "%s", err.c_str());
-  if (kernel_id && kernel_id_len) snprintf(kernel_id, kernel_id_len, "%s", c.kernel.c_str());
-  if (format) *format = (c.id <= K_V210_WRITE) ? c.format : -1;
-  if (how) *how = c.how;
-  return PH_OK;
-}
-
-int ph_program_create(ph_ctx *ctx, const char *src, const char *name, const uint32_t *gwi, int n_dims, uint32_t wipg,
-                      ph_program **out) {
-  if (!ctx || !name || !out) return fail(PH_E_INVALID, "ph_program_create: NULL argument");
-  ph::ProgramChoice c;
-  std::string err;
-  const int rc = ph::resolve_program(src, name, c, err);
-  if (rc != PH_OK) return fail(rc, "%s", err.c_str());
-  ph_program p{ctx, c.id, c.n_layers, c.format, c.kernel, {0, 0}, wipg};
-  for (int i = 0; i < n_dims && i < 2; ++i) p.global[i] = gwi ? gwi[i] : 0;
-  if (ctx->closed.load()) return closed_error("ph_program_create");
-  *out = new ph_program(p);
-  ctx_ref(ctx);
-  return PH_OK;
-}
-
-int ph_program_destroy(ph_program *p) {
-  if (!p) return PH_OK;
-  ph_ctx *ctx = p->ctx;
-  delete p;
-  ctx_unref(ctx);
-  return PH_OK;
-}
-
-const char *ph_program_kernel(const ph_program *p) { return p ? p->kernel.c_str() : ""; }
-
-// nodencl lets a caller map a buffer for writing (hostAccess('writeonly')), fill it and launch
-// without an explicit unmap (loadSave.ts:76-99): flush such mirrors on the launch queue first.
-static int flush_dirty_args(ph_ctx *ctx, const ph_arg *args, int n, int queue) {
-  for (int i = 0; i < n; ++i) {
-    if (args[i].kind != PH_ARG_BUF || !args[i].v.buf) continue;
-    ph_buf *b = args[i].v.buf;
-    if (b->host_dirty && b->hptr) {
-      hipStream_t s = stream_of(ctx, queue);
-      PH_HIP(hipMemcpyAsync(b->dptr, b->hptr, b->bytes, hipMemcpyHostToDevice, s));
-      mirror_mark(b, s);
-      b->host_dirty = false;
-      b->lut_dirty = b->lut_dirty || b->bytes >= 65536 * 4;
-    }
-  }
-  return PH_OK;
-}
-
 // a format the channel kernel does not write (fmt_chan_out): the same answer from ph_chan_compose and from a program's outPacking
-static int chan_out_refused(const char *fn, int fmt) {
+extern "C++" int chan_out_refused(const char *fn, int fmt) {
   return fail(PH_E_INVALID, "%s: the channel kernel does not write %s frames - run the separate kernels: the channel's frame as an image, then the format's writer (ph_pack_write)", fn,
               fmt_name(fmt));
 }
 
-// A channel's frame as the by-name program chan_compose_v210_<n> describes it (dispatch K_CHAN_COMPOSE; ph_run_programs puts several
-// such calls into one launch): the arguments checked and turned into ph_chan_compose's own.
-struct ChanCall {
-  ph_chan_layer layers[ph::kMaxLayers];
-  int n_layers, out_format;
-  uint32_t width, height, interlace;
-  void *out_planes[3];
-  ph_buf *rd_cm, *rd_lut, *rd_gm, *wr_cm, *wr_lut;
-};
-static int chan_call_parse(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n, bool check_only, ChanCall *call) {
-  ph_buf *b = nullptr, *c = nullptr, *d = nullptr, *o = nullptr;
-  int rc;
-#define TRY(x) \
-  if ((rc = (x)) != PH_OK) return rc
-  // l<i>In: a layer's source - a v210 frame (l<i>Width / l<i>Height: its size, default the output's) or an RGBA image buffer;
-  // l<i>Matrix (optional): its placement, a buffer whose host mirror holds the nine floats (Transform writes it through
-  // hostAccess: transform.ts:84-89), absent = 1:1; l<i>Transition: 0 cut / 1 dissolve / 2 wipe; l<i>Mix; l<i>Incoming(In|Matrix|
-  // Width|Height) and l<i>Mask(...): the transition's other sources; output: v210; colMatrix / gammaLut / gamutMatrix: the
-  // Loader's, outColMatrix / outGammaLut: the Saver's; interlace as 'write'
-  {
-      const uint32_t width = prog->global[0], height = prog->global[1];
-      if (!width || !height) return fail(PH_E_INVALID, "%s: globalWorkItems must be [width, height]", prog->kernel.c_str());
-      ph_chan_layer layers[ph::kMaxLayers];
-      memset(layers, 0, sizeof layers);
-      auto source = [&](int i, const char *role, ph_chan_source *s) -> int {
-        char nm[40];
-        ph_buf *x = nullptr;
-        snprintf(nm, sizeof nm, "l%d%sIn", i, role);
-        TRY(need_buf(args, n, nm, 0, &x));
-        double sw = width, sh = height;
-        s->data = x->dptr;
-        if (x->width > 0 && x->height > 0) {  // an image buffer (createBuffer with imageDims): f32 RGBA
-          s->format = PH_SRC_RGBA_F32, sw = x->width, sh = x->height;
-        } else {
-          s->format = PH_SRC_V210;
-          s->data_u = s->data_v = nullptr, s->col_matrix12 = nullptr;
-          // another wire format: l<i>Packing = its PH_FMT_* (1 yuv422p10, 2 yuv422p8, 3 yuv420p, 4 nv12, 7 yuv420p10, 8 p010: l<i>In the Y plane,
-          // l<i>InU / l<i>InV the chroma planes (nv12, p010: l<i>InU the CbCr plane), l<i>ColMatrix (optional) its own Loader matrix; 5 rgba8,
-          // 6 bgra8: l<i>In the frame)
-          double packing = 0;
-          snprintf(nm, sizeof nm, "l%d%sPacking", i, role);
-          if (find_arg(args, n, nm)) TRY(need_num(args, n, nm, &packing));
-          if (packing != 0) {
-            if (packing < PH_FMT_YUV422P10 || packing >= kFmtCount) return fail(PH_E_INVALID, "kernel argument '%s': %g is not a pack format other than v210", nm, packing);
-            s->format = src_of_fmt((int)packing);  // (PH_FMT_V210 is 0: every value from 1 on is another format)
-          }
-          snprintf(nm, sizeof nm, "l%d%sWidth", i, role);
-          if (find_arg(args, n, nm)) TRY(need_num(args, n, nm, &sw));
-          snprintf(nm, sizeof nm, "l%d%sHeight", i, role);
-          if (find_arg(args, n, nm)) TRY(need_num(args, n, nm, &sh));
-          const int fmt = fmt_of_src(s->format);
-          if (fmt_rgb8(fmt)) {
-            if (sw > 0 && sh > 0 && x->bytes < (size_t)sw * (size_t)sh * 4) return fail(PH_E_RANGE, "kernel argument 'l%d%sIn': buffer of %zu bytes is smaller than a %gx%g frame of 4 bytes per pixel", i, role, x->bytes, sw, sh);
-          } else if (fmt_planar(fmt)) {
-            size_t pb[3] = {0, 0, 0};
-            if (sw > 0 && sh > 0) ph_pack_plane_bytes(fmt, (uint32_t)sw, (uint32_t)sh, pb);
-            char nu[40];
-            ph_buf *pu = nullptr, *pv = nullptr, *pm = nullptr;
-            snprintf(nu, sizeof nu, "l%d%sInU", i, role);
-            TRY(need_buf(args, n, nu, pb[1], &pu));
-            s->data_u = pu->dptr;
-            if (fmt_planes(fmt) == 3) {
-              snprintf(nu, sizeof nu, "l%d%sInV", i, role);
-              TRY(need_buf(args, n, nu, pb[2], &pv));
-              s->data_v = pv->dptr;
-            }
-            snprintf(nu, sizeof nu, "l%d%sColMatrix", i, role);
-            if (find_arg(args, n, nu)) {
-              TRY(need_buf(args, n, nu, 48, &pm));
-              s->col_matrix12 = pm->dptr;
-            }
-            if (x->bytes < pb[0]) return fail(PH_E_RANGE, "kernel argument 'l%d%sIn': buffer of %zu bytes is smaller than the Y plane of a %gx%g frame", i, role, x->bytes, sw, sh);
-          } else if (sw > 0 && sh > 0 && x->bytes < (size_t)ph_v210_pitch_bytes((uint32_t)sw) * (size_t)sh)
-            return fail(PH_E_RANGE, "kernel argument 'l%d%sIn': buffer of %zu bytes is smaller than a %gx%g v210 frame", i, role, x->bytes, sw, sh);
-        }
-        s->width = (int)sw, s->height = (int)sh, s->matrix9_host = nullptr;
-        snprintf(nm, sizeof nm, "l%d%sMatrix", i, role);
-        if (find_arg(args, n, nm)) {
-          ph_buf *m = nullptr;
-          TRY(need_buf(args, n, nm, 36, &m));
-          if (!m->hptr) return fail(PH_E_INVALID, "kernel argument '%s': the matrix must have been written through hostAccess (its host copy is what the launch reads)", nm);
-          s->matrix9_host = (const float *)m->hptr;
-        }
-        return PH_OK;
-      };
-      for (int i = 0; i < prog->n_layers; ++i) {
-        char nm[40];
-        TRY(source(i, "", &layers[i].src));
-        double tr = 0, mix = 0;
-        snprintf(nm, sizeof nm, "l%dTransition", i);
-        if (find_arg(args, n, nm)) TRY(need_num(args, n, nm, &tr));
-        snprintf(nm, sizeof nm, "l%dMix", i);
-        if (find_arg(args, n, nm)) TRY(need_num(args, n, nm, &mix));
-        layers[i].transition = (int)tr, layers[i].mix = (float)mix;
-        if (layers[i].transition != PH_TRANSITION_CUT) TRY(source(i, "Incoming", &layers[i].incoming));
-        if (layers[i].transition == PH_TRANSITION_WIPE) TRY(source(i, "Mask", &layers[i].mask));
-      }
-      // output: the packed frame - v210, or with outPacking = PH_FMT_* another wire format: 1 yuv422p10 / 2 yuv422p8 / 3 yuv420p (output =
-      // the Y plane, outputU, outputV), 4 nv12 (output, outputC), 5 rgba8 / 6 bgra8 (no outColMatrix)
-      double interlace = 0, out_packing = 0;
-      ph_buf *wcm = nullptr, *wl = nullptr, *ou = nullptr, *ov = nullptr;
-      if (find_arg(args, n, "outPacking")) TRY(need_num(args, n, "outPacking", &out_packing));
-      const int ofmt = (int)out_packing;
-      size_t opb[3] = {0, 0, 0};
-      if (!fmt_known(ofmt)) return fail(PH_E_INVALID, "kernel argument 'outPacking': %g is not a pack format", out_packing);
-      if (!fmt_chan_out(ofmt)) return chan_out_refused("kernel argument 'outPacking'", ofmt);
-      if (ph_pack_plane_bytes(ofmt, width, height, opb) < 0) return fail(PH_E_INVALID, "kernel argument 'outPacking': %g is not a pack format", out_packing);
-      TRY(need_buf(args, n, "output", opb[0], &o));
-      if (fmt_chan_out(ofmt) && fmt_planes(ofmt) == 3) {  // (ph_chan_compose refuses the formats the kernel does not write)
-        TRY(need_buf(args, n, "outputU", opb[1], &ou));
-        TRY(need_buf(args, n, "outputV", opb[2], &ov));
-      } else if (fmt_chan_out(ofmt) && fmt_planes(ofmt) == 2) {  // nv12.ts:374: the interleaved CbCr plane is `outputC`
-        TRY(need_buf(args, n, "outputC", opb[1], &ou));
-      }
-      TRY(need_buf(args, n, "colMatrix", 48, &b));
-      TRY(need_buf(args, n, "gammaLut", 65536 * 4, &c));
-      TRY(need_buf(args, n, "gamutMatrix", 36, &d));
-      if (!fmt_rgb8(ofmt)) TRY(need_buf(args, n, "outColMatrix", 48, &wcm));
-      TRY(need_buf(args, n, "outGammaLut", 65536 * 4, &wl));
-      if (find_arg(args, n, "interlace")) TRY(need_num(args, n, "interlace", &interlace));
-      if (!check_only) refresh_buf_lut(ctx, c);
-      if (!check_only) refresh_buf_lut(ctx, wl);
-      ph_chan_layer *dst = call->layers;
-      memcpy(dst, layers, sizeof layers);
-      call->n_layers = prog->n_layers, call->out_format = ofmt, call->width = width, call->height = height, call->interlace = (uint32_t)interlace;
-      call->out_planes[0] = o->dptr, call->out_planes[1] = ou ? ou->dptr : nullptr, call->out_planes[2] = ov ? ov->dptr : nullptr;
-      call->rd_cm = b, call->rd_lut = c, call->rd_gm = d, call->wr_cm = wcm, call->wr_lut = wl;
-  }
-#undef TRY
-  return PH_OK;
-}
-
-// check_only: everything up to the launch - argument names, kinds, buffer sizes, geometry - and nothing on the device
-// (ph_check_program: a recording binding reports a bad job where it is posted, not where it is run)
-// fused_v210_combine_<n> (dispatch K_FUSED_V210; ph_run_programs puts several such calls of one shape into one launch):
-// l<i>In: v210 sources; colMatrix / gammaLut / gamutMatrix: the Loader's; outColMatrix / outGammaLut: the Saver's
-struct FusedCall {
-  const void *layers[ph::kMaxLayers];
-  int n;
-  void *out;
-  uint32_t width, height;
-  size_t frame_bytes;
-  ph_buf *rd_cm, *rd_lut, *rd_gm, *wr_cm, *wr_lut;
-};
-static int fused_call_parse(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n, bool check_only, FusedCall *call) {
-  int rc;
-#define TRY(x) \
-  if ((rc = (x)) != PH_OK) return rc
-  call->width = prog->global[0], call->height = prog->global[1], call->n = prog->n_layers;
-  if (!call->width || !call->height) return fail(PH_E_INVALID, "%s: globalWorkItems must be [width, height]", prog->kernel.c_str());
-  call->frame_bytes = (size_t)ph_v210_pitch_bytes(call->width) * call->height;
-  ph_buf *a = nullptr, *o = nullptr;
-  for (int i = 0; i < prog->n_layers; ++i) {
-    char nm[16];
-    snprintf(nm, sizeof nm, "l%dIn", i);
-    TRY(need_buf(args, n, nm, call->frame_bytes, &a));
-    call->layers[i] = a->dptr;
-  }
-  TRY(need_buf(args, n, "output", call->frame_bytes, &o));
-  call->out = o->dptr;
-  TRY(need_buf(args, n, "colMatrix", 48, &call->rd_cm));
-  TRY(need_buf(args, n, "gammaLut", 65536 * 4, &call->rd_lut));
-  TRY(need_buf(args, n, "gamutMatrix", 36, &call->rd_gm));
-  TRY(need_buf(args, n, "outColMatrix", 48, &call->wr_cm));
-  TRY(need_buf(args, n, "outGammaLut", 65536 * 4, &call->wr_lut));
-  if (!check_only) refresh_buf_lut(ctx, call->rd_lut);
-  if (!check_only) refresh_buf_lut(ctx, call->wr_lut);
-  return PH_OK;
-#undef TRY
-}
-
-// a compose_up_write_v210_<n> job's arguments (ph_run_program and ph_run_programs, which puts like jobs into one launch)
-struct UpCall {
-  int n;
-  bool rgb, pair;
-  ph_image_layer layers[ph::kMaxLayers], layers2[ph::kMaxLayers];
-  ph_buf *o, *o2, *wcm, *wl;
-  uint32_t width, height, interlace;
-};
-static int up_call_parse(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n, bool check_only, UpCall *u) {
-  int rc;
-#define TRY(x) \
-  if ((rc = (x)) != PH_OK) return rc
-  // l<i>In: the layer's image - an RGBA image buffer, or with packedRgb = 1 a buffer of packed f32 RGB (l<i>Width / l<i>Height:
-  // its size); l<i>Matrix: its placement (host mirror, as above); output: v210; outColMatrix / outGammaLut; interlace
-  const uint32_t width = prog->global[0], height = prog->global[1];
-  if (!width || !height) return fail(PH_E_INVALID, "%s: globalWorkItems must be [width, height]", prog->kernel.c_str());
-  double rgb = 0, interlace = 0;
-  if (find_arg(args, n, "packedRgb")) TRY(need_num(args, n, "packedRgb", &rgb));
-  // output2 + l<i>In2 (optional): a second job of the same shape in the same launch - the other field of a de-interlaced frame
-  // (ph_compose_up_write_v210_pair): same sizes, formats and placements, other data
-  const bool pair = find_arg(args, n, "output2") != nullptr;
-  for (int i = 0; i < prog->n_layers; ++i) {
-    char nm[24];
-    ph_buf *x = nullptr, *m = nullptr, *x2 = nullptr;
-    double lw = 0, lh = 0;
-    snprintf(nm, sizeof nm, "l%dIn", i);
-    TRY(need_buf(args, n, nm, 0, &x));
-    if (pair) {
-      snprintf(nm, sizeof nm, "l%dIn2", i);
-      TRY(need_buf(args, n, nm, x->bytes, &x2));
-      if (rgb == 0) {
-        int w2, h2, w1, h1;
-        TRY(need_image(x2, nm, &w2, &h2));
-        TRY(need_image(x, nm, &w1, &h1));
-        if (w1 != w2 || h1 != h2) return fail(PH_E_INVALID, "kernel argument '%s': the second job's image is %dx%d, the first's %dx%d", nm, w2, h2, w1, h1);
-      }
-      snprintf(nm, sizeof nm, "l%dIn", i);
-    }
-    if (rgb != 0) {
-      snprintf(nm, sizeof nm, "l%dWidth", i);
-      TRY(need_num(args, n, nm, &lw));
-      snprintf(nm, sizeof nm, "l%dHeight", i);
-      TRY(need_num(args, n, nm, &lh));
-      if (lw <= 0 || lh <= 0 || x->bytes < (size_t)lw * (size_t)lh * 12) return fail(PH_E_RANGE, "kernel argument 'l%dIn': smaller than its %gx%g packed-RGB image", i, lw, lh);
-    } else {
-      int iw, ih;
-      TRY(need_image(x, nm, &iw, &ih));
-      lw = iw, lh = ih;
-    }
-    snprintf(nm, sizeof nm, "l%dMatrix", i);
-    TRY(need_buf(args, n, nm, 36, &m));
-    if (!m->hptr) return fail(PH_E_INVALID, "kernel argument '%s': the matrix must have been written through hostAccess (its host copy is what the launch reads)", nm);
-    u->layers[i].data = x->dptr, u->layers[i].format = rgb != 0 ? PH_IMG_RGB_F32 : PH_IMG_RGBA_F32;
-    u->layers[i].width = (int)lw, u->layers[i].height = (int)lh, u->layers[i].matrix9_host = (const float *)m->hptr;
-    u->layers2[i] = u->layers[i];
-    if (pair) u->layers2[i].data = x2->dptr;
-  }
-  u->o = u->o2 = u->wcm = u->wl = nullptr;
-  TRY(need_buf(args, n, "output", (size_t)ph_v210_pitch_bytes(width) * height, &u->o));
-  if (pair) TRY(need_buf(args, n, "output2", (size_t)ph_v210_pitch_bytes(width) * height, &u->o2));
-  TRY(need_buf(args, n, "outColMatrix", 48, &u->wcm));
-  TRY(need_buf(args, n, "outGammaLut", 65536 * 4, &u->wl));
-  if (find_arg(args, n, "interlace")) TRY(need_num(args, n, "interlace", &interlace));
-  if (!check_only) refresh_buf_lut(ctx, u->wl);
-  u->n = prog->n_layers, u->rgb = rgb != 0, u->pair = pair, u->width = width, u->height = height, u->interlace = (uint32_t)interlace;
-#undef TRY
-  return PH_OK;
-}
-
 // the "fail_launches" fault injection (tests of a binding's error paths: node/test/soak_run.js, tests/test_boundary_gpu.py): does this launch fail?
-static bool inject_failure(ph_ctx *ctx) {
+extern "C++" bool inject_failure(ph_ctx *ctx) {
   const int v = ctx->fail_launches.load();
   if (v > 0) return true;
   if (v < 0 && ctx->fail_launches.fetch_add(1) == -1) ctx->fail_launches.store(1);  // the last one that goes through
   return false;
-}
-
-// ph_run_program's argument marshalling, one function per kernel family: each checks the job's named arguments against the frame geometry
-// (everything ph_check_program reports) and, unless check_only, makes the typed call.
-#define TRY(x) \
-  if ((rc = (x)) != PH_OK) return rc
-// the wire formats: v210 / pack readers and writers (v210.ts, yuv422p10.ts ... bgra8.ts; Reader / Writer geometry packer.ts:30-83)
-static int dispatch_wire(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n, int queue, bool check_only) {
-  ph_buf *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr, *o = nullptr;
-  double num = 0;
-  int rc, w, h;
-  (void)a, (void)b, (void)c, (void)d, (void)o, (void)num, (void)w, (void)h;
-  switch (prog->id) {
-    case K_PACK_READ:
-    case K_PACK_WRITE: {
-      const bool rd = prog->id == K_PACK_READ;
-      const int fmt = prog->format;
-      const bool rgb = fmt_rgb8(fmt), v420 = fmt_v420(fmt);
-      double il = 0;
-      TRY(need_num(args, n, "width", &num));
-      if (!rd) TRY(need_num(args, n, "interlace", &il));
-      const uint32_t width = (uint32_t)num, interlace = (uint32_t)il;
-      if (!prog->local || !width) return fail(PH_E_INVALID, "%s: width / workItemsPerGroup not set", prog->kernel.c_str());
-      // Readers: global = wipg*height (4:2:0: /2).  Writers: /2 when interlaced, 4:2:0 always /2
-      uint32_t height = prog->global[0] / prog->local;
-      if (v420) height *= 2;
-      else if (!rd && interlace) height *= 2;
-      size_t pb[3];
-      const int np = ph_pack_plane_bytes(fmt, width, height, pb);
-      static const char *in_names[3][3] = {{"input", "", ""}, {"inputY", "inputC", ""}, {"inputY", "inputU", "inputV"}};
-      static const char *out_names[3][3] = {{"output", "", ""}, {"outputY", "outputC", ""}, {"outputY", "outputU", "outputV"}};
-      const void *planes[3] = {nullptr, nullptr, nullptr};
-      ph_buf *pl = nullptr;
-      for (int i = 0; i < np; ++i) {
-        TRY(need_buf(args, n, (rd ? in_names : out_names)[np - 1][i], pb[i], &pl));
-        planes[i] = pl->dptr;
-      }
-      TRY(need_buf(args, n, rd ? "output" : "input", (size_t)width * height * 16, &o));
-      if (!rgb) TRY(need_buf(args, n, "colMatrix", 48, &b));
-      TRY(need_buf(args, n, "gammaLut", 65536 * 4, &c));
-      if (!check_only) refresh_buf_lut(ctx, c);
-      if (rd) {
-        TRY(need_buf(args, n, "gamutMatrix", 36, &d));
-        return check_only ? PH_OK : ph_pack_read(ctx, queue, fmt, planes, o->dptr, width, height, rgb ? nullptr : b->dptr, c->dptr, d->dptr);
-      }
-      return check_only ? PH_OK : ph_pack_write(ctx, queue, fmt, o->dptr, const_cast<void *const *>(planes), width, height, interlace,
-                           rgb ? nullptr : b->dptr, c->dptr);
-    }
-    case K_V210_READ: {
-      TRY(need_num(args, n, "width", &num));
-      const uint32_t width = (uint32_t)num;
-      if (!prog->local || !width) return fail(PH_E_INVALID, "v210 read: width / workItemsPerGroup not set");
-      const uint32_t height = prog->global[0] / prog->local;  // Reader: global = wipg * height (v210.ts:293-294)
-      TRY(need_buf(args, n, "input", (size_t)ph_v210_pitch_bytes(width) * height, &a));
-      TRY(need_buf(args, n, "output", (size_t)width * height * 16, &o));
-      TRY(need_buf(args, n, "colMatrix", 48, &b));
-      TRY(need_buf(args, n, "gammaLut", 65536 * 4, &c));
-      TRY(need_buf(args, n, "gamutMatrix", 36, &d));
-      if (!check_only) refresh_buf_lut(ctx, c);
-      return check_only ? PH_OK : ph_v210_read(ctx, queue, a->dptr, o->dptr, width, height, b->dptr, c->dptr, d->dptr);
-    }
-    case K_V210_WRITE: {
-      double il = 0;
-      TRY(need_num(args, n, "width", &num));
-      TRY(need_num(args, n, "interlace", &il));
-      const uint32_t width = (uint32_t)num, interlace = (uint32_t)il;
-      if (!prog->local || !width) return fail(PH_E_INVALID, "v210 write: width / workItemsPerGroup not set");
-      // Writer: global = wipg * height / (interlaced ? 2 : 1) (v210.ts:322-323)
-      const uint32_t height = prog->global[0] / prog->local * (interlace ? 2 : 1);
-      TRY(need_buf(args, n, "input", (size_t)width * height * 16, &a));
-      TRY(need_buf(args, n, "output", (size_t)ph_v210_pitch_bytes(width) * height, &o));
-      TRY(need_buf(args, n, "colMatrix", 48, &b));
-      TRY(need_buf(args, n, "gammaLut", 65536 * 4, &c));
-      if (!check_only) refresh_buf_lut(ctx, c);
-      return check_only ? PH_OK : ph_v210_write(ctx, queue, a->dptr, o->dptr, width, height, interlace, b->dptr, c->dptr);
-    }
-    case K_V210_READ_BATCH: {  // l<i>In: v210 frames; l<i>Out: RGBA images; colMatrix / gammaLut / gamutMatrix: the Loader's
-      const uint32_t width = prog->global[0], height = prog->global[1];
-      if (!width || !height) return fail(PH_E_INVALID, "%s: globalWorkItems must be [width, height]", prog->kernel.c_str());
-      const size_t vb = (size_t)ph_v210_pitch_bytes(width) * height, img = (size_t)width * height * 16;
-      const void *ins[ph::kMaxLayers];
-      void *outs[ph::kMaxLayers];
-      for (int i = 0; i < prog->n_layers; ++i) {
-        char nm[16];
-        ph_buf *x = nullptr;
-        snprintf(nm, sizeof nm, "l%dIn", i);
-        TRY(need_buf(args, n, nm, vb, &x));
-        ins[i] = x->dptr;
-        snprintf(nm, sizeof nm, "l%dOut", i);
-        TRY(need_buf(args, n, nm, img, &x));
-        outs[i] = x->dptr;
-      }
-      TRY(need_buf(args, n, "colMatrix", 48, &b));
-      TRY(need_buf(args, n, "gammaLut", 65536 * 4, &c));
-      TRY(need_buf(args, n, "gamutMatrix", 36, &d));
-      if (!check_only) refresh_buf_lut(ctx, c);
-      return check_only ? PH_OK : ph_v210_read_batch(ctx, queue, prog->n_layers, ins, outs, width, height, b->dptr, c->dptr, d->dptr);
-    }
-    default: break;
-  }
-  return fail(PH_E_UNKNOWN_KERNEL, "unhandled kernel id");
-}
-// de-interlacing: yadif, both parities in one launch, and the reader fused with it (yadifCl.ts, yadif.ts:88-145)
-static int dispatch_deint(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n, int queue, bool check_only) {
-  ph_buf *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr, *o = nullptr;
-  double num = 0;
-  int rc, w, h;
-  (void)a, (void)b, (void)c, (void)d, (void)o, (void)num, (void)w, (void)h;
-  switch (prog->id) {
-    case K_YADIF: {
-      double parity, tff, skip;
-      TRY(need_buf(args, n, "output", 0, &o));
-      TRY(need_image(o, "output", &w, &h));
-      const size_t img = (size_t)w * h * 16;
-      TRY(need_buf(args, n, "prev", img, &a));
-      TRY(need_buf(args, n, "cur", img, &b));
-      TRY(need_buf(args, n, "next", img, &c));
-      TRY(need_num(args, n, "parity", &parity));
-      TRY(need_num(args, n, "tff", &tff));
-      TRY(need_num(args, n, "skipSpatial", &skip));
-      return check_only ? PH_OK : ph_yadif(ctx, queue, a->dptr, b->dptr, c->dptr, w, h, (int)parity, (int)tff, (int)skip, o->dptr);
-    }
-    case K_YADIF_PAIR: {  // output0 / output1: what 'yadif' writes with parity 0 / 1
-      double tff, skip;
-      ph_buf *o1 = nullptr;
-      TRY(need_buf(args, n, "output0", 0, &o));
-      TRY(need_image(o, "output0", &w, &h));
-      const size_t img = (size_t)w * h * 16;
-      TRY(need_buf(args, n, "output1", img, &o1));
-      TRY(need_buf(args, n, "prev", img, &a));
-      TRY(need_buf(args, n, "cur", img, &b));
-      TRY(need_buf(args, n, "next", img, &c));
-      TRY(need_num(args, n, "tff", &tff));
-      TRY(need_num(args, n, "skipSpatial", &skip));
-      return check_only ? PH_OK : ph_yadif_pair(ctx, queue, a->dptr, b->dptr, c->dptr, w, h, (int)tff, (int)skip, o->dptr, o1->dptr);
-    }
-    case K_V210_YADIF_PAIR: {
-      // l<i>Prev / l<i>Cur / l<i>Next: v210 window; l<i>Out0 / l<i>Out1: RGBA; colMatrix / gammaLut / gamutMatrix: the Loader's
-      const uint32_t width = prog->global[0], height = prog->global[1];
-      if (!width || !height) return fail(PH_E_INVALID, "%s: globalWorkItems must be [width, height]", prog->kernel.c_str());
-      double tff, skip, rgb = 0, packing = 0;  // packedRgb (optional): 1 = the outputs are packed f32 RGB (12 bytes per pixel) for compose_up_write_v210_<n>
-      if (find_arg(args, n, "packedRgb")) TRY(need_num(args, n, "packedRgb", &rgb));
-      // packing (optional): 1 yuv422p10 / 2 yuv422p8 / 3 yuv420p / 4 nv12 - the windows are planar frames: l<i>Prev / Cur / Next their Y planes,
-      // l<i>PrevU, l<i>PrevV, l<i>CurU ... their chroma planes
-      if (find_arg(args, n, "packing")) TRY(need_num(args, n, "packing", &packing));
-      const int pfmt = (int)packing;
-      size_t pb[3] = {0, 0, 0};
-      if (!fmt_deint(pfmt))
-        return fail(PH_E_INVALID, "kernel argument 'packing': %g (0 v210, 1 yuv422p10, 2 yuv422p8, 3 yuv420p, 4 nv12)", packing);
-      ph_pack_plane_bytes(pfmt, width, height, pb);
-      const size_t vb = pb[0], img = (size_t)width * height * (rgb != 0 ? 12 : 16);
-      ph_deint_source src[ph::kMaxLayers];
-      memset(src, 0, sizeof src);
-      for (int i = 0; i < prog->n_layers; ++i) {
-        char nm[16];
-        ph_buf *x = nullptr;
-        if (pfmt != PH_FMT_V210) {
-          static const char *const which[3] = {"Prev", "Cur", "Next"};
-          const void **slots[3][2] = {{&src[i].prev_u, &src[i].prev_v}, {&src[i].cur_u, &src[i].cur_v}, {&src[i].next_u, &src[i].next_v}};
-          for (int f = 0; f < 3; ++f)
-            for (int c = 0; c < fmt_planes(pfmt) - 1; ++c) {  // (nv12: l<i>PrevU ... are the interleaved CbCr planes)
-              snprintf(nm, sizeof nm, "l%d%s%c", i, which[f], c ? 'V' : 'U');
-              TRY(need_buf(args, n, nm, pb[1 + c], &x));
-              *slots[f][c] = x->dptr;
-            }
-        }
-        snprintf(nm, sizeof nm, "l%dPrev", i);
-        TRY(need_buf(args, n, nm, vb, &x));
-        src[i].prev = x->dptr;
-        snprintf(nm, sizeof nm, "l%dCur", i);
-        TRY(need_buf(args, n, nm, vb, &x));
-        src[i].cur = x->dptr;
-        snprintf(nm, sizeof nm, "l%dNext", i);
-        TRY(need_buf(args, n, nm, vb, &x));
-        src[i].next = x->dptr;
-        snprintf(nm, sizeof nm, "l%dOut0", i);
-        TRY(need_buf(args, n, nm, img, &x));
-        src[i].out_parity0 = x->dptr;
-        snprintf(nm, sizeof nm, "l%dOut1", i);
-        TRY(need_buf(args, n, nm, img, &x));
-        src[i].out_parity1 = x->dptr;
-      }
-      TRY(need_buf(args, n, "colMatrix", 48, &b));
-      TRY(need_buf(args, n, "gammaLut", 65536 * 4, &c));
-      TRY(need_buf(args, n, "gamutMatrix", 36, &d));
-      TRY(need_num(args, n, "tff", &tff));
-      TRY(need_num(args, n, "skipSpatial", &skip));
-      if (!check_only) refresh_buf_lut(ctx, c);
-      return check_only ? PH_OK : ph_yadif_pair_packed(ctx, queue, prog->n_layers, src, pfmt, width, height, (int)tff, (int)skip, rgb != 0 ? PH_IMG_RGB_F32 : PH_IMG_RGBA_F32,
-                                    b->dptr, c->dptr, d->dptr);
-    }
-    default: break;
-  }
-  return fail(PH_E_UNKNOWN_KERNEL, "unhandled kernel id");
-}
-// the compositors: a channel's frame, enlarged layers, the buffer-addressed compositor, the headline kernel, combine_N (combine.ts, mixer.ts:189-228)
-static int dispatch_compose(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n, int queue, bool check_only) {
-  ph_buf *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr, *o = nullptr;
-  double num = 0;
-  int rc, w, h;
-  (void)a, (void)b, (void)c, (void)d, (void)o, (void)num, (void)w, (void)h;
-  switch (prog->id) {
-    case K_CHAN_COMPOSE: {
-      ChanCall call;
-      TRY(chan_call_parse(ctx, prog, args, n, check_only, &call));
-      return check_only ? PH_OK : ph_chan_compose(ctx, queue, call.n_layers, call.layers, call.out_format, call.out_planes, call.width, call.height, call.interlace,
-                                  call.rd_cm->dptr, call.rd_lut->dptr, call.rd_gm->dptr, call.wr_cm ? call.wr_cm->dptr : nullptr, call.wr_lut->dptr);
-    }
-    case K_COMPOSE_UP: {
-      UpCall u;
-      TRY(up_call_parse(ctx, prog, args, n, check_only, &u));
-      if (check_only) return PH_OK;
-      if (u.pair)
-        return ph_compose_up_write_v210_pair(ctx, queue, u.n, u.layers, u.layers2, u.o->dptr, u.o2->dptr, u.width, u.height, u.interlace, u.wcm->dptr, u.wl->dptr);
-      return ph_compose_up_write_v210(ctx, queue, u.n, u.layers, u.o->dptr, u.width, u.height, u.interlace, u.wcm->dptr, u.wl->dptr);
-    }
-    case K_COMPOSE_V210: {
-      // l<i>In: RGBA image; l<i>Matrix (optional): its 3x3 placement, absent = taken 1:1; l<i>WipeIn + l<i>WipeMask (optional):
-      // a wipe transition on the placed layer; output: v210; outColMatrix / outGammaLut: the Saver's; interlace as 'write'
-      const uint32_t width = prog->global[0], height = prog->global[1];
-      if (!width || !height) return fail(PH_E_INVALID, "%s: globalWorkItems must be [width, height]", prog->kernel.c_str());
-      ph_layer layers[ph::kMaxLayers];
-      ph_layer_wipe wipes[ph::kMaxLayers];
-      bool any_wipe = false;
-      for (int i = 0; i < prog->n_layers; ++i) {
-        char nm[24];
-        ph_buf *x = nullptr;
-        int lw, lh;
-        snprintf(nm, sizeof nm, "l%dIn", i);
-        TRY(need_buf(args, n, nm, 0, &x));
-        TRY(need_image(x, nm, &lw, &lh));
-        layers[i].rgba = x->dptr, layers[i].width = lw, layers[i].height = lh, layers[i].matrix9 = nullptr;
-        snprintf(nm, sizeof nm, "l%dMatrix", i);
-        if (find_arg(args, n, nm)) {
-          TRY(need_buf(args, n, nm, 36, &x));
-          layers[i].matrix9 = x->dptr;
-        }
-        wipes[i].incoming_rgba = wipes[i].mask_rgba = nullptr;
-        snprintf(nm, sizeof nm, "l%dWipeIn", i);
-        if (find_arg(args, n, nm)) {
-          TRY(need_buf(args, n, nm, (size_t)width * height * 16, &x));
-          wipes[i].incoming_rgba = x->dptr;
-          snprintf(nm, sizeof nm, "l%dWipeMask", i);
-          TRY(need_buf(args, n, nm, (size_t)width * height * 16, &x));
-          wipes[i].mask_rgba = x->dptr;
-          any_wipe = true;
-        }
-      }
-      double interlace = 0;
-      ph_buf *wcm = nullptr, *wl = nullptr;
-      TRY(need_buf(args, n, "output", (size_t)ph_v210_pitch_bytes(width) * height, &o));
-      TRY(need_buf(args, n, "outColMatrix", 48, &wcm));
-      TRY(need_buf(args, n, "outGammaLut", 65536 * 4, &wl));
-      if (find_arg(args, n, "interlace")) TRY(need_num(args, n, "interlace", &interlace));
-      if (!check_only) refresh_buf_lut(ctx, wl);
-      if (any_wipe)
-        return check_only ? PH_OK : ph_compose_wipe_write_v210(ctx, queue, prog->n_layers, layers, wipes, o->dptr, width, height, (uint32_t)interlace,
-                                          wcm->dptr, wl->dptr);
-      return check_only ? PH_OK : ph_compose_write_v210(ctx, queue, prog->n_layers, layers, o->dptr, width, height, (uint32_t)interlace, wcm->dptr, wl->dptr);
-    }
-    case K_COMBINE: {
-      const void *layers[ph::kMaxLayers];
-      TRY(need_buf(args, n, "output", 0, &o));
-      TRY(need_image(o, "output", &w, &h));
-      for (int i = 0; i < prog->n_layers; ++i) {
-        char nm[16];
-        snprintf(nm, sizeof nm, "l%dIn", i);
-        TRY(need_buf(args, n, nm, (size_t)w * h * 16, &a));
-        layers[i] = a->dptr;
-      }
-      return check_only ? PH_OK : ph_combine(ctx, queue, prog->n_layers, layers, w, h, o->dptr);
-    }
-    case K_FUSED_V210: {
-      FusedCall f;
-      TRY(fused_call_parse(ctx, prog, args, n, check_only, &f));
-      return check_only ? PH_OK : ph_fused_v210_combine(ctx, queue, f.n, f.layers, f.out, f.width, f.height, f.rd_cm->dptr, f.rd_lut->dptr, f.rd_gm->dptr,
-                                   f.wr_cm->dptr, f.wr_lut->dptr);
-    }
-    default: break;
-  }
-  return fail(PH_E_UNKNOWN_KERNEL, "unhandled kernel id");
-}
-// the f32 image operators: transform, resize, dissolve / mixer / wipe, transition_wipe (transform.ts, resize.ts, transition.ts, mix.ts, wipe.ts)
-static int dispatch_image(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n, int queue, bool check_only) {
-  ph_buf *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr, *o = nullptr;
-  double num = 0;
-  int rc, w, h;
-  (void)a, (void)b, (void)c, (void)d, (void)o, (void)num, (void)w, (void)h;
-  switch (prog->id) {
-    case K_TRANSFORM: {
-      int iw, ih;
-      TRY(need_buf(args, n, "input", 0, &a));
-      TRY(need_image(a, "input", &iw, &ih));
-      TRY(need_buf(args, n, "output", 0, &o));
-      TRY(need_image(o, "output", &w, &h));
-      TRY(need_buf(args, n, "transformMatrix", 32, &b));
-      return check_only ? PH_OK : ph_transform(ctx, queue, a->dptr, iw, ih, b->dptr, o->dptr, w, h);
-    }
-    case K_RESIZE: {
-      int iw, ih;
-      double scale, ox, oy;
-      TRY(need_buf(args, n, "input", 0, &a));
-      TRY(need_image(a, "input", &iw, &ih));
-      TRY(need_buf(args, n, "output", 0, &o));
-      TRY(need_image(o, "output", &w, &h));
-      TRY(need_buf(args, n, "flip", 16, &b));
-      TRY(need_num(args, n, "scale", &scale));
-      TRY(need_num(args, n, "offsetX", &ox));
-      TRY(need_num(args, n, "offsetY", &oy));
-      return check_only ? PH_OK : ph_resize(ctx, queue, a->dptr, iw, ih, (float)scale, (float)ox, (float)oy, b->dptr, o->dptr, w, h);
-    }
-    case K_DISSOLVE:
-    case K_MIXER:
-    case K_WIPE: {
-      TRY(need_buf(args, n, "output", 0, &o));
-      TRY(need_image(o, "output", &w, &h));
-      TRY(need_buf(args, n, "input0", (size_t)w * h * 16, &a));
-      TRY(need_buf(args, n, "input1", (size_t)w * h * 16, &b));
-      TRY(need_num(args, n, prog->id == K_WIPE ? "wipe" : "mix", &num));
-      if (prog->id == K_WIPE) return check_only ? PH_OK : ph_wipe(ctx, queue, a->dptr, b->dptr, (float)num, w, h, o->dptr);
-      if (prog->id == K_MIXER) return check_only ? PH_OK : ph_mixer(ctx, queue, a->dptr, b->dptr, (float)num, w, h, o->dptr);
-      return check_only ? PH_OK : ph_transition_dissolve(ctx, queue, a->dptr, b->dptr, (float)num, w, h, o->dptr);
-    }
-    case K_RGB_UNPACK: {  // image: an f32 RGBA image buffer whose first width * height * 12 bytes hold packed f32 RGB - expanded in place
-      TRY(need_buf(args, n, "image", 0, &o));
-      TRY(need_image(o, "image", &w, &h));
-      return check_only ? PH_OK : ph_image_unpack_rgb(ctx, queue, o->dptr, w, h);
-    }
-    case K_TWIPE: {
-      TRY(need_buf(args, n, "output", 0, &o));
-      TRY(need_image(o, "output", &w, &h));
-      TRY(need_buf(args, n, "input0", (size_t)w * h * 16, &a));
-      TRY(need_buf(args, n, "input1", (size_t)w * h * 16, &b));
-      TRY(need_buf(args, n, "maskIn", (size_t)w * h * 16, &c));
-      return check_only ? PH_OK : ph_transition_wipe(ctx, queue, a->dptr, b->dptr, c->dptr, w, h, o->dptr);
-    }
-    default: break;
-  }
-  return fail(PH_E_UNKNOWN_KERNEL, "unhandled kernel id");
-}
-#undef TRY
-static int dispatch(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n, int queue, bool check_only = false) {
-  if (!check_only && inject_failure(ctx)) return fail(PH_E_HIP, "%s: launch failed: injected (context option fail_launches)", prog->kernel.c_str());
-  switch (prog->id) {
-    case K_PACK_READ:
-    case K_PACK_WRITE:
-    case K_V210_READ:
-    case K_V210_WRITE:
-    case K_V210_READ_BATCH:
-      return dispatch_wire(ctx, prog, args, n, queue, check_only);
-    case K_YADIF:
-    case K_YADIF_PAIR:
-    case K_V210_YADIF_PAIR:
-      return dispatch_deint(ctx, prog, args, n, queue, check_only);
-    case K_CHAN_COMPOSE:
-    case K_COMPOSE_UP:
-    case K_COMPOSE_V210:
-    case K_COMBINE:
-    case K_FUSED_V210:
-      return dispatch_compose(ctx, prog, args, n, queue, check_only);
-    case K_TRANSFORM:
-    case K_RESIZE:
-    case K_DISSOLVE:
-    case K_MIXER:
-    case K_WIPE:
-    case K_TWIPE:
-    case K_RGB_UNPACK:
-      return dispatch_image(ctx, prog, args, n, queue, check_only);
-  }
-  return fail(PH_E_UNKNOWN_KERNEL, "unhandled kernel id");
-}
-
-int ph_run_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_args, int queue, ph_run_timings *t) {
-  if (!ctx || !prog || (n_args > 0 && !args)) return fail(PH_E_INVALID, "ph_run_program: NULL argument");
-  PH_QUEUE("ph_run_program", queue);
-  int rc = set_device(ctx);
-  if (rc) return rc;
-  rc = flush_dirty_args(ctx, args, n_args, queue);
-  if (rc) return rc;
-  if (!t) return dispatch(ctx, prog, args, n_args, queue);
-  hipStream_t s = stream_of(ctx, queue);
-  const auto t0 = std::chrono::steady_clock::now();
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;  // per call: timed runs may come from several threads
-  PH_HIP(hipEventCreate(&ev0));
-  if (hipEventCreate(&ev1) != hipSuccess) {
-    hipEventDestroy(ev0);
-    return fail(PH_E_HIP, "ph_run_program: hipEventCreate failed");
-  }
-  hipError_t te = hipEventRecord(ev0, s);
-  rc = te == hipSuccess ? dispatch(ctx, prog, args, n_args, queue) : fail(PH_E_HIP, "hipEventRecord: %s", hipGetErrorString(te));
-  float ms = 0.f;
-  if (rc == PH_OK) {
-    te = hipEventRecord(ev1, s);
-    if (te == hipSuccess) te = hipEventSynchronize(ev1);
-    if (te == hipSuccess) te = hipEventElapsedTime(&ms, ev0, ev1);
-    if (te != hipSuccess) rc = fail(PH_E_HIP, "ph_run_program: timing failed: %s", hipGetErrorString(te));
-  }
-  hipEventDestroy(ev0);
-  hipEventDestroy(ev1);
-  if (rc) return rc;
-  const auto t1 = std::chrono::steady_clock::now();
-  t->data_to_kernel = 0;  // arguments are device-resident: nothing moves at launch
-  t->kernel_exec = (uint32_t)(ms * 1000.0f + 0.5f);
-  t->total_time = (uint32_t)std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
-  return PH_OK;
-}
-
-int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_args, int queue) {
-  if (!ctx || !prog || (n_args > 0 && !args)) return fail(PH_E_INVALID, "ph_check_program: NULL argument");
-  PH_QUEUE("ph_check_program", queue);
-  return dispatch(ctx, prog, args, n_args, queue, true);
-}
-
-/* Several recorded jobs handed over in one call (a binding that records jobs and launches them later: node/defer.js).  Exactly the
- * ph_run_program calls in the order given - with the channel frames among them (chan_compose_v210_<n> programs of one geometry that name
- * the SAME Loader / Saver buffers and make v210 frames) put into launches together (ph_chan_compose_batch), likewise consecutive
- * fused_v210_combine_<n> frames; a job that reads or writes what an earlier job of its group writes (or writes what one reads) is
- * detected here and starts the next launch, so call order holds (include/phaneron_hip.h).  A call that fails after its checks
- * (a launch refused) has made the launches of the jobs before the failing group: ph_run_programs_progress says how many. */
-namespace {
-thread_local int g_programs_done = 0;  // jobs of the calling thread's last ph_run_programs call whose launches were made
-}
-int ph_run_programs_progress(int *jobs_done) {
-  if (!jobs_done) return fail(PH_E_INVALID, "ph_run_programs_progress: NULL argument");
-  *jobs_done = g_programs_done;
-  return PH_OK;
-}
-int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_arg *const *args, const int *n_args, int queue) {
-  if (!ctx || n_jobs < 1 || !progs || !args || !n_args) return fail(PH_E_INVALID, "ph_run_programs: NULL argument");
-  PH_QUEUE("ph_run_programs", queue);
-  g_programs_done = 0;
-  int rc = set_device(ctx);
-  if (rc) return rc;
-  if (ctx->fail_launches.load() > 0) return fail(PH_E_HIP, "ph_run_programs: launch failed: injected (context option fail_launches)");
-  std::vector<ChanCall> calls((size_t)n_jobs);
-  std::vector<FusedCall> fused((size_t)n_jobs);
-  std::vector<UpCall> ups;  // (sized when the first compose_up job shows up: most calls have none)
-  std::vector<char> kind((size_t)n_jobs, 0);  // 1: a v210 frame from the channel kernel, 2: fused_v210_combine, 3: compose_up_write_v210, 0: whatever else, launched as it is
-  for (int j = 0; j < n_jobs; ++j) {  // every job is checked before anything is launched: a bad one refuses the call as a whole
-    if (!progs[j] || (n_args[j] > 0 && !args[j])) return fail(PH_E_INVALID, "ph_run_programs: job %d: NULL argument", j);
-    if ((rc = flush_dirty_args(ctx, args[j], n_args[j], queue))) return rc;
-    if (progs[j]->id == K_CHAN_COMPOSE) {
-      if ((rc = chan_call_parse(ctx, progs[j], args[j], n_args[j], false, &calls[(size_t)j]))) return rc;
-      kind[(size_t)j] = calls[(size_t)j].out_format == PH_FMT_V210;
-    } else if (progs[j]->id == K_FUSED_V210) {
-      if ((rc = fused_call_parse(ctx, progs[j], args[j], n_args[j], false, &fused[(size_t)j]))) return rc;
-      kind[(size_t)j] = 2;
-    } else if (progs[j]->id == K_COMPOSE_UP) {
-      if (ups.empty()) ups.resize((size_t)n_jobs);
-      if ((rc = up_call_parse(ctx, progs[j], args[j], n_args[j], false, &ups[(size_t)j]))) return rc;
-      kind[(size_t)j] = 3;
-    } else if ((rc = dispatch(ctx, progs[j], args[j], n_args[j], queue, true))) {
-      return rc;
-    }
-  }
-  for (int j = 0; j < n_jobs;) {
-    if (!kind[(size_t)j]) {
-      if ((rc = dispatch(ctx, progs[j], args[j], n_args[j], queue))) return rc;
-      g_programs_done = ++j;
-      continue;
-    }
-    int k = j;
-    if (inject_failure(ctx)) return fail(PH_E_HIP, "ph_run_programs: launch failed: injected (context option fail_launches)");
-    if (kind[(size_t)j] == 2) {
-      // frames of one size, layer count and recipe: one launch of the headline kernel (ph_fused_v210_combine_batch).  A frame that reads
-      // what an earlier frame of the run writes (or writes what one reads or writes) starts the next launch: call order is kept.
-      const FusedCall &f0 = fused[(size_t)j];
-      std::vector<const void *> layers;
-      std::vector<void *> outs;
-      auto overlap = [&](const void *p, const void *q) {
-        const char *a0 = (const char *)p, *b0 = (const char *)q;
-        return a0 < b0 + f0.frame_bytes && b0 < a0 + f0.frame_bytes;
-      };
-      for (; k < n_jobs && kind[(size_t)k] == 2 && k - j < ph::kMaxBatch; ++k) {
-        const FusedCall &f = fused[(size_t)k];
-        if (f.n != f0.n || f.width != f0.width || f.height != f0.height || f.rd_cm != f0.rd_cm || f.rd_lut != f0.rd_lut || f.rd_gm != f0.rd_gm ||
-            f.wr_cm != f0.wr_cm || f.wr_lut != f0.wr_lut)
-          break;
-        bool clash = false;
-        for (size_t e = 0; e < outs.size() && !clash; ++e) {
-          clash = overlap(f.out, outs[e]);
-          for (int l = 0; l < f.n && !clash; ++l) clash = overlap(f.layers[l], outs[e]) || overlap(f.out, layers[e * (size_t)f0.n + (size_t)l]);
-        }
-        if (clash) break;
-        layers.insert(layers.end(), f.layers, f.layers + f.n);
-        outs.push_back(f.out);
-      }
-      rc = ph_fused_v210_combine_batch(ctx, queue, (int)outs.size(), f0.n, layers.data(), outs.data(), f0.width, f0.height, f0.rd_cm->dptr, f0.rd_lut->dptr,
-                                       f0.rd_gm->dptr, f0.wr_cm->dptr, f0.wr_lut->dptr);
-      if (rc) return rc;
-      g_programs_done = j = k;
-      continue;
-    }
-    if (kind[(size_t)j] == 3) {
-      // frames of the 2 x 2-block compositor of ONE shape (layer count, image format and sizes, placements, output size, field mode, Saver) -
-      // several channels' frames from de-interlaced fields, each job one frame or a frame's two fields - in one launch of up to
-      // kMaxUpJobs frames (ph_compose_up_write_v210_batch); a job that writes a frame an earlier one of the group writes starts the next
-      const UpCall &u0 = ups[(size_t)j];
-      const ph_image_layer *sets[ph::kMaxUpJobs];
-      void *outs[ph::kMaxUpJobs];
-      int frames = 0;
-      for (; k < n_jobs && kind[(size_t)k] == 3; ++k) {
-        const UpCall &u = ups[(size_t)k];
-        bool same = u.n == u0.n && u.rgb == u0.rgb && u.width == u0.width && u.height == u0.height && u.interlace == u0.interlace && u.wcm == u0.wcm && u.wl == u0.wl;
-        for (int l = 0; l < u.n && same; ++l) {
-          same = u.layers[l].width == u0.layers[l].width && u.layers[l].height == u0.layers[l].height;
-          for (int e = 0; e < 9 && same; ++e) same = u.layers[l].matrix9_host[e] == u0.layers[l].matrix9_host[e];
-        }
-        if (!same || frames + (u.pair ? 2 : 1) > ph::kMaxUpJobs) break;
-        bool clash = u.pair && u.o->dptr == u.o2->dptr;
-        for (int f = 0; f < frames && !clash; ++f) clash = outs[f] == u.o->dptr || (u.pair && outs[f] == u.o2->dptr);
-        if (clash) break;
-        sets[frames] = u.layers, outs[frames++] = u.o->dptr;
-        if (u.pair) sets[frames] = u.layers2, outs[frames++] = u.o2->dptr;
-      }
-      if (k == j) {  // (the first job does not fit a group of its own making - a pair writing one buffer twice: as it is, for its own error)
-        if ((rc = dispatch(ctx, progs[j], args[j], n_args[j], queue))) return rc;
-        g_programs_done = ++j;
-        continue;
-      }
-      rc = ph_compose_up_write_v210_batch(ctx, queue, frames, u0.n, sets, outs, u0.width, u0.height, u0.interlace, u0.wcm->dptr, u0.wl->dptr);
-      if (rc) return rc;
-      g_programs_done = j = k;
-      continue;
-    }
-    const ChanCall &c0 = calls[(size_t)j];
-    std::vector<ph_chan_job> batch;
-    // a frame that reads what an earlier frame of the group writes (a channel routed into another), or writes what one reads, starts the next
-    // call of ph_chan_compose_batch: the jobs of one such call may share launches, and call order has to hold
-    const size_t out_bytes = (size_t)ph_v210_pitch_bytes(c0.width) * c0.height;
-    auto touches = [&](const void *p, size_t bytes, const void *out) {
-      const char *a0 = (const char *)p, *b0 = (const char *)out;
-      return p && a0 < b0 + out_bytes && b0 < a0 + (bytes ? bytes : 1);
-    };
-    auto reads = [&](const ChanCall &c, const void *out) {  // does a source of c overlap the frame at `out`?
-      for (int l = 0; l < c.n_layers; ++l)
-        for (const ph_chan_source *s2 : {&c.layers[l].src, &c.layers[l].incoming, &c.layers[l].mask})
-          if (s2->data && (touches(s2->data, (size_t)s2->width * s2->height * 16u, out) || touches(s2->data_u, (size_t)s2->width * s2->height * 2u, out) ||
-                           touches(s2->data_v, (size_t)s2->width * s2->height * 2u, out)))
-            return true;
-      return false;
-    };
-    for (; k < n_jobs && kind[(size_t)k] == 1; ++k) {
-      const ChanCall &c = calls[(size_t)k];
-      if (c.width != c0.width || c.height != c0.height || c.rd_cm != c0.rd_cm || c.rd_lut != c0.rd_lut || c.rd_gm != c0.rd_gm || c.wr_cm != c0.wr_cm ||
-          c.wr_lut != c0.wr_lut)
-        break;
-      bool clash = false;
-      for (int e = j; e < k && !clash; ++e) clash = reads(c, calls[(size_t)e].out_planes[0]) || reads(calls[(size_t)e], c.out_planes[0]);
-      if (clash) break;
-      batch.push_back(ph_chan_job{c.n_layers, c.layers, c.out_planes[0], c.interlace});
-    }
-    rc = ph_chan_compose_batch(ctx, queue, (int)batch.size(), batch.data(), c0.width, c0.height, c0.rd_cm->dptr, c0.rd_lut->dptr, c0.rd_gm->dptr,
-                               c0.wr_cm->dptr, c0.wr_lut->dptr);
-    if (rc) return rc;
-    g_programs_done = j = k;
-  }
-  return PH_OK;
 }
 
 // ---- typed entry points ------------------------------------------------------------------------
