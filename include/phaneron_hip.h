@@ -40,7 +40,8 @@ extern "C" {
  *    keeps less than the working set
  * 8: additive over 7 - ph_trace_begin / ph_trace_end (which kernels made a frame; dry runs); ph_run_programs_progress; ph_buf_reuse; ph_image_unpack_rgb (program "rgb_unpack").
  *    Later additive within 8: the 10-bit 4:2:0 formats PH_FMT_YUV420P10 / PH_FMT_P010 and PH_SRC_YUV420P10 / PH_SRC_P010 - new enum
- *    values an older binding never passes; no signature or struct changed */
+ *    values an older binding never passes; no signature or struct changed.  ph_chan_compose_multi (ph_chan_output): several consumers'
+ *    frames of one channel in one launch; program "chan_compose_multi_<n>" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -256,7 +257,8 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * fused_v210_combine_<n> programs of one geometry, layer count and recipe (ph_fused_v210_combine_batch, up to eight per launch; a frame
  * that touches an earlier one's output starts the next launch), and consecutive compose_up_write_v210_<n> jobs of one shape - layer count,
  * image format and sizes, placements, frame size, field mode, Saver - each one frame or a frame's two fields (ph_compose_up_write_v210_batch, up to four frames
- * per launch). */
+ * per launch).  A chan_compose_multi_<n> job - chan_compose_v210_<n>'s arguments for output 0 and, for outputs k = 1..3, out<k>Packing,
+ * output<k> (output<k>U / V / C), out<k>ColMatrix, out<k>GammaLut, interlace<k>: ph_chan_compose_multi - runs in its turn as a launch of its own. */
 int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_arg *const *args, const int *n_args, int queue);
 /* How far the calling thread's LAST ph_run_programs call got: the launches of jobs 0 .. *jobs_done - 1 were made (n_jobs after a call
  * that returned PH_OK, 0 after one refused by its checks).  A call that fails at a launch has enqueued the jobs before the failing
@@ -533,6 +535,24 @@ typedef struct ph_chan_job {
 int ph_chan_compose_batch(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job *jobs, uint32_t out_width, uint32_t out_height,
                           const void *rd_col_matrix12, const void *rd_gamma_lut, const void *rd_gamut9, const void *wr_col_matrix12,
                           const void *wr_gamma_lut);
+/* Several CONSUMERS' frames of one channel in one launch.  A channel owns a list of consumers (channel.ts:40,64-88), each of which runs
+ * its own FromRGBA on the one combined image: v210 for SDI (fields on an interlaced channel), yuv422p8 for an encoder, rgba8 for the
+ * screen.  Here the composition - every source's reader, transforms, transitions, combine - runs once, for the union of the lines the
+ * outputs need, and only the writer's phase runs per output (outputs that name the same registered writer table share its load).
+ * Exactly the `n_out` calls of ph_chan_compose with each output's format, planes, interlace and writer recipe, bit for bit.
+ * n_out == 1 IS ph_chan_compose (same routes); 2..4 outputs are one launch of the channel kernel ("chan_compose_multi<mode>x<n_out>"
+ * in a trace; the enlarged-clip route is not taken).  Limits and errors as ph_chan_compose, per output; two outputs naming the same
+ * first plane, or n_out outside 1..4, are PH_E_INVALID.  A refused call writes nothing. */
+typedef struct ph_chan_output {
+  int format;                   /* a PH_FMT_* the channel kernel writes */
+  void *planes[3];              /* as ph_pack_plane_bytes(format, ...) sizes them */
+  uint32_t interlace;           /* as ph_v210_write, per output */
+  const void *wr_col_matrix12;  /* NULL for rgba8 / bgra8 */
+  const void *wr_gamma_lut;     /* registered (LDS form) */
+} ph_chan_output;
+int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs,
+                          uint32_t out_width, uint32_t out_height, const void *rd_col_matrix12, const void *rd_gamma_lut,
+                          const void *rd_gamut9);
 
 /* ---- gamma LUT placement.  The reference hands its kernels a 65536-entry f32 `gammaLut` buffer
  *      (loadSave.ts:65-73,152-160) and gathers from it 3x per pixel.  Registering the table's

@@ -88,6 +88,9 @@ class Deferral {
 			try { this._runMany(list, null) } catch (e) { /* recorded with the buffers */ }
 		}
 		this.earlyLaunch = ctx.earlyLaunch === true
+		// Several consumers' writes of ONE combined image (a channel's consumer list: channel.ts:64-88 - SDI plus an encoder or the screen)
+		// as outputs of one chan_compose_multi_<n> launch: see _siblings.  `multiWriter: false` on the context: every write its own launch.
+		this.multiWriter = ctx.multiWriter !== false
 	}
 
 	// ---- bookkeeping on buffers -----------------------------------------------------------------------------
@@ -331,6 +334,7 @@ class Deferral {
 				let plan = null
 				try { plan = this._plan(n) } catch (e) { if (n === must) failure = e; continue }
 				if (!plan) continue
+				if (plan.siblings) for (const w of plan.siblings) covered.add(w) // (the other consumers' writes of the same image: outputs of this plan's launch)
 				// a de-interlaced frame's two fields (planning has just launched its windows' reader): their compositor launch follows at
 				// once, while the fields are still in the cache - not after the other channels' readers (fieldBatch: see the constructor)
 				const twin = plan.up && !this.fieldBatch && plan.candidates[0][2]
@@ -373,6 +377,7 @@ class Deferral {
 	_fresh(plan) {
 		if (plan.node.state !== 'pending') return false
 		for (const u of plan.used) if (u.state !== 'pending') return false
+		if (plan.siblings) for (const w of plan.siblings) if (w.state !== 'pending') return false // (a sibling write ran or was dropped in between: plan again)
 		return true
 	}
 	// several channel frames in one launch: every plan's first candidate with the FIRST plan's Loader / Saver buffers (equal contents)
@@ -872,6 +877,30 @@ class Deferral {
 			candidates.push([`chan_compose_v210_${n}`, params])
 		}
 		if (!candidates.length) return null
+		// the other consumers' writes of the same image go with this one, as further outputs of the channel kernel's launch - for the
+		// classes of frame where that measured faster than a launch per consumer (profiles/chan_multi_bench.jsonl, DESIGN.md 5.1): the
+		// channel kernel's own frames and the headline's plain reads.  Frames of enlarged images (the 2 x 2-block compositor's) were not
+		// measured and keep a launch per consumer.
+		let siblings = null
+		const chanAt = candidates.findIndex((c) => c[0].startsWith('chan_compose_v210_'))
+		if (this.multiWriter && chanAt >= 0 && !candidates.some((c) => c[0].startsWith('compose_up_write_v210_'))) {
+			siblings = this._siblings(node, frame)
+			if (siblings.length) {
+				const params = Object.assign({}, candidates[chanAt][1])
+				siblings.forEach(({ frame: f, node: w }, i) => {
+					const k = i + 1
+					if (f.outFmt) params[`out${k}Packing`] = f.outFmt
+					params[`output${k}`] = f.output
+					if (f.outFmt === 4) params[`output${k}C`] = w.params.outputC
+					else if (f.outFmt >= 1 && f.outFmt < 5) { params[`output${k}U`] = w.params.outputU; params[`output${k}V`] = w.params.outputV }
+					if (!f.outRgb8) params[`out${k}ColMatrix`] = w.params.colMatrix
+					params[`out${k}GammaLut`] = w.params.gammaLut
+					params[`interlace${k}`] = f.interlace
+				})
+				siblings = siblings.map((v) => v.node)
+				candidates.unshift([`chan_compose_multi_${n}`, params, null, siblings])
+			} else siblings = null
+		}
 		// one call can take it together with other channels' frames: plain reads of the output's size (the headline kernel's batch form),
 		// or the channel kernel as the only candidate making a v210 frame (the batch kernel for v210 / image sources)
 		// (frames from planar / packed-RGB clips go along in the same call: the library runs those it cannot put into a shared launch in their turn,
@@ -879,20 +908,45 @@ class Deferral {
 		// ... or frames of the 2 x 2-block compositor (de-interlaced fields at their own size or enlarged: several 1080i channels in a tick)
 		const up = candidates[0][0].startsWith('compose_up_write_v210_')
 		const batchable = up || candidates[0][0].startsWith('fused_v210_combine_') || (candidates.length === 1 && candidates[0][0].startsWith('chan_compose_v210_') && !outFmt)
-		return { node, candidates, used, n, width, height, batchable, up, loader, saver }
+		return { node, candidates, used, n, width, height, batchable, up, loader, saver, siblings }
+	}
+	// The pending writes of other consumers on the image `node` writes: wire-format writes _writeFrame accepts, of the same geometry, on
+	// the same queue, into buffers of their own - at most three (the launch has four outputs).
+	_siblings(node, frame) {
+		const found = []
+		const outs = new Set(node.outs)
+		for (const w of frame.image._readers) {
+			if (found.length === 3) break
+			if (w === node || w.state !== 'pending' || w.program.name !== 'write' || w.params.input !== frame.image || w.queue !== node.queue) continue
+			// (a write that is not the registered producer of its outputs is still being recorded - record() runs what its output's present
+			// contents depend on before it registers the job, and that may be what brought us here: it is nobody's sibling yet)
+			if (!w.outs.length || w.outs.some((o) => o._producer !== w)) continue
+			let f = null
+			try { f = this._writeFrame(w) } catch (e) { f = null }
+			if (!f || f.width !== frame.width || f.height !== frame.height || w.outs.some((o) => outs.has(o))) continue
+			for (const o of w.outs) outs.add(o)
+			found.push({ node: w, frame: f })
+		}
+		return found
 	}
 	// launch the first candidate the library takes; false = none (nothing was launched)
 	_commit(plan) {
 		if (!this._fresh(plan)) return plan.node.state === 'pending' ? this._fused(plan.node) : true
-		for (const [name, params, twin] of plan.candidates) {
+		for (const [name, params, twin, siblings] of plan.candidates) {
 			if (!this._try(this._program(name, plan.width, plan.height), params, plan.node.queue)) continue
-			this._done(plan, twin)
+			this._done(plan, twin, siblings)
 			return true
 		}
 		return false
 	}
-	_done(plan, twin) {
+	_done(plan, twin, siblings) {
 		if (this.timed) { for (const u of plan.used) this.timed.push(u); this.timed.push(plan.node) }
+		if (siblings) for (const w of siblings) if (w.state === 'pending') { // the other consumers' frames came out of the same launch
+			if (this.timed) this.timed.push(w)
+			this.stats.fusedNodes++
+			this.stats.multiOutputs = (this.stats.multiOutputs || 0) + 1
+			this._retire(w, 'done')
+		}
 		if (twin && twin.node.state === 'pending') { // the other field's frame came out of the same launch
 			this.stats.fusedNodes += 1 + (plan.n > 1 ? 1 : 0) + plan.n
 			this._retire(twin.node, 'done')

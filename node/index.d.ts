@@ -71,6 +71,8 @@ export interface DeferredStats {
 	pending: number; recorded: number; launched: number; fused: number; fusedNodes: number; plain: number; dropped: number; fallbacks: number; lastFallback: string | null
 	/** frames that went to the device together with other channels' frames, several to a launch */
 	batched?: number
+	/** consumers' writes that came out of another write's launch as further outputs (multiWriter) */
+	multiOutputs?: number
 }
 
 export interface BufferStats {
@@ -91,12 +93,14 @@ export class clContext {
 	 * waitFinish(queue.process) returns at once - INTEGRATION.md 3a.
 	 * `profile` on a deferred context: a frame's terminal `write` is launched where it is posted and returns the fused launch's device time.
 	 * `earlyLaunch` (default false; PHANERON_EARLY_LAUNCH=1): launch a frame at the end of the tick that posted its terminal `write`.
+	 * `multiWriter` (default true; PHANERON_MULTI_WRITER=0): the pending `write` jobs of several consumers on ONE combined image (SDI plus an
+	 * encoder or the screen) are made by one launch of the channel kernel - one composition, a writer's phase per consumer; `false`: a launch per write.
 	 * `recycleBuffers` (default true; PHANERON_RECYCLE=0): released frames / images are parked for the next createBuffer of their shape,
 	 * up to `parkMb` MiB (default 4096) or the most that was ever in use at once.  A parked buffer is taken over as the same JS object;
 	 * `strictHandles` (default false; PHANERON_STRICT_HANDLES=1): a fresh object per takeover, so that a reference kept past release()
 	 * is refused ('... released buffer') instead of aliasing the next owner's buffer - for running an application under test. */
 	constructor(params?: { platformIndex?: number; deviceIndex?: number; overlapping?: boolean; profile?: boolean; spinWaitMicros?: number; deferred?: boolean;
-		earlyLaunch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
+		earlyLaunch?: boolean; multiWriter?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
 	readonly queue: { load: number; process: number; unload: number }
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo

@@ -158,6 +158,8 @@ class clContext {
 		// recording context: launch a frame's fused chain at the end of the tick that posted its terminal `write` instead of when somebody
 		// asks for the frame (node/defer.js: for hosts whose consumers map their frames long after posting them)
 		this.earlyLaunch = params.earlyLaunch === undefined ? process.env.PHANERON_EARLY_LAUNCH === '1' : !!params.earlyLaunch
+		// several consumers' writes of one combined image as outputs of ONE channel-kernel launch (node/defer.js _siblings); false: a launch per write
+		this.multiWriter = params.multiWriter === undefined ? process.env.PHANERON_MULTI_WRITER !== '0' : !!params.multiWriter
 		// released frames and images are parked and taken over whole by the next createBuffer of the same shape (free() above);
 		// `recycleBuffers: false` or PHANERON_RECYCLE=0 returns every buffer to the library at once.  parkMb: what may stay parked
 		// (default 4096 MiB - or as much as was ever in use at once, if that is more)

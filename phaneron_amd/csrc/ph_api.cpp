@@ -1613,6 +1613,101 @@ int ph_chan_compose(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, 
   return PH_OK;
 }
 
+/* Several consumers' frames of one composition in one launch: see include/phaneron_hip.h.  Every check is made before anything is
+ * launched; the checks and their texts are ph_chan_compose's, per output. */
+int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w,
+                          uint32_t out_h, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  if (!ctx || !layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "ph_chan_compose_multi: NULL argument");
+  if (n_out < 1 || n_out > ph::kMaxChanOuts) return fail(PH_E_INVALID, "ph_chan_compose_multi: 1..%d outputs (%d)", ph::kMaxChanOuts, n_out);
+  if (n_out == 1)
+    return ph_chan_compose(ctx, queue, n, layers, outs[0].format, outs[0].planes, out_w, out_h, outs[0].interlace, rd_cm, rd_lut, rd_gm, outs[0].wr_col_matrix12,
+                           outs[0].wr_gamma_lut);
+  PH_QUEUE("ph_chan_compose_multi", queue);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "ph_chan_compose_multi: 1..%d layers", ph::kMaxLayers);
+  if (!out_w) return fail(PH_E_INVALID, "ph_chan_compose_multi: width 0");
+  bool any_v210 = false, same_lines = true;
+  for (int k = 0; k < n_out; ++k) {
+    const ph_chan_output &o = outs[k];
+    if (!o.planes[0] || !o.wr_gamma_lut) return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: NULL argument", k);
+    if (!fmt_known(o.format)) return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: format %d is not a PH_FMT_*", k, o.format);
+    if (!fmt_chan_out(o.format)) return chan_out_refused("ph_chan_compose_multi", o.format);
+    if (!fmt_rgb8(o.format) && !o.wr_col_matrix12) return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: the writer's RGB -> YCbCr matrix is missing", k);
+    if (fmt_planar(o.format) && (!o.planes[1] || (fmt_planes(o.format) == 3 && !o.planes[2])))
+      return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: a planar output needs its three planes (nv12: Y and the interleaved CbCr plane)", k);
+    if (fmt_v420(o.format) && (out_h & 1)) return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: a 4:2:0 frame needs an even height (%u)", k, out_h);
+    if ((o.format == PH_FMT_V210 && (out_w & 1)) || (fmt_planar(o.format) && out_w % 8))
+      return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: width %u (a v210 frame needs an even width, a planar one a multiple of 8); run the separate kernels", k, out_w);
+    if (o.interlace != 0 && o.interlace != 1 && o.interlace != 3) return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: interlace must be 0, 1 or 3", k);
+    for (int j = 0; j < k; ++j)
+      if (outs[j].planes[0] == o.planes[0]) return fail(PH_E_INVALID, "ph_chan_compose_multi: outputs %d and %d name the same plane", j, k);
+    any_v210 = any_v210 || o.format == PH_FMT_V210;
+    same_lines = same_lines && o.interlace == outs[0].interlace;
+  }
+  const LutRef rref = lds_view(ctx, rd_lut);
+  if (!rref.get()) return fail(PH_E_INVALID, "ph_chan_compose_multi: the reader gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)");
+  LutRef wref[ph::kMaxChanOuts];
+  for (int k = 0; k < n_out; ++k) {
+    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
+    if (!wref[k].get())
+      return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", k);
+  }
+  ph::ChanMultiArgs m{};
+  ph::ChanArgs &a = m.c;
+  int n_ops = 0;
+  int rc = chan_ops(n, layers, out_w, out_h, a.op, a.plane_u, a.plane_v, a.cm_op, &a.planar, &n_ops);
+  if (rc) return rc;
+  a.n_ops = n_ops;
+  a.out_w = out_w, a.out_h = out_h;
+  // the lines composed: the field every output wants, or the whole frame (a field output then takes the index rows of its parity)
+  const uint32_t interlace = same_lines ? outs[0].interlace : 0u;
+  a.line_step = interlace ? 2 : 1, a.first_line = (interlace == 3) ? 1 : 0;
+  a.lines = interlace ? out_h / 2 : out_h;
+  a.rd_cm = (const float *)rd_cm, a.rd_gm = (const float *)rd_gm, a.rd = *rref.get();
+  a.out_tail_from = 0xFFFFFFFFu;
+  if (any_v210 && out_w % 48) {  // as ph_chan_compose: the tail instantiation writes lines that end in a tail / cleared slots
+    if (a.planar < 1) a.planar = 1;
+    if (out_w % 6) a.out_tail_from = out_w - out_w % 6u;
+  }
+  // the outputs grouped by writer table, in the order the tables first appear
+  int order[ph::kMaxChanOuts], placed = 0;
+  for (int k = 0; k < n_out; ++k) {
+    bool seen = false;
+    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    if (seen) continue;
+    for (int j = k; j < n_out; ++j)
+      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) order[placed++] = j;
+  }
+  m.n_out = (uint32_t)n_out;
+  for (int i = 0; i < n_out; ++i) {
+    const ph_chan_output &o = outs[order[i]];
+    ph::ChanOut &d = m.out[i];
+    d.fmt = (uint32_t)o.format;
+    d.pitch = o.format == PH_FMT_V210 ? ph_v210_pitch_bytes(out_w) / 16u : out_w;
+    d.plane[0] = o.planes[0], d.plane[1] = o.planes[1], d.plane[2] = o.planes[2];
+    d.tail_from = o.format == PH_FMT_V210 ? a.out_tail_from : 0xFFFFFFFFu;
+    d.takes = same_lines || !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
+    d.line_end = o.interlace ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as ph_chan_compose writes it)
+    d.field = o.interlace ? 1u : 0u;
+    d.round = o.format != PH_FMT_V210 && a.out_tail_from != 0xFFFFFFFFu ? 1u : 0u;
+    d.wr_cm = (const float *)(o.wr_col_matrix12 ? o.wr_col_matrix12 : rd_cm);
+    d.wr = *wref[order[i]].get();
+  }
+  a.wr = m.out[0].wr, a.wr_cm = m.out[0].wr_cm;
+  if (!a.lines) return PH_OK;
+  rc = set_device(ctx);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);
+  {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    rc = chan_index_reserve(ctx, queue, ph::chan_index_bytes(out_w, a.lines));
+    if (rc) return rc;
+    a.index = ctx->chan_index[queue];
+  }
+  hipError_t e = ph::launch_chan_compose_multi(stream_of(ctx, queue), m, (uint32_t)ctx->props.multiProcessorCount);
+  if (e != hipSuccess) return fail(PH_E_HIP, "ph_chan_compose_multi: launch failed: %s", hipGetErrorString(e));
+  return PH_OK;
+}
+
 /* Several channels' frames in one launch: see include/phaneron_hip.h.  Jobs the batch kernel does not take (planar / packed-RGB sources,
  * more ops or wave steps than one launch holds) run through ph_chan_compose_v210 in their turn, so the call as a whole is always the
  * `n_jobs` separate calls it stands for. */

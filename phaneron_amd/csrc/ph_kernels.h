@@ -118,6 +118,29 @@ struct ChanArgs {
   uint32_t images_only;           // launcher: every source is an f32 image (de-interlaced fields): nothing is looked up in the reader's table, it is not loaded
 };
 
+// Several consumers' frames of ONE composition in one launch (ph_chan_compose_multi): c describes the composition - the lines composed
+// are the union of what the outputs need, c.out* / c.wr* are unused - and every output brings its format, planes and writer recipe.
+// The launcher expects the outputs grouped by writer table.
+constexpr int kMaxChanOuts = 4;
+struct ChanOut {
+  uint32_t fmt;    // PH_FMT_* (one of fmt_chan_out)
+  uint32_t pitch;  // v210: quad slots per line; planar: luma samples per line; rgba8 / bgra8: pixels per line
+  void *plane[3];
+  uint32_t tail_from;  // v210: the first column of the line's tail (0xFFFFFFFF: none), as ChanArgs::out_tail_from
+  uint32_t takes;      // which of the composed lines are this output's: 0 all, 1 the even frame lines, 2 the odd ones
+  uint32_t line_end;   // lines from here on are not this output's (a field of a frame with an odd height)
+  uint32_t field;      // 1: a field write (4:2:0: the written line of a pair gives the chroma)
+  uint32_t round;      // 1: not v210, in a launch whose v210 output has a tail: tail pixels are parked truncated, with the rounding beside them
+  const float *wr_cm;
+  LutView wr;
+};
+struct ChanMultiArgs {
+  ChanArgs c;
+  uint32_t n_out;
+  ChanOut out[kMaxChanOuts];
+};
+static_assert(sizeof(ChanMultiArgs) < 4096, "kernel arguments are limited to 4 KiB");
+
 // Several channels' frames of ONE geometry and colour recipe in one launch (ph_chan_compose_batch) - what the reference runs: four
 // channels of <= 1080p in one context through one queue (src/index.ts:45-71,156-160, clJobQueue.ts:114-141).  A workgroup takes its
 // share of EVERY job, so the tables are loaded once and the wave steps of all jobs together are dealt to the waves in front of one
@@ -266,6 +289,7 @@ hipError_t launch_pack_write(hipStream_t s, int fmt, const void *in, void *const
 hipError_t launch_compose_write_v210(hipStream_t s, const ComposeArgs &a, uint32_t num_cus);
 size_t chan_index_bytes(uint32_t out_w, uint32_t lines);
 hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t num_cus);
+hipError_t launch_chan_compose_multi(hipStream_t s, const ChanMultiArgs &a, uint32_t num_cus);
 bool compose_can_wipe(const ComposeArgs &a);  // the buffer-addressed compositor serves this job (needed for wipe layers)
 hipError_t launch_v210_yadif_pair(hipStream_t s, DeintArgs a, int tff, uint32_t num_cus);
 hipError_t launch_yadif(hipStream_t s, const void *prev, const void *cur, const void *next, int w, int h, int parity,

@@ -757,7 +757,9 @@ __device__ __forceinline__ void chan_halo_pass(const ChanArgs &a, const ChanShar
 // graphics and f32 images; 2: planar YCbCr frames and f32
 // images only (a file decoder's clips, ffmpegProducer.ts:398-412: an instantiation without the v210 and packed-RGB samplers' code and scalar
 // state); TAILS: v210 frames (sources, output) may have lines that end in a tail
-template <bool STD, int SRC, bool TAILS, bool PSHARE = false>
+// DUAL (the several-outputs kernel): a pixel in a v210 line's tail is parked with the truncated index AND, in the spare upper half of its
+// second word, one bit per component that says whether the rounded index - what every other format's writer wants - is one higher
+template <bool STD, int SRC, bool TAILS, bool PSHARE = false, bool DUAL = false>
 __device__ __forceinline__ void chan_phase1(const ChanArgs &a, const ChanShare &sh, const ReadK &rk, const LutK &rlut) {
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   uint2 *const index = reinterpret_cast<uint2 *>(a.index);
@@ -834,7 +836,12 @@ __device__ __forceinline__ void chan_phase1(const ChanArgs &a, const ChanShare &
       auto index_of = [&](float t) __attribute__((always_inline)) {
         return __float_as_uint(TAILS ? lds_lut_index_unit_tail(t, trunc_idx) : lds_lut_index_unit(t)) & 0xFFFFu;
       };
-      const uint32_t ir = index_of(acc[p].r), ig = index_of(acc[p].g), ib = index_of(acc[p].b);
+      const uint32_t ir = index_of(acc[p].r), ig = index_of(acc[p].g);
+      uint32_t ib = index_of(acc[p].b);
+      if (TAILS && DUAL) {
+        auto up = [&](float t, uint32_t parked) __attribute__((always_inline)) { return (__float_as_uint(lds_lut_index_unit(t)) & 0xFFFFu) - parked; };
+        ib |= up(acc[p].r, ir) << 16 | up(acc[p].g, ig) << 17 | up(acc[p].b, ib) << 18;
+      }
       if (x < a.out_w) index[li[p] * a.out_w + x] = make_uint2(ir | (ig << 16), ib);  // (lanes beyond a short last chunk have nothing to park)
     }
   }
@@ -843,8 +850,14 @@ __device__ __forceinline__ void chan_phase1(const ChanArgs &a, const ChanShare &
 // PLANAR: the program has planar sources (an instantiation of its own: the v210 / image kernel is not touched by them)
 // the writer's phase for frames that are not v210 (FromRGBA with the Writers of the reference's other consumers: rgba8 for the screen,
 // screenConsumer.ts:131; yuv422p8 for an encoder, ffmpegConsumer.ts:144; yuv422p10).  Same indices, same table; what differs is the packing.
-template <int OUT>
-__device__ __forceinline__ void chan_phase2_other(const ChanArgs &a, const ChanShare &sh, const WriteK &wk, const LutK &wlut) {
+// A: ChanArgs, or one output of the several-outputs kernel (ChanOutView below).  What differs between the two is behind three small
+// functions: does the output take this line; is it a field write (4:2:0: the written line of a pair gives the chroma); and the rounded
+// index of a pixel that phase 1 parked truncated for a v210 output's tail.  For ChanArgs they are constants.
+__device__ __forceinline__ bool chan_out_takes(const ChanArgs &, uint32_t) { return true; }
+__device__ __forceinline__ bool chan_out_field(const ChanArgs &a) { return a.line_step == 2u; }
+__device__ __forceinline__ void chan_out_round(const ChanArgs &, uint32_t &, uint32_t &) {}
+template <int OUT, class A>
+__device__ __forceinline__ void chan_phase2_other(const A &a, const ChanShare &sh, const WriteK &wk, const LutK &wlut) {
   const uint2 *const index = reinterpret_cast<const uint2 *>(a.index);
   auto idx = [](uint32_t bits) __attribute__((always_inline)) { return __uint_as_float((bits & 0xFFFFu) | 0x4B400000u); };  // M + idx (ph_ldslut.h)
   if (fmt_rgb8(OUT)) {  // rgba8.ts:69-101: one pixel per lane, alpha 255
@@ -856,11 +869,13 @@ __device__ __forceinline__ void chan_phase2_other(const ChanArgs &a, const ChanS
       chan_place(a, sh, chunk, rp, x0);
       const uint32_t li = 2u * rp + (within >= kChanChunk ? 1u : 0u), x = x0 + (within >= kChanChunk ? within - kChanChunk : within);
       if (li >= a.lines || x >= a.out_w) continue;
-      const uint2 e = index[li * a.out_w + x];
+      const uint32_t line = a.first_line + li * a.line_step;
+      if (!chan_out_takes(a, line)) continue;
+      uint2 e = index[li * a.out_w + x];
+      chan_out_round(a, e.x, e.y);
       const PxPending pend = write_px_issue(idx(e.x), idx(e.x >> 16), idx(e.y), wlut);
       const float r = lds_lut_finish(pend.r), g = lds_lut_finish(pend.g), b = lds_lut_finish(pend.b);
       const uint32_t r8 = sat_u8_rte(r * 255.0f), g8 = sat_u8_rte(g * 255.0f), b8 = sat_u8_rte(b * 255.0f);
-      const uint32_t line = a.first_line + li * a.line_step;
       reinterpret_cast<uint32_t *>(a.out)[(size_t)line * a.out_pitch + x] = OUT == PH_FMT_RGBA8 ? (r8 | g8 << 8 | b8 << 16 | 0xff000000u) : (b8 | g8 << 8 | r8 << 16 | 0xff000000u);
     }
     return;
@@ -880,9 +895,13 @@ __device__ __forceinline__ void chan_phase2_other(const ChanArgs &a, const ChanS
     chan_place(a, sh, chunk, rp, x0);
     const uint32_t li = 2u * rp + (within >= kGroups ? 1u : 0u), x = x0 + 8u * (within >= kGroups ? within - kGroups : within);
     if (li >= a.lines || x >= a.out_w) continue;
+    const uint32_t line = a.first_line + li * a.line_step;
+    if (!chan_out_takes(a, line)) continue;
     const uint4 *const e4 = reinterpret_cast<const uint4 *>(index + li * a.out_w + x);
     const uint4 w0 = load_stream(e4), w1 = load_stream(e4 + 1), w2 = load_stream(e4 + 2), w3 = load_stream(e4 + 3);
-    const uint32_t pk[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
+    uint32_t pk[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) chan_out_round(a, pk[2 * j], pk[2 * j + 1]);
     uint32_t y[8], u[4], v[4];
 #pragma unroll
     for (int half = 0; half < 2; ++half) {  // four pixels' twelve table reads in flight at a time
@@ -898,14 +917,13 @@ __device__ __forceinline__ void chan_phase2_other(const ChanArgs &a, const ChanS
         if (!(p & 1)) u[p >> 1] = sat_u16_rte(dot4(gr, gg, gb, 1.0f, wk.u)), v[p >> 1] = sat_u16_rte(dot4(gr, gg, gb, 1.0f, wk.v));
       }
     }
-    const uint32_t line = a.first_line + li * a.line_step;
     const size_t o8 = ((size_t)line * a.out_pitch + x) >> 3;
     if (V420) {
       uint2 wy;
       wy.x = (y[0] & 0xff) | (y[1] & 0xff) << 8 | (y[2] & 0xff) << 16 | y[3] << 24;
       wy.y = (y[4] & 0xff) | (y[5] & 0xff) << 8 | (y[6] & 0xff) << 16 | y[7] << 24;
       reinterpret_cast<uint2 *>(a.out)[o8] = wy;
-      if (a.line_step == 2u || !(line & 1u)) {  // the line that gives its pair the chroma
+      if (chan_out_field(a) || !(line & 1u)) {  // the line that gives its pair the chroma
         const size_t c8 = ((size_t)(line >> 1) * a.out_pitch + x) >> 3;
         if (NV12) {
           uint2 wc;
@@ -934,6 +952,44 @@ __device__ __forceinline__ void chan_phase2_other(const ChanArgs &a, const ChanS
       reinterpret_cast<uint32_t *>(a.out_u)[o8] = (u[0] & 0xff) | (u[1] & 0xff) << 8 | (u[2] & 0xff) << 16 | u[3] << 24;
       reinterpret_cast<uint32_t *>(a.out_v)[o8] = (v[0] & 0xff) | (v[1] & 0xff) << 8 | (v[2] & 0xff) << 16 | v[3] << 24;
     }
+  }
+}
+
+// the writer's phase for v210 frames (A: as chan_phase2_other)
+template <bool TAILS, class A>
+__device__ __forceinline__ void chan_phase2_v210(const A &a, const ChanShare &sh, const WriteK &wk, const LutK &wlut) {
+  // phase 2: one quad per lane.  The indices were written by other waves of THIS workgroup: read past the L1.
+  // A line has out_qpitch quad slots.  Widths that are multiples of 48 fill them all; otherwise (the wire-format instantiation
+  // only) `full` whole quads are followed by the tail quad (v210.ts:169-194) and by slots the reference's writer clears (:131-136).
+  const uint32_t qpl = a.out_qpitch, full = a.out_w / 6u, remain = a.out_w - 6u * full;
+  const uint4 *const index = reinterpret_cast<const uint4 *>(a.index);
+  for (uint32_t q = threadIdx.x; q < 64u * sh.slots; q += kLdsBlock) {
+    const uint32_t chunk = chan_chunk(a, sh, q >> 6);
+    if (chunk == ~0u) continue;
+    uint32_t rp, x0;
+    chan_place(a, sh, chunk, rp, x0);
+    const uint32_t li = 2u * rp + ((q >> 5) & 1u);  // quads 0..31 of a chunk: its upper row, 32..63: its lower row
+    const uint32_t g = x0 / 6u + (q & 31u);
+    if (li >= a.lines || g >= qpl) continue;
+    const uint32_t line = a.first_line + li * a.line_step;
+    if (!chan_out_takes(a, line)) continue;
+    uint4 *const dst = reinterpret_cast<uint4 *>(a.out) + (size_t)line * qpl + g;
+    if (TAILS && g > full - (remain ? 0u : 1u)) {  // past the line's pixels
+      store_stream(dst, make_uint4(0u, 0u, 0u, 0u));
+      continue;
+    }
+    const uint32_t first_px = li * a.out_w + x0 + (q & 31u) * 6u;
+    const uint4 w0 = load_stream(index + (first_px >> 1)), w1 = load_stream(index + (first_px >> 1) + 1), w2 = load_stream(index + (first_px >> 1) + 2);
+    const uint32_t pk[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
+    float yi[18];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {  // M + idx: the index ORed into the mantissa of 1.5 * 2^23 (ph_ldslut.h)
+      yi[3 * j] = __uint_as_float((pk[2 * j] & 0xFFFFu) | 0x4B400000u);
+      yi[3 * j + 1] = __uint_as_float((pk[2 * j] >> 16) | 0x4B400000u);
+      yi[3 * j + 2] = __uint_as_float((pk[2 * j + 1] & 0xFFFFu) | 0x4B400000u);
+    }
+    if (TAILS && g == full) store_stream(dst, write_quad_idx_lds_tail(yi, wk, wlut, remain));  // (the index frame is padded: the tail's loads stay inside)
+    else store_stream(dst, write_quad_idx_lds(yi, wk, wlut));
   }
 }
 
@@ -977,39 +1033,76 @@ __global__ __launch_bounds__(kLdsBlock) void chan_compose_v210_kernel(ChanArgs a
     chan_phase2_other<OUT>(a, sh, wk, wlut);
     return;
   }
-  // phase 2: one quad per lane.  The indices were written by other waves of THIS workgroup: read past the L1.
-  // A line has out_qpitch quad slots.  Widths that are multiples of 48 fill them all; otherwise (the wire-format instantiation
-  // only) `full` whole quads are followed by the tail quad (v210.ts:169-194) and by slots the reference's writer clears (:131-136).
-  const uint32_t qpl = a.out_qpitch, full = a.out_w / 6u, remain = a.out_w - 6u * full;
-  const uint4 *const index = reinterpret_cast<const uint4 *>(a.index);
-  for (uint32_t q = threadIdx.x; q < 64u * sh.slots; q += kLdsBlock) {
-    const uint32_t chunk = chan_chunk(a, sh, q >> 6);
-    if (chunk == ~0u) continue;
-    uint32_t rp, x0;
-    chan_place(a, sh, chunk, rp, x0);
-    const uint32_t li = 2u * rp + ((q >> 5) & 1u);  // quads 0..31 of a chunk: its upper row, 32..63: its lower row
-    const uint32_t g = x0 / 6u + (q & 31u);
-    if (li >= a.lines || g >= qpl) continue;
-    const uint32_t line = a.first_line + li * a.line_step;
-    uint4 *const dst = reinterpret_cast<uint4 *>(a.out) + (size_t)line * qpl + g;
-    if (TAILS && g > full - (remain ? 0u : 1u)) {  // past the line's pixels
-      store_stream(dst, make_uint4(0u, 0u, 0u, 0u));
-      continue;
-    }
-    const uint32_t first_px = li * a.out_w + x0 + (q & 31u) * 6u;
-    const uint4 w0 = load_stream(index + (first_px >> 1)), w1 = load_stream(index + (first_px >> 1) + 1), w2 = load_stream(index + (first_px >> 1) + 2);
-    const uint32_t pk[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
-    float yi[18];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {  // M + idx: the index ORed into the mantissa of 1.5 * 2^23 (ph_ldslut.h)
-      yi[3 * j] = __uint_as_float((pk[2 * j] & 0xFFFFu) | 0x4B400000u);
-      yi[3 * j + 1] = __uint_as_float((pk[2 * j] >> 16) | 0x4B400000u);
-      yi[3 * j + 2] = __uint_as_float((pk[2 * j + 1] & 0xFFFFu) | 0x4B400000u);
-    }
-    if (TAILS && g == full) store_stream(dst, write_quad_idx_lds_tail(yi, wk, wlut, remain));  // (the index frame is padded: the tail's loads stay inside)
-    else store_stream(dst, write_quad_idx_lds(yi, wk, wlut));
-  }
+  chan_phase2_v210<TAILS>(a, sh, wk, wlut);
   PH_CPHASE(5);
+}
+
+// ---- several consumers' frames of ONE composition per launch ---------------------------------------------------------------------------
+// A channel's consumers each run their own FromRGBA on the one combined image (channel.ts:64-88: v210 for SDI, yuv422p8 for an encoder,
+// rgba8 for the screen).  Phase 1 - everything up to the index frame - does not depend on the consumer, so it runs once, for the union of
+// the lines the outputs need; phase 2 then runs once per output on the same indices.  Outputs arrive grouped by writer table: a table that
+// is already in the LDS is not loaded again.
+struct ChanOutView {  // one output with the field names the phase-2 functions read from ChanArgs
+  const void *index;
+  uint32_t out_w, lines, first_line, line_step, magic_cpr, magic_cpg;
+  void *out, *out_u, *out_v;
+  uint32_t out_pitch, out_qpitch;
+  uint32_t takes, line_end, field, round;
+};
+__device__ __forceinline__ bool chan_out_takes(const ChanOutView &a, uint32_t line) {
+  return line < a.line_end && (a.takes == 0u || (line & 1u) + 1u == a.takes);
+}
+__device__ __forceinline__ bool chan_out_field(const ChanOutView &a) { return a.field != 0u; }
+__device__ __forceinline__ void chan_out_round(const ChanOutView &a, uint32_t &rg, uint32_t &b) {
+  if (!a.round) return;  // uniform: no v210 output with a tail in this launch
+  rg += ((b >> 16) & 1u) + ((b >> 17) & 1u) * 0x10000u;
+  b = (b & 0xFFFFu) + ((b >> 18) & 1u);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kLdsBlock) void chan_compose_multi_kernel(ChanMultiArgs m) {
+  constexpr int SRC = MODE == 2 ? 1 : MODE == 5 ? 3 : MODE >= 3 ? 2 : 0;
+  constexpr bool TAILS = MODE >= 1, PSHARE = MODE == 4;
+  const ChanArgs &a = m.c;
+  const ReadK rk = load_read_k(a.rd_cm, a.rd_gm);
+  const LutK rlut = make_lut_k(a.rd);
+  const ChanShare sh = chan_share(a);
+  if (!a.images_only) lds_lut_load(a.rd);
+  __syncthreads();
+  if (ycbcr_matrix_is_standard(rk) && !(SRC >= 1 && a.any_cm)) {
+    chan_halo_pass<true, TAILS, SRC>(a, sh, rk, rlut);
+    chan_phase1<true, SRC, TAILS, PSHARE, true>(a, sh, rk, rlut);
+  } else {
+    chan_halo_pass<false, TAILS, SRC>(a, sh, rk, rlut);
+    chan_phase1<false, SRC, TAILS, PSHARE, true>(a, sh, rk, rlut);
+  }
+  const uint32_t *resident = nullptr;
+  // (unrolled: with the output's index a run-time value the compiler keeps a 20-byte stack slot that nothing uses - modes 0 and 1 would
+  // claim scratch memory that the one-output kernels do not)
+#pragma unroll
+  for (uint32_t k = 0; k < (uint32_t)kMaxChanOuts; ++k) {
+    if (k >= m.n_out) break;  // uniform
+    const ChanOut &o = m.out[k];
+    if (o.wr.blob != resident) {  // uniform.  The barrier in front: every index is stored and nobody reads the table in the LDS any more
+      __syncthreads();
+      lds_lut_load(o.wr);
+      __syncthreads();
+      resident = o.wr.blob;
+    }
+    const WriteK wk = load_write_k(o.wr_cm);
+    const LutK wlut = make_lut_k(o.wr);
+    const ChanOutView v{a.index, a.out_w, a.lines, a.first_line, a.line_step, a.magic_cpr, a.magic_cpg, o.plane[0], o.plane[1], o.plane[2],
+                        o.pitch, o.pitch, o.takes, o.line_end, o.field, o.round};
+    switch (o.fmt) {  // uniform
+      case PH_FMT_V210: chan_phase2_v210<TAILS>(v, sh, wk, wlut); break;
+      case PH_FMT_YUV422P10: chan_phase2_other<PH_FMT_YUV422P10>(v, sh, wk, wlut); break;
+      case PH_FMT_YUV422P8: chan_phase2_other<PH_FMT_YUV422P8>(v, sh, wk, wlut); break;
+      case PH_FMT_YUV420P: chan_phase2_other<PH_FMT_YUV420P>(v, sh, wk, wlut); break;
+      case PH_FMT_NV12: chan_phase2_other<PH_FMT_NV12>(v, sh, wk, wlut); break;
+      case PH_FMT_RGBA8: chan_phase2_other<PH_FMT_RGBA8>(v, sh, wk, wlut); break;
+      case PH_FMT_BGRA8: chan_phase2_other<PH_FMT_BGRA8>(v, sh, wk, wlut); break;
+    }
+  }
 }
 
 // ---- several channels' frames per launch ------------------------------------------------------------------------------------------
@@ -1358,13 +1451,18 @@ hipError_t launch_chan_compose_batch(hipStream_t s, const ChanBatchArgs &a, uint
 
 size_t chan_index_bytes(uint32_t out_w, uint32_t lines) { return (size_t)out_w * lines * 8u + 64u; }  // + a tail quad's reach past the last line
 
-hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t num_cus) {
-  if (!a.lines) return hipSuccess;
-  const uint32_t lds = a.rd.bytes > a.wr.bytes ? a.rd.bytes : a.wr.bytes;
+// What a launch of the one-frame kernels needs beside its arguments: the grid, the dynamic LDS and the phase-1 instantiation.  `b` gets the
+// launcher's fields (reciprocals, any_cm, images_only, the tap-sharing marks); lds: the larger of the tables the launch loads; lean_out: the
+// frame is one of the formats the lean phase-1 modes are instantiated for
+struct ChanPlan {
+  uint32_t grid, lds_total;
+  bool planar_share, clips_only, graphics;
+};
+static ChanPlan chan_plan(const ChanArgs &a, ChanArgs &b, uint32_t lds, bool lean_out, uint32_t num_cus) {
   const uint32_t cpr = (a.out_w + kChanChunk - 1u) / kChanChunk, cpg = (uint32_t)(PH_CHAN_GROUP_ROWS / 2) * cpr;
   const uint32_t chunks = cpr * ((a.lines + 1u) / 2u);  // 192 pixels x 2 rows each (a row's last chunk may be short)
   const uint32_t want = chunks;                         // a workgroup per chunk at most: 6 wave steps
-  ChanArgs b = a;
+  b = a;
   // reciprocals for the kernel's uniform divisions: umulhi(v, ceil(2^32 / d)) == v / d for every v * d < 2^32 (chunk counts are far below)
   b.magic_cpr = cpr > 1 ? (uint32_t)(((1ull << 32) + cpr - 1) / cpr) : 0u;
   b.magic_cpg = (uint32_t)(((1ull << 32) + cpg - 1) / cpg);
@@ -1377,7 +1475,6 @@ hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t n
   // Planar YCbCr clips share their taps in an instantiation of its own (mode 4): taken when the program has nothing but such clips and
   // f32 images, makes a v210 frame, and at least half of its ops are clips at their own scale (a full-frame clip; not config 2's one
   // background under three insets and a wipe: there the plain loop's better register allocation is worth more, 61.5 against 68.7 us)
-  const bool lean_out = a.out_fmt == PH_FMT_V210 || a.out_fmt == PH_FMT_YUV422P8 || a.out_fmt == PH_FMT_RGBA8;  // SDI, an encoder, the screen: the reference's three consumers
   bool clips_only = a.planar == 2 && lean_out;
   uint32_t own_scale = 0;
   for (int k = 0; k < b.n_ops; ++k) {
@@ -1427,6 +1524,16 @@ hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t n
     }
     if (n_share) b.halo_steps = steps, lds_total = b.halo_off + n_share * steps * 36u;
   }
+  return ChanPlan{grid, lds_total, planar_share, clips_only, graphics};
+}
+
+hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t num_cus) {
+  if (!a.lines) return hipSuccess;
+  const bool lean_out = a.out_fmt == PH_FMT_V210 || a.out_fmt == PH_FMT_YUV422P8 || a.out_fmt == PH_FMT_RGBA8;  // SDI, an encoder, the screen: the reference's three consumers
+  ChanArgs b;
+  const ChanPlan plan = chan_plan(a, b, a.rd.bytes > a.wr.bytes ? a.rd.bytes : a.wr.bytes, lean_out, num_cus);
+  const uint32_t grid = plan.grid, lds_total = plan.lds_total;
+  const bool planar_share = plan.planar_share, clips_only = plan.clips_only, graphics = plan.graphics;
   // (route trace: the instantiation is part of the route - <phase-1 mode, output format>)
   auto go = [&](auto kernel, int mode, int out_fmt) -> hipError_t {
     char name[48];
@@ -1459,6 +1566,30 @@ hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t n
   }
 #undef PH_CHAN_GO
   return hipErrorInvalidValue;
+}
+
+// Several consumers' frames of one composition: the phase-1 mode is the one a v210 frame of the program gets (phase 1 does not depend on
+// the frame's format), the LDS holds the largest table of the call
+hipError_t launch_chan_compose_multi(hipStream_t s, const ChanMultiArgs &m, uint32_t num_cus) {
+  if (!m.c.lines) return hipSuccess;
+  if (m.n_out < 1 || m.n_out > (uint32_t)kMaxChanOuts) return hipErrorInvalidValue;
+  uint32_t lds = m.c.rd.bytes;
+  for (uint32_t k = 0; k < m.n_out; ++k) lds = m.out[k].wr.bytes > lds ? m.out[k].wr.bytes : lds;
+  ChanMultiArgs b = m;
+  const ChanPlan plan = chan_plan(m.c, b.c, lds, true, num_cus);
+  auto go = [&](auto kernel, int mode) -> hipError_t {
+    char name[48];
+    snprintf(name, sizeof name, "chan_compose_multi<%d>x%u", mode, m.n_out);
+    if (trace_launch(name)) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
+    if (e != hipSuccess) return e;
+    kernel<<<plan.grid, kLdsBlock, plan.lds_total, s>>>(b);
+    return hipGetLastError();
+  };
+  if (m.c.planar == 2)
+    return plan.planar_share ? go(chan_compose_multi_kernel<4>, 4) : plan.clips_only ? go(chan_compose_multi_kernel<3>, 3)
+           : plan.graphics   ? go(chan_compose_multi_kernel<5>, 5) : go(chan_compose_multi_kernel<2>, 2);
+  return m.c.planar == 1 ? go(chan_compose_multi_kernel<1>, 1) : go(chan_compose_multi_kernel<0>, 0);
 }
 
 }  // namespace ph

@@ -234,6 +234,10 @@ struct ChanCall {
   uint32_t width, height, interlace;
   void *out_planes[3];
   Recipe r;
+  // chan_compose_multi_<n>: every output as ph_chan_compose_multi takes it (outs[0]: the one above)
+  bool multi;  // the program is chan_compose_multi_<n>
+  int n_out;
+  ph_chan_output outs[ph::kMaxChanOuts];
 };
 // l<i>In: a layer's source - a v210 frame (l<i>Width / l<i>Height: its size, default the output's) or an RGBA image buffer;
 // l<i>Matrix (optional): its placement, a buffer whose host mirror holds the nine floats (Transform writes it through
@@ -275,6 +279,30 @@ static void chan_source_parse(Args &a, int i, const char *role, uint32_t width, 
   s->width = (int)sw, s->height = (int)sh;
   if (const ph_buf *m = a.buf_or_null(36, "l%d%sMatrix", i, role)) s->matrix9_host = a.host_matrix(m);
 }
+// One output of a channel's frame.  Output 0 is named as chan_compose_v210_<n> names its only one (outPacking, output, outputU / V / C,
+// outColMatrix, outGammaLut, interlace); output k = 1..3 of chan_compose_multi_<n> puts its number behind the first word (out<k>Packing,
+// output<k>, output<k>U ..., out<k>ColMatrix, out<k>GammaLut, interlace<k>).  The same reads, checks and texts for all of them.
+static int chan_output_parse(Args &a, int k, uint32_t width, uint32_t height, ph_chan_output *o, ph_buf **wr_cm, ph_buf **wr_lut, Recipe *loader = nullptr) {
+  char num[4] = "", packing_arg[48], refused[80], prefix[16];
+  if (k) snprintf(num, sizeof num, "%d", k);
+  snprintf(packing_arg, sizeof packing_arg, "out%sPacking", num);
+  snprintf(prefix, sizeof prefix, "output%s", num);
+  // the packed frame - v210, or with outPacking = PH_FMT_* another wire format: 1 yuv422p10 / 2 yuv422p8 / 3 yuv420p (output = the Y
+  // plane, outputU, outputV), 4 nv12 (output, outputC), 5 rgba8 / 6 bgra8 (no outColMatrix)
+  const double out_packing = a.num_or(0, "%s", packing_arg);
+  const int ofmt = (int)out_packing;
+  if (!fmt_known(ofmt)) return a.fail(PH_E_INVALID, "kernel argument '%s': %g is not a pack format", packing_arg, out_packing);
+  snprintf(refused, sizeof refused, "kernel argument '%s'", packing_arg);
+  if (!a.rc && !fmt_chan_out(ofmt)) return a.rc = chan_out_refused(refused, ofmt);
+  o->planes[0] = o->planes[1] = o->planes[2] = nullptr;
+  if (a.planes(ofmt, width, height, prefix, "", o->planes) < 0) return a.fail(PH_E_INVALID, "kernel argument '%s': %g is not a pack format", packing_arg, out_packing);
+  if (loader) a.loader(loader);  // (output 0: the Loader's triple is read here, between the frame and the Saver's pair, as it always was)
+  *wr_cm = fmt_rgb8(ofmt) ? nullptr : a.buf(48, "out%sColMatrix", num);
+  *wr_lut = a.table("out%sGammaLut", num);
+  o->format = ofmt, o->interlace = (uint32_t)a.num_or(0, "interlace%s", num);
+  o->wr_col_matrix12 = dptr(*wr_cm), o->wr_gamma_lut = (*wr_lut)->dptr;
+  return a.rc;
+}
 static int chan_call_parse(Args &a, ChanCall *call) {
   const int n_layers = a.prog->n_layers;
   uint32_t width, height;
@@ -287,18 +315,17 @@ static int chan_call_parse(Args &a, ChanCall *call) {
     if (l.transition != PH_TRANSITION_CUT) chan_source_parse(a, i, "Incoming", width, height, &l.incoming);
     if (l.transition == PH_TRANSITION_WIPE) chan_source_parse(a, i, "Mask", width, height, &l.mask);
   }
-  // output: the packed frame - v210, or with outPacking = PH_FMT_* another wire format: 1 yuv422p10 / 2 yuv422p8 / 3 yuv420p (output =
-  // the Y plane, outputU, outputV), 4 nv12 (output, outputC), 5 rgba8 / 6 bgra8 (no outColMatrix)
-  const double out_packing = a.num_or(0, "outPacking");
-  const int ofmt = (int)out_packing;
-  if (!fmt_known(ofmt)) return a.fail(PH_E_INVALID, "kernel argument 'outPacking': %g is not a pack format", out_packing);
-  if (!a.rc && !fmt_chan_out(ofmt)) return a.rc = chan_out_refused("kernel argument 'outPacking'", ofmt);
-  call->out_planes[0] = call->out_planes[1] = call->out_planes[2] = nullptr;
-  if (a.planes(ofmt, width, height, "output", "", call->out_planes) < 0) return a.fail(PH_E_INVALID, "kernel argument 'outPacking': %g is not a pack format", out_packing);
   call->r = Recipe();
-  a.loader(&call->r);
-  a.saver(&call->r, !fmt_rgb8(ofmt));
-  call->interlace = (uint32_t)a.num_or(0, "interlace");
+  chan_output_parse(a, 0, width, height, &call->outs[0], &call->r.wr_cm, &call->r.wr_lut, &call->r);
+  call->n_out = 1;
+  call->multi = a.prog->kernel.compare(0, 19, "chan_compose_multi_") == 0;
+  if (call->multi) {  // the outputs named, in turn
+    ph_buf *wr_cm, *wr_lut;
+    for (int k = 1; k < ph::kMaxChanOuts && !a.rc && a.has("output%d", k); ++k) chan_output_parse(a, k, width, height, &call->outs[call->n_out++], &wr_cm, &wr_lut);
+  }
+  const int ofmt = call->outs[0].format;
+  for (int p = 0; p < 3; ++p) call->out_planes[p] = call->outs[0].planes[p];
+  call->interlace = call->outs[0].interlace;
   call->n_layers = n_layers, call->out_format = ofmt, call->width = width, call->height = height;
   return a.rc;
 }
@@ -499,8 +526,12 @@ static int dispatch_compose(Args &a, int queue) {
     case K_CHAN_COMPOSE: {
       ChanCall call;
       chan_call_parse(a, &call);
-      return a.done() ? a.rc : ph_chan_compose(ctx, queue, call.n_layers, call.layers, call.out_format, call.out_planes, call.width, call.height, call.interlace,
-                                               call.r.rd_cm->dptr, call.r.rd_lut->dptr, call.r.rd_gm->dptr, dptr(call.r.wr_cm), call.r.wr_lut->dptr);
+      if (a.done()) return a.rc;
+      if (call.multi)  // chan_compose_multi_<n>: chan_compose_v210_<n>'s arguments (output 0) and up to three more outputs (chan_output_parse)
+        return ph_chan_compose_multi(ctx, queue, call.n_layers, call.layers, call.n_out, call.outs, call.width, call.height, call.r.rd_cm->dptr, call.r.rd_lut->dptr,
+                                     call.r.rd_gm->dptr);
+      return ph_chan_compose(ctx, queue, call.n_layers, call.layers, call.out_format, call.out_planes, call.width, call.height, call.interlace,
+                             call.r.rd_cm->dptr, call.r.rd_lut->dptr, call.r.rd_gm->dptr, dptr(call.r.wr_cm), call.r.wr_lut->dptr);
     }
     case K_COMPOSE_UP: {
       UpCall u;
@@ -668,7 +699,8 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * ph_run_program calls in the order given - with the channel frames among them (chan_compose_v210_<n> programs of one geometry that name
  * the SAME Loader / Saver buffers and make v210 frames) put into launches together (ph_chan_compose_batch), likewise consecutive
  * fused_v210_combine_<n> frames; a job that reads or writes what an earlier job of its group writes (or writes what one reads) is
- * detected here and starts the next launch, so call order holds (include/phaneron_hip.h).  A call that fails after its checks
+ * detected here and starts the next launch, so call order holds (include/phaneron_hip.h).  A chan_compose_multi_<n> job runs in its turn
+ * as a launch of its own - it ends the group in front of it, so whatever that group writes is there for it, and all its outputs for what follows.  A call that fails after its checks
  * (a launch refused) has made the launches of the jobs before the failing group: ph_run_programs_progress says how many. */
 namespace {
 thread_local int g_programs_done = 0;  // jobs of the calling thread's last ph_run_programs call whose launches were made
@@ -695,7 +727,7 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
     Args job{ctx, progs[j], args[j], n_args[j], false};
     if (progs[j]->id == K_CHAN_COMPOSE) {
       if ((rc = chan_call_parse(job, &calls[(size_t)j]))) return rc;
-      kind[(size_t)j] = calls[(size_t)j].out_format == PH_FMT_V210;
+      kind[(size_t)j] = calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi;  // (a chan_compose_multi_<n> job: a launch of its own, in its turn)
     } else if (progs[j]->id == K_FUSED_V210) {
       if ((rc = fused_call_parse(job, &fused[(size_t)j]))) return rc;
       kind[(size_t)j] = 2;
