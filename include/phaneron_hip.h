@@ -41,7 +41,8 @@ extern "C" {
  * 8: additive over 7 - ph_trace_begin / ph_trace_end (which kernels made a frame; dry runs); ph_run_programs_progress; ph_buf_reuse; ph_image_unpack_rgb (program "rgb_unpack").
  *    Later additive within 8: the 10-bit 4:2:0 formats PH_FMT_YUV420P10 / PH_FMT_P010 and PH_SRC_YUV420P10 / PH_SRC_P010 - new enum
  *    values an older binding never passes; no signature or struct changed.  ph_chan_compose_multi (ph_chan_output): several consumers'
- *    frames of one channel in one launch; program "chan_compose_multi_<n>" */
+ *    frames of one channel in one launch; program "chan_compose_multi_<n>".  ph_compose_up_write_multi: the same for the 2 x 2-block
+ *    compositor (enlarged images), with every writer the channel kernel has */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -258,7 +259,11 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * that touches an earlier one's output starts the next launch), and consecutive compose_up_write_v210_<n> jobs of one shape - layer count,
  * image format and sizes, placements, frame size, field mode, Saver - each one frame or a frame's two fields (ph_compose_up_write_v210_batch, up to four frames
  * per launch).  A chan_compose_multi_<n> job - chan_compose_v210_<n>'s arguments for output 0 and, for outputs k = 1..3, out<k>Packing,
- * output<k> (output<k>U / V / C), out<k>ColMatrix, out<k>GammaLut, interlace<k>: ph_chan_compose_multi - runs in its turn as a launch of its own. */
+ * output<k> (output<k>U / V / C), out<k>ColMatrix, out<k>GammaLut, interlace<k>: ph_chan_compose_multi - runs in its turn as a launch of its own.
+ * So does a compose_up_multi_<n> job (ph_compose_up_write_multi): compose_up_write_v210_<n>'s layers (l<i>In, l<i>Matrix, packedRgb,
+ * l<i>Width / l<i>Height) and chan_compose_multi_<n>'s outputs.  Its twin - the other field of a de-interlaced frame - is announced by
+ * l0In2 (l<i>In2: its images), and its planes carry the first job's names behind the word twin: twinOutput (twinOutputU / V / C),
+ * twinOutput<k> (twinOutput<k>U / V / C) - `output2` being output 2's frame here. */
 int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_arg *const *args, const int *n_args, int queue);
 /* How far the calling thread's LAST ph_run_programs call got: the launches of jobs 0 .. *jobs_done - 1 were made (n_jobs after a call
  * that returned PH_OK, 0 after one refused by its checks).  A call that fails at a launch has enqueued the jobs before the failing
@@ -553,6 +558,28 @@ typedef struct ph_chan_output {
 int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs,
                           uint32_t out_width, uint32_t out_height, const void *rd_col_matrix12, const void *rd_gamma_lut,
                           const void *rd_gamut9);
+/* Several consumers' frames of one ENLARGED composition in one launch: the 2 x 2-block compositor (ph_compose_up_write_v210) with any
+ * writer the channel kernel has - v210, yuv422p10, yuv422p8, yuv420p, nv12, rgba8, bgra8 - and up to four outputs.  The composition
+ * runs once; the block's twelve writer-table reads are made once, and every output packs the same twelve values with its own writer
+ * matrix.  A screen (rgba8) or an encoder (yuv422p8) beside the SDI output of a channel whose sources are de-interlaced fields
+ * (ph_v210_yadif_pair_fmt, packed RGB) costs no further launch, and no ph_image_unpack_rgb of the fields.
+ * outs: jobs x n_out entries, job-major; entry [j][k] differs from [0][k] in its planes only.  jobs: 1..4 sets of layers that differ
+ * in their data only, as ph_compose_up_write_v210_batch (the bound is the kernel's argument block: 4 jobs x 4 outputs x 3 planes).
+ * Exactly the jobs x n_out separate frames, bit for bit: ph_compose_up_write_v210 for a v210 output, ph_transform x n + ph_combine +
+ * ph_pack_write for the others.
+ * Lines: if every output of a launch wants the same `interlace`, that field's rows are composed; otherwise the whole frame, a field
+ * output taking the rows of its parity.  The placement must qualify (as ph_compose_up_write_v210) on the geometry that is composed.
+ * Launches: outputs that name the same registered writer table share a launch ("compose_up_multi<rgb|rgba>x<outputs>j<jobs>" in a
+ * trace); a call whose outputs name different tables is one launch per table, outputs keeping their order.  A v210 output whose
+ * lines end in a tail quad (width % 48 != 0) truncates its table indices there where every other writer rounds: it is split off into
+ * a launch of today's kernel ("compose_up_write_v210"), as is a v210 output that is alone with its table - so jobs = 1, n_out = 1,
+ * PH_FMT_V210 IS ph_compose_up_write_v210.
+ * PH_E_INVALID: a placement that does not qualify; a format the channel kernel does not write (yuv420p10, p010); an odd width, a
+ * planar output whose width is not a multiple of 8, a 4:2:0 output with an odd height; n_out outside 1..4, jobs outside 1..4; two
+ * outputs, of any job, naming the same first plane; a writer table that is not registered; layers of different image formats.
+ * A refused call writes nothing. */
+int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, int n_out,
+                              const ph_chan_output *outs, uint32_t out_width, uint32_t out_height);
 
 /* ---- gamma LUT placement.  The reference hands its kernels a 65536-entry f32 `gammaLut` buffer
  *      (loadSave.ts:65-73,152-160) and gathers from it 3x per pixel.  Registering the table's

@@ -54,6 +54,9 @@ const LAYER_MASK = LAYER_PREFIX.map((p) => `${p}Mask`)
 const NONE = Object.freeze([])
 const pushNew = (list, v) => { if (!list.includes(v)) list.push(v) }
 
+// what `upWriters` is where the context does not say: see the constructor
+const UP_WRITERS_DEFAULT = { alone: true, several: true } // (both measured 4 - 6 x faster than today's launches: profiles/up_out_bench.jsonl)
+
 class Deferral {
 	constructor(ctx) {
 		this.ctx = ctx // the clContext: _native, _ctx, queue, createProgram
@@ -91,6 +94,12 @@ class Deferral {
 		// Several consumers' writes of ONE combined image (a channel's consumer list: channel.ts:64-88 - SDI plus an encoder or the screen)
 		// as outputs of one chan_compose_multi_<n> launch: see _siblings.  `multiWriter: false` on the context: every write its own launch.
 		this.multiWriter = ctx.multiWriter !== false
+		// Frames of the 2 x 2-block compositor (de-interlaced fields at their own size or enlarged) for consumers other than SDI, and for
+		// several consumers at once: compose_up_multi_<n> (ph_compose_up_write_multi) from the packed fields, ahead of today's candidates
+		// (fields unpacked, the channel kernel, a launch per consumer).  Per class of frame - `alone`: one consumer that is not SDI;
+		// `several`: sibling writes of one image folded into the launch - on where it measured faster by more than the separate side's
+		// spread (profiles/up_out_bench.jsonl, DESIGN.md 5.1).  `upWriters: true / false` on the context sets both.
+		this.upWriters = ctx.upWriters === undefined || ctx.upWriters === null ? Object.assign({}, UP_WRITERS_DEFAULT) : { alone: !!ctx.upWriters, several: !!ctx.upWriters }
 	}
 
 	// ---- bookkeeping on buffers -----------------------------------------------------------------------------
@@ -378,6 +387,8 @@ class Deferral {
 		if (plan.node.state !== 'pending') return false
 		for (const u of plan.used) if (u.state !== 'pending') return false
 		if (plan.siblings) for (const w of plan.siblings) if (w.state !== 'pending') return false // (a sibling write ran or was dropped in between: plan again)
+		// (a compose_up_multi_<n> plan that was told packedRgb: a field somebody - another consumer's launch - has unpacked since is an RGBA image)
+		if (plan.packedSources) for (const b of plan.packedSources) if (b._packed == null) return false
 		return true
 	}
 	// several channel frames in one launch: every plan's first candidate with the FIRST plan's Loader / Saver buffers (equal contents)
@@ -610,7 +621,8 @@ class Deferral {
 		for (const l of layers) { const t = this.fieldTwin.get(l.source); if (!t || t._producer || t._failed) return null }
 		const sameWrite = (w) => w !== node && w.state === 'pending' && w.program.name === 'write' && w.program.format === node.program.format &&
 			w.program.workItemsPerGroup === node.program.workItemsPerGroup && w.program.globalWorkItems[0] === node.program.globalWorkItems[0] &&
-			(w.params.interlace || 0) === (node.params.interlace || 0) && w.params.output && w.params.output !== node.params.output &&
+			(w.params.interlace || 0) === (node.params.interlace || 0) && (w.params.output || w.params.outputY) && // (a planar frame: its Y plane)
+			(w.params.output || w.params.outputY) !== (node.params.output || node.params.outputY) &&
 			Deferral.same(w.params.colMatrix, node.params.colMatrix) && Deferral.same(w.params.gammaLut, node.params.gammaLut)
 		const placedTwin = (img, l) => { // img: a layer of the other frame; l: this frame's layer in that position
 			const p = img && img._producer
@@ -628,7 +640,7 @@ class Deferral {
 					for (const w of c.params.output._readers) if (sameWrite(w) && w.params.input === c.params.output) write = w
 				}
 				if (!write || images.some((im, i) => !placedTwin(im, layers[i]))) continue
-				return { node: write, output: write.params.output, sources: layers.map((l) => this.fieldTwin.get(l.source)) }
+				return { node: write, output: write.params.output || write.params.outputY, sources: layers.map((l) => this.fieldTwin.get(l.source)) }
 			}
 		}
 		return null
@@ -689,7 +701,9 @@ class Deferral {
 			if (!interlace && d.width === width && d.height === height && q[0] === 1 && q[4] === 1 && q[2] === 0 && q[5] === 0) return true
 			return q[0] * d.width <= 0.99 * width && q[4] * d.height * (interlace ? 2 : 1) <= 0.99 * height
 		}
-		const packFields = this.packFields && !outFmt && width % 2 === 0 && layerImages.every(fieldLayer)
+		// (... or by its several-outputs form, which has every writer: planar frames in widths that are multiples of 8, 4:2:0 in even heights)
+		const upOut = !outFmt || ((this.upWriters.alone || this.upWriters.several) && (outRgb8 || (width % 8 === 0 && (outFmt < 3 || height % 2 === 0))))
+		const packFields = this.packFields && upOut && width % 2 === 0 && layerImages.every(fieldLayer)
 		return { outFmt, outRgb8, image, top, width, height, interlace, output, m, layerImages, packFields }
 	}
 	// The Yadif windows of ALL the frames about to be planned go to the device in shared launches (up to eight windows each): the reference's
@@ -827,7 +841,20 @@ class Deferral {
 			if (!interlace && d.width === width && d.height === height && f[0] === 1 && f[4] === 1 && f[2] === 0 && f[5] === 0) return true // the default fill of a frame-size image
 			return f[0] * d.width <= 0.99 * width && f[4] * d.height * (interlace ? 2 : 1) <= 0.99 * height
 		}
-		if (!outFmt && !anyV210 && width % 2 === 0 && layers.every((l) => l.matrix && !l.transition && enlarged(l))) {
+		let upMulti = null // what a compose_up_multi_<n> candidate is made of (below, once the siblings are known)
+		const upShape = !anyV210 && width % 2 === 0 && layers.every((l) => l.matrix && !l.transition && enlarged(l))
+		if (upShape && outFmt && (outRgb8 || (width % 8 === 0 && (outFmt < 3 || height % 2 === 0)))) {
+			const packedLayers = layers.every((l) => l.source._packed != null)
+			if (!packedLayers) for (const l of layers) if (l.source._packed != null) this._unpack(l.source)
+			const params = Object.assign({ output, interlace }, saver)
+			if (packedLayers) params.packedRgb = 1
+			layers.forEach((l, i) => {
+				params[`l${i}In`] = l.source; params[`l${i}Matrix`] = l.matrix
+				if (packedLayers) { params[`l${i}Width`] = l.source.imageDims.width; params[`l${i}Height`] = l.source.imageDims.height }
+			})
+			upMulti = { params, packedLayers, twin: null }
+		}
+		if (!outFmt && upShape) {
 			const params = Object.assign({ output, interlace }, saver)
 			// packed field images: all of them, or none (the compositor takes one image format per launch)
 			const packedLayers = layers.every((l) => l.source._packed != null)
@@ -845,6 +872,7 @@ class Deferral {
 				candidates.push([`compose_up_write_v210_${n}`, both, twin])
 			}
 			candidates.push([`compose_up_write_v210_${n}`, params])
+			upMulti = { params, packedLayers, twin }
 		}
 		// the channel kernel wants a whole Loader recipe even if no layer turns out to need its YCbCr matrix (packed RGB and image layers only)
 		const anyCm = packedCm || (reader && reader.colMatrix) || (this.lastReader && this.lastReader.colMatrix)
@@ -879,8 +907,8 @@ class Deferral {
 		if (!candidates.length) return null
 		// the other consumers' writes of the same image go with this one, as further outputs of the channel kernel's launch - for the
 		// classes of frame where that measured faster than a launch per consumer (profiles/chan_multi_bench.jsonl, DESIGN.md 5.1): the
-		// channel kernel's own frames and the headline's plain reads.  Frames of enlarged images (the 2 x 2-block compositor's) were not
-		// measured and keep a launch per consumer.
+		// channel kernel's own frames and the headline's plain reads.  Frames of enlarged images (the 2 x 2-block compositor's) fold into
+		// that compositor's own several-outputs launch instead (upWriters, below).
 		let siblings = null
 		const chanAt = candidates.findIndex((c) => c[0].startsWith('chan_compose_v210_'))
 		if (this.multiWriter && chanAt >= 0 && !candidates.some((c) => c[0].startsWith('compose_up_write_v210_'))) {
@@ -901,6 +929,62 @@ class Deferral {
 				candidates.unshift([`chan_compose_multi_${n}`, params, null, siblings])
 			} else siblings = null
 		}
+		// the 2 x 2-block compositor's several-outputs form, ahead of all of these: the frame of a consumer that is not SDI, and the other
+		// consumers' writes of the same image as further outputs - with the frame's other field (the twin) where every one of these
+		// consumers has posted its write of that field too.  Refused, today's candidates follow (packed fields are unpacked by whoever
+		// launches with them: _launch).
+		let upSiblings = null
+		if (upMulti) {
+			const found = this.upWriters.several ? this._siblings(node, frame).filter((v) => v.frame.outRgb8 || !v.frame.outFmt || (width % 8 === 0 && (v.frame.outFmt < 3 || height % 2 === 0))) : []
+			if (found.length ? true : outFmt && this.upWriters.alone) {
+				const outputsOf = (params, prefix, f, w, k) => { // output k's planes under the program's names (prefix: 'output' / 'twinOutput')
+					const name = k ? `${prefix}${k}` : prefix
+					params[name] = f.output
+					if (f.outFmt === 4) params[`${name}C`] = w.params.outputC
+					else if (f.outFmt >= 1 && f.outFmt < 5) { params[`${name}U`] = w.params.outputU; params[`${name}V`] = w.params.outputV }
+				}
+				const params = Object.assign({}, upMulti.params)
+				found.forEach(({ frame: f, node: w }, i) => {
+					const k = i + 1
+					if (f.outFmt) params[`out${k}Packing`] = f.outFmt
+					outputsOf(params, 'output', f, w, k)
+					if (!f.outRgb8) params[`out${k}ColMatrix`] = w.params.colMatrix
+					params[`out${k}GammaLut`] = w.params.gammaLut
+					params[`interlace${k}`] = f.interlace
+				})
+				upSiblings = found.map((v) => v.node)
+				// the twin: this write's (found above for a v210 frame; the same search for the others) and, output by output, its siblings'
+				let twin = upMulti.twin || (outFmt ? this._twinWrite(node, layers) : null)
+				if (twin && !twin.sources.every((im) => (im._packed != null) === upMulti.packedLayers)) twin = null
+				let twinSiblings = []
+				let tf = null
+				if (twin) { try { tf = this._writeFrame(twin.node) } catch (e) { tf = null } }
+				if (twin && !tf) twin = null
+				if (twin && found.length) {
+					const theirs = this._siblings(twin.node, tf)
+					for (const { frame: f } of found) { // each of the twin's writes is taken once (two screens: two different frames)
+						const at = theirs.findIndex((t) => t.frame.outFmt === f.outFmt && t.frame.interlace === f.interlace)
+						if (at < 0) { twin = null; twinSiblings = []; break }
+						twinSiblings.push(theirs.splice(at, 1)[0])
+					}
+				}
+				if (twin) {
+					const both = Object.assign({}, params)
+					twin.sources.forEach((im, i) => { both[`l${i}In2`] = im })
+					outputsOf(both, 'twinOutput', tf, twin.node, 0) // (not `output2`, compose_up_write_v210_<n>'s name for it: here that is output 2's frame)
+					twinSiblings.forEach(({ frame: f, node: w }, i) => outputsOf(both, 'twinOutput', f, w, i + 1))
+					candidates.unshift([`compose_up_multi_${n}`, params, null, upSiblings])
+					candidates.unshift([`compose_up_multi_${n}`, both, twin, upSiblings.concat(twinSiblings.map((t) => t.node))])
+				} else {
+					candidates.unshift([`compose_up_multi_${n}`, params, null, upSiblings])
+				}
+				// (a plan made for packed fields is stale once somebody has unpacked one: _fresh looks)
+				if (upMulti.packedLayers) frame.packedSources = layers.map((l) => l.source).concat(twin ? twin.sources : [])
+				// (what _fresh watches: this field's sibling writes and the twin's - one that ran in between would be written a second time)
+				const watched = upSiblings.concat(twinSiblings.map((t) => t.node))
+				siblings = siblings ? siblings.concat(watched.filter((w) => !siblings.includes(w))) : watched
+			}
+		}
 		// one call can take it together with other channels' frames: plain reads of the output's size (the headline kernel's batch form),
 		// or the channel kernel as the only candidate making a v210 frame (the batch kernel for v210 / image sources)
 		// (frames from planar / packed-RGB clips go along in the same call: the library runs those it cannot put into a shared launch in their turn,
@@ -908,7 +992,7 @@ class Deferral {
 		// ... or frames of the 2 x 2-block compositor (de-interlaced fields at their own size or enlarged: several 1080i channels in a tick)
 		const up = candidates[0][0].startsWith('compose_up_write_v210_')
 		const batchable = up || candidates[0][0].startsWith('fused_v210_combine_') || (candidates.length === 1 && candidates[0][0].startsWith('chan_compose_v210_') && !outFmt)
-		return { node, candidates, used, n, width, height, batchable, up, loader, saver, siblings }
+		return { node, candidates, used, n, width, height, batchable, up, loader, saver, siblings, packedSources: frame.packedSources || null }
 	}
 	// The pending writes of other consumers on the image `node` writes: wire-format writes _writeFrame accepts, of the same geometry, on
 	// the same queue, into buffers of their own - at most three (the launch has four outputs).

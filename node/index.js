@@ -160,6 +160,9 @@ class clContext {
 		this.earlyLaunch = params.earlyLaunch === undefined ? process.env.PHANERON_EARLY_LAUNCH === '1' : !!params.earlyLaunch
 		// several consumers' writes of one combined image as outputs of ONE channel-kernel launch (node/defer.js _siblings); false: a launch per write
 		this.multiWriter = params.multiWriter === undefined ? process.env.PHANERON_MULTI_WRITER !== '0' : !!params.multiWriter
+		// frames of the 2 x 2-block compositor for consumers other than SDI and for several consumers at once (node/defer.js upWriters);
+		// undefined: per class of frame as measured; true / false or PHANERON_UP_WRITERS=1 / 0: for every class
+		this.upWriters = params.upWriters === undefined ? (process.env.PHANERON_UP_WRITERS === undefined ? undefined : process.env.PHANERON_UP_WRITERS !== '0') : !!params.upWriters
 		// released frames and images are parked and taken over whole by the next createBuffer of the same shape (free() above);
 		// `recycleBuffers: false` or PHANERON_RECYCLE=0 returns every buffer to the library at once.  parkMb: what may stay parked
 		// (default 4096 MiB - or as much as was ever in use at once, if that is more)

@@ -35,7 +35,7 @@ EXPORTS = [
     "ph_route_group_end", "ph_route_send", "ph_route_recv", "ph_route_after_queue", "ph_queue_after_route",
     "ph_route_wait", "ph_route_stream", "ph_route_comm_count", "ph_chan_compose_v210", "ph_chan_compose_batch", "ph_run_programs", "ph_event_record_timed", "ph_event_elapsed_us", "ph_ctx_host_pool_stats",
     "ph_v210_yadif_pair_fmt", "ph_compose_up_write_v210", "ph_trace_begin", "ph_trace_end", "ph_run_programs_progress", "ph_buf_reuse", "ph_image_unpack_rgb",
-    "ph_chan_compose_multi",
+    "ph_chan_compose_multi", "ph_compose_up_write_multi",
 ]
 
 
@@ -203,6 +203,7 @@ def lib():
         "ph_chan_compose": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(C.c_void_p), cu, cu, cu, vp, vp, vp, vp, vp]),
         "ph_chan_compose_batch": (ci, [vp, ci, ci, C.POINTER(PhChanJob), cu, cu, vp, vp, vp, vp, vp]),
         "ph_chan_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
+        "ph_compose_up_write_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_ctx_host_pool_stats": (ci, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
         "ph_event_record_timed": (ci, [vp, ci, C.POINTER(vp)]),
         "ph_event_elapsed_us": (ci, [vp, vp, C.POINTER(cu)]),
@@ -533,6 +534,46 @@ class Context:
                 check(fn(*args), h)
             return job
         check(lib().ph_compose_up_write_v210(*args), self.h)
+
+    def compose_up_write_multi(self, layer_sets, outputs, out_w, out_h, queue=QUEUE_PROCESS, rgb=False, prepare_only=False):
+        """Several consumers' frames of one enlarged composition in one launch (ph_compose_up_write_multi).  layer_sets: 1..4 sets of
+        layers as compose_up_write_v210_batch takes them; outputs: per set a list of 1..4 dicts as chan_compose_multi takes them
+        ({fmt, planes, interlace, wr_cm, wr_lut}) - set j's outputs differ from set 0's in their planes only."""
+        import numpy as np
+        keep = []
+        arrs = []
+        for layers in layer_sets:
+            arr = (PhImageLayer * len(layers))()
+            for i, (t, w, h, m) in enumerate(layers):
+                mh = np.ascontiguousarray(m, np.float32)
+                keep.append(mh)
+                arr[i].data, arr[i].width, arr[i].height = _ptr(t).value, w, h
+                arr[i].format = IMG_RGB_F32 if rgb else IMG_RGBA_F32
+                arr[i].matrix9_host = mh.ctypes.data_as(C.POINTER(C.c_float))
+            arrs.append(arr)
+        sets = (C.POINTER(PhImageLayer) * len(arrs))(*[C.cast(a, C.POINTER(PhImageLayer)) for a in arrs])
+        n_out = len(outputs[0])
+        outs = (PhChanOutput * max(len(outputs) * n_out, 1))()
+        for j, per_job in enumerate(outputs):
+            if len(per_job) != n_out:
+                raise PhaneronError("compose_up_write_multi: every set of layers needs the same number of outputs")
+            for k, o in enumerate(per_job):
+                d = outs[j * n_out + k]
+                planes = o["planes"] if isinstance(o["planes"], (list, tuple)) else [o["planes"]]
+                d.format = FORMATS[o["fmt"]]
+                for i, p in enumerate(planes):
+                    d.planes[i] = _ptr(p).value
+                d.interlace = int(o.get("interlace", 0))
+                d.wr_col_matrix12 = None if o.get("wr_cm") is None else _ptr(o["wr_cm"]).value
+                d.wr_gamma_lut = _ptr(o["wr_lut"]).value
+        args = (self.h, queue, len(layer_sets), len(layer_sets[0]), sets, n_out, outs, out_w, out_h)
+        fn, h = lib().ph_compose_up_write_multi, self.h
+        if prepare_only:
+
+            def job(_keep=(keep, arrs, layer_sets, outputs, sets, outs)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
 
     def image_unpack_rgb(self, image, width, height, queue=QUEUE_PROCESS):
         """a packed f32 RGB image (12 bytes per pixel) expanded in place into the f32 RGBA image its buffer is sized for (ph_image_unpack_rgb)"""

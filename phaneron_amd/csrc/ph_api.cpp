@@ -1903,25 +1903,9 @@ int ph_v210_yadif_pair(ph_ctx *ctx, int queue, int n, const ph_deint_source *src
   return ph_v210_yadif_pair_fmt(ctx, queue, n, src, width, height, tff, skip, PH_IMG_RGBA_F32, cm, lut, gm);
 }
 
-// `jobs` sets of layers that differ in their data only (same count, formats, sizes and placements), each into its own output: one launch
-static int compose_up_common(const char *fn, ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *sets, void *const *outs,
-                             uint32_t out_w, uint32_t out_h, uint32_t interlace, const void *wr_cm, const void *wr_lut) {
-  if (!ctx || !sets || !outs || !wr_cm || !wr_lut) return fail(PH_E_INVALID, "%s: NULL argument", fn);
-  if (jobs < 1 || jobs > ph::kMaxUpJobs) return fail(PH_E_INVALID, "%s: 1..%d jobs", fn, ph::kMaxUpJobs);
-  for (int j = 0; j < jobs; ++j)
-    if (!sets[j] || !outs[j]) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+// the layers of `jobs` sets (the same count, formats, sizes and placements; 1 <= n <= kMaxLayers checked) into a launch's arguments
+static int compose_up_layers(const char *fn, int jobs, int n, const ph_image_layer *const *sets, ph::UpArgs &a, int *image_fmt) {
   const ph_image_layer *layers = sets[0];
-  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
-  // (a width that is not a multiple of 48 - 1280 - ends its lines in a tail quad and cleared slots: the kernel's TAILS instantiation)
-  if (!out_w || out_w % 2) return fail(PH_E_INVALID, "%s: width %u is odd (a v210 frame needs an even width); run the separate kernels", fn, out_w);
-  if (interlace != 0 && interlace != 1 && interlace != 3) return fail(PH_E_INVALID, "%s: interlace must be 0, 1 or 3", fn);
-  for (int j = 1; j < jobs; ++j)
-    for (int k = 0; k < j; ++k)
-      if (outs[j] == outs[k]) return fail(PH_E_INVALID, jobs == 2 ? "%s: the two outputs are the same buffer" : "%s: two jobs have the same output buffer", fn);
-  const LutRef wref = lds_view(ctx, wr_lut);
-  const ph::LutView *wv = wref.get();
-  if (!wv) return fail(PH_E_INVALID, "%s: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn);
-  ph::UpArgs a{};
   a.n = n;
   const int fmt = layers[0].format;
   if (fmt != PH_IMG_RGBA_F32 && fmt != PH_IMG_RGB_F32) return fail(PH_E_INVALID, "%s: image format %d", fn, fmt);
@@ -1942,14 +1926,46 @@ static int compose_up_common(const char *fn, ph_ctx *ctx, int queue, int jobs, i
       a.more_ptr[j - 1][i] = B.data;
     }
   }
-  a.out = outs[0], a.jobs = (uint32_t)jobs, a.out_w = out_w, a.out_h = out_h;
-  for (int j = 1; j < jobs; ++j) a.more_out[j - 1] = outs[j];
+  a.jobs = (uint32_t)jobs;
+  *image_fmt = fmt;
+  return PH_OK;
+}
+static void compose_up_lines(ph::UpArgs &a, uint32_t out_w, uint32_t out_h, uint32_t interlace) {
+  a.out_w = out_w, a.out_h = out_h;
   a.line_step = interlace ? 2 : 1, a.first_line = (interlace == 3) ? 1 : 0;
   a.lines = interlace ? out_h / 2 : out_h;
+}
+static int compose_up_not_eligible(const char *fn) {
+  return fail(PH_E_INVALID, "%s: every layer must be enlarged (by 1 %% or more in both directions, per written row) without "
+                            "rotation or mirroring and be below 1 GiB; use ph_compose_write_v210", fn);
+}
+
+// `jobs` sets of layers that differ in their data only (same count, formats, sizes and placements), each into its own output: one launch
+static int compose_up_common(const char *fn, ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *sets, void *const *outs,
+                             uint32_t out_w, uint32_t out_h, uint32_t interlace, const void *wr_cm, const void *wr_lut) {
+  if (!ctx || !sets || !outs || !wr_cm || !wr_lut) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (jobs < 1 || jobs > ph::kMaxUpJobs) return fail(PH_E_INVALID, "%s: 1..%d jobs", fn, ph::kMaxUpJobs);
+  for (int j = 0; j < jobs; ++j)
+    if (!sets[j] || !outs[j]) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  // (a width that is not a multiple of 48 - 1280 - ends its lines in a tail quad and cleared slots: the kernel's TAILS instantiation)
+  if (!out_w || out_w % 2) return fail(PH_E_INVALID, "%s: width %u is odd (a v210 frame needs an even width); run the separate kernels", fn, out_w);
+  if (interlace != 0 && interlace != 1 && interlace != 3) return fail(PH_E_INVALID, "%s: interlace must be 0, 1 or 3", fn);
+  for (int j = 1; j < jobs; ++j)
+    for (int k = 0; k < j; ++k)
+      if (outs[j] == outs[k]) return fail(PH_E_INVALID, jobs == 2 ? "%s: the two outputs are the same buffer" : "%s: two jobs have the same output buffer", fn);
+  const LutRef wref = lds_view(ctx, wr_lut);
+  const ph::LutView *wv = wref.get();
+  if (!wv) return fail(PH_E_INVALID, "%s: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn);
+  ph::UpArgs a{};
+  int fmt = 0;
+  const int lrc = compose_up_layers(fn, jobs, n, sets, a, &fmt);
+  if (lrc) return lrc;
+  a.out = outs[0];
+  for (int j = 1; j < jobs; ++j) a.more_out[j - 1] = outs[j];
+  compose_up_lines(a, out_w, out_h, interlace);
   a.wr_cm = (const float *)wr_cm, a.wr = *wv;
-  if (!ph::compose_up_eligible(a))
-    return fail(PH_E_INVALID, "%s: every layer must be enlarged (by 1 %% or more in both directions, per written row) without "
-                              "rotation or mirroring and be below 1 GiB; use ph_compose_write_v210", fn);
+  if (!ph::compose_up_eligible(a)) return compose_up_not_eligible(fn);
   if (!a.lines) return PH_OK;
   PH_LAUNCH(ph::launch_compose_up_write_v210(stream_of(ctx, queue), a, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount));
 }
@@ -1971,6 +1987,118 @@ int ph_compose_up_write_v210_pair(ph_ctx *ctx, int queue, int n, const ph_image_
 int ph_compose_up_write_v210_batch(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, void *const *outs, uint32_t out_w,
                                    uint32_t out_h, uint32_t interlace, const void *wr_cm, const void *wr_lut) {
   return compose_up_common("ph_compose_up_write_v210_batch", ctx, queue, jobs, n, layer_sets, outs, out_w, out_h, interlace, wr_cm, wr_lut);
+}
+
+/* Several consumers' frames of one enlarged composition: see include/phaneron_hip.h.  Every check is made, and every launch of the call
+ * is planned, before anything is launched. */
+int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, int n_out, const ph_chan_output *outs,
+                              uint32_t out_w, uint32_t out_h) {
+  const char *const fn = "ph_compose_up_write_multi";
+  if (!ctx || !layer_sets || !outs) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n_out < 1 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
+  if (jobs < 1 || jobs > ph::kMaxUpJobs) return fail(PH_E_INVALID, "%s: 1..%d jobs (%d)", fn, ph::kMaxUpJobs, jobs);
+  if (jobs == 1 && n_out == 1 && outs[0].format == PH_FMT_V210)
+    return ph_compose_up_write_v210(ctx, queue, n, layer_sets[0], outs[0].planes[0], out_w, out_h, outs[0].interlace, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
+  PH_QUEUE(fn, queue);
+  for (int j = 0; j < jobs; ++j)
+    if (!layer_sets[j]) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  if (!out_w || out_w % 2) return fail(PH_E_INVALID, "%s: width %u is odd (a block is two pixels wide); run the separate kernels", fn, out_w);
+  for (int k = 0; k < n_out; ++k) {
+    const ph_chan_output &o = outs[k];
+    if (!o.planes[0] || !o.wr_gamma_lut) return fail(PH_E_INVALID, "%s: output %d: NULL argument", fn, k);
+    if (!fmt_known(o.format)) return fail(PH_E_INVALID, "%s: output %d: format %d is not a PH_FMT_*", fn, k, o.format);
+    if (!fmt_chan_out(o.format))
+      return fail(PH_E_INVALID, "%s: output %d: the compositor does not write %s frames - run the separate kernels: the frame as an image, then the format's writer (ph_pack_write)", fn, k,
+                  fmt_name(o.format));
+    if (!fmt_rgb8(o.format) && !o.wr_col_matrix12) return fail(PH_E_INVALID, "%s: output %d: the writer's RGB -> YCbCr matrix is missing", fn, k);
+    if (fmt_v420(o.format) && (out_h & 1)) return fail(PH_E_INVALID, "%s: output %d: a 4:2:0 frame needs an even height (%u)", fn, k, out_h);
+    if (fmt_planar(o.format) && out_w % 8)
+      return fail(PH_E_INVALID, "%s: output %d: width %u (a planar frame needs a multiple of 8); run the separate kernels", fn, k, out_w);
+    if (o.interlace != 0 && o.interlace != 1 && o.interlace != 3) return fail(PH_E_INVALID, "%s: output %d: interlace must be 0, 1 or 3", fn, k);
+    for (int j = 0; j < jobs; ++j) {
+      const ph_chan_output &b = outs[j * n_out + k];
+      if (b.format != o.format || b.interlace != o.interlace || b.wr_col_matrix12 != o.wr_col_matrix12 || b.wr_gamma_lut != o.wr_gamma_lut)
+        return fail(PH_E_INVALID, "%s: output %d of job %d differs from job 0's in more than its planes", fn, k, j);
+      if (!b.planes[0] || (fmt_planar(o.format) && (!b.planes[1] || (fmt_planes(o.format) == 3 && !b.planes[2]))))
+        return fail(PH_E_INVALID, "%s: output %d: a planar output needs its three planes (nv12: Y and the interleaved CbCr plane)", fn, k);
+      for (int i = 0; i < j * n_out + k; ++i)
+        if (outs[i].planes[0] == b.planes[0]) return fail(PH_E_INVALID, "%s: outputs %d and %d name the same plane", fn, i, j * n_out + k);
+    }
+  }
+  LutRef wref[ph::kMaxUpOuts];
+  for (int k = 0; k < n_out; ++k) {
+    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
+    if (!wref[k].get())
+      return fail(PH_E_INVALID, "%s: output %d: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn, k);
+  }
+  ph::UpArgs base{};
+  int fmt = 0;
+  int rc = compose_up_layers(fn, jobs, n, layer_sets, base, &fmt);
+  if (rc) return rc;
+  // the launches: per writer table, in the order the tables first appear, a v210 output that cannot share (its lines end in a tail quad,
+  // or nobody else names its table) through today's kernel, then the rest as one several-outputs launch
+  struct Launch {
+    bool solo;  // compose_up_write_v210_kernel: m.up alone
+    ph::UpMultiArgs m;
+  };
+  std::vector<Launch> launches;
+  for (int k = 0; k < n_out; ++k) {
+    bool seen = false;
+    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    if (seen) continue;
+    int group[ph::kMaxUpOuts], members = 0;
+    for (int j = k; j < n_out; ++j)
+      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) group[members++] = j;
+    Launch shared{};
+    shared.solo = false, shared.m.up = base, shared.m.up.wr = *wref[k].get();
+    for (int g = 0; g < members; ++g) {
+      const ph_chan_output &o = outs[group[g]];
+      if (o.format == PH_FMT_V210 && (out_w % 48 || members == 1)) {
+        Launch own{};
+        own.solo = true, own.m.up = base, own.m.up.wr = *wref[k].get(), own.m.up.wr_cm = (const float *)o.wr_col_matrix12;
+        own.m.up.out = o.planes[0];
+        for (int j = 1; j < jobs; ++j) own.m.up.more_out[j - 1] = outs[j * n_out + group[g]].planes[0];
+        compose_up_lines(own.m.up, out_w, out_h, o.interlace);
+        launches.push_back(own);
+        continue;
+      }
+      ph::UpOut &d = shared.m.out[shared.m.n_out];
+      d.fmt = (uint32_t)o.format;
+      d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48)
+      d.wr_cm = (const float *)o.wr_col_matrix12;
+      for (int j = 0; j < jobs; ++j)
+        for (int i = 0; i < 3; ++i) d.plane[j][i] = outs[j * n_out + group[g]].planes[i];
+      d.takes = o.interlace, ++shared.m.n_out;  // (takes: settled below, once the launch's lines are known)
+    }
+    if (!shared.m.n_out) continue;
+    // a split-off v210 output does not count: the first output that stays decides what "the same" is
+    const uint32_t first_il = shared.m.out[0].takes;
+    bool same_lines = true;
+    for (uint32_t i = 0; i < shared.m.n_out; ++i) same_lines = same_lines && shared.m.out[i].takes == first_il;
+    compose_up_lines(shared.m.up, out_w, out_h, same_lines ? first_il : 0u);
+    for (uint32_t i = 0; i < shared.m.n_out; ++i) {
+      ph::UpOut &d = shared.m.out[i];
+      const uint32_t il = d.takes;
+      d.takes = same_lines || !il ? 0u : il == 1 ? 1u : 2u;
+      d.line_end = il ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as the one-output kernels write it)
+      d.field = il ? 1u : 0u;
+    }
+    launches.push_back(shared);
+  }
+  for (const Launch &l : launches)
+    if (!ph::compose_up_eligible(l.m.up)) return compose_up_not_eligible(fn);
+  rc = set_device(ctx);
+  if (rc) return rc;
+  for (const Launch &l : launches) {
+    if (!l.m.up.lines) continue;
+    hipError_t e = hipSuccess;
+    if (!l.solo) e = ph::launch_compose_up_multi(stream_of(ctx, queue), l.m, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount);
+    else if (!ph::trace_launch("compose_up_write_v210"))
+      e = ph::launch_compose_up_write_v210(stream_of(ctx, queue), l.m.up, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount);
+    if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  }
+  return PH_OK;
 }
 
 int ph_v210_yadif_pair_fmt(ph_ctx *ctx, int queue, int n, const ph_deint_source *src, uint32_t width, uint32_t height, int tff,

@@ -72,6 +72,18 @@ __device__ __forceinline__ WriteK load_write_k(const float *__restrict__ cm) {
   return k;
 }
 
+// The writers' arithmetic AFTER the table lookups, from a pixel's three table values - shared by the channel kernel's writer phase
+// (ph_kernels_chan.hip chan_phase2_other) and the 2 x 2-block compositor's several-outputs form (ph_kernels_up.hip up_write_outs).
+// Packed 8-bit RGB (rgba8.ts:69-101): convert_uchar_sat_rte(x * 255), alpha 255; FMT: PH_FMT_RGBA8 or PH_FMT_BGRA8
+template <int FMT>
+__device__ __forceinline__ uint32_t rgb8_pack(float gr, float gg, float gb) {
+  const uint32_t r8 = sat_u8_rte(gr * 255.0f), g8 = sat_u8_rte(gg * 255.0f), b8 = sat_u8_rte(gb * 255.0f);
+  return FMT == PH_FMT_RGBA8 ? (r8 | g8 << 8 | b8 << 16 | 0xff000000u) : (b8 | g8 << 8 | r8 << 16 | 0xff000000u);
+}
+// One YCbCr code value (yuv422p10.ts:140-189 and the other planar writers; v210.ts:145-162): a row of the writer's matrix, rounded to 16
+// bits - the planar stores cut it to the sample width
+__device__ __forceinline__ uint32_t ycbcr_code(float gr, float gg, float gb, const float4 row) { return sat_u16_rte(dot4(gr, gg, gb, 1.0f, row)); }
+
 // One pixel of the v210 read kernel (v210.ts:65-78; tail :96-109 passes last = 0).
 __device__ __forceinline__ float4 read_px(float y, float cb, float cr, float last, const ReadK &k,
                                           const float *__restrict__ lut) {

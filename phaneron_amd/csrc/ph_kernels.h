@@ -240,6 +240,29 @@ uint32_t clip_up_plan(ClipUpArgs &a, bool rgb12, uint32_t num_cus);
 hipError_t launch_clip_up_write_v210(hipStream_t s, const ClipUpArgs &a, bool rgb12, uint32_t grid);
 bool compose_up_eligible(const UpArgs &a);
 hipError_t launch_compose_up_write_v210(hipStream_t s, const UpArgs &a, bool rgb12, uint32_t num_cus);
+// Several consumers' frames of ONE enlarged composition in one launch (ph_compose_up_write_multi): up describes the composition - the
+// lines composed are the union of what the outputs need, up.out / up.more_out / up.wr_cm are unused, up.wr is the ONE writer table of
+// the launch - and every output brings its format, its planes per job and its writer matrix.  A v210 output's lines end on a 48-pixel
+// block here (the caller sends a v210 frame with a tail through launch_compose_up_write_v210).
+// The bound on jobs x outputs is the argument block's: kMaxUpJobs x kMaxUpOuts x 3 plane pointers are 384 of its 4096 bytes.
+constexpr int kMaxUpOuts = 4;
+struct UpOut {
+  uint32_t fmt;       // PH_FMT_* (one of fmt_chan_out)
+  uint32_t pitch;     // v210: quad slots per line; planar: luma samples per line; rgba8 / bgra8: pixels per line
+  uint32_t takes;     // which of the composed lines are this output's: 0 all, 1 the even frame lines, 2 the odd ones
+  uint32_t line_end;  // lines from here on are not this output's (a field of a frame with an odd height)
+  uint32_t field;     // 1: a field write (4:2:0: the written line of a pair gives the chroma)
+  uint32_t pad;
+  const float *wr_cm;  // (unused for rgba8 / bgra8)
+  void *plane[kMaxUpJobs][3];
+};
+struct UpMultiArgs {
+  UpArgs up;
+  uint32_t n_out;
+  UpOut out[kMaxUpOuts];
+};
+static_assert(sizeof(UpMultiArgs) < 4096, "kernel arguments are limited to 4 KiB");
+hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb12, uint32_t num_cus);
 
 struct DeintArgs {  // ph_kernels_deint.hip
   const uint4 *prev[kMaxLayers], *cur[kMaxLayers], *next[kMaxLayers];  // v210 frames, width x height

@@ -875,8 +875,7 @@ __device__ __forceinline__ void chan_phase2_other(const A &a, const ChanShare &s
       chan_out_round(a, e.x, e.y);
       const PxPending pend = write_px_issue(idx(e.x), idx(e.x >> 16), idx(e.y), wlut);
       const float r = lds_lut_finish(pend.r), g = lds_lut_finish(pend.g), b = lds_lut_finish(pend.b);
-      const uint32_t r8 = sat_u8_rte(r * 255.0f), g8 = sat_u8_rte(g * 255.0f), b8 = sat_u8_rte(b * 255.0f);
-      reinterpret_cast<uint32_t *>(a.out)[(size_t)line * a.out_pitch + x] = OUT == PH_FMT_RGBA8 ? (r8 | g8 << 8 | b8 << 16 | 0xff000000u) : (b8 | g8 << 8 | r8 << 16 | 0xff000000u);
+      reinterpret_cast<uint32_t *>(a.out)[(size_t)line * a.out_pitch + x] = rgb8_pack<OUT>(r, g, b);
     }
     return;
   }
@@ -913,8 +912,8 @@ __device__ __forceinline__ void chan_phase2_other(const A &a, const ChanShare &s
       for (int j = 0; j < 4; ++j) {
         const int p = 4 * half + j;
         const float gr = lds_lut_finish(pend[j].r), gg = lds_lut_finish(pend[j].g), gb = lds_lut_finish(pend[j].b);
-        y[p] = sat_u16_rte(dot4(gr, gg, gb, 1.0f, wk.y));
-        if (!(p & 1)) u[p >> 1] = sat_u16_rte(dot4(gr, gg, gb, 1.0f, wk.u)), v[p >> 1] = sat_u16_rte(dot4(gr, gg, gb, 1.0f, wk.v));
+        y[p] = ycbcr_code(gr, gg, gb, wk.y);
+        if (!(p & 1)) u[p >> 1] = ycbcr_code(gr, gg, gb, wk.u), v[p >> 1] = ycbcr_code(gr, gg, gb, wk.v);
       }
     }
     const size_t o8 = ((size_t)line * a.out_pitch + x) >> 3;

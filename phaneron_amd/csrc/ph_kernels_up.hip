@@ -20,6 +20,7 @@
 #include "ph_kernels.h"
 #include "ph_ldslut.h"
 
+#include <cstdlib>
 #include <type_traits>
 
 #pragma clang fp contract(off)
@@ -65,9 +66,11 @@ struct UpShare {  // as ChanShare (ph_kernels_chan.hip): units dealt XCD-aware i
   uint32_t units, upg, upr, xcd, v0, vstep, vend, slots;
   bool banded;
 };
+// COLS: the output columns of a wave step - 126 (63 lanes: 21 v210 quads), or 128 (all 64 lanes) in launches without a v210 output
+template <uint32_t COLS = kUpCols>
 __device__ __forceinline__ UpShare up_share(const UpArgs &a) {
   UpShare s;
-  s.upr = (a.cover_w + kUpCols - 1u) / kUpCols;  // wave steps per row pair
+  s.upr = (a.cover_w + COLS - 1u) / COLS;  // wave steps per row pair
   s.units = s.upr * ((a.lines + 1u) / 2u) * a.jobs;  // a further job's row pairs follow the one before's
   s.upg = (uint32_t)(PH_UP_GROUP_ROWS / 2) * s.upr;
   s.banded = (gridDim.x & 7u) == 0;
@@ -142,6 +145,7 @@ struct UpStep {
 // usually partial (2160p: 8.2 rounds) and its units are dealt one per SIMD instead - workgroup first, wave second (the waves of a
 // workgroup go round its four SIMDs) - so that the tail runs as single waves on otherwise idle SIMDs all over the chip, not as a few
 // CUs with sixteen waves each doing a ninth step.
+template <uint32_t COLS = kUpCols>
 __device__ __forceinline__ bool up_step(const UpArgs &a, const UpShare &sh, uint32_t &base, uint32_t wave, uint32_t lane, UpStep &st) {
   while (base < sh.vend) {
     const uint32_t left = sh.vend - base, nwg = sh.vstep / (kUpBlock / 64), wg = sh.v0 / (kUpBlock / 64);
@@ -155,8 +159,8 @@ __device__ __forceinline__ bool up_step(const UpArgs &a, const UpShare &sh, uint
     const uint32_t col_unit = unit - rp * sh.upr, rp_per_job = (a.lines + 1u) / 2u;
     st.job = (rp >= rp_per_job ? 1u : 0u) + (rp >= 2u * rp_per_job ? 1u : 0u) + (rp >= 3u * rp_per_job ? 1u : 0u);  // kMaxUpJobs == 4
     rp -= st.job * rp_per_job;
-    st.x0 = col_unit * kUpCols + 2u * lane;  // even
-    st.live = lane < 63u && st.x0 < a.out_w;               // lane 63 has no quad; the row's last step may be short
+    st.x0 = col_unit * COLS + 2u * lane;  // even
+    st.live = (COLS == 128u || lane < 63u) && st.x0 < a.out_w;  // lane 63 has no quad; the row's last step may be short
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy) {
       st.li[dy] = 2u * rp + (uint32_t)dy < a.lines ? 2u * rp + (uint32_t)dy : 2u * rp;  // an odd field's last row is its own partner
@@ -295,6 +299,16 @@ __device__ __forceinline__ void up_filter(const UpPatch &p, const UpGeo &g, UpAc
   up_over<FIRST>(lo1, acc[1][1]);
 }
 
+// The half of a packed quad that lane A (role 0: w0, w1) or lane C (role 2: w2, w3) stores, from the lane's own four code values and
+// lane B's gifts: to A (the lane before it) Cb2 << 10 | Y2 << 20, to C (the lane after it) Cr2 | Y3 << 10.  Every lane of the wave calls it.
+__device__ __forceinline__ uint2 up_v210_half(uint32_t ey, uint32_t eu, uint32_t ev, uint32_t y1, uint32_t role) {
+  const uint32_t to_prev = eu << 10 | ey << 20, to_next = ev | y1 << 10;
+  const uint32_t from_next = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)to_prev, 0x130 /* wave_shl:1: lane i reads lane i + 1 */, 0xf, 0xf, false);
+  const uint32_t from_prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)to_next, 0x138 /* wave_shr:1: lane i reads lane i - 1 */, 0xf, 0xf, false);
+  if (role == 0u) return make_uint2(ev << 20 | ey << 10 | eu, from_next | y1);  // w0, w1
+  return make_uint2(eu << 20 | from_prev, y1 << 20 | ev << 10 | ey);            // w2, w3 (lane C)
+}
+
 // writer (v210.ts:145-162) of the lane's block: the even pixel gives Y, Cb, Cr, the odd one Y; then the quad's three lanes trade halves
 // TAILS: lines that do not end on a 48-pixel block (1280: src/config.ts:43-54) - `full` whole quads, the tail quad of out_w % 6 = 2 or 4
 // pixels with the reference's tail arithmetic (table indices truncated, code values through round() and a truncating convert, the words
@@ -327,13 +341,7 @@ __device__ __forceinline__ void up_write(const UpArgs &a, const UpStep &st, cons
     };
     const uint32_t ey = code(dot4(er, eg, eb, 1.0f, wk.y)), eu = code(dot4(er, eg, eb, 1.0f, wk.u)), ev = code(dot4(er, eg, eb, 1.0f, wk.v));
     const uint32_t y1 = code(dot4(orr, og, ob, 1.0f, wk.y));
-    // lane B's gifts: to A (the lane before it) Cb2 << 10 | Y2 << 20, to C (the lane after it) Cr2 | Y3 << 10
-    const uint32_t to_prev = eu << 10 | ey << 20, to_next = ev | y1 << 10;
-    const uint32_t from_next = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)to_prev, 0x130 /* wave_shl:1: lane i reads lane i + 1 */, 0xf, 0xf, false);
-    const uint32_t from_prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)to_next, 0x138 /* wave_shr:1: lane i reads lane i - 1 */, 0xf, 0xf, false);
-    uint2 half;
-    if (role == 0u) half = make_uint2(ev << 20 | ey << 10 | eu, from_next | y1);  // w0, w1
-    else half = make_uint2(eu << 20 | from_prev, y1 << 20 | ev << 10 | ey);      // w2, w3 (lane C)
+    const uint2 half = up_v210_half(ey, eu, ev, y1, role);
     // (TAILS: every quad slot of the pitch is written - the tail quad's unset words and the cleared slots come out of the zero lanes)
     const bool store = (TAILS ? (threadIdx.x & 63u) < 63u && quad < qpl : st.live) && role != 1u && (dy == 0 || st.li[1] != st.li[0]);
     if (store) {
@@ -364,6 +372,7 @@ __global__ __launch_bounds__(kUpBlock) void compose_up_write_v210_kernel(UpArgs 
     for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
       for (int dx = 0; dx < 2; ++dx) acc[dy][dx] = UpAcc{0.0f, 0.0f, 0.0f};
+    // (up_layers below is a copy of this loop for compose_up_multi_kernel: keep the two in step)
     // one layer at a time.  Variants built and measured slower at 2160p x 4 layers: layers in pairs with both patches in
     // flight (76 against 70 us; again with the shared geometry: 84 against 68 us, 128 registers and spills) and a patch
     // carried in flight across loop turns (85 us) - two patches plus the writer's temporaries do not fit 128 registers
@@ -399,6 +408,171 @@ __global__ __launch_bounds__(kUpBlock) void compose_up_write_v210_kernel(UpArgs 
       layers(std::false_type{}, std::false_type{});
     }
     up_write<TAILS>(a, st, acc, role, wk, lk);
+  }
+}
+
+// ---- several consumers' frames of ONE enlarged composition per launch ---------------------------------------------------------------
+// A channel's consumers each run their own FromRGBA on the one combined image (channel.ts:64-88: v210 for SDI, rgba8 for the screen,
+// yuv422p8 for an encoder).  The writers differ only AFTER the table lookups (ph_kernels_chan.hip chan_phase2_other: same indices, same
+// table, another matrix and packing), and the block's four pixels are in registers when the writer is reached: the twelve table reads
+// are made once, then every output packs the same twelve values with its own matrix.  A block with even x and y is one 4:2:0 chroma site.
+// Every output of a launch names the launch's ONE table (the kernel is persistent and single-phase: no point at which all waves could
+// swap it), and rounds its indices - a v210 output whose lines end in a tail quad, which truncates them there, is launched on its own
+// by the caller (compose_up_write_v210_kernel<RGB12, true>).
+//
+// Stores.  rgba8 / bgra8 store 8 bytes per lane and row - a wave's row segment without a gap, as the v210 halves; the planar writers
+// store the lane's two luma samples (2 or 4 bytes) and its one chroma site per plane (1 or 2 bytes), again contiguous over the wave's
+// lanes, through the cache.  With the v210 writer's 126-column step (63 lanes, three to a quad) two neighbouring wave steps share the
+// sector at every step boundary - 126 is no multiple of 32 - so launches WITHOUT a v210 output take a 128-column step (COLS = 128, all
+// 64 lanes): a wave's store instruction then covers 128 or 256 contiguous bytes of luma and 64 or 128 of a chroma plane, which are
+// whole, aligned 32-byte sectors where the row pitch is a multiple of 32 luma samples (64 for the 8-bit 4:2:0 chroma planes) - 1920 and
+// 3840 are; the entry asks for a multiple of 8 only, and other widths share a sector between rows as any writer's would.
+// Of the two ways to whole sectors this one was built; trading samples by DPP into 8-byte stores (which would also serve launches that
+// have a v210 output) was not.  Measured, four packed-RGB 1080p images, one output
+// (tools/up_out_bench.py, two processes; the separate side agrees to 0.4 us between them): 128 against 126 columns - yuv420p 27.8 against
+// 28.0 us, yuv422p8 28.4 against 28.4, rgba8 27.5 against 27.5 (profiles/up_out_bench.jsonl, profiles/up_out_bench_step126.jsonl): the
+// 128-column step is never slower and 0.2 us (0.8 %, three times the spread) faster for the 4:2:0 writer - it is the one taken.
+//
+// The writer matrices are loaded per output and wave step (load_write_k: twelve scalar loads from the scalar cache).  Loading all four
+// outputs' matrices once per wave in front of the step loop was built and dropped on the compiler's own figures: 48 more values live over
+// the loop take the kernel from 110 / 114 to 128 vector registers with 35 - 38 of them spilled (160 - 176 bytes of scratch per lane)
+// at 1024 lanes - the scalar file is full (106) either way (profiles/up_out_resources.txt).
+__device__ __forceinline__ bool up_out_takes(const UpOut &o, uint32_t line) { return line < o.line_end && (o.takes == 0u || (line & 1u) + 1u == o.takes); }
+
+// A wave step's layers, bottom to top, into the block's four accumulators (zero on entry): the layer loop of compose_up_write_v210_kernel,
+// which keeps its own copy - called from here that kernel's registers are allocated differently, and its code is pinned
+// (profiles/up_out_resources.txt)
+template <bool RGB12>
+__device__ __forceinline__ void up_layers(const UpArgs &a, const UpStep &st, UpAcc (&acc)[2][2], const LutK &lk) {
+  // one layer at a time.  Variants built and measured slower at 2160p x 4 layers: layers in pairs with both patches in
+  // flight (76 against 70 us; again with the shared geometry: 84 against 68 us, 128 registers and spills) and a patch
+  // carried in flight across loop turns (85 us) - two patches plus the writer's temporaries do not fit 128 registers
+  // The bottom layer is peeled off the loop (it is taken as it is; above it the accumulators are updated in place), and the loop
+  // exists three times - shared geometry with every texel inside (packed RGB: no alpha arithmetic at all), shared geometry, a
+  // geometry per layer - so that inside a loop nothing about an accumulator is decided by a branch
+  UpGeo geo;
+  auto layers = [&](auto inside_tag, auto shared_tag) __attribute__((always_inline)) {
+    constexpr bool INSIDE = decltype(inside_tag)::value, SHARED = decltype(shared_tag)::value;
+    {
+      UpLayer L = a.layer[0];  // one 48-byte scalar load
+      if (st.job) L.ptr = a.more_ptr[st.job - 1u][0];
+      if (!SHARED) geo = up_geo<RGB12>(L, st);
+      UpPatch p;
+      up_fetch<RGB12>(L, geo, p);
+      up_filter<RGB12, INSIDE, true>(p, geo, acc, lk);
+    }
+#pragma unroll 1
+    for (int l = 1; l < a.n; ++l) {
+      UpLayer L = a.layer[l];
+      if (st.job) L.ptr = a.more_ptr[st.job - 1u][l];
+      if (!SHARED) geo = up_geo<RGB12>(L, st);
+      UpPatch p;
+      up_fetch<RGB12>(L, geo, p);
+      up_filter<RGB12, INSIDE, false>(p, geo, acc, lk);
+    }
+  };
+  if (a.shared) {  // uniform
+    geo = up_geo<RGB12>(a.layer[0], st);
+    if (RGB12 && geo.all_inside) layers(std::true_type{}, std::true_type{});  // uniform
+    else layers(std::false_type{}, std::true_type{});
+  } else {
+    layers(std::false_type{}, std::false_type{});
+  }
+}
+
+template <int OUT>
+__device__ __forceinline__ void up_write_out(const UpOut &o, const UpStep &st, const float (&t)[2][2][3], uint32_t role) {
+  constexpr bool WIDE = fmt_wide(OUT), V420 = fmt_v420(OUT), NV12 = fmt_cbcr(OUT);
+  char *const p0 = static_cast<char *>(o.plane[st.job][0]);
+  WriteK wk;
+  if (!fmt_rgb8(OUT)) wk = load_write_k(o.wr_cm);
+#pragma unroll
+  for (int dy = 0; dy < 2; ++dy) {
+    const uint32_t line = st.line[dy];
+    if (!((dy == 0 || st.li[1] != st.li[0]) && up_out_takes(o, line))) continue;  // uniform
+    const float *const e = t[dy][0], *const d = t[dy][1];  // the even pixel, the odd one
+    if (fmt_rgb8(OUT)) {  // rgba8.ts:69-101
+      typedef uint32_t ph_u2v __attribute__((ext_vector_type(2)));
+      const ph_u2v px{rgb8_pack<OUT>(e[0], e[1], e[2]), rgb8_pack<OUT>(d[0], d[1], d[2])};
+      if (st.live) __builtin_nontemporal_store(px, reinterpret_cast<ph_u2v *>(p0 + ((size_t)line * o.pitch + st.x0) * 4u));
+      continue;
+    }
+    // chroma from the even pixel (v210.ts:145-162 and every planar writer)
+    const uint32_t ey = ycbcr_code(e[0], e[1], e[2], wk.y), eu = ycbcr_code(e[0], e[1], e[2], wk.u), ev = ycbcr_code(e[0], e[1], e[2], wk.v);
+    const uint32_t y1 = ycbcr_code(d[0], d[1], d[2], wk.y);
+    if (OUT == PH_FMT_V210) {  // (every lane trades, then lanes A and C store: up_write)
+      typedef uint32_t ph_u2v __attribute__((ext_vector_type(2)));
+      const uint2 half = up_v210_half(ey, eu, ev, y1, role);
+      ph_u2v *dst = reinterpret_cast<ph_u2v *>(reinterpret_cast<uint4 *>(p0) + (size_t)line * o.pitch + st.x0 / 6u) + (role == 2u ? 1 : 0);
+      if (st.live && role != 1u) __builtin_nontemporal_store(ph_u2v{half.x, half.y}, dst);
+      continue;
+    }
+    if (!st.live) continue;
+    // planar (yuv422p10.ts:140-189, yuv422p8.ts:166-168, yuv420p.ts:150-216, nv12.ts:139-196): codes cut to the sample width on store
+    const size_t at = (size_t)line * o.pitch + st.x0;  // in luma samples; even
+    if (WIDE) *reinterpret_cast<uint32_t *>(p0 + at * 2u) = ey | y1 << 16;
+    else *reinterpret_cast<uint16_t *>(p0 + at) = (uint16_t)((ey & 0xffu) | (y1 & 0xffu) << 8);
+    char *const p1 = static_cast<char *>(o.plane[st.job][1]), *const p2 = static_cast<char *>(o.plane[st.job][2]);
+    if (V420) {  // a chroma line serves a line pair: from the pair's upper line, or from the one line of the pair that a field writes
+      if (!(o.field || !(line & 1u))) continue;  // uniform
+      const size_t cat = (size_t)(line >> 1) * o.pitch + st.x0;
+      if (NV12) *reinterpret_cast<uint16_t *>(p1 + cat) = (uint16_t)((eu & 0xffu) | (ev & 0xffu) << 8);
+      else p1[cat >> 1] = (char)(eu & 0xffu), p2[cat >> 1] = (char)(ev & 0xffu);
+    } else if (WIDE) {
+      *reinterpret_cast<uint16_t *>(p1 + at) = (uint16_t)eu, *reinterpret_cast<uint16_t *>(p2 + at) = (uint16_t)ev;
+    } else {
+      p1[at >> 1] = (char)(eu & 0xffu), p2[at >> 1] = (char)(ev & 0xffu);
+    }
+  }
+}
+
+template <bool RGB12, uint32_t COLS>
+__global__ __launch_bounds__(kUpBlock) void compose_up_multi_kernel(UpMultiArgs m) {
+  const UpArgs &a = m.up;
+  const LutK lk = make_lut_k(a.wr);
+  lds_lut_load<kUpBlock>(a.wr);
+  __syncthreads();
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const UpShare sh = up_share<COLS>(a);
+  const uint32_t role = lane - 3u * (lane / 3u);
+  UpStep st;
+  for (uint32_t base = 0; up_step<COLS>(a, sh, base, wave, lane, st);) {
+    UpAcc acc[2][2];
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) acc[dy][dx] = UpAcc{0.0f, 0.0f, 0.0f};
+    up_layers<RGB12>(a, st, acc, lk);
+    // the twelve table reads of the block's four pixels, started together - once for all outputs
+    float t[2][2][3];
+    {
+      PxPending pend[2][2];
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx)
+          pend[dy][dx] = write_px_issue(lds_lut_index_unit(acc[dy][dx].r), lds_lut_index_unit(acc[dy][dx].g), lds_lut_index_unit(acc[dy][dx].b), lk);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx)
+          t[dy][dx][0] = lds_lut_finish(pend[dy][dx].r), t[dy][dx][1] = lds_lut_finish(pend[dy][dx].g), t[dy][dx][2] = lds_lut_finish(pend[dy][dx].b);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kMaxUpOuts; ++k) {
+      if (k >= m.n_out) break;  // uniform
+      const UpOut &o = m.out[k];
+      switch (o.fmt) {  // uniform
+        case PH_FMT_V210: up_write_out<PH_FMT_V210>(o, st, t, role); break;
+        case PH_FMT_YUV422P10: up_write_out<PH_FMT_YUV422P10>(o, st, t, role); break;
+        case PH_FMT_YUV422P8: up_write_out<PH_FMT_YUV422P8>(o, st, t, role); break;
+        case PH_FMT_YUV420P: up_write_out<PH_FMT_YUV420P>(o, st, t, role); break;
+        case PH_FMT_NV12: up_write_out<PH_FMT_NV12>(o, st, t, role); break;
+        case PH_FMT_RGBA8: up_write_out<PH_FMT_RGBA8>(o, st, t, role); break;
+        case PH_FMT_BGRA8: up_write_out<PH_FMT_BGRA8>(o, st, t, role); break;
+      }
+    }
   }
 }
 
@@ -756,6 +930,25 @@ bool compose_up_eligible(const UpArgs &a) {
   return true;
 }
 
+// what the launcher adds to a launch's arguments; returns the number of workgroups
+static uint32_t up_plan(UpArgs &b, bool tails, uint32_t num_cus, uint32_t cols = kUpCols) {
+  if (!b.jobs) b.jobs = 1;
+  b.out_qpitch = v210_pitch_bytes(b.out_w) / 16u;
+  b.cover_w = tails ? b.out_qpitch * 6u : b.out_w;
+  b.shared = 1;  // every layer has the size and the placement of the first: the patch geometry and the weights are computed once per block
+  for (int l = 1; l < b.n; ++l) {
+    b.shared = b.shared && b.layer[l].w == b.layer[0].w && b.layer[l].h == b.layer[0].h && b.layer[l].pitch == b.layer[0].pitch;
+    for (int k = 0; k < 6; ++k) b.shared = b.shared && b.layer[l].m[k] == b.layer[0].m[k];
+  }
+  const uint32_t upr = (b.cover_w + cols - 1u) / cols, upg = (uint32_t)(PH_UP_GROUP_ROWS / 2) * upr;
+  const uint32_t units = upr * ((b.lines + 1u) / 2u) * b.jobs;
+  // reciprocals for the kernel's uniform divisions: umulhi(v, ceil(2^32 / d)) == v / d while v * d < 2^32
+  b.magic_upr = upr > 1 ? (uint32_t)(((1ull << 32) + upr - 1) / upr) : 0u;
+  b.magic_upg = (uint32_t)(((1ull << 32) + upg - 1) / upg);
+  const uint32_t want = (units + kUpBlock / 64 - 1) / (kUpBlock / 64);
+  return want < num_cus ? want : num_cus;
+}
+
 hipError_t launch_compose_up_write_v210(hipStream_t s, const UpArgs &a, bool rgb12, uint32_t num_cus) {
   if (!a.lines) return hipSuccess;
   const bool tails = a.out_w % 48u != 0;  // lines that end in a tail quad and / or cleared slots: an instantiation of its own
@@ -766,26 +959,40 @@ hipError_t launch_compose_up_write_v210(hipStream_t s, const UpArgs &a, bool rgb
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
   if (e != hipSuccess) return e;
   UpArgs b = a;
-  if (!b.jobs) b.jobs = 1;
-  b.out_qpitch = v210_pitch_bytes(a.out_w) / 16u;
-  b.cover_w = tails ? b.out_qpitch * 6u : a.out_w;
-  b.shared = 1;  // every layer has the size and the placement of the first: the patch geometry and the weights are computed once per block
-  for (int l = 1; l < a.n; ++l) {
-    b.shared = b.shared && a.layer[l].w == a.layer[0].w && a.layer[l].h == a.layer[0].h && a.layer[l].pitch == a.layer[0].pitch;
-    for (int k = 0; k < 6; ++k) b.shared = b.shared && a.layer[l].m[k] == a.layer[0].m[k];
-  }
-  const uint32_t upr = (b.cover_w + kUpCols - 1u) / kUpCols, upg = (uint32_t)(PH_UP_GROUP_ROWS / 2) * upr;
-  const uint32_t units = upr * ((a.lines + 1u) / 2u) * b.jobs;
-  // reciprocals for the kernel's uniform divisions: umulhi(v, ceil(2^32 / d)) == v / d while v * d < 2^32
-  b.magic_upr = upr > 1 ? (uint32_t)(((1ull << 32) + upr - 1) / upr) : 0u;
-  b.magic_upg = (uint32_t)(((1ull << 32) + upg - 1) / upg);
-  const uint32_t want = (units + kUpBlock / 64 - 1) / (kUpBlock / 64);
-  const uint32_t grid = want < num_cus ? want : num_cus;
+  const uint32_t grid = up_plan(b, tails, num_cus);
   if (tails && rgb12) compose_up_write_v210_kernel<true, true><<<grid, kUpBlock, a.wr.bytes, s>>>(b);
   else if (tails) compose_up_write_v210_kernel<false, true><<<grid, kUpBlock, a.wr.bytes, s>>>(b);
   else if (rgb12) compose_up_write_v210_kernel<true><<<grid, kUpBlock, a.wr.bytes, s>>>(b);
   else compose_up_write_v210_kernel<false><<<grid, kUpBlock, a.wr.bytes, s>>>(b);
   return hipGetLastError();
+}
+
+// Several outputs of one composition: named compose_up_multi<rgb|rgba>x<outputs>j<jobs> in a route trace
+hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb12, uint32_t num_cus) {
+  if (!m.up.lines) return hipSuccess;
+  if (m.n_out < 1 || m.n_out > (uint32_t)kMaxUpOuts || m.up.jobs < 1 || m.up.jobs > (uint32_t)kMaxUpJobs) return hipErrorInvalidValue;
+  for (uint32_t k = 0; k < m.n_out; ++k)
+    if (!fmt_chan_out((int)m.out[k].fmt) || (m.out[k].fmt == PH_FMT_V210 && m.up.out_w % 48u)) return hipErrorInvalidValue;
+  char name[48];
+  snprintf(name, sizeof name, "compose_up_multi<%s>x%uj%u", rgb12 ? "rgb" : "rgba", m.n_out, m.up.jobs);
+  if (trace_launch(name)) return hipSuccess;
+  // the wave step: 126 columns with a v210 output (its quads), else 128 - every store instruction of a wave then covers whole 32-byte
+  // sectors of its row where the pitch allows (see compose_up_multi_kernel).  PH_UP_OUT_STEP=126 in the environment keeps 126 for every
+  // launch: the A/B that tools/up_out_bench.py step=126 recorded in profiles/up_out_bench_step126.jsonl
+  static const bool narrow_always = [] { const char *e = getenv("PH_UP_OUT_STEP"); return e && atoi(e) == 126; }();
+  bool v210 = false;
+  for (uint32_t k = 0; k < m.n_out; ++k) v210 = v210 || m.out[k].fmt == PH_FMT_V210;
+  const bool wide = !v210 && !narrow_always;
+  UpMultiArgs b = m;
+  const uint32_t grid = up_plan(b.up, false, num_cus, wide ? 128u : kUpCols);
+  auto go = [&](auto kernel) -> hipError_t {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
+    if (e != hipSuccess) return e;
+    kernel<<<grid, kUpBlock, b.up.wr.bytes, s>>>(b);
+    return hipGetLastError();
+  };
+  if (wide) return rgb12 ? go(compose_up_multi_kernel<true, 128u>) : go(compose_up_multi_kernel<false, 128u>);
+  return rgb12 ? go(compose_up_multi_kernel<true, kUpCols>) : go(compose_up_multi_kernel<false, kUpCols>);
 }
 
 }  // namespace ph

@@ -194,6 +194,7 @@ int resolve_program(const char *src, const char *name, ProgramChoice &c, std::st
   if (0 == strncmp(name, "chan_compose_v210_", 18)) return layers("chan_compose_v210_", 1, K_CHAN_COMPOSE);
   if (0 == strncmp(name, "chan_compose_multi_", 19)) return layers("chan_compose_multi_", 1, K_CHAN_COMPOSE);  // (the same program with more outputs: told apart by name, ph_run.cpp)
   if (0 == strncmp(name, "compose_up_write_v210_", 22)) return layers("compose_up_write_v210_", 1, K_COMPOSE_UP);
+  if (0 == strncmp(name, "compose_up_multi_", 17)) return layers("compose_up_multi_", 1, K_COMPOSE_UP);  // (the same program with any writer and more outputs: told apart by name, ph_run.cpp)
   if (0 == strcmp(name, "transform")) return set(c, K_TRANSFORM, name, how);
   if (0 == strcmp(name, "resize")) return set(c, K_RESIZE, name, how);
   if (0 == strncmp(name, "combine_", 8)) return layers("combine_", 2, K_COMBINE);

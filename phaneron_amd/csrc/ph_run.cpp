@@ -360,6 +360,10 @@ struct UpCall {
   ph_buf *o, *o2;
   Recipe r;  // (the Saver's pair)
   uint32_t width, height, interlace;
+  // compose_up_multi_<n>: every output as ph_compose_up_write_multi takes it, job-major (outs[1]: the twin's)
+  bool multi;  // the program is compose_up_multi_<n>
+  int n_out;
+  ph_chan_output outs[2][ph::kMaxUpOuts];
 };
 static int up_call_parse(Args &a, UpCall *u) {
   // l<i>In: the layer's image - an RGBA image buffer, or with packedRgb = 1 a buffer of packed f32 RGB (l<i>Width / l<i>Height:
@@ -368,7 +372,13 @@ static int up_call_parse(Args &a, UpCall *u) {
   u->n = a.prog->n_layers, u->rgb = a.num_or(0, "packedRgb") != 0;
   // output2 + l<i>In2 (optional): a second job of the same shape in the same launch - the other field of a de-interlaced frame
   // (ph_compose_up_write_v210_pair): same sizes, formats and placements, other data
-  u->pair = a.has("output2");
+  // compose_up_multi_<n>: the same layers; the outputs as chan_compose_multi_<n> names them (chan_output_parse: output, outPacking,
+  // outputU / V / C, outColMatrix, outGammaLut, interlace, then out<k>Packing, output<k>[U|V|C], out<k>ColMatrix, out<k>GammaLut,
+  // interlace<k>, k = 1..3).  There `output2` is output 2's frame, so the twin is announced by l0In2 and its planes are the first
+  // job's names behind the word twin: twinOutput, twinOutputU / V / C, twinOutput<k>, twinOutput<k>U / V / C.
+  u->multi = a.prog->kernel.compare(0, 17, "compose_up_multi_") == 0;
+  u->n_out = 0;
+  u->pair = u->multi ? a.has("l0In2") : a.has("output2");
   for (int i = 0; i < u->n; ++i) {
     const ph_buf *x = a.buf(0, "l%dIn", i), *x2 = nullptr;
     double lw = 0, lh = 0;
@@ -395,12 +405,47 @@ static int up_call_parse(Args &a, UpCall *u) {
     u->layers2[i] = u->layers[i];
     if (u->pair) u->layers2[i].data = x2->dptr;
   }
+  if (u->multi) {
+    u->o = u->o2 = nullptr, u->r = Recipe(), u->interlace = 0;
+    for (int k = 0; k < ph::kMaxUpOuts && !a.rc && (k == 0 || a.has("output%d", k)); ++k) {
+      ph_buf *wr_cm, *wr_lut;
+      ph_chan_output &o = u->outs[0][u->n_out++];
+      if (chan_output_parse(a, k, u->width, u->height, &o, &wr_cm, &wr_lut)) break;
+      for (int j = 0; j < k; ++j)
+        if (u->outs[0][j].planes[0] == o.planes[0]) return a.fail(PH_E_INVALID, "kernel argument 'output%d': the buffer is another output's too", k);
+      if (!u->pair) continue;
+      char prefix[24];
+      if (k) snprintf(prefix, sizeof prefix, "twinOutput%d", k);
+      else snprintf(prefix, sizeof prefix, "twinOutput");
+      ph_chan_output &t = u->outs[1][k];
+      t = o, t.planes[0] = t.planes[1] = t.planes[2] = nullptr;
+      a.planes(o.format, u->width, u->height, prefix, "", t.planes);
+      for (int j = 0; j <= k && !a.rc; ++j)
+        if (u->outs[0][j].planes[0] == t.planes[0] || (j < k && u->outs[1][j].planes[0] == t.planes[0]))
+          return a.fail(PH_E_INVALID, "kernel argument '%s': the buffer is another output's too", prefix);
+    }
+    // the outputs are numbered without a gap: an output<k> behind a missing one would be ignored without a word (`output2` alone is
+    // what compose_up_write_v210_<n> calls its twin: here the twin is l0In2 / twinOutput)
+    for (int k = u->n_out + 1; k < ph::kMaxUpOuts && !a.rc; ++k)
+      if (a.has("output%d", k)) return a.fail(PH_E_INVALID, "kernel argument 'output%d': there is no output%d (outputs are numbered without a gap; the twin's frame is twinOutput)", k, u->n_out);
+    return a.rc;
+  }
   u->o = a.buf(v210_bytes(u->width, u->height), "output");
   u->o2 = u->pair ? a.buf(v210_bytes(u->width, u->height), "output2") : nullptr;
   u->r = Recipe();
   a.saver(&u->r);
   u->interlace = (uint32_t)a.num_or(0, "interlace");
   return a.rc;
+}
+
+// a compose_up_multi_<n> job as the typed call
+static int up_call_multi(ph_ctx *ctx, int queue, const UpCall &u) {
+  const ph_image_layer *sets[2] = {u.layers, u.layers2};
+  ph_chan_output outs[2 * ph::kMaxUpOuts];
+  const int jobs = u.pair ? 2 : 1;
+  for (int j = 0; j < jobs; ++j)
+    for (int k = 0; k < u.n_out; ++k) outs[j * u.n_out + k] = u.outs[j][k];
+  return ph_compose_up_write_multi(ctx, queue, jobs, u.n, sets, u.n_out, outs, u.width, u.height);
 }
 
 // ph_run_program's argument marshalling, one function per kernel family: each checks the job's named arguments against the frame geometry
@@ -537,6 +582,7 @@ static int dispatch_compose(Args &a, int queue) {
       UpCall u;
       up_call_parse(a, &u);
       if (a.done()) return a.rc;
+      if (u.multi) return up_call_multi(ctx, queue, u);
       if (u.pair)
         return ph_compose_up_write_v210_pair(ctx, queue, u.n, u.layers, u.layers2, u.o->dptr, u.o2->dptr, u.width, u.height, u.interlace, u.r.wr_cm->dptr, u.r.wr_lut->dptr);
       return ph_compose_up_write_v210(ctx, queue, u.n, u.layers, u.o->dptr, u.width, u.height, u.interlace, u.r.wr_cm->dptr, u.r.wr_lut->dptr);
@@ -734,7 +780,7 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
     } else if (progs[j]->id == K_COMPOSE_UP) {
       if (ups.empty()) ups.resize((size_t)n_jobs);
       if ((rc = up_call_parse(job, &ups[(size_t)j]))) return rc;
-      kind[(size_t)j] = 3;
+      kind[(size_t)j] = ups[(size_t)j].multi ? 0 : 3;  // (a compose_up_multi_<n> job: a launch of its own, in its turn)
     } else if ((rc = dispatch(ctx, progs[j], args[j], n_args[j], queue, true))) {
       return rc;
     }
