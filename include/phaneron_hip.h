@@ -42,7 +42,8 @@ extern "C" {
  *    Later additive within 8: the 10-bit 4:2:0 formats PH_FMT_YUV420P10 / PH_FMT_P010 and PH_SRC_YUV420P10 / PH_SRC_P010 - new enum
  *    values an older binding never passes; no signature or struct changed.  ph_chan_compose_multi (ph_chan_output): several consumers'
  *    frames of one channel in one launch; program "chan_compose_multi_<n>".  ph_compose_up_write_multi: the same for the 2 x 2-block
- *    compositor (enlarged images), with every writer the channel kernel has */
+ *    compositor (enlarged images), with every writer the channel kernel has.  ph_chan_compose_batch_out (ph_chan_job_out): several
+ *    channels' frames for any consumers in one launch; context option "chan_batch_outs" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -558,6 +559,23 @@ typedef struct ph_chan_output {
 int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs,
                           uint32_t out_width, uint32_t out_height, const void *rd_col_matrix12, const void *rd_gamma_lut,
                           const void *rd_gamut9);
+/* Several CHANNELS' frames for any consumers in one launch: ph_chan_compose_batch's sharing (the tables loaded once, the wave steps of
+ * all jobs in front of one barrier) with ph_chan_compose_multi's outputs - an encoder's yuv422p8 / yuv420p / nv12 frame, the screen's
+ * rgba8 beside SDI's v210.  Exactly, in order, `n_jobs` calls of ph_chan_compose_multi (a job with n_out == 1: ph_chan_compose), bit for
+ * bit.  The entry point itself sees to it that no job of a launch reads or writes what another job of it writes: a job that does starts
+ * the next launch (two jobs may still be the two fields of one frame that is not 4:2:0).  A launch holds up to 4 jobs, 24 ops and 8
+ * outputs of ONE writer table and one set of composed lines ("chan_compose_batch_out<0|1|2>x<jobs>o<outputs>" in a trace); longer calls
+ * are split, and jobs a shared launch does not take - outputs that name another or several writer tables, one v210 frame that the
+ * enlarged-clip routes serve better, more than 24 ops - run in their turn through ph_chan_compose_multi.  Limits and errors as
+ * ph_chan_compose_multi, per job and output; every check is made before anything is launched: a refused call writes nothing. */
+typedef struct ph_chan_job_out {
+  int n;                       /* layers */
+  const ph_chan_layer *layers;
+  int n_out;                   /* 1..4 */
+  const ph_chan_output *outs;  /* as ph_chan_compose_multi takes them */
+} ph_chan_job_out;
+int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job_out *jobs, uint32_t out_width, uint32_t out_height,
+                              const void *rd_col_matrix12, const void *rd_gamma_lut, const void *rd_gamut9);
 /* Several consumers' frames of one ENLARGED composition in one launch: the 2 x 2-block compositor (ph_compose_up_write_v210) with any
  * writer the channel kernel has - v210, yuv422p10, yuv422p8, yuv420p, nv12, rgba8, bgra8 - and up to four outputs.  The composition
  * runs once; the block's twelve writer-table reads are made once, and every output packs the same twelve values with its own writer
@@ -628,7 +646,10 @@ int ph_lut_layout_of(const float *host_lut65536, ph_lut_layout *layout, void *ld
  *          "chan_enlarged" (default 1; 0 when PH_CHAN_ENLARGED=0 is in the environment): ph_chan_compose* make a frame all of whose
  *          layers are ENLARGED v210 clips (a 720p or SD clip filling a 1080 channel: the reference uploads clips at their own size,
  *          ffmpegProducer.ts:395-442) by ph_v210_read into scratch images + ph_compose_up_write_v210 - one conversion per source pixel
- *          instead of four per output pixel, the same bits; 0: the channel kernel for those frames too. */
+ *          instead of four per output pixel, the same bits; 0: the channel kernel for those frames too;
+ *          "chan_batch_outs" (default 0): 1 lets ph_run_programs put consecutive channel frames for other consumers than SDI
+ *          (chan_compose_v210_<n> with outPacking, chan_compose_multi_<n>) of one geometry and Loader recipe into shared launches
+ *          (ph_chan_compose_batch_out); 0: each such job a launch of its own, in its turn.  The same bits either way. */
 int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value);
 
 /* ---- host colour maths (src/process/colourMaths.ts, run by Loader/Saver constructors

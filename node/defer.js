@@ -100,6 +100,12 @@ class Deferral {
 		// `several`: sibling writes of one image folded into the launch - on where it measured faster by more than the separate side's
 		// spread (profiles/up_out_bench.jsonl, DESIGN.md 5.1).  `upWriters: true / false` on the context sets both.
 		this.upWriters = ctx.upWriters === undefined || ctx.upWriters === null ? Object.assign({}, UP_WRITERS_DEFAULT) : { alone: !!ctx.upWriters, several: !!ctx.upWriters }
+		// Several channels' frames of a tick for consumers other than SDI - an encoder's, the screen's - and for several consumers at once
+		// (chan_compose_multi_<n>) as ONE launch: they go down in one runPrograms call with the library's context option "chan_batch_outs"
+		// set (ph_chan_compose_batch_out).  `batchOuts: true` on the context; off unless asked for (DESIGN.md 5.1: measured through the
+		// library, not yet through node).
+		this.batchOuts = ctx.batchOuts === true
+		this.batchOutsSet = false
 	}
 
 	// ---- bookkeeping on buffers -----------------------------------------------------------------------------
@@ -367,7 +373,14 @@ class Deferral {
 					g.push(p)
 					continue
 				}
-				let g = groups.find((v) => !v[0].up && v[0].batchable && v.length < 8 && v[0].width === p.width && v[0].height === p.height && v[0].node.queue === p.node.queue &&
+				if (p.outs) { // frames for other consumers (batchOuts): one Loader recipe and one Saver table - every output brings its own matrix
+					let g = groups.find((v) => v[0].outs && v.length < 8 && v[0].width === p.width && v[0].height === p.height && v[0].node.queue === p.node.queue &&
+						Deferral.sameRecipe(v[0].loader, p.loader) && Deferral.same(v[0].saver.outGammaLut, p.saver.outGammaLut))
+					if (!g) groups.push((g = []))
+					g.push(p)
+					continue
+				}
+				let g = groups.find((v) => !v[0].up && !v[0].outs && v[0].batchable && v.length < 8 && v[0].width === p.width && v[0].height === p.height && v[0].node.queue === p.node.queue &&
 					Deferral.sameRecipe(v[0].loader, p.loader) && Deferral.same(v[0].saver.outColMatrix, p.saver.outColMatrix) && Deferral.same(v[0].saver.outGammaLut, p.saver.outGammaLut))
 				if (!g) groups.push((g = []))
 				g.push(p)
@@ -408,7 +421,10 @@ class Deferral {
 			for (const k of Object.keys(params)) {
 				let v = params[k]
 				if (v === undefined || v === null) continue
-				if ((k === 'colMatrix' || k === 'gammaLut' || k === 'gamutMatrix' || k === 'outColMatrix' || k === 'outGammaLut') && first[k]) v = first[k]
+				if (plans[0].outs) { // (the outputs keep their own writer matrices; every Saver table of the first plan's contents is named by its buffer)
+					if ((k === 'colMatrix' || k === 'gammaLut' || k === 'gamutMatrix') && first[k]) v = first[k]
+					else if (/^out\d*GammaLut$/.test(k) && first.outGammaLut && Deferral.same(v, first.outGammaLut)) v = first.outGammaLut
+				} else if ((k === 'colMatrix' || k === 'gammaLut' || k === 'gamutMatrix' || k === 'outColMatrix' || k === 'outGammaLut') && first[k]) v = first[k]
 				// (a packed field image as a source of a batched frame: the real image first - unless the frame is the compositor's and was told)
 				if (v && v._packed != null && !(params.packedRgb && /^l\d+In2?$/.test(k))) this._unpack(v)
 				nm.push(k)
@@ -418,6 +434,7 @@ class Deferral {
 			values.push(vs)
 		}
 		const queue = plans[0].node.queue
+		if (plans[0].outs && !this.batchOutsSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'chan_batch_outs', 1); this.batchOutsSet = true }
 		try {
 			this.ctx._native.runPrograms(this.ctx._ctx, progs, names, values, queue)
 		} catch (e) {
@@ -430,14 +447,14 @@ class Deferral {
 				this.stats.launched++
 				this.stats.batched = (this.stats.batched || 0) + made
 				this.launchedOn.set(queue, (this.launchedOn.get(queue) || 0) + 1)
-				for (const p of plans.slice(0, made)) this._done(p, p.candidates[0][2] || null)
+				for (const p of plans.slice(0, made)) this._done(p, p.candidates[0][2] || null, p.candidates[0][3])
 			}
 			return false
 		}
 		this.stats.launched++
 		this.stats.batched = (this.stats.batched || 0) + plans.length
 		this.launchedOn.set(queue, (this.launchedOn.get(queue) || 0) + 1)
-		for (const p of plans) this._done(p, p.candidates[0][2] || null) // (a compositor job that made both fields' frames: the twin's write is done too)
+		for (const p of plans) this._done(p, p.candidates[0][2] || null, p.candidates[0][3]) // (a several-outputs job: the siblings' writes are done too; a compositor job that made both fields' frames: the twin's write is done too)
 		return true
 	}
 
@@ -992,7 +1009,9 @@ class Deferral {
 		// ... or frames of the 2 x 2-block compositor (de-interlaced fields at their own size or enlarged: several 1080i channels in a tick)
 		const up = candidates[0][0].startsWith('compose_up_write_v210_')
 		const batchable = up || candidates[0][0].startsWith('fused_v210_combine_') || (candidates.length === 1 && candidates[0][0].startsWith('chan_compose_v210_') && !outFmt)
-		return { node, candidates, used, n, width, height, batchable, up, loader, saver, siblings, packedSources: frame.packedSources || null }
+		// ... or, with batchOuts, the channel kernel's frame for another consumer than SDI, or for several consumers (ph_chan_compose_batch_out)
+		const outs = this.batchOuts && !batchable && (candidates[0][0].startsWith('chan_compose_multi_') || (candidates.length === 1 && candidates[0][0].startsWith('chan_compose_v210_') && !!outFmt))
+		return { node, candidates, used, n, width, height, batchable: batchable || outs, outs, up, loader, saver, siblings, packedSources: frame.packedSources || null }
 	}
 	// The pending writes of other consumers on the image `node` writes: wire-format writes _writeFrame accepts, of the same geometry, on
 	// the same queue, into buffers of their own - at most three (the launch has four outputs).

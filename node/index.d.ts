@@ -98,12 +98,15 @@ export class clContext {
 	 * `upWriters` (default true for both classes of frame, as measured: DESIGN.md 5.1; PHANERON_UP_WRITERS=0): frames made from de-interlaced fields or
 	 * enlarged images for a consumer that is not SDI, and the writes of several consumers on one such image, are one launch of the 2 x 2-block
 	 * compositor from the packed fields (`compose_up_multi_<n>`); `false`: the fields unpacked and the channel kernel, a launch per consumer.
+	 * `batchOuts` (default false; PHANERON_BATCH_OUTS=1): the frames several channels post in one tick for consumers other than SDI (an encoder's
+	 * yuv422p8, the screen's rgba8) and for several consumers at once share ONE launch of the channel kernel (the library's context option
+	 * `chan_batch_outs`, ph_chan_compose_batch_out); `false`: a launch per channel, in its turn.  The same bytes either way.
 	 * `recycleBuffers` (default true; PHANERON_RECYCLE=0): released frames / images are parked for the next createBuffer of their shape,
 	 * up to `parkMb` MiB (default 4096) or the most that was ever in use at once.  A parked buffer is taken over as the same JS object;
 	 * `strictHandles` (default false; PHANERON_STRICT_HANDLES=1): a fresh object per takeover, so that a reference kept past release()
 	 * is refused ('... released buffer') instead of aliasing the next owner's buffer - for running an application under test. */
 	constructor(params?: { platformIndex?: number; deviceIndex?: number; overlapping?: boolean; profile?: boolean; spinWaitMicros?: number; deferred?: boolean;
-		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
+		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; batchOuts?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
 	readonly queue: { load: number; process: number; unload: number }
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo

@@ -163,6 +163,8 @@ class clContext {
 		// frames of the 2 x 2-block compositor for consumers other than SDI and for several consumers at once (node/defer.js upWriters);
 		// undefined: per class of frame as measured; true / false or PHANERON_UP_WRITERS=1 / 0: for every class
 		this.upWriters = params.upWriters === undefined ? (process.env.PHANERON_UP_WRITERS === undefined ? undefined : process.env.PHANERON_UP_WRITERS !== '0') : !!params.upWriters
+		// several channels' frames of a tick for consumers other than SDI, or for several consumers, as one launch (node/defer.js batchOuts): off unless asked for
+		this.batchOuts = params.batchOuts === undefined ? process.env.PHANERON_BATCH_OUTS === '1' : !!params.batchOuts
 		// released frames and images are parked and taken over whole by the next createBuffer of the same shape (free() above);
 		// `recycleBuffers: false` or PHANERON_RECYCLE=0 returns every buffer to the library at once.  parkMb: what may stay parked
 		// (default 4096 MiB - or as much as was ever in use at once, if that is more)

@@ -35,7 +35,7 @@ EXPORTS = [
     "ph_route_group_end", "ph_route_send", "ph_route_recv", "ph_route_after_queue", "ph_queue_after_route",
     "ph_route_wait", "ph_route_stream", "ph_route_comm_count", "ph_chan_compose_v210", "ph_chan_compose_batch", "ph_run_programs", "ph_event_record_timed", "ph_event_elapsed_us", "ph_ctx_host_pool_stats",
     "ph_v210_yadif_pair_fmt", "ph_compose_up_write_v210", "ph_trace_begin", "ph_trace_end", "ph_run_programs_progress", "ph_buf_reuse", "ph_image_unpack_rgb",
-    "ph_chan_compose_multi", "ph_compose_up_write_multi",
+    "ph_chan_compose_multi", "ph_compose_up_write_multi", "ph_chan_compose_batch_out",
 ]
 
 
@@ -79,6 +79,10 @@ class PhChanJob(C.Structure):
 
 class PhChanOutput(C.Structure):
     _fields_ = [("format", C.c_int), ("planes", C.c_void_p * 3), ("interlace", C.c_uint32), ("wr_col_matrix12", C.c_void_p), ("wr_gamma_lut", C.c_void_p)]
+
+
+class PhChanJobOut(C.Structure):
+    _fields_ = [("n", C.c_int), ("layers", C.POINTER(PhChanLayer)), ("n_out", C.c_int), ("outs", C.POINTER(PhChanOutput))]
 
 
 class PhImageLayer(C.Structure):
@@ -204,6 +208,7 @@ def lib():
         "ph_chan_compose_batch": (ci, [vp, ci, ci, C.POINTER(PhChanJob), cu, cu, vp, vp, vp, vp, vp]),
         "ph_chan_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_compose_up_write_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
+        "ph_chan_compose_batch_out": (ci, [vp, ci, ci, C.POINTER(PhChanJobOut), cu, cu, vp, vp, vp]),
         "ph_ctx_host_pool_stats": (ci, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
         "ph_event_record_timed": (ci, [vp, ci, C.POINTER(vp)]),
         "ph_event_elapsed_us": (ci, [vp, vp, C.POINTER(cu)]),
@@ -724,11 +729,8 @@ class Context:
             return job
         check(fn(*args), h)
 
-    def chan_compose_multi(self, layers, outputs, out_w, out_h, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
-        """Several consumers' frames of one composition in one launch (ph_chan_compose_multi).  layers as chan_compose_v210 takes
-        them; outputs: 1..4 dicts {fmt: a FORMATS name, planes: the frame's plane tensors (a v210 / packed-RGB frame: one),
-        interlace: 0 / 1 / 3, wr_cm: the writer's matrix tensor (None for rgba8 / bgra8), wr_lut: its registered table}."""
-        arr, keep = self._chan_layers(layers)
+    @staticmethod
+    def _chan_outputs(outputs):
         outs = (PhChanOutput * max(len(outputs), 1))()
         for k, o in enumerate(outputs):
             planes = o["planes"] if isinstance(o["planes"], (list, tuple)) else [o["planes"]]
@@ -738,6 +740,33 @@ class Context:
             outs[k].interlace = int(o.get("interlace", 0))
             outs[k].wr_col_matrix12 = None if o.get("wr_cm") is None else _ptr(o["wr_cm"]).value
             outs[k].wr_gamma_lut = _ptr(o["wr_lut"]).value
+        return outs
+
+    def chan_compose_batch_out(self, jobs, out_w, out_h, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
+        """Several channels' frames for any consumers in one launch (ph_chan_compose_batch_out).  jobs: list of (layers, outputs) -
+        layers as chan_compose_v210 takes them, outputs 1..4 dicts as chan_compose_multi takes them."""
+        arr = (PhChanJobOut * max(len(jobs), 1))()
+        keep = []
+        for j, (layers, outputs) in enumerate(jobs):
+            la, k = self._chan_layers(layers)
+            outs = self._chan_outputs(outputs)
+            keep.append((la, k, layers, outputs, outs))
+            arr[j].n, arr[j].layers, arr[j].n_out, arr[j].outs = len(layers), la, len(outputs), outs
+        args = (self.h, queue, len(jobs), arr, out_w, out_h, _ptr(rd_cm), _ptr(rd_lut), _ptr(rd_gm))
+        fn, h = lib().ph_chan_compose_batch_out, self.h
+        if prepare_only:
+
+            def job(_keep=(keep, arr)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
+
+    def chan_compose_multi(self, layers, outputs, out_w, out_h, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
+        """Several consumers' frames of one composition in one launch (ph_chan_compose_multi).  layers as chan_compose_v210 takes
+        them; outputs: 1..4 dicts {fmt: a FORMATS name, planes: the frame's plane tensors (a v210 / packed-RGB frame: one),
+        interlace: 0 / 1 / 3, wr_cm: the writer's matrix tensor (None for rgba8 / bgra8), wr_lut: its registered table}."""
+        arr, keep = self._chan_layers(layers)
+        outs = self._chan_outputs(outputs)
         args = (self.h, queue, len(layers), arr, len(outputs), outs, out_w, out_h, _ptr(rd_cm), _ptr(rd_lut), _ptr(rd_gm))
         fn, h = lib().ph_chan_compose_multi, self.h
         if prepare_only:

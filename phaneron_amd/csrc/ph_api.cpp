@@ -3,6 +3,7 @@
 // `runProgram` contract the reference's clJobQueue drives) are ph_run.cpp, which calls the typed entry points.
 //
 // No CPU path exists here: every entry point that does work needs a HIP device.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdarg>
@@ -942,6 +943,10 @@ int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value) {
   }
   if (0 == strcmp(name, "fail_launches")) return ctx->fail_launches.store(value), PH_OK;
   if (0 == strcmp(name, "chan_enlarged")) return ctx->chan_enlarged = (value < 0 || value > 2 ? 1 : value), PH_OK;  // 2: never the one-launch form (A/B, tests)
+  if (0 == strcmp(name, "chan_batch_outs")) {
+    if (value != 0 && value != 1) return fail(PH_E_INVALID, "chan_batch_outs: 0 (a launch per such job) or 1 (shared launches)");
+    return ctx->chan_batch_outs = value, PH_OK;
+  }
   if (0 == strcmp(name, "host_pool_mb")) {
     if (value < 0) return fail(PH_E_INVALID, "host_pool_mb: a size in MiB");
     std::vector<ph_ctx::HostBlock> drop;
@@ -1613,6 +1618,21 @@ int ph_chan_compose(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, 
   return PH_OK;
 }
 
+// One output of a several-outputs call, checked as ph_chan_compose checks its only one.  where: "" or "job <j>: " (ph_chan_compose_batch_out)
+static int chan_output_check(const char *fn, const char *where, int k, const ph_chan_output &o, uint32_t out_w, uint32_t out_h) {
+  if (!o.planes[0] || !o.wr_gamma_lut) return fail(PH_E_INVALID, "%s: %soutput %d: NULL argument", fn, where, k);
+  if (!fmt_known(o.format)) return fail(PH_E_INVALID, "%s: %soutput %d: format %d is not a PH_FMT_*", fn, where, k, o.format);
+  if (!fmt_chan_out(o.format)) return chan_out_refused(fn, o.format);
+  if (!fmt_rgb8(o.format) && !o.wr_col_matrix12) return fail(PH_E_INVALID, "%s: %soutput %d: the writer's RGB -> YCbCr matrix is missing", fn, where, k);
+  if (fmt_planar(o.format) && (!o.planes[1] || (fmt_planes(o.format) == 3 && !o.planes[2])))
+    return fail(PH_E_INVALID, "%s: %soutput %d: a planar output needs its three planes (nv12: Y and the interleaved CbCr plane)", fn, where, k);
+  if (fmt_v420(o.format) && (out_h & 1)) return fail(PH_E_INVALID, "%s: %soutput %d: a 4:2:0 frame needs an even height (%u)", fn, where, k, out_h);
+  if ((o.format == PH_FMT_V210 && (out_w & 1)) || (fmt_planar(o.format) && out_w % 8))
+    return fail(PH_E_INVALID, "%s: %soutput %d: width %u (a v210 frame needs an even width, a planar one a multiple of 8); run the separate kernels", fn, where, k, out_w);
+  if (o.interlace != 0 && o.interlace != 1 && o.interlace != 3) return fail(PH_E_INVALID, "%s: %soutput %d: interlace must be 0, 1 or 3", fn, where, k);
+  return PH_OK;
+}
+
 /* Several consumers' frames of one composition in one launch: see include/phaneron_hip.h.  Every check is made before anything is
  * launched; the checks and their texts are ph_chan_compose's, per output. */
 int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w,
@@ -1628,16 +1648,7 @@ int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
   bool any_v210 = false, same_lines = true;
   for (int k = 0; k < n_out; ++k) {
     const ph_chan_output &o = outs[k];
-    if (!o.planes[0] || !o.wr_gamma_lut) return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: NULL argument", k);
-    if (!fmt_known(o.format)) return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: format %d is not a PH_FMT_*", k, o.format);
-    if (!fmt_chan_out(o.format)) return chan_out_refused("ph_chan_compose_multi", o.format);
-    if (!fmt_rgb8(o.format) && !o.wr_col_matrix12) return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: the writer's RGB -> YCbCr matrix is missing", k);
-    if (fmt_planar(o.format) && (!o.planes[1] || (fmt_planes(o.format) == 3 && !o.planes[2])))
-      return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: a planar output needs its three planes (nv12: Y and the interleaved CbCr plane)", k);
-    if (fmt_v420(o.format) && (out_h & 1)) return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: a 4:2:0 frame needs an even height (%u)", k, out_h);
-    if ((o.format == PH_FMT_V210 && (out_w & 1)) || (fmt_planar(o.format) && out_w % 8))
-      return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: width %u (a v210 frame needs an even width, a planar one a multiple of 8); run the separate kernels", k, out_w);
-    if (o.interlace != 0 && o.interlace != 1 && o.interlace != 3) return fail(PH_E_INVALID, "ph_chan_compose_multi: output %d: interlace must be 0, 1 or 3", k);
+    if (const int bad = chan_output_check("ph_chan_compose_multi", "", k, o, out_w, out_h)) return bad;
     for (int j = 0; j < k; ++j)
       if (outs[j].planes[0] == o.planes[0]) return fail(PH_E_INVALID, "ph_chan_compose_multi: outputs %d and %d name the same plane", j, k);
     any_v210 = any_v210 || o.format == PH_FMT_V210;
@@ -1882,6 +1893,216 @@ int ph_chan_compose_batch(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job 
     b.n_ops += (uint32_t)k, ++b.jobs;
   }
   if ((rc = flush_enlarged())) return rc;
+  return flush();
+}
+
+/* Several channels' frames for any consumers in one launch: see include/phaneron_hip.h.  Every check of every job is made before anything
+ * is launched.  Jobs the shared launch does not take run through ph_chan_compose_multi in their turn; a launch that ends up with one job
+ * is that call too, so a job on its own keeps the routes it has today. */
+namespace {
+struct ChanSpan {  // bytes a job reads or writes; for an output's planes also what lets two fields of one frame share a launch
+  const char *p;
+  size_t n;
+  int fmt;             // an output's PH_FMT_* (-1: a source)
+  uint32_t interlace;
+};
+bool spans_meet(const ChanSpan &a, const ChanSpan &b) { return a.n && b.n && a.p < b.p + b.n && b.p < a.p + a.n; }
+// two outputs that may be written side by side although their bytes meet: the two fields of one frame (not 4:2:0: both fields of a
+// line pair write the pair's chroma line, and the later call has to win)
+bool spans_interleave(const ChanSpan &a, const ChanSpan &b) {
+  return a.p == b.p && a.fmt >= 0 && a.fmt == b.fmt && !fmt_v420(a.fmt) && a.interlace && b.interlace && a.interlace != b.interlace;
+}
+struct ChanOutJob {
+  ph::ChanArgs one{};  // the job's program (op, plane_u / plane_v, cm_op, planar)
+  int n_ops = 0;
+  uint32_t interlace = 0;  // the lines the job composes: the field every output wants, or the frame
+  bool same_lines = true, any_v210 = false, joins = false;
+  const void *table = nullptr;  // the writer table all its outputs name (NULL: they name several)
+  std::vector<ChanSpan> reads, writes;
+};
+}  // namespace
+
+int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job_out *jobs, uint32_t out_w, uint32_t out_h, const void *rd_cm,
+                              const void *rd_lut, const void *rd_gm) {
+  static const char *const fn = "ph_chan_compose_batch_out";
+  if (!ctx) {  // (a caller whose ph_ctx_create found no device gets that answer here too: there is no CPU path)
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(PH_E_NO_DEVICE, "%s: no HIP device available; libphaneron_hip has no CPU path", fn);
+  }
+  if (!ctx || !jobs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  PH_QUEUE(fn, queue);
+  if (n_jobs < 1) return fail(PH_E_INVALID, "%s: no jobs", fn);
+  if (!out_w) return fail(PH_E_INVALID, "%s: width 0", fn);
+  const LutRef rref = lds_view(ctx, rd_lut);
+  if (!rref.get()) return fail(PH_E_INVALID, "%s: the reader gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn);
+  std::vector<ChanOutJob> plan((size_t)n_jobs);
+  uint32_t plan_jobs = 0, plan_ops = 0, plan_outs = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const ph_chan_job_out &J = jobs[j];
+    ChanOutJob &P = plan[(size_t)j];
+    char where[24];
+    snprintf(where, sizeof where, "job %d: ", j);
+    if (!J.layers || !J.outs) return fail(PH_E_INVALID, "%s: %sNULL argument", fn, where);
+    if (J.n_out < 1 || J.n_out > ph::kMaxChanOuts) return fail(PH_E_INVALID, "%s: %s1..%d outputs (%d)", fn, where, ph::kMaxChanOuts, J.n_out);
+    if (J.n < 1 || J.n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: %s1..%d layers", fn, where, ph::kMaxLayers);
+    P.table = J.outs[0].wr_gamma_lut;
+    for (int k = 0; k < J.n_out; ++k) {
+      const ph_chan_output &o = J.outs[k];
+      if (const int bad = chan_output_check(fn, where, k, o, out_w, out_h)) return bad;
+      for (int i = 0; i < k; ++i)
+        if (J.outs[i].planes[0] == o.planes[0]) return fail(PH_E_INVALID, "%s: %soutputs %d and %d name the same plane", fn, where, i, k);
+      if (!lds_view(ctx, o.wr_gamma_lut).found)
+        return fail(PH_E_INVALID, "%s: %soutput %d: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn, where, k);
+      P.any_v210 = P.any_v210 || o.format == PH_FMT_V210;
+      P.same_lines = P.same_lines && o.interlace == J.outs[0].interlace;
+      if (o.wr_gamma_lut != P.table) P.table = nullptr;
+      size_t bytes[3];
+      const int planes = ph::pack_plane_bytes(o.format, out_w, out_h, bytes);
+      for (int i = 0; i < planes; ++i) P.writes.push_back(ChanSpan{(const char *)o.planes[i], bytes[i], o.format, o.interlace});  // (every plane of a 4:2:2 or packed frame has a row per line: fields interleave in all of them)
+    }
+    P.interlace = P.same_lines ? J.outs[0].interlace : 0u;
+    if (const int bad = chan_ops(J.n, J.layers, out_w, out_h, P.one.op, P.one.plane_u, P.one.plane_v, P.one.cm_op, &P.one.planar, &P.n_ops)) return bad;
+    for (int i = 0; i < P.n_ops; ++i) {
+      const ph::ChanSrc &src = P.one.op[i].src;
+      P.reads.push_back(ChanSpan{(const char *)src.ptr, (size_t)src.pitch * src.h, -1, 0u});
+      // a planar frame's chroma planes, sized as the kernel sizes them (ph_kernels_chan.hip planes_of)
+      const bool v420 = src.kind == ph::kChanP8x420 || src.kind == ph::kChanNv12 || src.kind == ph::kChanP10x420 || src.kind == ph::kChanP010;
+      const bool cbcr = src.kind == ph::kChanNv12 || src.kind == ph::kChanP010;
+      const size_t chroma = (size_t)(cbcr ? src.pitch : src.pitch >> 1) * (v420 ? (src.h + 1u) >> 1 : src.h);
+      if (P.one.plane_u[i]) P.reads.push_back(ChanSpan{(const char *)P.one.plane_u[i], chroma, -1, 0u});
+      if (P.one.plane_v[i]) P.reads.push_back(ChanSpan{(const char *)P.one.plane_v[i], chroma, -1, 0u});
+    }
+    // what the shared launch takes: one writer table, a program and outputs that fit, lines to compose - and not the one v210 frame
+    // that the enlarged-clip routes make better (ph_chan_compose takes them; with several outputs nobody does)
+    const ph_chan_output &o0 = J.outs[0];
+    const bool enlarged = J.n_out == 1 && o0.format == PH_FMT_V210 && o0.wr_col_matrix12 && ctx->chan_enlarged &&
+                          chan_layers_enlarged(J.n, J.layers, out_w, out_h, o0.interlace);
+    uint32_t own_cms = 0;  // (an over-estimate: the same matrix named twice counts twice)
+    for (int i = 0; i < P.n_ops; ++i) own_cms += P.one.cm_op[i] && P.one.cm_op[i] != (const float *)rd_cm ? 1u : 0u;
+    P.joins = chan_batch_on() && P.table && P.n_ops <= ph::kMaxChanOutOps && own_cms <= 8u && (P.interlace ? out_h / 2 : out_h) && !enlarged;
+    if (P.joins) ++plan_jobs, plan_ops += (uint32_t)P.n_ops, plan_outs += (uint32_t)J.n_out;
+  }
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  // how many jobs a launch should take so that the launches come out even (five jobs are 3 + 2, not 4 + 1: a job alone shares nothing)
+  auto over = [](uint32_t n, int per) { return (n + (uint32_t)per - 1u) / (uint32_t)per; };
+  uint32_t launches = over(plan_jobs, ph::kMaxChanOutJobs);
+  launches = std::max(launches, std::max(over(plan_ops, ph::kMaxChanOutOps), over(plan_outs, ph::kMaxChanBatchOuts)));
+  const uint32_t jobs_per_launch = launches ? (plan_jobs + launches - 1u) / launches : 1u;
+  auto hand_on = [&](int j) {
+    const ph_chan_job_out &J = jobs[j];
+    return ph_chan_compose_multi(ctx, queue, J.n, J.layers, J.n_out, J.outs, out_w, out_h, rd_cm, rd_lut, rd_gm);
+  };
+  // the launch being collected: its jobs [first_job, first_job + b.jobs), its writer table (a copy that holds across the jobs handed on) and its lines
+  ph::ChanBatchOutArgs b{};
+  int first_job = 0;
+  const void *table = nullptr;
+  LutRef wref;
+  uint32_t planar = 0;
+  bool fields = false, any_v210 = false;  // fields: the launch's jobs compose one field each (of either parity: a job's first line is its own)
+  auto flush = [&]() -> int {
+    if (!b.jobs) return PH_OK;
+    const uint32_t n_launch = b.jobs;
+    b.jobs = 0;
+    if (n_launch == 1) {
+      b = ph::ChanBatchOutArgs{};
+      return hand_on(first_job);
+    }
+    b.jobs = n_launch;
+    b.out_w = out_w, b.out_h = out_h, b.line_step = fields ? 2 : 1, b.lines = fields ? out_h / 2 : out_h;
+    b.rd_cm = (const float *)rd_cm, b.rd_gm = (const float *)rd_gm, b.rd = rref.view, b.wr = wref.view;
+    if (any_v210 && out_w % 48 && planar < 1) planar = 1;  // as ph_chan_compose: the tail instantiation writes lines that end in a tail / cleared slots
+    b.tails = planar >= 1 ? 1u : 0u, b.planar = planar == 2 ? 1u : 0u;
+    b.out_tail_from = any_v210 && out_w % 6 ? out_w - out_w % 6u : 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < b.n_out; ++k) {
+      ph::ChanBatchOut &d = b.out[k];
+      d.tail_from = d.fmt == PH_FMT_V210 ? b.out_tail_from : 0xFFFFFFFFu;
+      d.round = d.fmt != PH_FMT_V210 && b.out_tail_from != 0xFFFFFFFFu ? 1u : 0u;
+    }
+    const size_t each = (ph::chan_index_bytes(out_w, b.lines) + 255u) & ~(size_t)255u;
+    int r = PH_OK;
+    {
+      std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);
+      {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        r = chan_index_reserve(ctx, queue, each * b.jobs);
+        for (uint32_t j = 0; j < b.jobs && !r; ++j) b.job[j].index = (char *)ctx->chan_index[queue] + each * j;
+      }
+      if (!r) {
+        hipError_t e = ph::launch_chan_compose_batch_out(stream_of(ctx, queue), b, (uint32_t)ctx->props.multiProcessorCount);
+        if (e != hipSuccess) r = fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+      }
+    }
+    b = ph::ChanBatchOutArgs{};
+    return r;
+  };
+  for (int j = 0; j < n_jobs; ++j) {
+    const ph_chan_job_out &J = jobs[j];
+    const ChanOutJob &P = plan[(size_t)j];
+    if (!P.joins) {  // in its turn, on its own
+      if ((rc = flush())) return rc;
+      if ((rc = hand_on(j))) return rc;
+      continue;
+    }
+    // no job of a launch reads or writes what another job of it writes (two fields of one frame excepted): such a job starts the next launch
+    bool clash = false;
+    for (int i = first_job; i < first_job + (int)b.jobs && !clash; ++i) {
+      const ChanOutJob &Q = plan[(size_t)i];
+      for (const ChanSpan &w : P.writes) {
+        for (const ChanSpan &r : Q.reads) clash = clash || spans_meet(w, r);
+        for (const ChanSpan &v : Q.writes) clash = clash || (spans_meet(w, v) && !spans_interleave(w, v));
+      }
+      for (const ChanSpan &r : P.reads)
+        for (const ChanSpan &v : Q.writes) clash = clash || spans_meet(r, v);
+    }
+    // the job's Loader matrices as indices into the launch's small table (those already there are found again)
+    uint8_t cm_of[ph::kMaxChanOps] = {};
+    const float *tab[8];
+    auto place_cms = [&]() {
+      for (int t = 0; t < 8; ++t) tab[t] = b.cm_tab[t];
+      for (int i = 0; i < P.n_ops; ++i) {
+        cm_of[i] = 0;
+        const float *cm = P.one.cm_op[i];
+        if (!cm || cm == (const float *)rd_cm) continue;
+        int at = 0;
+        while (at < 8 && tab[at] && tab[at] != cm) ++at;
+        if (at == 8) return false;
+        tab[at] = cm, cm_of[i] = (uint8_t)(at + 1);
+      }
+      return true;
+    };
+    if (b.jobs && (clash || P.table != table || (P.interlace != 0) != fields || b.jobs >= jobs_per_launch || b.n_ops + (uint32_t)P.n_ops > (uint32_t)ph::kMaxChanOutOps ||
+                   b.n_out + (uint32_t)J.n_out > (uint32_t)ph::kMaxChanBatchOuts || !place_cms()))
+      if ((rc = flush())) return rc;
+    if (!b.jobs) {
+      first_job = j, table = P.table, wref = lds_view(ctx, table), fields = P.interlace != 0, planar = 0, any_v210 = false;
+      if (!wref.found) return fail(PH_E_INVALID, "%s: job %d: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn, j);
+    }
+    place_cms();  // (fits an empty table: the job has at most eight matrices of its own)
+    for (int t = 0; t < 8; ++t) b.cm_tab[t] = tab[t];
+    planar = std::max(planar, P.one.planar), any_v210 = any_v210 || P.any_v210;
+    ph::ChanJob &jb = b.job[b.jobs];
+    jb.first_op = b.n_ops, jb.n_ops = (uint32_t)P.n_ops, jb.first_line = P.interlace == 3 ? 1u : 0u;
+    for (int i = 0; i < P.n_ops; ++i) {
+      const uint32_t at = b.n_ops + (uint32_t)i;
+      b.op[at] = P.one.op[i], b.op_job[at] = (uint8_t)b.jobs;
+      b.plane_u[at] = P.one.plane_u[i], b.plane_v[at] = P.one.plane_v[i], b.cm_idx[at] = cm_of[i];
+      b.any_cm |= cm_of[i] ? 1u : 0u;
+    }
+    for (int k = 0; k < J.n_out; ++k) {
+      const ph_chan_output &o = J.outs[k];
+      ph::ChanBatchOut &d = b.out[b.n_out++];
+      d.fmt = (uint32_t)o.format;
+      d.pitch = o.format == PH_FMT_V210 ? ph_v210_pitch_bytes(out_w) / 16u : out_w;
+      d.plane[0] = o.planes[0], d.plane[1] = o.planes[1], d.plane[2] = o.planes[2];
+      d.takes = P.same_lines || !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
+      d.line_end = o.interlace ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as ph_chan_compose writes it)
+      d.field = o.interlace ? 1u : 0u;
+      d.job = b.jobs;
+      d.wr_cm = (const float *)(o.wr_col_matrix12 ? o.wr_col_matrix12 : rd_cm);
+    }
+    b.n_ops += (uint32_t)P.n_ops, ++b.jobs;
+  }
   return flush();
 }
 

@@ -62,6 +62,8 @@ struct ph_ctx {
   // 33 MB per tick: round 5 measured 40 ms per tick under the fixed 1 GiB of round 4)
   // option "chan_enlarged" (default 1; PH_CHAN_ENLARGED=0 in the environment makes it 0): frames of enlarged clips by read + 2 x 2-block compositor
   int chan_enlarged = !(getenv("PH_CHAN_ENLARGED") && getenv("PH_CHAN_ENLARGED")[0] == '0');
+  // option "chan_batch_outs" (default 0): ph_run_programs puts channel frames for other consumers than SDI into shared launches (ph_chan_compose_batch_out)
+  int chan_batch_outs = 0;
   std::atomic<int> fail_launches{0};  // option "fail_launches" (a TEST hook): > 0 every launch through ph_run_program(s) fails; -k: the next k go through, then every one fails
   int host_pool_mb = 4096;
   size_t host_live_bytes = 0, host_peak_bytes = 0;  // mirrors attached to buffers now / at most

@@ -185,6 +185,52 @@ static_assert(sizeof(ChanBatchArgs) <= 4096, "kernel arguments are limited to 4 
 bool trace_launch(const char *name);
 hipError_t launch_chan_compose_batch(hipStream_t s, const ChanBatchArgs &a, uint32_t num_cus);
 
+// Several channels' frames for ANY consumer format, several consumers per channel, in one launch (ph_chan_compose_batch_out): the batch
+// kernel's halo pass and phase 1 - the fields they read have ChanBatchArgs' names - and then the writer's phase per output on its job's
+// index frame, as the several-outputs kernel runs it.  ChanBatchArgs has no room for output descriptors, so ops are traded for outputs:
+// the reference's four channels, 24 ops, 8 outputs in all.  ONE writer table per launch (wr); an output brings its own writer matrix.
+// All jobs of a launch compose the same lines (lines, line_step; a job's first_line is its own): a job's lines are the union of what
+// its outputs want, as in ChanMultiArgs.
+constexpr int kMaxChanOutJobs = 4;
+constexpr int kMaxChanOutOps = 24;
+constexpr int kMaxChanBatchOuts = 8;
+struct ChanBatchOut {  // ChanOut without the table, with the job it belongs to
+  uint32_t fmt, pitch;
+  void *plane[3];
+  uint32_t tail_from, takes, line_end, field, round;
+  uint32_t job;
+  const float *wr_cm;
+};
+static_assert(sizeof(ChanBatchOut) == 64, "an output descriptor is one 64-byte scalar load");
+struct ChanBatchOutArgs {
+  ChanOp op[kMaxChanOutOps];
+  ChanJob job[kMaxChanOutJobs];  // (out is unused: the outputs name their planes)
+  ChanBatchOut out[kMaxChanBatchOuts];  // grouped by job, in the jobs' order
+  uint8_t op_job[kMaxChanOutOps];
+  uint32_t share_op[8];
+  uint32_t jobs, n_ops, n_share, n_out;
+  uint32_t magic_cpr, magic_cpg;
+  uint32_t steps;
+  uint32_t magic_spj;
+  uint32_t out_w, out_h, lines, line_step;
+  const float *rd_cm, *rd_gm;
+  LutView rd, wr;
+  uint32_t tails;
+  uint32_t out_tail_from;  // the first column of a v210 output's line tail (0xFFFFFFFF: no v210 output, or no tail): phase 1 parks those pixels truncated
+  uint32_t job_rot[kMaxChanOutJobs][4];
+  uint32_t sched_off;
+  uint32_t halo_off, halo_steps;
+  uint32_t images_only;
+  const void *plane_u[kMaxChanOutOps], *plane_v[kMaxChanOutOps];
+  const float *cm_tab[8];
+  uint8_t cm_idx[kMaxChanOutOps];
+  uint32_t planar;
+  uint32_t any_cm;
+};
+static_assert(sizeof(ChanBatchOutArgs) <= 4096, "kernel arguments are limited to 4 KiB");
+// refuses (hipErrorInvalidValue) more jobs, ops or outputs than the struct holds: callers split
+hipError_t launch_chan_compose_batch_out(hipStream_t s, const ChanBatchOutArgs &a, uint32_t num_cus);
+
 // ph_kernels_up.hip: the 2 x 2-block compositor for magnifying placements
 struct UpLayer {
   const void *ptr;       // f32 RGBA (16 bytes per texel) or packed f32 RGB (12)

@@ -1150,7 +1150,8 @@ __device__ __forceinline__ ChanJobShare chan_job_share(const ChanBatchArgs &a, c
   s.v0 = s.v0 >= sh.vstep ? s.v0 - sh.vstep : s.v0;
   return s;
 }
-__device__ __forceinline__ uint32_t chan_chunk_of(const ChanBatchArgs &a, const ChanShare &sh, uint32_t v0, uint32_t xcd, uint32_t vend, uint32_t slot) {
+template <class A>  // A: ChanBatchArgs, or ChanBatchOutArgs (the same fields under the same names)
+__device__ __forceinline__ uint32_t chan_chunk_of(const A &a, const ChanShare &sh, uint32_t v0, uint32_t xcd, uint32_t vend, uint32_t slot) {
   const uint32_t v = v0 + slot * sh.vstep;
   if (v >= vend) return ~0u;
   if (!sh.banded) return v;
@@ -1164,8 +1165,8 @@ __device__ __forceinline__ uint32_t chan_chunk_of(const ChanBatchArgs &a, const 
 // (Asking for the columns' words BEFORE the table's DMA and converting them after it was built and measured: the table then takes
 // 3.7 us to arrive instead of 1.6 - its wait is for the words too, which come late in the chip-wide rush for the table - 6.0 us of
 // prologue against 4.3.)
-template <bool STD, bool TAILS>
-__device__ __forceinline__ void chan_halo_pass_batch(const ChanBatchArgs &a, const ChanShare &sh, const ReadK &rk, const LutK &rlut) {
+template <bool STD, bool TAILS, class A>
+__device__ __forceinline__ void chan_halo_pass_batch(const A &a, const ChanShare &sh, const ReadK &rk, const LutK &rlut) {
   if (!a.n_share) return;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
   const uint32_t wps = (uint32_t)(kLdsBlock / 64) / a.n_share, s = wave / wps, ws = wave - s * wps;
@@ -1202,8 +1203,9 @@ __device__ __forceinline__ void chan_halo_pass_batch(const ChanBatchArgs &a, con
   }
 }
 
-template <bool STD, bool TAILS, bool PLANAR = false>
-__device__ __forceinline__ void chan_phase1_batch(const ChanBatchArgs &a, const ChanShare &sh, const ReadK &rk, const LutK &rlut) {
+// DUAL: as chan_phase1's - a launch with outputs of several formats parks a v210 tail's pixels truncated, the rounding beside them
+template <bool STD, bool TAILS, bool PLANAR = false, bool DUAL = false, class A>
+__device__ __forceinline__ void chan_phase1_batch(const A &a, const ChanShare &sh, const ReadK &rk, const LutK &rlut) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t S = a.steps, total = a.jobs * S;  // S: the most wave steps any workgroup has per job (a step beyond this workgroup's own has no chunk)
   const float fow = (float)(int)a.out_w, foh = (float)(int)a.out_h;
@@ -1277,7 +1279,12 @@ __device__ __forceinline__ void chan_phase1_batch(const ChanBatchArgs &a, const 
       auto index_of = [&](float t) __attribute__((always_inline)) {
         return __float_as_uint(TAILS ? lds_lut_index_unit_tail(t, trunc_idx) : lds_lut_index_unit(t)) & 0xFFFFu;
       };
-      const uint32_t ir = index_of(acc[p].r), ig = index_of(acc[p].g), ib = index_of(acc[p].b);
+      const uint32_t ir = index_of(acc[p].r), ig = index_of(acc[p].g);
+      uint32_t ib = index_of(acc[p].b);
+      if (TAILS && DUAL) {
+        auto up = [&](float t, uint32_t parked) __attribute__((always_inline)) { return (__float_as_uint(lds_lut_index_unit(t)) & 0xFFFFu) - parked; };
+        ib |= up(acc[p].r, ir) << 16 | up(acc[p].g, ig) << 17 | up(acc[p].b, ib) << 18;
+      }
       if (x < a.out_w) index[li[p] * a.out_w + x] = make_uint2(ir | (ig << 16), ib);
     }
   }
@@ -1373,6 +1380,69 @@ __global__ __launch_bounds__(kLdsBlock) void chan_compose_batch_kernel(ChanBatch
   PH_CPHASE(5);
 }
 
+// ---- several channels' frames for any consumer, several consumers per channel, per launch --------------------------------------------
+// The batch kernel's prologue, halo pass and phase 1 (phase 1 in the several-outputs kernel's DUAL form: a v210 output with a line tail
+// and a rounding output share an index frame), then the writer's phase per OUTPUT: each names its job, whose share of this workgroup and
+// index frame it walks with the functions the several-outputs kernel uses.  One writer table per launch.
+template <bool TAILS, bool PLANAR = false>
+__global__ __launch_bounds__(kLdsBlock) void chan_compose_batch_out_kernel(ChanBatchOutArgs a) {
+  const ReadK rk = load_read_k(a.rd_cm, a.rd_gm);
+  const LutK rlut = make_lut_k(a.rd);
+  const ChanShare sh = chan_share(a);
+  // the jobs' shares where the steps can index them per lane (chan_compose_batch_kernel; the pointers are read by scalar code here)
+  if (threadIdx.x < a.jobs) {
+    const uint32_t j = threadIdx.x;
+    const uint4 rot = chan_arg_lane<uint4>(offsetof(ChanBatchOutArgs, job_rot), j);
+    const uint32_t xcd = sh.banded ? (sh.xcd + j) & 7u : 0u;
+    const uint32_t vend = sh.banded ? ((sh.groups + 7u - xcd) >> 3) * sh.cpg : sh.chunks;
+    const uint32_t word = (xcd >> 1) == 0u ? rot.x : (xcd >> 1) == 1u ? rot.y : (xcd >> 1) == 2u ? rot.z : rot.w;
+    uint32_t v0 = sh.v0 + ((xcd & 1u) ? word >> 16 : word & 0xFFFFu);
+    v0 = v0 >= sh.vstep ? v0 - sh.vstep : v0;
+    reinterpret_cast<uint4 *>(g_lds + a.sched_off + kSchedShare)[j] = make_uint4(v0, xcd, vend, 0u);
+  }
+  if (threadIdx.x == 64u) *reinterpret_cast<uint32_t *>(g_lds + a.sched_off) = 0u;  // the counter the waves take their steps from
+  uint32_t touched = 0u;  // the argument block asked for at once, as the batch kernel does
+  if (PH_CHAN_ARG_PREFETCH && threadIdx.x >= (uint32_t)kLdsBlock - 64u && (threadIdx.x & 63u) * 64u < (uint32_t)sizeof(ChanBatchOutArgs))
+    touched = *(const __attribute__((address_space(1))) uint32_t *)((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + (threadIdx.x & 63u) * 64u);
+  if (!a.images_only) lds_lut_load(a.rd);  // (uniform)
+  if (touched == 0x9E3779B9u && a.jobs == 0xFFFFFFFFu) reinterpret_cast<uint32_t *>(g_lds + a.sched_off)[3] = touched;  // (never: keeps the loads above)
+  __syncthreads();
+  if (ycbcr_matrix_is_standard(rk) && !(PLANAR && a.any_cm)) {
+    chan_halo_pass_batch<true, TAILS>(a, sh, rk, rlut);
+    __syncthreads();
+    chan_phase1_batch<true, TAILS, PLANAR, true>(a, sh, rk, rlut);
+  } else {
+    chan_halo_pass_batch<false, TAILS>(a, sh, rk, rlut);
+    __syncthreads();
+    chan_phase1_batch<false, TAILS, PLANAR, true>(a, sh, rk, rlut);
+  }
+  __syncthreads();  // every index of this workgroup is stored, nobody reads the reader's table any more
+  lds_lut_load(a.wr);  // (the jobs' shares stay where they are: sched_off lies behind the larger of the two tables)
+  __syncthreads();
+  const LutK wlut = make_lut_k(a.wr);
+#pragma unroll 1  // one copy of the writers whatever the number of outputs; an output's descriptor is one 64-byte scalar load
+  for (uint32_t k = 0; k < a.n_out; ++k) {
+    const ChanBatchOut o = a.out[k];
+    const ChanJob jb = a.job[o.job];
+    const uint4 jsv = reinterpret_cast<const uint4 *>(g_lds + a.sched_off + kSchedShare)[o.job];
+    ChanShare js = sh;  // the job's share of this workgroup, with the fields chan_chunk reads
+    js.v0 = __builtin_amdgcn_readfirstlane(jsv.x), js.xcd = __builtin_amdgcn_readfirstlane(jsv.y), js.vend = __builtin_amdgcn_readfirstlane(jsv.z);
+    js.slots = js.v0 < js.vend ? (js.vend - js.v0 + js.vstep - 1u) / js.vstep : 0u;
+    const WriteK wk = load_write_k(o.wr_cm);
+    const ChanOutView v{jb.index, a.out_w, a.lines, jb.first_line, a.line_step, a.magic_cpr, a.magic_cpg, o.plane[0], o.plane[1], o.plane[2],
+                        o.pitch, o.pitch, o.takes, o.line_end, o.field, o.round};
+    switch (o.fmt) {  // uniform
+      case PH_FMT_V210: chan_phase2_v210<TAILS>(v, js, wk, wlut); break;
+      case PH_FMT_YUV422P10: chan_phase2_other<PH_FMT_YUV422P10>(v, js, wk, wlut); break;
+      case PH_FMT_YUV422P8: chan_phase2_other<PH_FMT_YUV422P8>(v, js, wk, wlut); break;
+      case PH_FMT_YUV420P: chan_phase2_other<PH_FMT_YUV420P>(v, js, wk, wlut); break;
+      case PH_FMT_NV12: chan_phase2_other<PH_FMT_NV12>(v, js, wk, wlut); break;
+      case PH_FMT_RGBA8: chan_phase2_other<PH_FMT_RGBA8>(v, js, wk, wlut); break;
+      case PH_FMT_BGRA8: chan_phase2_other<PH_FMT_BGRA8>(v, js, wk, wlut); break;
+    }
+  }
+}
+
 // the most slots (chunks) any workgroup of a `grid`-workgroup launch has (chan_share)
 static uint32_t chan_max_slots(uint32_t out_w, uint32_t lines, uint32_t grid) {
   const uint32_t cpr = (out_w + kChanChunk - 1u) / kChanChunk, cpg = (uint32_t)(PH_CHAN_GROUP_ROWS / 2) * cpr;
@@ -1387,15 +1457,16 @@ static uint32_t chan_grid(uint32_t out_w, uint32_t lines, uint32_t num_cus) {
   const uint32_t cpr = (out_w + kChanChunk - 1u) / kChanChunk, chunks = cpr * ((lines + 1u) / 2u);
   return chunks < num_cus ? chunks : num_cus;
 }
-hipError_t launch_chan_compose_batch(hipStream_t s, const ChanBatchArgs &a, uint32_t num_cus) {
-  if (!a.lines || !a.jobs) return hipSuccess;
-  if (a.jobs > (uint32_t)kMaxChanJobs || a.n_ops > (uint32_t)kMaxChanBatchOps) return hipErrorInvalidValue;
+// What a launch of the batch kernels needs beside its jobs: b = a with the launcher's fields (reciprocals, the jobs' rotations, the LDS
+// layout, the tap-sharing marks), the grid and the dynamic LDS.  A: ChanBatchArgs or ChanBatchOutArgs
+template <class A>
+static hipError_t chan_batch_plan(const A &a, A &b, uint32_t num_cus, uint32_t &grid, uint32_t &lds_total) {
   const uint32_t lds = a.rd.bytes > a.wr.bytes ? a.rd.bytes : a.wr.bytes;
   const uint32_t cpr = (a.out_w + kChanChunk - 1u) / kChanChunk, cpg = (uint32_t)(PH_CHAN_GROUP_ROWS / 2) * cpr;
-  const uint32_t grid = chan_grid(a.out_w, a.lines, num_cus);
+  grid = chan_grid(a.out_w, a.lines, num_cus);
   const uint32_t chunks = cpr * ((a.lines + 1u) / 2u);
   const uint32_t slots = chan_max_slots(a.out_w, a.lines, grid), steps = 3u * slots;
-  ChanBatchArgs b = a;
+  b = a;
   b.magic_cpr = cpr > 1 ? (uint32_t)(((1ull << 32) + cpr - 1) / cpr) : 0u;
   b.magic_cpg = (uint32_t)(((1ull << 32) + cpg - 1) / cpg);
   b.steps = steps;
@@ -1414,7 +1485,6 @@ hipError_t launch_chan_compose_batch(hipStream_t s, const ChanBatchArgs &a, uint
       else b.job_rot[j][x >> 1] = rot;
     }
   b.magic_spj = (uint32_t)(((1ull << 32) + steps - 1) / steps);
-  b.magic_qpj = (uint32_t)(((1ull << 32) + 64u * slots - 1) / (64u * slots));
   b.sched_off = (lds + 15u) & ~15u;
   b.halo_off = b.sched_off + kSchedBytes;
   if (b.halo_off > 160u * 1024u) return hipErrorInvalidValue;
@@ -1435,7 +1505,18 @@ hipError_t launch_chan_compose_batch(hipStream_t s, const ChanBatchArgs &a, uint
     b.share_op[b.n_share++] = k | j << 8 | b.job[j].first_line << 16;
   }
   if (b.n_share) b.halo_steps = steps;
-  const uint32_t lds_total = b.halo_off + b.n_share * steps * 36u;
+  lds_total = b.halo_off + b.n_share * steps * 36u;
+  return hipSuccess;
+}
+
+hipError_t launch_chan_compose_batch(hipStream_t s, const ChanBatchArgs &a, uint32_t num_cus) {
+  if (!a.lines || !a.jobs) return hipSuccess;
+  if (a.jobs > (uint32_t)kMaxChanJobs || a.n_ops > (uint32_t)kMaxChanBatchOps) return hipErrorInvalidValue;
+  ChanBatchArgs b;
+  uint32_t grid, lds_total;
+  const hipError_t planned = chan_batch_plan(a, b, num_cus, grid, lds_total);
+  if (planned != hipSuccess) return planned;
+  b.magic_qpj = (uint32_t)(((1ull << 32) + 64u * (b.steps / 3u) - 1) / (64u * (b.steps / 3u)));
   auto go = [&](auto kernel) -> hipError_t {
     char name[48];
     snprintf(name, sizeof name, "chan_compose_batch<%u>x%u", a.planar ? 2u : a.tails ? 1u : 0u, a.jobs);  // (route trace: the instantiation - 0 whole blocks, 1 line tails, 2 planar sources - and the jobs sharing it)
@@ -1446,6 +1527,27 @@ hipError_t launch_chan_compose_batch(hipStream_t s, const ChanBatchArgs &a, uint
     return hipGetLastError();
   };
   return a.planar ? go(chan_compose_batch_kernel<true, true>) : a.tails ? go(chan_compose_batch_kernel<true>) : go(chan_compose_batch_kernel<false>);
+}
+
+hipError_t launch_chan_compose_batch_out(hipStream_t s, const ChanBatchOutArgs &a, uint32_t num_cus) {
+  if (!a.lines || !a.jobs) return hipSuccess;
+  if (a.jobs > (uint32_t)kMaxChanOutJobs || a.n_ops > (uint32_t)kMaxChanOutOps || a.n_out < 1 || a.n_out > (uint32_t)kMaxChanBatchOuts) return hipErrorInvalidValue;
+  for (uint32_t k = 0; k < a.n_out; ++k)
+    if (a.out[k].job >= a.jobs) return hipErrorInvalidValue;
+  ChanBatchOutArgs b;
+  uint32_t grid, lds_total;
+  const hipError_t planned = chan_batch_plan(a, b, num_cus, grid, lds_total);
+  if (planned != hipSuccess) return planned;
+  auto go = [&](auto kernel) -> hipError_t {
+    char name[56];
+    snprintf(name, sizeof name, "chan_compose_batch_out<%u>x%uo%u", a.planar ? 2u : a.tails ? 1u : 0u, a.jobs, a.n_out);  // (route trace: as the batch kernel's, and the outputs made)
+    if (trace_launch(name)) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
+    if (e != hipSuccess) return e;
+    kernel<<<grid, kLdsBlock, lds_total, s>>>(b);
+    return hipGetLastError();
+  };
+  return a.planar ? go(chan_compose_batch_out_kernel<true, true>) : a.tails ? go(chan_compose_batch_out_kernel<true>) : go(chan_compose_batch_out_kernel<false>);
 }
 
 size_t chan_index_bytes(uint32_t out_w, uint32_t lines) { return (size_t)out_w * lines * 8u + 64u; }  // + a tail quad's reach past the last line

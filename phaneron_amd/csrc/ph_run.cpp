@@ -746,7 +746,9 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * the SAME Loader / Saver buffers and make v210 frames) put into launches together (ph_chan_compose_batch), likewise consecutive
  * fused_v210_combine_<n> frames; a job that reads or writes what an earlier job of its group writes (or writes what one reads) is
  * detected here and starts the next launch, so call order holds (include/phaneron_hip.h).  A chan_compose_multi_<n> job runs in its turn
- * as a launch of its own - it ends the group in front of it, so whatever that group writes is there for it, and all its outputs for what follows.  A call that fails after its checks
+ * as a launch of its own - it ends the group in front of it, so whatever that group writes is there for it, and all its outputs for what follows.
+ * With the context option "chan_batch_outs" = 1 (default 0) consecutive chan_compose_multi_<n> jobs and chan_compose_v210_<n> jobs that
+ * make another format than v210 (outPacking) share launches as well (ph_chan_compose_batch_out).  A call that fails after its checks
  * (a launch refused) has made the launches of the jobs before the failing group: ph_run_programs_progress says how many. */
 namespace {
 thread_local int g_programs_done = 0;  // jobs of the calling thread's last ph_run_programs call whose launches were made
@@ -766,14 +768,18 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
   std::vector<ChanCall> calls((size_t)n_jobs);
   std::vector<FusedCall> fused((size_t)n_jobs);
   std::vector<UpCall> ups;  // (sized when the first compose_up job shows up: most calls have none)
-  std::vector<char> kind((size_t)n_jobs, 0);  // 1: a v210 frame from the channel kernel, 2: fused_v210_combine, 3: compose_up_write_v210, 0: whatever else, launched as it is
+  // 1: a v210 frame from the channel kernel, 2: fused_v210_combine, 3: compose_up_write_v210, 4: a channel's frame for other consumers
+  // (option "chan_batch_outs"), 0: whatever else, launched as it is
+  std::vector<char> kind((size_t)n_jobs, 0);
   for (int j = 0; j < n_jobs; ++j) {  // every job is checked before anything is launched: a bad one refuses the call as a whole
     if (!progs[j] || (n_args[j] > 0 && !args[j])) return fail(PH_E_INVALID, "ph_run_programs: job %d: NULL argument", j);
     if ((rc = flush_dirty_args(ctx, args[j], n_args[j], queue))) return rc;
     Args job{ctx, progs[j], args[j], n_args[j], false};
     if (progs[j]->id == K_CHAN_COMPOSE) {
       if ((rc = chan_call_parse(job, &calls[(size_t)j]))) return rc;
-      kind[(size_t)j] = calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi;  // (a chan_compose_multi_<n> job: a launch of its own, in its turn)
+      // (a frame for another consumer, or a chan_compose_multi_<n> job: a launch of its own, in its turn - unless the context option
+      // "chan_batch_outs" lets such jobs share launches too: ph_chan_compose_batch_out)
+      kind[(size_t)j] = calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
     } else if (progs[j]->id == K_FUSED_V210) {
       if ((rc = fused_call_parse(job, &fused[(size_t)j]))) return rc;
       kind[(size_t)j] = 2;
@@ -849,6 +855,22 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
         continue;
       }
       rc = ph_compose_up_write_v210_batch(ctx, queue, frames, u0.n, sets, outs, u0.width, u0.height, u0.interlace, u0.r.wr_cm->dptr, u0.r.wr_lut->dptr);
+      if (rc) return rc;
+      g_programs_done = j = k;
+      continue;
+    }
+    if (kind[(size_t)j] == 4) {
+      // channels' frames for consumers other than SDI, or for several consumers, of one geometry and one Loader recipe: one call of
+      // ph_chan_compose_batch_out, which itself starts the next launch where a job reads or writes what an earlier one writes, and runs
+      // the jobs that name another Saver table in their turn
+      const ChanCall &c0 = calls[(size_t)j];
+      std::vector<ph_chan_job_out> batch;
+      for (; k < n_jobs && kind[(size_t)k] == 4; ++k) {
+        const ChanCall &c = calls[(size_t)k];
+        if (c.width != c0.width || c.height != c0.height || c.r.rd_cm != c0.r.rd_cm || c.r.rd_lut != c0.r.rd_lut || c.r.rd_gm != c0.r.rd_gm) break;
+        batch.push_back(ph_chan_job_out{c.n_layers, c.layers, c.n_out, c.outs});
+      }
+      rc = ph_chan_compose_batch_out(ctx, queue, (int)batch.size(), batch.data(), c0.width, c0.height, c0.r.rd_cm->dptr, c0.r.rd_lut->dptr, c0.r.rd_gm->dptr);
       if (rc) return rc;
       g_programs_done = j = k;
       continue;
