@@ -458,7 +458,8 @@ int ph_compose_up_write_v210_pair(ph_ctx *ctx, int queue, int n, const ph_image_
                                   const void *wr_gamma_lut);
 /* The same for 1 .. 4 sets of layers that differ in their data only - several channels showing clips of one size under one placement
  * (the reference's channels share a context and a queue: src/index.ts:45-71,156-160): layer_sets[j][l] is layer l of job j, outs[j] its
- * output (all different).  ph_chan_compose_batch uses it for the frames of enlarged clips among its jobs. */
+ * output (all different).  The jobs of one call run side by side: no job may read - as a layer image - what another job of the call
+ * writes (ph_run_programs sees to that for its by-name jobs).  ph_chan_compose_batch uses it for the frames of enlarged clips among its jobs. */
 int ph_compose_up_write_v210_batch(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, void *const *outs,
                                    uint32_t out_width, uint32_t out_height, uint32_t interlace, const void *wr_col_matrix12,
                                    const void *wr_gamma_lut);

@@ -290,11 +290,13 @@ class Deferral {
 		Deferral.adopt(buf)
 		if (dir === 'readonly') { this.force(buf); if (buf._packed != null) this._unpack(buf) } // (whoever reads it on the host or sends it away gets the image it is declared as)
 		else {
-			buf._packed = null
 			if (buf._digest) buf._digest = null
 			this._untwin(buf)
 			this.beforeWrite(buf)
 			if (buf._producer) this.force(buf) // (a recorded result the host overwrites: run it rather than reason about partial writes)
+			// (only now, as record() does it: a pending reader of the old contents that is not the compositor has just been given the real
+			// image - _launch unpacks what is still marked - and what the host writes next is the image the buffer is declared as)
+			buf._packed = null
 			buf._failed = null
 		}
 		for (const [q, epoch] of this.launchedOn) {
@@ -433,6 +435,9 @@ class Deferral {
 			names.push(nm)
 			values.push(vs)
 		}
+		// (putting a frame's arguments together may have unpacked a field an earlier frame of the call was told is packed: nothing is launched,
+		// the caller goes through the frames one by one and plans the stale ones again)
+		for (const p of plans) if (!this._fresh(p)) return false
 		const queue = plans[0].node.queue
 		if (plans[0].outs && !this.batchOutsSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'chan_batch_outs', 1); this.batchOutsSet = true }
 		try {
@@ -883,6 +888,9 @@ class Deferral {
 			})
 			let twin = this._twinWrite(node, layers) // the frame's other field, recorded too: both in one launch
 			if (twin && !twin.sources.every((im) => (im._packed != null) === packedLayers)) twin = null
+			// (a plan made for packed fields is stale once somebody has unpacked one - a plain consumer of the same field run while the other
+			// frames of the tick were planned: _fresh looks, for this field's images and the twin's)
+			if (packedLayers) frame.packedSources = layers.map((l) => l.source).concat(twin ? twin.sources : [])
 			if (twin) {
 				const both = Object.assign({ output2: twin.output }, params)
 				twin.sources.forEach((im, i) => { both[`l${i}In2`] = im })
@@ -996,7 +1004,7 @@ class Deferral {
 					candidates.unshift([`compose_up_multi_${n}`, params, null, upSiblings])
 				}
 				// (a plan made for packed fields is stale once somebody has unpacked one: _fresh looks)
-				if (upMulti.packedLayers) frame.packedSources = layers.map((l) => l.source).concat(twin ? twin.sources : [])
+				if (upMulti.packedLayers) frame.packedSources = (frame.packedSources || []).concat(layers.map((l) => l.source), twin ? twin.sources : [])
 				// (what _fresh watches: this field's sibling writes and the twin's - one that ran in between would be written a second time)
 				const watched = upSiblings.concat(twinSiblings.map((t) => t.node))
 				siblings = siblings ? siblings.concat(watched.filter((w) => !siblings.includes(w))) : watched

@@ -545,13 +545,16 @@ static int marshal_args(napi_env env, napi_value names_arr, napi_value values_ar
 }
 
 /* runPrograms(ctx, progs[], names[][], values[][], queue): several recorded jobs in one call (ph_run_programs) - the jobs in their
- * order, channel frames of one shape among them in one launch.  Asynchronous like an untimed runProgram; throws what the library refuses. */
+ * order, channel frames of one shape among them in one launch.  Asynchronous like an untimed runProgram; throws what the library refuses.
+ * runProgramsProgress() is 0 after a call that threw before it reached the library (a bad handle, an argument that does not marshal):
+ * nothing was launched, and the count of the call before must not stand (node/defer.js retires that many frames as made). */
 static napi_value RunPrograms(napi_env env, napi_callback_info info) {
   size_t argc = 5;
   napi_value argv[5];
   ctx_box *c;
   uint32_t jobs = 0;
   int32_t q = PH_QUEUE_PROCESS;
+  (void)ph_run_programs(NULL, 0, NULL, NULL, NULL, 0); /* a call the library refuses at once: it leaves this thread's progress at 0 */
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < 4 || !get_box(env, argv[0], (void **)&c)) return throw_ph(env, "runPrograms: bad context");
   napi_get_array_length(env, argv[1], &jobs);

@@ -668,8 +668,9 @@ static int dispatch_image(Args &a, int queue) {
   }
   return fail(PH_E_UNKNOWN_KERNEL, "unhandled kernel id");
 }
-static int dispatch(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n, int queue, bool check_only = false) {
-  if (!check_only && inject_failure(ctx)) return fail(PH_E_HIP, "%s: launch failed: injected (context option fail_launches)", prog->kernel.c_str());
+// (injection_asked: the caller has put this launch to the "fail_launches" fault injection itself)
+static int dispatch(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n, int queue, bool check_only = false, bool injection_asked = false) {
+  if (!check_only && !injection_asked && inject_failure(ctx)) return fail(PH_E_HIP, "%s: launch failed: injected (context option fail_launches)", prog->kernel.c_str());
   Args a{ctx, prog, args, n, check_only};
   switch (prog->id) {
     case K_PACK_READ:
@@ -759,9 +760,9 @@ int ph_run_programs_progress(int *jobs_done) {
   return PH_OK;
 }
 int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_arg *const *args, const int *n_args, int queue) {
+  g_programs_done = 0;  // first of all: a call refused by ANY check has made nothing, and must not leave the call before it standing
   if (!ctx || n_jobs < 1 || !progs || !args || !n_args) return fail(PH_E_INVALID, "ph_run_programs: NULL argument");
   PH_QUEUE("ph_run_programs", queue);
-  g_programs_done = 0;
   int rc = set_device(ctx);
   if (rc) return rc;
   if (ctx->fail_launches.load() > 0) return fail(PH_E_HIP, "ph_run_programs: launch failed: injected (context option fail_launches)");
@@ -830,11 +831,26 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
     if (kind[(size_t)j] == 3) {
       // frames of the 2 x 2-block compositor of ONE shape (layer count, image format and sizes, placements, output size, field mode, Saver) -
       // several channels' frames from de-interlaced fields, each job one frame or a frame's two fields - in one launch of up to
-      // kMaxUpJobs frames (ph_compose_up_write_v210_batch); a job that writes a frame an earlier one of the group writes starts the next
+      // kMaxUpJobs frames (ph_compose_up_write_v210_batch).  The frames of one launch are made side by side, so a job that writes a frame an
+      // earlier one of the group writes, whose layer images (either field's) overlap a frame an earlier one writes, or whose frame overlaps
+      // an earlier one's layer images starts the next launch: call order is kept.  By byte range, as the headline kernel's groups - a
+      // layer image is any buffer of w * h * 16 bytes (packedRgb: 12), a frame any buffer of v210_bytes.
       const UpCall &u0 = ups[(size_t)j];
       const ph_image_layer *sets[ph::kMaxUpJobs];
       void *outs[ph::kMaxUpJobs];
       int frames = 0;
+      const size_t frame_bytes = v210_bytes(u0.width, u0.height);
+      auto overlap = [](const void *p, size_t p_bytes, const void *q, size_t q_bytes) {
+        const char *a0 = (const char *)p, *b0 = (const char *)q;
+        return a0 < b0 + q_bytes && b0 < a0 + p_bytes;
+      };
+      auto reads = [&](const UpCall &u, const void *frame) {  // does a layer image of u - either field's - overlap the frame at `frame`?
+        for (int l = 0; l < u.n; ++l) {
+          const size_t bytes = (size_t)u.layers[l].width * (size_t)u.layers[l].height * (u.rgb ? 12u : 16u);
+          if (overlap(u.layers[l].data, bytes, frame, frame_bytes) || (u.pair && overlap(u.layers2[l].data, bytes, frame, frame_bytes))) return true;
+        }
+        return false;
+      };
       for (; k < n_jobs && kind[(size_t)k] == 3; ++k) {
         const UpCall &u = ups[(size_t)k];
         bool same = u.n == u0.n && u.rgb == u0.rgb && u.width == u0.width && u.height == u0.height && u.interlace == u0.interlace && u.r == u0.r;
@@ -843,14 +859,17 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
           for (int e = 0; e < 9 && same; ++e) same = u.layers[l].matrix9_host[e] == u0.layers[l].matrix9_host[e];
         }
         if (!same || frames + (u.pair ? 2 : 1) > ph::kMaxUpJobs) break;
-        bool clash = u.pair && u.o->dptr == u.o2->dptr;
-        for (int f = 0; f < frames && !clash; ++f) clash = outs[f] == u.o->dptr || (u.pair && outs[f] == u.o2->dptr);
+        bool clash = u.pair && overlap(u.o->dptr, frame_bytes, u.o2->dptr, frame_bytes);
+        for (int f = 0; f < frames && !clash; ++f)  // written twice, or read here after it is written there
+          clash = overlap(outs[f], frame_bytes, u.o->dptr, frame_bytes) || (u.pair && overlap(outs[f], frame_bytes, u.o2->dptr, frame_bytes)) || reads(u, outs[f]);
+        for (int e = j; e < k && !clash; ++e)  // written here after it is read there
+          clash = reads(ups[(size_t)e], u.o->dptr) || (u.pair && reads(ups[(size_t)e], u.o2->dptr));
         if (clash) break;
         sets[frames] = u.layers, outs[frames++] = u.o->dptr;
         if (u.pair) sets[frames] = u.layers2, outs[frames++] = u.o2->dptr;
       }
       if (k == j) {  // (the first job does not fit a group of its own making - a pair writing one buffer twice: as it is, for its own error)
-        if ((rc = dispatch(ctx, progs[j], args[j], n_args[j], queue))) return rc;
+        if ((rc = dispatch(ctx, progs[j], args[j], n_args[j], queue, false, true))) return rc;  // (the injection was asked above, once per launch)
         g_programs_done = ++j;
         continue;
       }
@@ -884,12 +903,20 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       const char *a0 = (const char *)p, *b0 = (const char *)out;
       return p && a0 < b0 + out_bytes && b0 < a0 + (bytes ? bytes : 1);
     };
+    // (the bytes a source's planes hold: an f32 image 16 per pixel, a wire-format frame what its format's planes take - a range taken
+    // wider than that runs into whatever buffer lies behind the plane, and where the launches of a call end would depend on where its
+    // buffers were allocated)
     auto reads = [&](const ChanCall &c, const void *out) {  // does a source of c overlap the frame at `out`?
       for (int l = 0; l < c.n_layers; ++l)
-        for (const ph_chan_source *s2 : {&c.layers[l].src, &c.layers[l].incoming, &c.layers[l].mask})
-          if (s2->data && (touches(s2->data, (size_t)s2->width * s2->height * 16u, out) || touches(s2->data_u, (size_t)s2->width * s2->height * 2u, out) ||
-                           touches(s2->data_v, (size_t)s2->width * s2->height * 2u, out)))
-            return true;
+        for (const ph_chan_source *s2 : {&c.layers[l].src, &c.layers[l].incoming, &c.layers[l].mask}) {
+          if (!s2->data) continue;
+          size_t pb[3];
+          const int fmt = fmt_of_src(s2->format);
+          // an f32 image (or a frame whose planes have no size of their own - odd 4:2:0 dims, which the launch refuses: the widest any format takes)
+          if (fmt < 0 || ((s2->width | s2->height) & 1) || pack_plane_bytes(fmt, (uint32_t)s2->width, (uint32_t)s2->height, pb) < 0)
+            pb[0] = (size_t)s2->width * s2->height * 16u, pb[1] = pb[2] = (size_t)s2->width * s2->height * 2u;
+          if (touches(s2->data, pb[0], out) || touches(s2->data_u, pb[1], out) || touches(s2->data_v, pb[2], out)) return true;
+        }
       return false;
     };
     for (; k < n_jobs && kind[(size_t)k] == 1; ++k) {

@@ -601,6 +601,21 @@ def test_run_programs_reports_how_far_a_failing_call_got(ctx):
         ctx.run_programs([jobs[0], (p2, bad)])
     capi.check(capi.lib().ph_run_programs_progress(ctypes.byref(done)))
     assert done.value == 0
-    for x in dev + outs:
+    # a compositor job that writes one buffer twice is no launch group of its own making and runs as it is, for its own error: the
+    # injection is asked once per launch, so with one launch let through the job fails with that error, not with "injected"
+    img = upload(ctx, frames.rgba_random(192, 30, 1600).reshape(-1), svm="coarse", dims=(192, 30))
+    fill = np.zeros(12, np.float32)
+    fill[:9] = capi.transform_matrix(w, h)
+    bf = upload(ctx, fill)
+    ctx.wait(capi.QUEUE_LOAD)
+    up = ctx.create_program("phaneron:up", "compose_up_write_v210_1", [w, h])
+    twice = dict(outColMatrix=col.wr_cm, outGammaLut=col.wr_lut, interlace=0, l0In=img, l0In2=img, l0Matrix=bf, output=outs[0], output2=outs[0])
+    ctx.set_option("fail_launches", -1)
+    try:
+        with pytest.raises(capi.PhaneronError, match="same buffer"):
+            ctx.run_programs([(up, twice)])
+    finally:
+        ctx.set_option("fail_launches", 0)
+    for x in dev + outs + [img, bf]:
         x.release()
     col.release()

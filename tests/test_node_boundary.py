@@ -693,6 +693,36 @@ def test_recording_graph_logic_without_a_device():
 
 
 @needs_node
+def test_packed_fields_are_never_read_in_the_wrong_layout_without_a_device():
+    """node/test/packed_state_check.js: the counting stand-in with a layout per buffer handle (rgba / packed f32 RGB) and the rules of
+    who may read which at every launch, alone or in a runPrograms call - a compositor plan made for packed fields and a plain consumer
+    of the same field (or of the twin's) forced inside the same _runMany, in both recording orders; hostAccess 'writeonly' / 'none' of a
+    packed field somebody still reads; a runPrograms call that throws behind one that went through; then 300 seeded random streams of
+    these jobs with and without runPrograms, earlyLaunch on and off (PH_FUZZ_SEED: the first stream's seed)"""
+    seed = os.environ.get("PH_FUZZ_SEED", "1")
+    r = subprocess.run([NODE, os.path.join(ROOT, "node", "test", "packed_state_check.js"), seed, "300"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    res = json.loads(r.stdout)
+    assert res["problems"] == [], res["problems"][:3]
+    assert res["streams"] == 300 and res["checks"] >= 1200 + 60, res["checks"]
+
+
+@needs_node
+@pytest.mark.gpu
+def test_packed_field_hazards_on_the_real_addon():
+    """node/test/hazard_run.js: the two directed packed-field scenarios (a compositor plan and a plain consumer of the same field, of the
+    twin's field) at 192 x 54 fields on a 384 x 108 channel through the recording context and through the launch-as-posted one - the
+    frames are byte-equal; after a runPrograms that throws at marshalling (a bad program handle) runProgramsProgress() is 0"""
+    _build_addon()
+    r = subprocess.run([NODE, os.path.join(ROOT, "node", "test", "hazard_run.js")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    assert res["problems"] == [], res["problems"][:3]
+    assert res["scenarios"] >= 4 and res["frames"] >= 3 * res["scenarios"] and res["unpacked"] >= 1, res
+    assert res["progress"] == {"afterBatch": 2, "afterThrow": 0}, res["progress"]
+
+
+@needs_node
 @pytest.mark.gpu
 def test_random_job_streams_give_the_same_bytes_through_the_recording_context():
     """node/test/defer_fuzz.js: seeded random streams of reads, transforms, transitions, combines, de-interlaces, frame and
