@@ -187,20 +187,7 @@ def test_edited_kernel_text_is_still_told_apart_by_signature_and_body():
 
 
 # ---- the LDS form of a gamma table (ph_lut_layout_of: host code of the product, no device) --------------------------------
-def _lds_lookup(layout, image, idx):
-    """The table kernels' lookup (phaneron_amd/csrc/ph_ldslut.h) restated with numpy on the LDS image: every float operation of it
-    is exact, so float64 arithmetic narrowed to float32 reproduces it."""
-    magic = np.float64(12582912.0)  # 1.5 * 2^23: y = idx + magic is what the rounding add leaves
-    y = idx.astype(np.float64) + magic
-    a_scale = np.float64(layout["a_scale"])
-    fs = (y * a_scale - (magic - layout["index_bias"]) * a_scale).astype(np.float32)
-    assert np.array_equal(fs.astype(np.float64), (idx.astype(np.float64) + layout["index_bias"]) * a_scale)  # exact
-    a_addr = (fs.view(np.uint32) >> np.uint32(layout["shift"] - 2)) & np.uint32(0xFFFFFFFC)
-    d_addr = np.uint32(layout["delta_off"]) + 2 * idx.astype(np.uint32)
-    assert a_addr.min() >= layout["hole"] and a_addr.max() + 4 <= layout["delta_off"] and d_addr.max() + 2 <= layout["lds_bytes"]
-    anchors = image[: layout["delta_off"]].view(np.uint32)
-    deltas = image[layout["delta_off"]:].view(np.uint16)
-    return anchors[a_addr >> 2] + deltas[idx].astype(np.uint32)
+from luts import _lds_lookup  # (the kernels' lookup restated with numpy: shared with test_lut_layouts_cpu.py)
 
 
 @pytest.mark.parametrize("spec", ["709", "2020", "601-625", "601-525", "sRGB"])

@@ -15,10 +15,22 @@ pytestmark = pytest.mark.gpu
 
 
 def colour(rspec, wspec):
+    """(oracle reader, oracle writer, device reader, device writer) of two colour spaces.  Instead of a name either side may be a
+    colour tuple of its own - (oracle (matrix, table, gamut), device (matrix, table, gamut)) for the reader, (oracle (matrix, table),
+    device (matrix, table)) for the writer - with tables the caller registered (tests/luts.py); a reader tuple given for both
+    sides (callers that make their writers themselves) leaves the writer None"""
     import hip_harness as hh
-    rd_o = (orc.ycbcr2rgb_matrix(rspec), orc.gamma2linear_lut(rspec), orc.rgb2rgb_matrix(rspec, wspec))
-    wr_o = (orc.rgb2ycbcr_matrix(wspec), orc.linear2gamma_lut(wspec))
-    return rd_o, wr_o, hh.ColourParams.reader(rspec, wspec), hh.ColourParams.writer(wspec)
+    named = isinstance(rspec, str), isinstance(wspec, str)
+    if named[0]:
+        gamut = wspec if named[1] else "709"
+        rd_o, rd_d = (orc.ycbcr2rgb_matrix(rspec), orc.gamma2linear_lut(rspec), orc.rgb2rgb_matrix(rspec, gamut)), hh.ColourParams.reader(rspec, gamut)
+    else:
+        rd_o, rd_d = rspec
+    if named[1]:
+        wr_o, wr_d = (orc.rgb2ycbcr_matrix(wspec), orc.linear2gamma_lut(wspec)), hh.ColourParams.writer(wspec)
+    else:
+        wr_o, wr_d = (None, None) if wspec is rspec else wspec
+    return rd_o, wr_o, rd_d, wr_d
 
 
 class Src:
@@ -483,21 +495,22 @@ def test_other_output_formats(fmt, interlace):
     check_format(layers, w, h, fmt, "%s interlace %d" % (fmt, interlace), interlace)
 
 
-def check_format(layers, w, h, fmt, what, interlace=0):
+def check_format(layers, w, h, fmt, what, interlace=0, reader="709", wr_table=None):
     """the channel's frame in another wire format against the oracle's chain ending in that format's writer; the planes are
-    poisoned first (a field write leaves the other field's lines alone)"""
+    poisoned first (a field write leaves the other field's lines alone).  reader: a colour tuple as colour() takes it; wr_table:
+    (host table, registered device table) for the writer instead of the 709 one"""
     import torch
     import hip_harness as hh
     from phaneron_amd import capi
-    rd_o, _, rd_d, _ = colour("709", "709")
+    rd_o, _, rd_d, _ = colour(reader, reader)
     rng = orc.FORMAT_RANGE[fmt]
     wcm_o = None if rng is None else orc.rgb2ycbcr_matrix("709", *rng)
-    wlut_o = orc.linear2gamma_lut("709")
+    wlut_o = orc.linear2gamma_lut("709") if wr_table is None else wr_table[0]
     before = [np.full(n, 0x5A, np.uint8) for n in frames.pack_plane_bytes(fmt, w, h)]
     want = orc.pack_write(fmt, placed_and_combined(layers, w, h, rd_o), w, h, interlace, wcm_o, wlut_o, planes=before)
     k = hh.ctx()
     dst = [hh.dev(b.copy()) for b in before]
-    wlut_d = hh.ColourParams.writer("709")[1]
+    wlut_d = hh.ColourParams.writer("709")[1] if wr_table is None else wr_table[1]
     wcm_d = None if rng is None else hh.dev(capi.rgb2ycbcr_matrix("709", *rng))
     dl = [dict(src=L["src"].device()) for L in layers]
     k.chan_compose_v210(dl, dst, w, h, interlace, *rd_d, wcm_d, wlut_d, out_fmt=fmt)

@@ -36,9 +36,12 @@ _writers = {}
 
 def writer(fmt, spec, own_table=False):
     """a format's writer recipe on both sides: (oracle matrix, oracle table, device matrix, device table); own_table: a table of the same
-    contents registered under a pointer of its own"""
+    contents registered under a pointer of its own; spec: a colour space's name, or a table of the caller's own"""
     import hip_harness as hh
     from phaneron_amd import capi
+    if not isinstance(spec, str):  # (host table, registered device table) of the caller's own (tests/luts.py) under the 709 matrix; not cached
+        rng = orc.FORMAT_RANGE[fmt]
+        return (None if rng is None else orc.rgb2ycbcr_matrix("709", *rng), spec[0], None if rng is None else hh.dev(capi.rgb2ycbcr_matrix("709", *rng)), spec[1])
     key = (fmt, spec, own_table)
     if key not in _writers:
         rng = orc.FORMAT_RANGE[fmt]

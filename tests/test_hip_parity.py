@@ -297,6 +297,39 @@ def test_lut_registry_reports_lds_form():
         assert 0 < hh.ctx().lut_info(wlut)["lds_bytes"] <= 160 * 1024
 
 
+def test_lut_registry_reports_a_forced_layout():
+    """what lut_info says of a table made for one layout (tests/luts.py): its footprint, index bias and blocks per octave"""
+    import hip_harness as hh
+    import luts
+    for (bias, m_), want in (((16, 9), 157712), ((32, 7), 137232), ((128, 8), 141328)):
+        with luts.register(luts.layout_table(bias, m_, 5 + bias + m_)) as dlut:
+            assert hh.ctx().lut_info(dlut) == dict(lds_bytes=want, index_bias=bias, blocks_per_octave_log2=m_)
+        assert hh.ctx().lut_info(dlut)["lds_bytes"] == 0  # unregistered
+
+
+def test_another_layout_registered_at_the_same_pointer_is_the_one_the_next_launch_uses():
+    """register, unregister, register a table of a DIFFERENT layout at the same device pointer: one read with each, against the oracle"""
+    import torch
+    import hip_harness as hh
+    import luts
+    w, h = 100, 6
+    words = frames.v210_random(w, h, 31, legal=False)
+    cm, gm = orc.ycbcr2rgb_matrix("709"), orc.rgb2rgb_matrix("709", "2020")
+    dcm, dgm, src = hh.dev(cm), hh.dev(np.concatenate([gm, np.zeros(3, np.float32)])), hh.dev(words)
+    dlut = torch.zeros(65536, dtype=torch.float32, device="cuda")
+    for bias, m_ in ((16, 9), (128, 7), (64, 8)):
+        tab = luts.layout_table(bias, m_, 77 + bias + m_)
+        hh.host(dlut)  # (nothing reads the old contents any more)
+        dlut.copy_(torch.from_numpy(tab))
+        torch.cuda.synchronize()
+        assert hh.ctx().register_lut(dlut, tab)
+        assert hh.ctx().lut_info(dlut) == dict(lds_bytes=luts.LDS_BYTES[(bias, m_)], index_bias=bias, blocks_per_octave_log2=m_)
+        out = torch.full((w * h * 4,), float("nan"), dtype=torch.float32, device="cuda")
+        hh.ctx().v210_read(src, out, w, h, dcm, dlut, dgm)
+        assert_bits(hh.host(out), orc.v210_read(words, w, h, cm, tab, gm), "v210_read with the (%d, %d) table at a reused pointer" % (bias, m_))
+        hh.ctx().unregister_lut(dlut)
+
+
 def test_incompressible_lut_falls_back_to_gather_kernels():
     """A table that is not locally smooth cannot be held exactly in LDS: it must stay plain and
     the global-gather kernels must still give the exact answer."""
