@@ -43,7 +43,8 @@ extern "C" {
  *    values an older binding never passes; no signature or struct changed.  ph_chan_compose_multi (ph_chan_output): several consumers'
  *    frames of one channel in one launch; program "chan_compose_multi_<n>".  ph_compose_up_write_multi: the same for the 2 x 2-block
  *    compositor (enlarged images), with every writer the channel kernel has.  ph_chan_compose_batch_out (ph_chan_job_out): several
- *    channels' frames for any consumers in one launch; context option "chan_batch_outs" */
+ *    channels' frames for any consumers in one launch; context option "chan_batch_outs".  ph_pack_write_multi: one f32 RGBA image packed
+ *    for up to four consumers, any pack format each, in one launch; program "pack_write_multi_<n>" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -264,7 +265,9 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * So does a compose_up_multi_<n> job (ph_compose_up_write_multi): compose_up_write_v210_<n>'s layers (l<i>In, l<i>Matrix, packedRgb,
  * l<i>Width / l<i>Height) and chan_compose_multi_<n>'s outputs.  Its twin - the other field of a de-interlaced frame - is announced by
  * l0In2 (l<i>In2: its images), and its planes carry the first job's names behind the word twin: twinOutput (twinOutputU / V / C),
- * twinOutput<k> (twinOutput<k>U / V / C) - `output2` being output 2's frame here. */
+ * twinOutput<k> (twinOutput<k>U / V / C) - `output2` being output 2's frame here.
+ * And so does a pack_write_multi_<n> job (ph_pack_write_multi; globalWorkItems [width, height]): input - the f32 RGBA image - width, and
+ * its n = 1..4 outputs as chan_compose_multi_<n> names them, outPacking / out<k>Packing being any PH_FMT_* here (7 and 8 included). */
 int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_arg *const *args, const int *n_args, int queue);
 /* How far the calling thread's LAST ph_run_programs call got: the launches of jobs 0 .. *jobs_done - 1 were made (n_jobs after a call
  * that returned PH_OK, 0 after one refused by its checks).  A call that fails at a launch has enqueued the jobs before the failing
@@ -551,7 +554,7 @@ int ph_chan_compose_batch(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job 
  * in a trace; the enlarged-clip route is not taken).  Limits and errors as ph_chan_compose, per output; two outputs naming the same
  * first plane, or n_out outside 1..4, are PH_E_INVALID.  A refused call writes nothing. */
 typedef struct ph_chan_output {
-  int format;                   /* a PH_FMT_* the channel kernel writes */
+  int format;                   /* a PH_FMT_* the channel kernel writes or, for ph_pack_write_multi, any PH_FMT_* */
   void *planes[3];              /* as ph_pack_plane_bytes(format, ...) sizes them */
   uint32_t interlace;           /* as ph_v210_write, per output */
   const void *wr_col_matrix12;  /* NULL for rgba8 / bgra8 */
@@ -599,6 +602,24 @@ int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
  * A refused call writes nothing. */
 int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, int n_out,
                               const ph_chan_output *outs, uint32_t out_width, uint32_t out_height);
+/* One f32 RGBA image packed for up to four CONSUMERS in one call: a frame that exists as an image (a routed channel, a Combiner
+ * passthrough, a frame whose fused launch was refused) and that every consumer runs its own FromRGBA on (channel.ts:40,64-88) - v210 for
+ * SDI, p010 / yuv420p10 for a Main10 encoder, rgba8 for the screen.  outs: n_out = 1..4 outputs (ph_chan_output) in ANY
+ * PH_FMT_*, the 10-bit 4:2:0 formats included.  Exactly, bit for bit and in order, the n_out calls of ph_pack_write with each output's
+ * format, planes, interlace, matrix and table; the call takes everything those take.
+ * Launches: outputs that name the same REGISTERED writer table share one launch ("pack_write_multi x<outputs>" in a trace), in which
+ * every pixel is loaded once and looked up in the table once; each output then applies its own writer matrix and packing.  If every
+ * output of the launch wants the same `interlace`, only that field's rows are read; otherwise the whole frame, a field output taking
+ * the rows of its parity.  Outputs that name different tables are one launch per table, outputs keeping their order.  An output the
+ * shared kernel does not take is split off into ph_pack_write's launch inside the call, under its present name: a table that is not
+ * registered (or the context option "lds_lut" = 0), a planar output at width % 8 != 0 (the tail octet rounds twice), a v210 output at
+ * width % 48 != 0 (its tail quad truncates the table index, and its cleared slots belong to the pitch), and an output that is alone
+ * with its table - so n_out == 1 IS ph_pack_write, same route.
+ * PH_E_INVALID, decided before anything is launched (a refused call writes nothing): a NULL ctx / in / outs, width 0, n_out outside
+ * 1..4, an unknown format, interlace not 0 / 1 / 3, a missing plane, a missing matrix for a YCbCr format, a missing table, an odd width
+ * or height for a format defined for even sizes only, two outputs naming the same first plane.  height == 0 is PH_OK. */
+int ph_pack_write_multi(ph_ctx *ctx, int queue, const void *in, int n_out, const ph_chan_output *outs, uint32_t width,
+                        uint32_t height);
 
 /* ---- gamma LUT placement.  The reference hands its kernels a 65536-entry f32 `gammaLut` buffer
  *      (loadSave.ts:65-73,152-160) and gathers from it 3x per pixel.  Registering the table's

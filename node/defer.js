@@ -105,6 +105,12 @@ class Deferral {
 		// set (ph_chan_compose_batch_out).  `batchOuts: true` on the context; off unless asked for (DESIGN.md 5.1: measured through the
 		// library, not yet through node).
 		this.batchOuts = ctx.batchOuts === true
+		// Wire-format writes that are launched as posted - the image exists (a routed channel's, a Combiner passthrough), the fused launch was
+		// refused, or the consumer is a 10-bit 4:2:0 one (yuv420p10 / p010: no fused kernel writes them) - take the pending writes of the
+		// other consumers of the same image with them: ONE pack_write_multi_<n> launch (ph_pack_write_multi) reads and looks up the image
+		// once for all of them.  `imageWriters: true` on the context; off unless asked for - three consumers measured 27 % faster, but
+		// v210 + rgba8 alone 4 % slower when the image comes from HBM (profiles/pack_write_multi_bench.jsonl, DESIGN.md 5.1).
+		this.imageWriters = ctx.imageWriters === true
 		this.batchOutsSet = false
 	}
 
@@ -333,7 +339,7 @@ class Deferral {
 			this.terminals = this.terminals.filter((n) => n.state === 'pending' && n !== node && n.queue !== node.queue)
 			if (others.length) return this._runMany([node, ...others], node)
 		}
-		if (!this._fused(node)) this._plain(node)
+		if (!this._fused(node)) this._asPosted(node)
 	}
 	// Several terminal writes at once.  `must` (or null) has to be done when this returns - fused, or as recorded; the others are
 	// launched only if their chain folds (what does not fold stays recorded until somebody asks).  Frames the channel kernel (or the
@@ -356,7 +362,7 @@ class Deferral {
 				// once, while the fields are still in the cache - not after the other channels' readers (fieldBatch: see the constructor)
 				const twin = plan.up && !this.fieldBatch && plan.candidates[0][2]
 				if (twin) { // (the other field's write is done with it - or still pending, and planned next)
-					if (this._fresh(plan) && !this._commit(plan) && plan.node === must) this._plain(plan.node)
+					if (this._fresh(plan) && !this._commit(plan) && plan.node === must) this._asPosted(plan.node)
 					continue
 				}
 				plans.push(plan)
@@ -389,11 +395,11 @@ class Deferral {
 			}
 			for (const g of groups) {
 				const live = g.filter((p) => this._fresh(p))
-				for (const p of g) if (!live.includes(p) && p.node.state === 'pending' && p.node === must) { if (!this._fused(p.node)) this._plain(p.node) } // (planning another frame ran part of this one's chain: look again)
+				for (const p of g) if (!live.includes(p) && p.node.state === 'pending' && p.node === must) { if (!this._fused(p.node)) this._asPosted(p.node) } // (planning another frame ran part of this one's chain: look again)
 				if (live.length > 1 && this._batch(live)) continue
-				for (const p of live) if (this._fresh(p) && !this._commit(p) && p.node === must) this._plain(p.node)  // (fresh: a batch that failed half way has made some)
+				for (const p of live) if (this._fresh(p) && !this._commit(p) && p.node === must) this._asPosted(p.node)  // (fresh: a batch that failed half way has made some)
 			}
-			if (must && must.state === 'pending' && !failure) { if (!this._fused(must)) this._plain(must) }
+			if (must && must.state === 'pending' && !failure) { if (!this._fused(must)) this._asPosted(must) }
 		} finally { this.running = false }
 		if (failure) throw failure
 	}
@@ -509,6 +515,75 @@ class Deferral {
 		this._launch(this._program('rgb_unpack', buf.imageDims.width, buf.imageDims.height), { image: buf }, queue) // (a failure leaves it marked: nobody takes packed pixels for an image)
 		buf._packed = null
 		this.stats.unpacked = (this.stats.unpacked || 0) + 1
+	}
+	// A job that no fused launch stands in for: launched as it was posted - a wire-format write, with imageWriters, together with its siblings
+	_asPosted(node) {
+		if (this.imageWriters && node.program.name === 'write' && this._imageWrite(node)) return
+		this._plain(node)
+	}
+	// The write's image made real, then one pack_write_multi_<n> launch for it and the pending writes of up to three other consumers of
+	// the same image: _siblings' rule (same queue, outputs of their own of which they are the registered producer) without _writeFrame's
+	// limits - any of the nine formats, and the image need not have a pending producer.  false: nothing was launched for `node` (no
+	// sibling, a shape this does not describe, a refused launch: stats.fallbacks) - the caller launches it as posted, the siblings in their turn.
+	_imageWrite(node) {
+		const FMT = { v210: 0, yuv422p10: 1, yuv422p8: 2, yuv420p: 3, nv12: 4, rgba8: 5, bgra8: 6, yuv420p10: 7, p010: 8 }
+		const image = node.params.input
+		const dims = image && image.imageDims
+		if (!dims || FMT[node.program.format] === undefined) return false
+		// one consumer's frame as the program's output k: null where the write is not a whole frame of the image as its Writer lays it out
+		const output = (w) => {
+			const fmt = FMT[w.program.format]
+			if (fmt === undefined || w.params.input !== image || w.params.width !== dims.width || !w.params.gammaLut) return null
+			const interlace = w.params.interlace || 0
+			const v420 = fmt === 3 || fmt === 4 || fmt === 7 || fmt === 8
+			if (Deferral._frameOf(w).lines !== (interlace && !v420 ? dims.height / 2 : dims.height)) return null
+			const rgb8 = fmt === 5 || fmt === 6
+			if (!rgb8 && !w.params.colMatrix) return null
+			const planes = fmt === 0 || rgb8 ? [w.params.output] : fmt === 4 || fmt === 8 ? [w.params.outputY, w.params.outputC] : [w.params.outputY, w.params.outputU, w.params.outputV]
+			if (planes.some((p) => !p)) return null
+			// (its recipe buffers are what the host wrote: a pending or failed producer of one is for the write's own launch to deal with)
+			for (const b of w.ins) if (b !== image && (b._producer || b._failed)) return null
+			return { fmt, interlace, rgb8, planes, cm: w.params.colMatrix, lut: w.params.gammaLut }
+		}
+		const first = output(node)
+		if (!first) return false
+		const found = [{ node, out: first }]
+		const taken = new Set(node.outs)
+		for (const w of image._readers) {
+			if (found.length === 4) break
+			if (w === node || w.state !== 'pending' || w.program.name !== 'write' || w.queue !== node.queue) continue
+			if (!w.outs.length || w.outs.some((o) => o._producer !== w || taken.has(o))) continue // (still being recorded, or a buffer another consumer writes)
+			const out = output(w)
+			if (!out) continue
+			for (const o of w.outs) taken.add(o)
+			found.push({ node: w, out })
+		}
+		if (found.length < 2) return false
+		try { // the image itself, as _plain makes it real
+			if (image._producer && image._producer !== node) this.force(image)
+			else if (image._failed) return false
+		} catch (e) { return false } // (the write's own launch reports it)
+		if (found.some((v) => v.node.state !== 'pending')) return node.state !== 'pending' // (making the image real ran one of them: as posted, then)
+		const params = { input: image, width: dims.width }
+		found.forEach(({ out }, k) => {
+			const num = k ? String(k) : ''
+			const names = out.planes.length === 1 ? [''] : out.planes.length === 2 ? ['', 'C'] : ['', 'U', 'V']
+			out.planes.forEach((p, i) => { params[`output${num}${names[i]}`] = p })
+			params[`out${num}Packing`] = out.fmt
+			if (!out.rgb8) params[`out${num}ColMatrix`] = out.cm
+			// (every consumer's Saver makes its own table: loadSave.ts:152-160 - tables of the same contents are named by the first one's buffer, so they share the launch)
+			const same = found.slice(0, k).find((v) => Deferral.same(v.out.lut, out.lut))
+			params[`out${num}GammaLut`] = same ? same.out.lut : out.lut
+			params[`interlace${num}`] = out.interlace
+		})
+		if (!this._try(this._program(`pack_write_multi_${found.length}`, dims.width, dims.height), params, node.queue)) return false
+		this.stats.imageWrites = (this.stats.imageWrites || 0) + 1
+		for (const { node: w } of found) {
+			if (this.timed) this.timed.push(w)
+			if (w !== node) this.stats.multiOutputs = (this.stats.multiOutputs || 0) + 1
+			this._retire(w, 'done')
+		}
+		return true
 	}
 	_plain(node) {
 		let failure = null

@@ -71,7 +71,7 @@ export interface DeferredStats {
 	pending: number; recorded: number; launched: number; fused: number; fusedNodes: number; plain: number; dropped: number; fallbacks: number; lastFallback: string | null
 	/** frames that went to the device together with other channels' frames, several to a launch */
 	batched?: number
-	/** consumers' writes that came out of another write's launch as further outputs (multiWriter) */
+	/** consumers' writes that came out of another write's launch as further outputs (multiWriter, upWriters, imageWriters) */
 	multiOutputs?: number
 }
 
@@ -101,12 +101,16 @@ export class clContext {
 	 * `batchOuts` (default false; PHANERON_BATCH_OUTS=1): the frames several channels post in one tick for consumers other than SDI (an encoder's
 	 * yuv422p8, the screen's rgba8) and for several consumers at once share ONE launch of the channel kernel (the library's context option
 	 * `chan_batch_outs`, ph_chan_compose_batch_out); `false`: a launch per channel, in its turn.  The same bytes either way.
+	 * `imageWriters` (default false; PHANERON_IMAGE_WRITERS=1): wire-format `write` jobs that are launched as posted (no fused plan, or every fused
+	 * candidate refused) take the pending writes of the other consumers of the same image - any of the nine formats, yuv420p10 / p010 included -
+	 * with them as ONE `pack_write_multi_<n>` launch (ph_pack_write_multi: the image read and looked up once); `false`: a launch per write.
+	 * The same bytes either way.  Measured: three consumers 27 % faster, v210 + rgba8 alone 4 % slower from HBM (DESIGN.md 5.1).
 	 * `recycleBuffers` (default true; PHANERON_RECYCLE=0): released frames / images are parked for the next createBuffer of their shape,
 	 * up to `parkMb` MiB (default 4096) or the most that was ever in use at once.  A parked buffer is taken over as the same JS object;
 	 * `strictHandles` (default false; PHANERON_STRICT_HANDLES=1): a fresh object per takeover, so that a reference kept past release()
 	 * is refused ('... released buffer') instead of aliasing the next owner's buffer - for running an application under test. */
 	constructor(params?: { platformIndex?: number; deviceIndex?: number; overlapping?: boolean; profile?: boolean; spinWaitMicros?: number; deferred?: boolean;
-		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; batchOuts?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
+		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; batchOuts?: boolean; imageWriters?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
 	readonly queue: { load: number; process: number; unload: number }
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo

@@ -165,6 +165,9 @@ class clContext {
 		this.upWriters = params.upWriters === undefined ? (process.env.PHANERON_UP_WRITERS === undefined ? undefined : process.env.PHANERON_UP_WRITERS !== '0') : !!params.upWriters
 		// several channels' frames of a tick for consumers other than SDI, or for several consumers, as one launch (node/defer.js batchOuts): off unless asked for
 		this.batchOuts = params.batchOuts === undefined ? process.env.PHANERON_BATCH_OUTS === '1' : !!params.batchOuts
+		// wire-format writes of one image that are launched as posted - a routed channel's image, a frame whose fused launch was refused, the 10-bit
+		// 4:2:0 consumers - as ONE pack_write_multi_<n> launch (node/defer.js imageWriters): off unless asked for (DESIGN.md 5.1: v210 + rgba8 alone measured slower)
+		this.imageWriters = params.imageWriters === undefined ? process.env.PHANERON_IMAGE_WRITERS === '1' : !!params.imageWriters
 		// released frames and images are parked and taken over whole by the next createBuffer of the same shape (free() above);
 		// `recycleBuffers: false` or PHANERON_RECYCLE=0 returns every buffer to the library at once.  parkMb: what may stay parked
 		// (default 4096 MiB - or as much as was ever in use at once, if that is more)

@@ -35,7 +35,7 @@ EXPORTS = [
     "ph_route_group_end", "ph_route_send", "ph_route_recv", "ph_route_after_queue", "ph_queue_after_route",
     "ph_route_wait", "ph_route_stream", "ph_route_comm_count", "ph_chan_compose_v210", "ph_chan_compose_batch", "ph_run_programs", "ph_event_record_timed", "ph_event_elapsed_us", "ph_ctx_host_pool_stats",
     "ph_v210_yadif_pair_fmt", "ph_compose_up_write_v210", "ph_trace_begin", "ph_trace_end", "ph_run_programs_progress", "ph_buf_reuse", "ph_image_unpack_rgb",
-    "ph_chan_compose_multi", "ph_compose_up_write_multi", "ph_chan_compose_batch_out",
+    "ph_chan_compose_multi", "ph_compose_up_write_multi", "ph_chan_compose_batch_out", "ph_pack_write_multi",
 ]
 
 
@@ -208,6 +208,7 @@ def lib():
         "ph_chan_compose_batch": (ci, [vp, ci, ci, C.POINTER(PhChanJob), cu, cu, vp, vp, vp, vp, vp]),
         "ph_chan_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_compose_up_write_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
+        "ph_pack_write_multi": (ci, [vp, ci, vp, ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_chan_compose_batch_out": (ci, [vp, ci, ci, C.POINTER(PhChanJobOut), cu, cu, vp, vp, vp]),
         "ph_ctx_host_pool_stats": (ci, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
         "ph_event_record_timed": (ci, [vp, ci, C.POINTER(vp)]),
@@ -734,13 +735,26 @@ class Context:
         outs = (PhChanOutput * max(len(outputs), 1))()
         for k, o in enumerate(outputs):
             planes = o["planes"] if isinstance(o["planes"], (list, tuple)) else [o["planes"]]
-            outs[k].format = FORMATS[o["fmt"]]
+            outs[k].format = o["fmt"] if isinstance(o["fmt"], int) else FORMATS[o["fmt"]]  # (a raw number: a caller that tests the refusal of a bad one)
             for i, p in enumerate(planes):
-                outs[k].planes[i] = _ptr(p).value
+                outs[k].planes[i] = None if p is None else _ptr(p).value
             outs[k].interlace = int(o.get("interlace", 0))
             outs[k].wr_col_matrix12 = None if o.get("wr_cm") is None else _ptr(o["wr_cm"]).value
-            outs[k].wr_gamma_lut = _ptr(o["wr_lut"]).value
+            outs[k].wr_gamma_lut = None if o.get("wr_lut") is None else _ptr(o["wr_lut"]).value
         return outs
+
+    def pack_write_multi(self, src, outs, width, height, queue=QUEUE_PROCESS, prepare_only=False):
+        """One f32 RGBA image packed for 1..4 consumers in one call (ph_pack_write_multi): exactly the pack_write calls, outputs that
+        name one registered table sharing a launch.  outs: dicts as chan_compose_multi takes them, fmt any FORMATS name."""
+        arr = self._chan_outputs(outs)
+        args = (self.h, queue, None if src is None else _ptr(src), len(outs), arr, width, height)
+        fn, h = lib().ph_pack_write_multi, self.h
+        if prepare_only:
+
+            def job(_keep=(src, outs, arr)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
 
     def chan_compose_batch_out(self, jobs, out_w, out_h, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
         """Several channels' frames for any consumers in one launch (ph_chan_compose_batch_out).  jobs: list of (layers, outputs) -

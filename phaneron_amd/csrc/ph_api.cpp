@@ -1220,6 +1220,98 @@ int ph_pack_write(ph_ctx *ctx, int queue, int format, const void *in, void *cons
                                   lds_view(ctx, lut).get(), (uint32_t)ctx->props.multiProcessorCount));
 }
 
+/* One image packed for several consumers: see include/phaneron_hip.h.  Every check is ph_pack_write's, per output, and is made - and every
+ * launch of the call planned - before anything is launched. */
+int ph_pack_write_multi(ph_ctx *ctx, int queue, const void *in, int n_out, const ph_chan_output *outs, uint32_t width, uint32_t height) {
+  const char *const fn = "ph_pack_write_multi";
+  if (!ctx || !in || !outs || !width) return fail(PH_E_INVALID, "%s: NULL/zero argument", fn);
+  if (n_out < 1 || n_out > ph::kMaxPackOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxPackOuts, n_out);
+  if (n_out == 1)
+    return ph_pack_write(ctx, queue, outs[0].format, in, outs[0].planes, width, height, outs[0].interlace, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
+  PH_QUEUE(fn, queue);
+  for (int k = 0; k < n_out; ++k) {
+    const ph_chan_output &o = outs[k];
+    if (!o.wr_gamma_lut) return fail(PH_E_INVALID, "%s: output %d: the writer's gamma LUT is missing", fn, k);
+    if (!fmt_known(o.format)) return fail(PH_E_INVALID, "%s: output %d: unknown format %d", fn, k, o.format);
+    if (o.interlace != 0 && o.interlace != 1 && o.interlace != 3) return fail(PH_E_INVALID, "%s: output %d: interlace must be 0, 1 or 3", fn, k);
+    if (const int rc = even_dims(fn, o.format, width, height)) return rc;
+    for (int i = 0; i < fmt_planes(o.format); ++i)
+      if (!o.planes[i]) return fail(PH_E_INVALID, "%s: output %d: plane %d is NULL", fn, k, i);
+    if (!fmt_rgb8(o.format) && !o.wr_col_matrix12) return fail(PH_E_INVALID, "%s: output %d: YCbCr formats need a colMatrix", fn, k);
+    for (int j = 0; j < k; ++j)
+      if (outs[j].planes[0] == o.planes[0]) return fail(PH_E_INVALID, "%s: outputs %d and %d name the same plane", fn, j, k);
+  }
+  if (!height) return PH_OK;
+  // the launches: per writer table, in the order the tables first appear - the outputs the shared kernel does not take (and an output that
+  // would be alone in it) through ph_pack_write, in their order, then the others as one shared launch
+  struct Launch {
+    int solo;  // >= 0: outs[solo] through ph_pack_write
+    ph::PackMultiArgs m;
+  };
+  std::vector<Launch> launches;
+  for (int k = 0; k < n_out; ++k) {
+    bool seen = false;
+    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    if (seen) continue;
+    const LutRef wref = lds_view(ctx, outs[k].wr_gamma_lut);
+    int group[ph::kMaxPackOuts], members = 0, share = 0;
+    bool shared_ok[ph::kMaxPackOuts];
+    for (int j = k; j < n_out; ++j) {
+      if (outs[j].wr_gamma_lut != outs[k].wr_gamma_lut) continue;
+      const int f = outs[j].format;
+      shared_ok[members] = wref.get() && !(f == PH_FMT_V210 && width % 48) && !(fmt_planar(f) && width % 8);
+      share += shared_ok[members] ? 1 : 0;
+      group[members++] = j;
+    }
+    Launch shared{};
+    shared.solo = -1;
+    for (int g = 0; g < members; ++g) {
+      const ph_chan_output &o = outs[group[g]];
+      if (!shared_ok[g] || share < 2) {
+        Launch own{};
+        own.solo = group[g];
+        launches.push_back(own);
+        continue;
+      }
+      ph::PackOut &d = shared.m.out[shared.m.n_out++];
+      d.fmt = (uint32_t)o.format;
+      d.pitch = o.format == PH_FMT_V210 ? width / 6u : ph::pack_pitch(o.format, width);  // (v210 here: a multiple of 48, no padding)
+      d.wr_cm = fmt_rgb8(o.format) ? nullptr : (const float *)o.wr_col_matrix12;
+      for (int i = 0; i < 3; ++i) d.plane[i] = i < fmt_planes(o.format) ? o.planes[i] : nullptr;
+      d.takes = o.interlace;  // (settled below, once the launch's lines are known)
+    }
+    if (!shared.m.n_out) continue;
+    ph::PackMultiArgs &m = shared.m;
+    const uint32_t first_il = m.out[0].takes;
+    bool same_lines = true;
+    for (uint32_t i = 0; i < m.n_out; ++i) same_lines = same_lines && m.out[i].takes == first_il;
+    const uint32_t il = same_lines ? first_il : 0u;
+    m.in = in, m.width = width, m.wr = *wref.get();
+    m.line_step = il ? 2 : 1, m.first_line = il == 3 ? 1 : 0, m.lines = il ? height / 2 : height;
+    for (uint32_t i = 0; i < m.n_out; ++i) {
+      ph::PackOut &d = m.out[i];
+      const uint32_t oil = d.takes;
+      d.takes = same_lines || !oil ? 0u : oil == 1 ? 1u : 2u;
+      // a field: height / 2 lines; a 4:2:0 frame: its line pairs (an odd height leaves the last line alone, as ph_pack_write does)
+      d.line_end = oil || fmt_v420((int)d.fmt) ? 2u * (height / 2u) : height;
+      d.field = oil ? 1u : 0u;
+    }
+    launches.push_back(shared);
+  }
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  for (const Launch &l : launches) {
+    if (l.solo >= 0) {
+      const ph_chan_output &o = outs[l.solo];
+      if ((rc = ph_pack_write(ctx, queue, o.format, in, o.planes, width, height, o.interlace, o.wr_col_matrix12, o.wr_gamma_lut))) return rc;
+      continue;
+    }
+    const hipError_t e = ph::launch_pack_write_multi(stream_of(ctx, queue), l.m, (uint32_t)ctx->props.multiProcessorCount);
+    if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  }
+  return PH_OK;
+}
+
 static int compose_write(ph_ctx *ctx, int queue, int n, const ph_layer *layers, const ph_layer_wipe *wipes, void *out, uint32_t out_w,
                          uint32_t out_h, uint32_t interlace, const void *wr_cm, const void *wr_lut);
 

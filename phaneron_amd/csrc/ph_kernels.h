@@ -355,6 +355,34 @@ hipError_t launch_pack_read_batch(hipStream_t s, int fmt, int n, const void *con
 hipError_t launch_pack_write(hipStream_t s, int fmt, const void *in, void *const planes[3], uint32_t width,
                              uint32_t height, uint32_t interlace, const void *cm, const void *table, const LutView *lv,
                              uint32_t num_cus);
+// One f32 RGBA image packed for several consumers in one launch (ph_pack_write_multi; ph_kernels_fmt.hip): every pixel is loaded once and
+// looked up once in the ONE writer table of the launch (wr, in its LDS form); every output brings its format - any PH_FMT_* - its planes
+// and its writer matrix.  The launch reads the lines first_line + i * line_step, i < lines: the field every output wants, or the whole
+// frame, of which a field output takes the lines of its parity.  A planar output needs width % 8 == 0, a v210 output width % 48 == 0
+// (the caller sends the others through launch_pack_write / launch_v210_write_lds: their line tails round differently).
+constexpr int kMaxPackOuts = 4;
+struct PackOut {
+  uint32_t fmt;       // PH_FMT_*
+  uint32_t pitch;     // v210: quad slots per line; planar: luma samples per line; rgba8 / bgra8: pixels per line
+  uint32_t takes;     // which of the launch's lines are this output's: 0 all, 1 the even frame lines, 2 the odd ones
+  uint32_t line_end;  // lines from here on are not this output's (a field of an odd height; a 4:2:0 frame's unpaired last line)
+  uint32_t field;     // 1: a field write (4:2:0: the written line of a pair gives the chroma; a frame write: the pair's upper line)
+  uint32_t pad;
+  const float *wr_cm;  // (unused for rgba8 / bgra8)
+  void *plane[3];
+  uint64_t pad2;
+};
+static_assert(sizeof(PackOut) == 64, "an output descriptor is one 64-byte scalar load");
+struct PackMultiArgs {
+  const void *in;  // width x height f32 RGBA
+  uint32_t width, lines, first_line, line_step;
+  uint32_t n_out;
+  uint32_t units_per_line;  // launcher: a lane's work unit is an octet of pixels
+  LutView wr;
+  PackOut out[kMaxPackOuts];
+};
+// named "pack_write_multi x<outputs>" in a route trace
+hipError_t launch_pack_write_multi(hipStream_t s, const PackMultiArgs &a, uint32_t num_cus);
 hipError_t launch_compose_write_v210(hipStream_t s, const ComposeArgs &a, uint32_t num_cus);
 size_t chan_index_bytes(uint32_t out_w, uint32_t lines);
 hipError_t launch_chan_compose_v210(hipStream_t s, const ChanArgs &a, uint32_t num_cus);

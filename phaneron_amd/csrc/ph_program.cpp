@@ -11,6 +11,7 @@
 //   3. the argument list of the named kernel, plus - only where two formats share an argument list
 //      (yuv422p8 / yuv420p, rgba8 / bgra8) - one structural probe of that kernel's BODY, comments removed.
 // The 10-bit 4:2:0 formats (yuv420p10, p010) have no reference text: their programs resolve by tag only.
+// pack_write_multi_<n> (not a reference kernel): one image packed for n = 1..4 consumers (ph_pack_write_multi).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -167,19 +168,20 @@ int resolve_program(const char *src, const char *name, ProgramChoice &c, std::st
     return set(c, is_read ? K_PACK_READ : K_PACK_WRITE, std::string(fmt_name(fmt)) + (is_read ? "_read" : "_write"), how);
   }
   const int how = tagged ? PH_RESOLVED_BY_TAG : PH_RESOLVED_BY_NAME;
-  auto layers = [&](const char *prefix, int lo, KernelId id) {
+  // (hi / what: pack_write_multi_<n> counts its outputs)
+  auto layers = [&](const char *prefix, int lo, KernelId id, int hi = kMaxLayers, const char *what = "layer") {
     // the whole suffix must be the layer count: "combine_4x" is not combine_4
     const char *digits = name + strlen(prefix);
     char *end = nullptr;
     const long parsed = strtol(digits, &end, 10);
     if (end == digits || *end != '\0' || digits[0] < '0' || digits[0] > '9') {
-      err = std::string("unknown kernel '") + name + "' (" + prefix + "<n> takes a plain layer count)";
+      err = std::string("unknown kernel '") + name + "' (" + prefix + "<n> takes a plain " + what + " count)";
       return (int)PH_E_UNKNOWN_KERNEL;
     }
     const int n = parsed > 1000 ? 1000 : (int)parsed;
-    if (n < lo || n > kMaxLayers) {
+    if (n < lo || n > hi) {
       char b[96];
-      snprintf(b, sizeof b, "%s%d: %d..%d layers are built", prefix, n, lo, kMaxLayers);
+      snprintf(b, sizeof b, "%s%d: %d..%d %ss are built", prefix, n, lo, hi, what);
       err = b;
       return (int)PH_E_UNKNOWN_KERNEL;
     }
@@ -195,6 +197,10 @@ int resolve_program(const char *src, const char *name, ProgramChoice &c, std::st
   if (0 == strncmp(name, "chan_compose_multi_", 19)) return layers("chan_compose_multi_", 1, K_CHAN_COMPOSE);  // (the same program with more outputs: told apart by name, ph_run.cpp)
   if (0 == strncmp(name, "compose_up_write_v210_", 22)) return layers("compose_up_write_v210_", 1, K_COMPOSE_UP);
   if (0 == strncmp(name, "compose_up_multi_", 17)) return layers("compose_up_multi_", 1, K_COMPOSE_UP);  // (the same program with any writer and more outputs: told apart by name, ph_run.cpp)
+  if (0 == strncmp(name, "pack_write_multi_", 17)) {  // (the Writers' program with several outputs: told apart by name, ph_run.cpp; no one format)
+    c.format = -1;
+    return layers("pack_write_multi_", 1, K_PACK_WRITE, kMaxPackOuts, "output");
+  }
   if (0 == strcmp(name, "transform")) return set(c, K_TRANSFORM, name, how);
   if (0 == strcmp(name, "resize")) return set(c, K_RESIZE, name, how);
   if (0 == strncmp(name, "combine_", 8)) return layers("combine_", 2, K_COMBINE);

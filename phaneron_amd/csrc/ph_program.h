@@ -6,7 +6,7 @@ namespace ph {
 
 enum KernelId {
   K_PACK_READ,   // any pack format other than v210 (ProgramChoice::format)
-  K_PACK_WRITE,
+  K_PACK_WRITE,  // (pack_write_multi_<n>: one f32 RGBA image for n consumers, any pack format each - ph_pack_write_multi; told apart by name, format -1)
   K_V210_READ,
   K_V210_WRITE,
   K_YADIF,
@@ -29,7 +29,7 @@ enum KernelId {
 
 struct ProgramChoice {
   KernelId id;
-  int n_layers;        // combine_N / fused_v210_combine_N
+  int n_layers;        // combine_N / fused_v210_combine_N; pack_write_multi_N: the outputs
   int format;          // PH_FMT_* of a read / write program
   std::string kernel;  // "v210_read", "yuv420p_write", "combine_4", ...
   int how;             // PH_RESOLVED_*

@@ -282,7 +282,9 @@ static void chan_source_parse(Args &a, int i, const char *role, uint32_t width, 
 // One output of a channel's frame.  Output 0 is named as chan_compose_v210_<n> names its only one (outPacking, output, outputU / V / C,
 // outColMatrix, outGammaLut, interlace); output k = 1..3 of chan_compose_multi_<n> puts its number behind the first word (out<k>Packing,
 // output<k>, output<k>U ..., out<k>ColMatrix, out<k>GammaLut, interlace<k>).  The same reads, checks and texts for all of them.
-static int chan_output_parse(Args &a, int k, uint32_t width, uint32_t height, ph_chan_output *o, ph_buf **wr_cm, ph_buf **wr_lut, Recipe *loader = nullptr) {
+// any_format: the program writes every pack format (pack_write_multi_<n>), not only those the channel kernel does
+static int chan_output_parse(Args &a, int k, uint32_t width, uint32_t height, ph_chan_output *o, ph_buf **wr_cm, ph_buf **wr_lut, Recipe *loader = nullptr,
+                             bool any_format = false) {
   char num[4] = "", packing_arg[48], refused[80], prefix[16];
   if (k) snprintf(num, sizeof num, "%d", k);
   snprintf(packing_arg, sizeof packing_arg, "out%sPacking", num);
@@ -293,7 +295,7 @@ static int chan_output_parse(Args &a, int k, uint32_t width, uint32_t height, ph
   const int ofmt = (int)out_packing;
   if (!fmt_known(ofmt)) return a.fail(PH_E_INVALID, "kernel argument '%s': %g is not a pack format", packing_arg, out_packing);
   snprintf(refused, sizeof refused, "kernel argument '%s'", packing_arg);
-  if (!a.rc && !fmt_chan_out(ofmt)) return a.rc = chan_out_refused(refused, ofmt);
+  if (!a.rc && !any_format && !fmt_chan_out(ofmt)) return a.rc = chan_out_refused(refused, ofmt);
   o->planes[0] = o->planes[1] = o->planes[2] = nullptr;
   if (a.planes(ofmt, width, height, prefix, "", o->planes) < 0) return a.fail(PH_E_INVALID, "kernel argument '%s': %g is not a pack format", packing_arg, out_packing);
   if (loader) a.loader(loader);  // (output 0: the Loader's triple is read here, between the frame and the Saver's pair, as it always was)
@@ -448,6 +450,27 @@ static int up_call_multi(ph_ctx *ctx, int queue, const UpCall &u) {
   return ph_compose_up_write_multi(ctx, queue, jobs, u.n, sets, u.n_out, outs, u.width, u.height);
 }
 
+// pack_write_multi_<n> (K_PACK_WRITE, told apart by its name): input: the f32 RGBA image; width (globalWorkItems [width, height]); the n outputs as
+// chan_compose_multi_<n> names them (chan_output_parse: outPacking - any pack format here - output, outputU / V / C, outColMatrix, outGammaLut,
+// interlace, then out<k>Packing, output<k>[U|V|C], out<k>ColMatrix, out<k>GammaLut, interlace<k>, k = 1..n-1)
+static int pack_write_multi_job(Args &a, int queue) {
+  ph_ctx *ctx = a.ctx;
+  const ph_program *prog = a.prog;
+  uint32_t gw, height;
+  a.frame(&gw, &height);
+  const uint32_t width = (uint32_t)a.num("width");
+  if (!a.rc && width != gw) return a.fail(PH_E_INVALID, "%s: globalWorkItems must be [width, height] (width %u, globalWorkItems[0] %u)", prog->kernel.c_str(), width, gw);
+  const ph_buf *image = a.buf(image_bytes(width, height), "input");
+  ph_chan_output outs[ph::kMaxPackOuts];
+  for (int k = 0; k < prog->n_layers && !a.rc; ++k) {
+    ph_buf *wr_cm, *wr_lut;
+    if (chan_output_parse(a, k, width, height, &outs[k], &wr_cm, &wr_lut, nullptr, true)) break;
+    for (int j = 0; j < k; ++j)
+      if (outs[j].planes[0] == outs[k].planes[0]) return a.fail(PH_E_INVALID, "kernel argument 'output%d': the buffer is another output's too", k);
+  }
+  return a.done() ? a.rc : ph_pack_write_multi(ctx, queue, image->dptr, prog->n_layers, outs, width, height);
+}
+
 // ph_run_program's argument marshalling, one function per kernel family: each checks the job's named arguments against the frame geometry
 // (everything ph_check_program reports) and, unless check_only, makes the typed call.
 // the wire formats: v210 / pack readers and writers (v210.ts, yuv422p10.ts ... bgra8.ts; Reader / Writer geometry packer.ts:30-83)
@@ -458,6 +481,7 @@ static int dispatch_wire(Args &a, int queue) {
   switch (prog->id) {
     case K_PACK_READ:
     case K_PACK_WRITE: {
+      if (prog->id == K_PACK_WRITE && prog->kernel.compare(0, 17, "pack_write_multi_") == 0) return pack_write_multi_job(a, queue);
       const bool rd = prog->id == K_PACK_READ;
       const int fmt = prog->format;
       const uint32_t width = (uint32_t)a.num("width"), interlace = rd ? 0 : (uint32_t)a.num("interlace");
@@ -748,6 +772,7 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * fused_v210_combine_<n> frames; a job that reads or writes what an earlier job of its group writes (or writes what one reads) is
  * detected here and starts the next launch, so call order holds (include/phaneron_hip.h).  A chan_compose_multi_<n> job runs in its turn
  * as a launch of its own - it ends the group in front of it, so whatever that group writes is there for it, and all its outputs for what follows.
+ * So does a pack_write_multi_<n> job (ph_pack_write_multi).
  * With the context option "chan_batch_outs" = 1 (default 0) consecutive chan_compose_multi_<n> jobs and chan_compose_v210_<n> jobs that
  * make another format than v210 (outPacking) share launches as well (ph_chan_compose_batch_out).  A call that fails after its checks
  * (a launch refused) has made the launches of the jobs before the failing group: ph_run_programs_progress says how many. */
