@@ -91,6 +91,10 @@ SWEEPS = [
     ("test_fmt10_gpu", "test_batch_read_of_small_ragged_frames_equals_separate_reads", "fmt", packfmt.PLANAR_10_420),
     ("test_fmt10_gpu", "test_odd_frames_are_refused_on_the_device_entry_points", "fmt", packfmt.names(even_size=True)),
     ("test_fmt10_gpu", "test_deinterlacing_reader_refuses_the_formats", "fmt", [n for n in packfmt.NOT_DEINT if packfmt.get(n).planar]),
+    # between guard bands (tests/guard.py): no byte read or written outside the planes the format's sizes promise
+    ("test_guard_gpu", "test_pack_formats_between_guards", "fmt", packfmt.STANDALONE),
+    ("test_guard_gpu", "test_deinterlacing_reader_between_guards", "fmt", packfmt.names(deint=True)),
+    ("test_guard_gpu", "test_channel_kernel_between_guards", "fmt", packfmt.names(chan_source=True)),
 ]
 
 
@@ -110,6 +114,8 @@ def test_the_sweeps_together_run_every_format():
     assert run({"test_other_output_formats"}) | set(packfmt.V210) == set(packfmt.names(chan_out=True))
     assert run({"test_refusals_of_the_formats_the_kernel_does_not_write"}) == everything - set(packfmt.names(chan_out=True))
     assert set(packfmt.SWEPT) == everything
+    assert run({"test_pack_formats_between_guards"}) | set(packfmt.V210) == everything == run({"test_channel_kernel_between_guards"})
+    assert run({"test_deinterlacing_reader_between_guards"}) == everything - set(packfmt.NOT_DEINT)
     import test_chan_gpu
     assert set(test_chan_gpu.RANDOM_FORMATS_10) | set(packfmt.V210) == everything
     new = [f for f in test_chan_gpu.RANDOM_FORMATS_10 if f in packfmt.PLANAR_10_420]
