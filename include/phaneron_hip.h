@@ -44,7 +44,9 @@ extern "C" {
  *    frames of one channel in one launch; program "chan_compose_multi_<n>".  ph_compose_up_write_multi: the same for the 2 x 2-block
  *    compositor (enlarged images), with every writer the channel kernel has.  ph_chan_compose_batch_out (ph_chan_job_out): several
  *    channels' frames for any consumers in one launch; context option "chan_batch_outs".  ph_pack_write_multi: one f32 RGBA image packed
- *    for up to four consumers, any pack format each, in one launch; program "pack_write_multi_<n>" */
+ *    for up to four consumers, any pack format each, in one launch; program "pack_write_multi_<n>".  ph_fused_v210_combine_multi: the
+ *    plain-layer composite (ph_fused_v210_combine's chain) for up to four consumers in one launch; program
+ *    "fused_v210_combine_multi_<n>"; context option "fused_multi_wgs" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -620,6 +622,27 @@ int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_
  * or height for a format defined for even sizes only, two outputs naming the same first plane.  height == 0 is PH_OK. */
 int ph_pack_write_multi(ph_ctx *ctx, int queue, const void *in, int n_out, const ph_chan_output *outs, uint32_t width,
                         uint32_t height);
+/* The plain-layer composite - ph_fused_v210_combine's chain: n v210 layers of the output's size, read, combined, written - for up to
+ * four CONSUMERS in one call: an encoder's yuv422p8 / yuv420p / nv12 / yuv422p10 frame or the screen's rgba8 / bgra8 beside, or instead
+ * of, SDI's v210.  Exactly, bit for bit and in order, the n_out calls of ph_chan_compose on the same layers taken 1:1 (PH_SRC_V210,
+ * matrix9_host == NULL, PH_TRANSITION_CUT) with each output's format, planes, interlace, matrix and table; a v210 frame output is
+ * therefore ph_fused_v210_combine's frame.
+ * Routes: n_out == 1, PH_FMT_V210, interlace == 0 IS ph_fused_v210_combine, same route.  Otherwise one launch of the headline kernel's
+ * several-outputs form ("fused_v210_combine_multi x<outputs>" in a trace): its phase 1 is the headline kernel's; between the phases a quad
+ * is its 18 writer-table indices in registers, and the writer's phase runs once per distinct writer table among the outputs - the 18
+ * table reads made once, every output of that table packing the same 18 values with its own writer matrix.  No second composition
+ * and no index frame in memory.  The whole frame is always composed; a field output (interlace 1 / 3) stores the quads of its lines.
+ * The shared launch needs width % 48 == 0, the reader's table and every writer's table registered, and the context option "lds_lut"
+ * = 1; a call that does not qualify runs ph_chan_compose_multi on the equivalent layers inside the call, under that call's trace name,
+ * so the entry takes everything ph_chan_compose_multi takes and answers its errors.
+ * PH_E_INVALID, decided before anything is launched (a refused call writes nothing): NULL arguments, n outside 1..8, n_out outside
+ * 1..4, an unknown format, a format the channel kernel does not write (yuv420p10, p010), interlace not 0 / 1 / 3, a missing plane,
+ * matrix or table, an odd height for a 4:2:0 output, two outputs naming the same first plane.  height == 0 is PH_OK.
+ * Context option "fused_multi_wgs" (default 0: no cap): the most workgroups the shared launch may have - a test and A/B hook that lets
+ * a small frame reach several slices per lane and a second tile; the same bytes whatever its value. */
+int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const *layers, int n_out, const ph_chan_output *outs,
+                                uint32_t width, uint32_t height, const void *rd_col_matrix12, const void *rd_gamma_lut,
+                                const void *rd_gamut9);
 
 /* ---- gamma LUT placement.  The reference hands its kernels a 65536-entry f32 `gammaLut` buffer
  *      (loadSave.ts:65-73,152-160) and gathers from it 3x per pixel.  Registering the table's
@@ -671,7 +694,8 @@ int ph_lut_layout_of(const float *host_lut65536, ph_lut_layout *layout, void *ld
  *          instead of four per output pixel, the same bits; 0: the channel kernel for those frames too;
  *          "chan_batch_outs" (default 0): 1 lets ph_run_programs put consecutive channel frames for other consumers than SDI
  *          (chan_compose_v210_<n> with outPacking, chan_compose_multi_<n>) of one geometry and Loader recipe into shared launches
- *          (ph_chan_compose_batch_out); 0: each such job a launch of its own, in its turn.  The same bits either way. */
+ *          (ph_chan_compose_batch_out); 0: each such job a launch of its own, in its turn.  The same bits either way;
+ *          "fused_multi_wgs" (default 0: no cap) - tests and A/B runs: the most workgroups a ph_fused_v210_combine_multi launch may have. */
 int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value);
 
 /* ---- host colour maths (src/process/colourMaths.ts, run by Loader/Saver constructors

@@ -111,6 +111,12 @@ class Deferral {
 		// once for all of them.  `imageWriters: true` on the context; off unless asked for - three consumers measured 27 % faster, but
 		// v210 + rgba8 alone 4 % slower when the image comes from HBM (profiles/pack_write_multi_bench.jsonl, DESIGN.md 5.1).
 		this.imageWriters = ctx.imageWriters === true
+		// A frame whose chain is the headline's - plain reads of the output's size, combine, write - for a consumer that is not a v210 frame
+		// (an encoder's yuv422p8, the screen's bgra8, a field), or with sibling writes on the combined image: ONE
+		// fused_v210_combine_multi_<n> launch (ph_fused_v210_combine_multi: the headline kernel's phase 1, the table reads once per
+		// quad for all outputs) ahead of the channel kernel's candidates.  `fusedWriters: true` on the context; off unless asked for
+		// (DESIGN.md 5.1 has what it measured through the library) - with it off the recorded stream reaches the device exactly as before.
+		this.fusedWriters = ctx.fusedWriters === true
 		this.batchOutsSet = false
 	}
 
@@ -1010,9 +1016,10 @@ class Deferral {
 		// channel kernel's own frames and the headline's plain reads.  Frames of enlarged images (the 2 x 2-block compositor's) fold into
 		// that compositor's own several-outputs launch instead (upWriters, below).
 		let siblings = null
+		let found = [] // (the sibling writes as _siblings found them: fusedWriters below names them again)
 		const chanAt = candidates.findIndex((c) => c[0].startsWith('chan_compose_v210_'))
 		if (this.multiWriter && chanAt >= 0 && !candidates.some((c) => c[0].startsWith('compose_up_write_v210_'))) {
-			siblings = this._siblings(node, frame)
+			siblings = found = this._siblings(node, frame)
 			if (siblings.length) {
 				const params = Object.assign({}, candidates[chanAt][1])
 				siblings.forEach(({ frame: f, node: w }, i) => {
@@ -1028,6 +1035,25 @@ class Deferral {
 				siblings = siblings.map((v) => v.node)
 				candidates.unshift([`chan_compose_multi_${n}`, params, null, siblings])
 			} else siblings = null
+		}
+		// fusedWriters: the headline's plain reads, for a terminal write that is not a v210 frame or that has sibling writes - the headline
+		// kernel's several-outputs form ahead of the channel kernel's.  Refused (a width that is no multiple of 48 with a table the channel
+		// kernel cannot take either, a 10-bit 4:2:0 sibling), today's candidates follow.
+		if (this.fusedWriters && reader && reader.colMatrix && (outFmt || interlace || found.length) &&
+			layers.every((l) => l.v210 && !l.planar && !l.matrix && !l.transition)) {
+			const params = Object.assign({ output, interlace }, reader, saver)
+			layers.forEach((l, i) => { params[`l${i}In`] = l.source })
+			found.forEach(({ frame: f, node: w }, i) => {
+				const k = i + 1
+				if (f.outFmt) params[`out${k}Packing`] = f.outFmt
+				params[`output${k}`] = f.output
+				if (f.outFmt === 4) params[`output${k}C`] = w.params.outputC
+				else if (f.outFmt >= 1 && f.outFmt < 5) { params[`output${k}U`] = w.params.outputU; params[`output${k}V`] = w.params.outputV }
+				if (!f.outRgb8) params[`out${k}ColMatrix`] = w.params.colMatrix
+				params[`out${k}GammaLut`] = w.params.gammaLut
+				params[`interlace${k}`] = f.interlace
+			})
+			candidates.unshift([`fused_v210_combine_multi_${n}`, params, null, found.length ? found.map((v) => v.node) : null])
 		}
 		// the 2 x 2-block compositor's several-outputs form, ahead of all of these: the frame of a consumer that is not SDI, and the other
 		// consumers' writes of the same image as further outputs - with the frame's other field (the twin) where every one of these
@@ -1091,7 +1117,7 @@ class Deferral {
 		// and makes the ones of enlarged clips of one shape together)
 		// ... or frames of the 2 x 2-block compositor (de-interlaced fields at their own size or enlarged: several 1080i channels in a tick)
 		const up = candidates[0][0].startsWith('compose_up_write_v210_')
-		const batchable = up || candidates[0][0].startsWith('fused_v210_combine_') || (candidates.length === 1 && candidates[0][0].startsWith('chan_compose_v210_') && !outFmt)
+		const batchable = up || (candidates[0][0].startsWith('fused_v210_combine_') && !candidates[0][0].startsWith('fused_v210_combine_multi_')) || (candidates.length === 1 && candidates[0][0].startsWith('chan_compose_v210_') && !outFmt)
 		// ... or, with batchOuts, the channel kernel's frame for another consumer than SDI, or for several consumers (ph_chan_compose_batch_out)
 		const outs = this.batchOuts && !batchable && (candidates[0][0].startsWith('chan_compose_multi_') || (candidates.length === 1 && candidates[0][0].startsWith('chan_compose_v210_') && !!outFmt))
 		return { node, candidates, used, n, width, height, batchable: batchable || outs, outs, up, loader, saver, siblings, packedSources: frame.packedSources || null }

@@ -71,7 +71,7 @@ export interface DeferredStats {
 	pending: number; recorded: number; launched: number; fused: number; fusedNodes: number; plain: number; dropped: number; fallbacks: number; lastFallback: string | null
 	/** frames that went to the device together with other channels' frames, several to a launch */
 	batched?: number
-	/** consumers' writes that came out of another write's launch as further outputs (multiWriter, upWriters, imageWriters) */
+	/** consumers' writes that came out of another write's launch as further outputs (multiWriter, upWriters, imageWriters, fusedWriters) */
 	multiOutputs?: number
 }
 
@@ -105,12 +105,16 @@ export class clContext {
 	 * candidate refused) take the pending writes of the other consumers of the same image - any of the nine formats, yuv420p10 / p010 included -
 	 * with them as ONE `pack_write_multi_<n>` launch (ph_pack_write_multi: the image read and looked up once); `false`: a launch per write.
 	 * The same bytes either way.  Measured: three consumers 27 % faster, v210 + rgba8 alone 4 % slower from HBM (DESIGN.md 5.1).
+	 * `fusedWriters` (default false; PHANERON_FUSED_WRITERS=1): a frame whose chain is the headline's - plain `read`s of the output's size, `combine_<n>`,
+	 * `write` - whose terminal write is not a v210 frame (an encoder's, the screen's, a field), or which has sibling writes on the combined image,
+	 * is ONE `fused_v210_combine_multi_<n>` launch (ph_fused_v210_combine_multi: up to four outputs) instead of the channel kernel's; `false`: the
+	 * recorded stream reaches the device exactly as without the option.  The same bytes either way.
 	 * `recycleBuffers` (default true; PHANERON_RECYCLE=0): released frames / images are parked for the next createBuffer of their shape,
 	 * up to `parkMb` MiB (default 4096) or the most that was ever in use at once.  A parked buffer is taken over as the same JS object;
 	 * `strictHandles` (default false; PHANERON_STRICT_HANDLES=1): a fresh object per takeover, so that a reference kept past release()
 	 * is refused ('... released buffer') instead of aliasing the next owner's buffer - for running an application under test. */
 	constructor(params?: { platformIndex?: number; deviceIndex?: number; overlapping?: boolean; profile?: boolean; spinWaitMicros?: number; deferred?: boolean;
-		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; batchOuts?: boolean; imageWriters?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
+		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; batchOuts?: boolean; imageWriters?: boolean; fusedWriters?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
 	readonly queue: { load: number; process: number; unload: number }
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo

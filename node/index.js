@@ -168,6 +168,9 @@ class clContext {
 		// wire-format writes of one image that are launched as posted - a routed channel's image, a frame whose fused launch was refused, the 10-bit
 		// 4:2:0 consumers - as ONE pack_write_multi_<n> launch (node/defer.js imageWriters): off unless asked for (DESIGN.md 5.1: v210 + rgba8 alone measured slower)
 		this.imageWriters = params.imageWriters === undefined ? process.env.PHANERON_IMAGE_WRITERS === '1' : !!params.imageWriters
+		// a headline-shaped frame (plain reads of the output's size -> combine -> write) for a consumer that is not a v210 frame, or for several
+		// consumers, as ONE fused_v210_combine_multi_<n> launch (node/defer.js fusedWriters): off unless asked for
+		this.fusedWriters = params.fusedWriters === undefined ? process.env.PHANERON_FUSED_WRITERS === '1' : !!params.fusedWriters
 		// released frames and images are parked and taken over whole by the next createBuffer of the same shape (free() above);
 		// `recycleBuffers: false` or PHANERON_RECYCLE=0 returns every buffer to the library at once.  parkMb: what may stay parked
 		// (default 4096 MiB - or as much as was ever in use at once, if that is more)

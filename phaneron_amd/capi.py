@@ -36,6 +36,7 @@ EXPORTS = [
     "ph_route_wait", "ph_route_stream", "ph_route_comm_count", "ph_chan_compose_v210", "ph_chan_compose_batch", "ph_run_programs", "ph_event_record_timed", "ph_event_elapsed_us", "ph_ctx_host_pool_stats",
     "ph_v210_yadif_pair_fmt", "ph_compose_up_write_v210", "ph_trace_begin", "ph_trace_end", "ph_run_programs_progress", "ph_buf_reuse", "ph_image_unpack_rgb",
     "ph_chan_compose_multi", "ph_compose_up_write_multi", "ph_chan_compose_batch_out", "ph_pack_write_multi",
+    "ph_fused_v210_combine_multi",
 ]
 
 
@@ -209,6 +210,7 @@ def lib():
         "ph_chan_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_compose_up_write_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_pack_write_multi": (ci, [vp, ci, vp, ci, C.POINTER(PhChanOutput), cu, cu]),
+        "ph_fused_v210_combine_multi": (ci, [vp, ci, ci, C.POINTER(C.c_void_p), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_chan_compose_batch_out": (ci, [vp, ci, ci, C.POINTER(PhChanJobOut), cu, cu, vp, vp, vp]),
         "ph_ctx_host_pool_stats": (ci, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
         "ph_event_record_timed": (ci, [vp, ci, C.POINTER(vp)]),
@@ -801,6 +803,20 @@ class Context:
                 check(fn(*args), h)
             return job
         check(lib().ph_fused_v210_combine(*args), self.h)
+
+    def fused_v210_combine_multi(self, layers, outputs, width, height, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
+        """The plain-layer composite for 1..4 consumers in one launch (ph_fused_v210_combine_multi).  layers: v210 frames of the
+        output's size, as fused_v210_combine takes them; outputs: dicts as chan_compose_multi takes them."""
+        arr = (C.c_void_p * max(len(layers), 1))(*[None if l is None else _ptr(l).value for l in layers])
+        outs = self._chan_outputs(outputs)
+        args = (self.h, queue, len(layers), arr, len(outputs), outs, width, height) + tuple(None if t is None else _ptr(t) for t in (rd_cm, rd_lut, rd_gm))
+        fn, h = lib().ph_fused_v210_combine_multi, self.h
+        if prepare_only:
+
+            def job(_keep=(arr, layers, outputs, outs)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
 
     def fused_v210_combine_batch(self, jobs, dsts, width, height, rd_cm, rd_lut, rd_gm, wr_cm, wr_lut, queue=QUEUE_PROCESS):
         """jobs: list of per-frame layer lists (equal length); dsts: one output per job"""

@@ -947,6 +947,10 @@ int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value) {
     if (value != 0 && value != 1) return fail(PH_E_INVALID, "chan_batch_outs: 0 (a launch per such job) or 1 (shared launches)");
     return ctx->chan_batch_outs = value, PH_OK;
   }
+  if (0 == strcmp(name, "fused_multi_wgs")) {
+    if (value < 0) return fail(PH_E_INVALID, "fused_multi_wgs: a number of workgroups, or 0 for no cap");
+    return ctx->fused_multi_wgs = value, PH_OK;
+  }
   if (0 == strcmp(name, "host_pool_mb")) {
     if (value < 0) return fail(PH_E_INVALID, "host_pool_mb: a size in MiB");
     std::vector<ph_ctx::HostBlock> drop;
@@ -1808,6 +1812,78 @@ int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
   }
   hipError_t e = ph::launch_chan_compose_multi(stream_of(ctx, queue), m, (uint32_t)ctx->props.multiProcessorCount);
   if (e != hipSuccess) return fail(PH_E_HIP, "ph_chan_compose_multi: launch failed: %s", hipGetErrorString(e));
+  return PH_OK;
+}
+
+/* The plain-layer composite for several consumers: see include/phaneron_hip.h.  The call IS the n_out calls of ph_chan_compose on the layers
+ * taken 1:1; every check is made before anything is launched, with ph_chan_compose_multi's texts per output.  A call the shared kernel
+ * does not take runs ph_chan_compose_multi on those layers, which answers for everything else. */
+int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const *layers, int n_out, const ph_chan_output *outs, uint32_t width,
+                                uint32_t height, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  const char *const fn = "ph_fused_v210_combine_multi";
+  if (!ctx || !layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  if (n_out < 1 || n_out > ph::kMaxFusedOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxFusedOuts, n_out);
+  for (int i = 0; i < n; ++i)
+    if (!layers[i]) return fail(PH_E_INVALID, "%s: layer %d is NULL", fn, i);
+  PH_QUEUE(fn, queue);
+  if (!width) return fail(PH_E_INVALID, "%s: width 0", fn);
+  for (int k = 0; k < n_out; ++k) {
+    if (const int bad = chan_output_check(fn, "", k, outs[k], width, height)) return bad;
+    for (int j = 0; j < k; ++j)
+      if (outs[j].planes[0] == outs[k].planes[0]) return fail(PH_E_INVALID, "%s: outputs %d and %d name the same plane", fn, j, k);
+  }
+  // one v210 frame: the headline kernel itself, same route
+  if (n_out == 1 && outs[0].format == PH_FMT_V210 && outs[0].interlace == 0)
+    return ph_fused_v210_combine(ctx, queue, n, layers, outs[0].planes[0], width, height, rd_cm, rd_lut, rd_gm, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
+  // the shared launch: lines of whole 48-pixel blocks, every table in its LDS form (none is with the option "lds_lut" = 0), a frame
+  // small enough for the kernel's quad -> line division by reciprocal
+  const LutRef rref = lds_view(ctx, rd_lut);
+  LutRef wref[ph::kMaxFusedOuts];
+  bool shared = width % 48 == 0 && rref.get() && (uint64_t)(width / 6) * height * (width / 6) < (1ull << 32);
+  for (int k = 0; k < n_out && shared; ++k) {
+    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
+    shared = wref[k].get() != nullptr;
+  }
+  if (!shared) {
+    ph_chan_layer cl[ph::kMaxLayers];
+    memset(cl, 0, sizeof cl);
+    for (int i = 0; i < n; ++i) {
+      cl[i].src.data = layers[i], cl[i].src.format = PH_SRC_V210, cl[i].src.width = (int)width, cl[i].src.height = (int)height;
+      cl[i].transition = PH_TRANSITION_CUT;
+    }
+    return ph_chan_compose_multi(ctx, queue, n, cl, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
+  }
+  if (!height) return PH_OK;
+  ph::FusedMultiArgs m{};
+  for (int i = 0; i < n; ++i) m.layers[i] = layers[i];
+  m.quads_per_line = width / 6, m.total_quads = m.quads_per_line * height;
+  m.rd_cm = (const float *)rd_cm, m.rd_gm = (const float *)rd_gm, m.rd = *rref.get();
+  // the outputs grouped by writer table, in the order the tables first appear
+  int order[ph::kMaxFusedOuts], placed = 0;
+  for (int k = 0; k < n_out; ++k) {
+    bool seen = false;
+    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    if (seen) continue;
+    for (int j = k; j < n_out; ++j)
+      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) order[placed++] = j;
+  }
+  m.n_out = (uint32_t)n_out;
+  for (int i = 0; i < n_out; ++i) {
+    const ph_chan_output &o = outs[order[i]];
+    ph::FusedOut &d = m.out[i];
+    d.fmt = (uint32_t)o.format;
+    d.takes = !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;  // the whole frame is composed: a field output takes the lines of its parity
+    d.line_end = o.interlace ? 2u * (height / 2u) : height;    // (a field of an odd height: height / 2 lines, as ph_chan_compose writes it)
+    d.field = o.interlace ? 1u : 0u;
+    d.wr_cm = (const float *)(o.wr_col_matrix12 ? o.wr_col_matrix12 : rd_cm);
+    d.plane[0] = o.planes[0], d.plane[1] = o.planes[1], d.plane[2] = o.planes[2];
+    d.wr = *wref[order[i]].get();
+  }
+  const int rc = set_device(ctx);
+  if (rc) return rc;
+  const hipError_t e = ph::launch_fused_v210_combine_multi(stream_of(ctx, queue), n, m, (uint32_t)ctx->props.multiProcessorCount, (uint32_t)ctx->fused_multi_wgs);
+  if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   return PH_OK;
 }
 

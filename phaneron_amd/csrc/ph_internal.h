@@ -64,6 +64,8 @@ struct ph_ctx {
   int chan_enlarged = !(getenv("PH_CHAN_ENLARGED") && getenv("PH_CHAN_ENLARGED")[0] == '0');
   // option "chan_batch_outs" (default 0): ph_run_programs puts channel frames for other consumers than SDI into shared launches (ph_chan_compose_batch_out)
   int chan_batch_outs = 0;
+  // option "fused_multi_wgs" (default 0 = no cap): the most workgroups a ph_fused_v210_combine_multi launch may have (tests, A/B runs)
+  int fused_multi_wgs = 0;
   std::atomic<int> fail_launches{0};  // option "fail_launches" (a TEST hook): > 0 every launch through ph_run_program(s) fails; -k: the next k go through, then every one fails
   int host_pool_mb = 4096;
   size_t host_live_bytes = 0, host_peak_bytes = 0;  // mirrors attached to buffers now / at most

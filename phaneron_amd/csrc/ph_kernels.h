@@ -46,6 +46,36 @@ struct FusedLdsArgs {
   void *more_out[kMaxBatch - 1];
 };
 
+// Several consumers' frames of ONE plain-layer composite in one launch (ph_fused_v210_combine_multi; ph_kernels_fused_multi.hip): the
+// headline kernel's phase 1, then the writer's phase once per distinct writer table - the quad's 18 table reads made once, every
+// output of that table packing them with its own writer matrix.  width % 48 == 0 only: a line is quads_per_line whole quads, a planar
+// pitch is the width.  The whole frame is composed; a field output stores the quads whose line has its parity.
+// The launcher expects the outputs grouped by writer table.
+constexpr int kMaxFusedOuts = 4;
+struct FusedOut {
+  uint32_t fmt;         // PH_FMT_* (one of fmt_chan_out)
+  uint32_t takes;       // which lines are this output's: 0 all, 1 the even frame lines, 2 the odd ones
+  uint32_t line_end;    // a field output: lines from here on are not its own (a field of a frame with an odd height)
+  uint32_t field;       // 1: a field write (4:2:0: the written line of a pair gives the chroma)
+  uint32_t half_pitch;  // launcher: chroma samples per chroma row
+  uint32_t pad;
+  const float *wr_cm;   // (unused for rgba8 / bgra8)
+  void *plane[3];
+  LutView wr;
+};
+struct FusedMultiArgs {
+  const void *layers[kMaxLayers];
+  uint32_t quads_per_line, total_quads;  // width / 6, quads_per_line * height
+  uint32_t magic_qpl, need_line;         // launcher: ceil(2^32 / quads_per_line); 1: some output is a field or 4:2:0
+  const float *rd_cm, *rd_gm;
+  LutView rd;
+  uint32_t n_out;
+  FusedOut out[kMaxFusedOuts];
+};
+// named "fused_v210_combine_multi x<outputs>" in a route trace; n = 1..8 layers; one workgroup per CU, never more than slices and - a test
+// and A/B hook, 0 = no cap - never more than max_wgs
+hipError_t launch_fused_v210_combine_multi(hipStream_t s, int n, const FusedMultiArgs &a, uint32_t num_cus, uint32_t max_wgs);
+
 struct ComposeArgs {
   const void *layers[kMaxLayers];
   const float *matrix[kMaxLayers];  // device 3x3 (transform) or NULL = the layer is used 1:1

@@ -354,6 +354,37 @@ static int fused_call_parse(Args &a, FusedCall *call) {
   return a.rc;
 }
 
+// fused_v210_combine_multi_<n> (K_FUSED_V210, told apart by its name): l<i>In and the Loader's triple as fused_v210_combine_<n> names them; the
+// outputs as chan_compose_multi_<n> names them (chan_output_parse: outPacking, output, outputU / V / C, outColMatrix, outGammaLut, interlace,
+// then out<k>Packing, output<k>[U|V|C], out<k>ColMatrix, out<k>GammaLut, interlace<k> while output<k> is there, k = 1..3)
+static bool fused_is_multi(const ph_program *prog) { return prog->kernel.compare(0, 25, "fused_v210_combine_multi_") == 0; }
+static int fused_multi_job(Args &a, int queue) {
+  ph_ctx *ctx = a.ctx;
+  const int n = a.prog->n_layers;
+  uint32_t width, height;
+  a.frame(&width, &height);
+  const void *layers[ph::kMaxLayers];
+  for (int i = 0; i < n; ++i) layers[i] = a.buf(v210_bytes(width, height), "l%dIn", i)->dptr;
+  Recipe r;
+  ph_chan_output outs[ph::kMaxFusedOuts];
+  int n_out = 1;
+  chan_output_parse(a, 0, width, height, &outs[0], &r.wr_cm, &r.wr_lut, &r);
+  for (int k = 1; k < ph::kMaxFusedOuts && !a.rc && a.has("output%d", k); ++k) {
+    ph_buf *wr_cm, *wr_lut;
+    chan_output_parse(a, k, width, height, &outs[n_out++], &wr_cm, &wr_lut);
+  }
+  // what the typed call refuses about the outputs together, so that a check answers as a launch does
+  for (int k = 0; k < n_out && !a.rc; ++k) {
+    char num[4] = "";
+    if (k) snprintf(num, sizeof num, "%d", k);
+    if (outs[k].interlace != 0 && outs[k].interlace != 1 && outs[k].interlace != 3) return a.fail(PH_E_INVALID, "kernel argument 'interlace%s': must be 0, 1 or 3", num);
+    if (fmt_v420(outs[k].format) && (height & 1)) return a.fail(PH_E_INVALID, "kernel argument 'out%sPacking': a 4:2:0 frame needs an even height (%u)", num, height);
+    for (int j = 0; j < k; ++j)
+      if (outs[j].planes[0] == outs[k].planes[0]) return a.fail(PH_E_INVALID, "kernel argument 'output%d': the buffer is another output's too", k);
+  }
+  return a.done() ? a.rc : ph_fused_v210_combine_multi(ctx, queue, n, layers, n_out, outs, width, height, r.rd_cm->dptr, r.rd_lut->dptr, r.rd_gm->dptr);
+}
+
 // a compose_up_write_v210_<n> job's arguments (ph_run_program and ph_run_programs, which puts like jobs into one launch)
 struct UpCall {
   int n;
@@ -645,6 +676,7 @@ static int dispatch_compose(Args &a, int queue) {
       return a.done() ? a.rc : ph_combine(ctx, queue, prog->n_layers, layers, w, h, out->dptr);
     }
     case K_FUSED_V210: {
+      if (fused_is_multi(prog)) return fused_multi_job(a, queue);
       FusedCall f;
       fused_call_parse(a, &f);
       return a.done() ? a.rc : ph_fused_v210_combine(ctx, queue, f.n, f.layers, f.out, f.width, f.height, f.r.rd_cm->dptr, f.r.rd_lut->dptr, f.r.rd_gm->dptr,
@@ -772,7 +804,7 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * fused_v210_combine_<n> frames; a job that reads or writes what an earlier job of its group writes (or writes what one reads) is
  * detected here and starts the next launch, so call order holds (include/phaneron_hip.h).  A chan_compose_multi_<n> job runs in its turn
  * as a launch of its own - it ends the group in front of it, so whatever that group writes is there for it, and all its outputs for what follows.
- * So does a pack_write_multi_<n> job (ph_pack_write_multi).
+ * So does a pack_write_multi_<n> job (ph_pack_write_multi), and a fused_v210_combine_multi_<n> job (ph_fused_v210_combine_multi).
  * With the context option "chan_batch_outs" = 1 (default 0) consecutive chan_compose_multi_<n> jobs and chan_compose_v210_<n> jobs that
  * make another format than v210 (outPacking) share launches as well (ph_chan_compose_batch_out).  A call that fails after its checks
  * (a launch refused) has made the launches of the jobs before the failing group: ph_run_programs_progress says how many. */
@@ -806,7 +838,7 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       // (a frame for another consumer, or a chan_compose_multi_<n> job: a launch of its own, in its turn - unless the context option
       // "chan_batch_outs" lets such jobs share launches too: ph_chan_compose_batch_out)
       kind[(size_t)j] = calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
-    } else if (progs[j]->id == K_FUSED_V210) {
+    } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j])) {  // (a fused_v210_combine_multi_<n> job: a launch of its own, in its turn)
       if ((rc = fused_call_parse(job, &fused[(size_t)j]))) return rc;
       kind[(size_t)j] = 2;
     } else if (progs[j]->id == K_COMPOSE_UP) {
