@@ -46,7 +46,8 @@ extern "C" {
  *    channels' frames for any consumers in one launch; context option "chan_batch_outs".  ph_pack_write_multi: one f32 RGBA image packed
  *    for up to four consumers, any pack format each, in one launch; program "pack_write_multi_<n>".  ph_fused_v210_combine_multi: the
  *    plain-layer composite (ph_fused_v210_combine's chain) for up to four consumers in one launch; program
- *    "fused_v210_combine_multi_<n>"; context option "fused_multi_wgs" */
+ *    "fused_v210_combine_multi_<n>"; context option "fused_multi_wgs".  ph_fused_v210_combine_multi_batch: several channels' such frames in one
+ *    launch; context option "fused_multi_batch" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -643,6 +644,22 @@ int ph_pack_write_multi(ph_ctx *ctx, int queue, const void *in, int n_out, const
 int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const *layers, int n_out, const ph_chan_output *outs,
                                 uint32_t width, uint32_t height, const void *rd_col_matrix12, const void *rd_gamma_lut,
                                 const void *rd_gamut9);
+/* Several CHANNELS' plain-layer composites, each for the same list of consumers, in one call: `jobs` = 1..8 frames of one geometry, layer
+ * count and reader recipe.  layers: [jobs * n], job-major; outs: [jobs * n_out], job-major - outs[j * n_out + k] is outs[k] in everything
+ * (format, interlace, writer matrix, writer table) but its planes.  Exactly, bit for bit and in order, the `jobs` calls of
+ * ph_fused_v210_combine_multi.
+ * Routes: jobs == 1 IS ph_fused_v210_combine_multi, same route.  Every job one v210 frame (n_out == 1, PH_FMT_V210, interlace == 0) IS
+ * ph_fused_v210_combine_batch, same route.  Otherwise one launch ("fused_v210_combine_multi x<outputs>j<jobs>" in a trace): max(1, CUs /
+ * jobs) workgroups per job - never more than a job's slices, "fused_multi_wgs" caps them per job - each owning an equal contiguous quad
+ * range of its job; arithmetic and order within a job are ph_fused_v210_combine_multi's.  A call the shared launch does not take
+ * (width % 48 != 0, a table without its LDS form, "lds_lut" = 0, a frame too large for the kernel's division by reciprocal) runs
+ * ph_fused_v210_combine_multi per job, in order, inside the call, under those calls' trace names.
+ * PH_E_INVALID, decided before anything is launched (a refused call writes nothing): jobs outside 1..8; everything
+ * ph_fused_v210_combine_multi refuses, per job and output; an output that differs from job 0's in anything but its planes; two outputs
+ * of any jobs naming the same first plane.  height == 0 is PH_OK. */
+int ph_fused_v210_combine_multi_batch(ph_ctx *ctx, int queue, int jobs, int n, const void *const *layers /* [jobs * n], job-major */,
+                                      int n_out, const ph_chan_output *outs /* [jobs * n_out], job-major */, uint32_t width, uint32_t height,
+                                      const void *rd_col_matrix12, const void *rd_gamma_lut, const void *rd_gamut9);
 
 /* ---- gamma LUT placement.  The reference hands its kernels a 65536-entry f32 `gammaLut` buffer
  *      (loadSave.ts:65-73,152-160) and gathers from it 3x per pixel.  Registering the table's
@@ -695,7 +712,12 @@ int ph_lut_layout_of(const float *host_lut65536, ph_lut_layout *layout, void *ld
  *          "chan_batch_outs" (default 0): 1 lets ph_run_programs put consecutive channel frames for other consumers than SDI
  *          (chan_compose_v210_<n> with outPacking, chan_compose_multi_<n>) of one geometry and Loader recipe into shared launches
  *          (ph_chan_compose_batch_out); 0: each such job a launch of its own, in its turn.  The same bits either way;
- *          "fused_multi_wgs" (default 0: no cap) - tests and A/B runs: the most workgroups a ph_fused_v210_combine_multi launch may have. */
+ *          "fused_multi_wgs" (default 0: no cap) - tests and A/B runs: the most workgroups a ph_fused_v210_combine_multi launch may have
+ *          (a ph_fused_v210_combine_multi_batch launch: per job);
+ *          "fused_multi_batch" (default 0): 1 lets ph_run_programs put consecutive fused_v210_combine_multi_<n> jobs of one geometry,
+ *          layer count, Loader recipe and output list (formats, field modes, writer matrices and tables, in order) into shared launches,
+ *          up to 8 jobs each (ph_fused_v210_combine_multi_batch); 0: each such job a launch of its own, in its turn.  The same bits
+ *          either way.  Any other value is PH_E_INVALID. */
 int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value);
 
 /* ---- host colour maths (src/process/colourMaths.ts, run by Loader/Saver constructors

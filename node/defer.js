@@ -117,7 +117,13 @@ class Deferral {
 		// quad for all outputs) ahead of the channel kernel's candidates.  `fusedWriters: true` on the context; off unless asked for
 		// (DESIGN.md 5.1 has what it measured through the library) - with it off the recorded stream reaches the device exactly as before.
 		this.fusedWriters = ctx.fusedWriters === true
+		// Several channels' such frames of a tick - one size, layer count, Loader recipe and list of consumers - as ONE launch: they go down
+		// in one runPrograms call with the library's context option "fused_multi_batch" set (ph_fused_v210_combine_multi_batch).
+		// `fusedBatch: true` on the context, with `fusedWriters`; off unless asked for (DESIGN.md 5.1: measured through the library, not
+		// yet through node).
+		this.fusedBatch = ctx.fusedBatch === true
 		this.batchOutsSet = false
+		this.fusedBatchSet = false
 	}
 
 	// ---- bookkeeping on buffers -----------------------------------------------------------------------------
@@ -139,6 +145,17 @@ class Deferral {
 		for (const x of [a, b])
 			if (!x._digest) x._digest = require('crypto').createHash('sha1').update(x).digest('hex')
 		return a._digest === b._digest
+	}
+	// two several-outputs jobs' output lists: output by output the same format and field mode, writer matrices and tables of equal contents
+	static sameOutputs(a, b) {
+		for (let k = 0; k < 4; ++k) {
+			const at = (name) => (k ? name.replace(/^(output|out|interlace)/, `$1${k}`) : name)
+			if (!a[at('output')] !== !b[at('output')]) return false
+			if (!a[at('output')]) continue
+			if ((a[at('outPacking')] || 0) !== (b[at('outPacking')] || 0) || (a[at('interlace')] || 0) !== (b[at('interlace')] || 0)) return false
+			if (!Deferral.same(a[at('outColMatrix')] || null, b[at('outColMatrix')] || null) || !Deferral.same(a[at('outGammaLut')] || null, b[at('outGammaLut')] || null)) return false
+		}
+		return true
 	}
 	static sameRecipe(r, q) { return Deferral.same(r.colMatrix, q.colMatrix) && Deferral.same(r.gammaLut, q.gammaLut) && Deferral.same(r.gamutMatrix, q.gamutMatrix) }
 	// The recorded nodes' hold on a buffer: a count beside the owners' own (buf._refs, node/index.js) - the buffer goes when both are
@@ -394,7 +411,14 @@ class Deferral {
 					g.push(p)
 					continue
 				}
-				let g = groups.find((v) => !v[0].up && !v[0].outs && v[0].batchable && v.length < 8 && v[0].width === p.width && v[0].height === p.height && v[0].node.queue === p.node.queue &&
+				if (p.fusedOuts) { // the headline kernel's several-outputs frames (fusedBatch): one layer count, Loader recipe and list of outputs
+					let g = groups.find((v) => v[0].fusedOuts && v.length < 8 && v[0].width === p.width && v[0].height === p.height && v[0].n === p.n && v[0].node.queue === p.node.queue &&
+						Deferral.sameRecipe(v[0].loader, p.loader) && Deferral.sameOutputs(v[0].candidates[0][1], p.candidates[0][1]))
+					if (!g) groups.push((g = []))
+					g.push(p)
+					continue
+				}
+				let g = groups.find((v) => !v[0].up && !v[0].outs && !v[0].fusedOuts && v[0].batchable && v.length < 8 && v[0].width === p.width && v[0].height === p.height && v[0].node.queue === p.node.queue &&
 					Deferral.sameRecipe(v[0].loader, p.loader) && Deferral.same(v[0].saver.outColMatrix, p.saver.outColMatrix) && Deferral.same(v[0].saver.outGammaLut, p.saver.outGammaLut))
 				if (!g) groups.push((g = []))
 				g.push(p)
@@ -435,7 +459,9 @@ class Deferral {
 			for (const k of Object.keys(params)) {
 				let v = params[k]
 				if (v === undefined || v === null) continue
-				if (plans[0].outs) { // (the outputs keep their own writer matrices; every Saver table of the first plan's contents is named by its buffer)
+				if (plans[0].fusedOuts) { // (the Loader's triple and, output by output, the writer's matrix and table - of equal contents - by the first plan's buffers)
+					if ((k === 'colMatrix' || k === 'gammaLut' || k === 'gamutMatrix' || /^out\d*(ColMatrix|GammaLut)$/.test(k)) && first[k]) v = first[k]
+				} else if (plans[0].outs) { // (the outputs keep their own writer matrices; every Saver table of the first plan's contents is named by its buffer)
 					if ((k === 'colMatrix' || k === 'gammaLut' || k === 'gamutMatrix') && first[k]) v = first[k]
 					else if (/^out\d*GammaLut$/.test(k) && first.outGammaLut && Deferral.same(v, first.outGammaLut)) v = first.outGammaLut
 				} else if ((k === 'colMatrix' || k === 'gammaLut' || k === 'gamutMatrix' || k === 'outColMatrix' || k === 'outGammaLut') && first[k]) v = first[k]
@@ -451,6 +477,7 @@ class Deferral {
 		// the caller goes through the frames one by one and plans the stale ones again)
 		for (const p of plans) if (!this._fresh(p)) return false
 		const queue = plans[0].node.queue
+		if (plans[0].fusedOuts && !this.fusedBatchSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'fused_multi_batch', 1); this.fusedBatchSet = true }
 		if (plans[0].outs && !this.batchOutsSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'chan_batch_outs', 1); this.batchOutsSet = true }
 		try {
 			this.ctx._native.runPrograms(this.ctx._ctx, progs, names, values, queue)
@@ -1120,7 +1147,9 @@ class Deferral {
 		const batchable = up || (candidates[0][0].startsWith('fused_v210_combine_') && !candidates[0][0].startsWith('fused_v210_combine_multi_')) || (candidates.length === 1 && candidates[0][0].startsWith('chan_compose_v210_') && !outFmt)
 		// ... or, with batchOuts, the channel kernel's frame for another consumer than SDI, or for several consumers (ph_chan_compose_batch_out)
 		const outs = this.batchOuts && !batchable && (candidates[0][0].startsWith('chan_compose_multi_') || (candidates.length === 1 && candidates[0][0].startsWith('chan_compose_v210_') && !!outFmt))
-		return { node, candidates, used, n, width, height, batchable: batchable || outs, outs, up, loader, saver, siblings, packedSources: frame.packedSources || null }
+		// ... or, with fusedBatch, the headline kernel's several-outputs frame (ph_fused_v210_combine_multi_batch)
+		const fusedOuts = this.fusedBatch && this.fusedWriters && candidates[0][0].startsWith('fused_v210_combine_multi_')
+		return { node, candidates, used, n, width, height, batchable: batchable || outs || fusedOuts, outs, fusedOuts, up, loader, saver, siblings, packedSources: frame.packedSources || null }
 	}
 	// The pending writes of other consumers on the image `node` writes: wire-format writes _writeFrame accepts, of the same geometry, on
 	// the same queue, into buffers of their own - at most three (the launch has four outputs).

@@ -109,12 +109,18 @@ export class clContext {
 	 * `write` - whose terminal write is not a v210 frame (an encoder's, the screen's, a field), or which has sibling writes on the combined image,
 	 * is ONE `fused_v210_combine_multi_<n>` launch (ph_fused_v210_combine_multi: up to four outputs) instead of the channel kernel's; `false`: the
 	 * recorded stream reaches the device exactly as without the option.  The same bytes either way.
+	 * `fusedBatch` (default false; PHANERON_FUSED_BATCH=1; only with `fusedWriters`): the `fused_v210_combine_multi_<n>` frames several channels post in one
+	 * tick - one size, layer count, Loader recipe and list of consumers - go down in ONE runPrograms call and share ONE launch (the library's context option
+	 * `fused_multi_batch`, ph_fused_v210_combine_multi_batch; counted under `deferredStats().batched`); a refused batch falls back frame by frame; `false`: a
+	 * launch per channel, in its turn.  The same bytes either way.  Measured through the library, not through node (DESIGN.md 5.1), per call: four 1080p
+	 * channels' yuv422p8 frames 75.5 -> 53.7 us, SDI + the screen 89.7 -> 69.4, eight nv12 channels 149.7 -> 102.5, two channels with three consumers
+	 * 47.5 -> 40.7; two 2160p channels 106.4 -> 103.6 - a win, and the smallest.  No shape lost.
 	 * `recycleBuffers` (default true; PHANERON_RECYCLE=0): released frames / images are parked for the next createBuffer of their shape,
 	 * up to `parkMb` MiB (default 4096) or the most that was ever in use at once.  A parked buffer is taken over as the same JS object;
 	 * `strictHandles` (default false; PHANERON_STRICT_HANDLES=1): a fresh object per takeover, so that a reference kept past release()
 	 * is refused ('... released buffer') instead of aliasing the next owner's buffer - for running an application under test. */
 	constructor(params?: { platformIndex?: number; deviceIndex?: number; overlapping?: boolean; profile?: boolean; spinWaitMicros?: number; deferred?: boolean;
-		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; batchOuts?: boolean; imageWriters?: boolean; fusedWriters?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
+		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; batchOuts?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
 	readonly queue: { load: number; process: number; unload: number }
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo

@@ -171,6 +171,8 @@ class clContext {
 		// a headline-shaped frame (plain reads of the output's size -> combine -> write) for a consumer that is not a v210 frame, or for several
 		// consumers, as ONE fused_v210_combine_multi_<n> launch (node/defer.js fusedWriters): off unless asked for
 		this.fusedWriters = params.fusedWriters === undefined ? process.env.PHANERON_FUSED_WRITERS === '1' : !!params.fusedWriters
+		// several channels' such frames of a tick as ONE launch (node/defer.js fusedBatch; only with fusedWriters): off unless asked for
+		this.fusedBatch = params.fusedBatch === undefined ? process.env.PHANERON_FUSED_BATCH === '1' : !!params.fusedBatch
 		// released frames and images are parked and taken over whole by the next createBuffer of the same shape (free() above);
 		// `recycleBuffers: false` or PHANERON_RECYCLE=0 returns every buffer to the library at once.  parkMb: what may stay parked
 		// (default 4096 MiB - or as much as was ever in use at once, if that is more)

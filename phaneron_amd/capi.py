@@ -37,6 +37,7 @@ EXPORTS = [
     "ph_v210_yadif_pair_fmt", "ph_compose_up_write_v210", "ph_trace_begin", "ph_trace_end", "ph_run_programs_progress", "ph_buf_reuse", "ph_image_unpack_rgb",
     "ph_chan_compose_multi", "ph_compose_up_write_multi", "ph_chan_compose_batch_out", "ph_pack_write_multi",
     "ph_fused_v210_combine_multi",
+    "ph_fused_v210_combine_multi_batch",
 ]
 
 
@@ -211,6 +212,7 @@ def lib():
         "ph_compose_up_write_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_pack_write_multi": (ci, [vp, ci, vp, ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_fused_v210_combine_multi": (ci, [vp, ci, ci, C.POINTER(C.c_void_p), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
+        "ph_fused_v210_combine_multi_batch": (ci, [vp, ci, ci, ci, C.POINTER(C.c_void_p), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_chan_compose_batch_out": (ci, [vp, ci, ci, C.POINTER(PhChanJobOut), cu, cu, vp, vp, vp]),
         "ph_ctx_host_pool_stats": (ci, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
         "ph_event_record_timed": (ci, [vp, ci, C.POINTER(vp)]),
@@ -814,6 +816,24 @@ class Context:
         if prepare_only:
 
             def job(_keep=(arr, layers, outputs, outs)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
+
+    def fused_v210_combine_multi_batch(self, jobs_layers, jobs_outputs, width, height, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
+        """Several channels' plain-layer composites, each for the same list of consumers, in one launch
+        (ph_fused_v210_combine_multi_batch).  jobs_layers: per job the layer list fused_v210_combine_multi takes (equal lengths);
+        jobs_outputs: per job its output dicts (equal lengths; a job's outputs are job 0's in everything but their planes)."""
+        n = len(jobs_layers[0]) if jobs_layers else 0
+        n_out = len(jobs_outputs[0]) if jobs_outputs else 0
+        flat = [None if l is None else _ptr(l).value for job in jobs_layers for l in job]
+        arr = (C.c_void_p * max(len(flat), 1))(*flat)
+        outs = self._chan_outputs([o for job in jobs_outputs for o in job])
+        args = (self.h, queue, len(jobs_layers), n, arr, n_out, outs, width, height) + tuple(None if t is None else _ptr(t) for t in (rd_cm, rd_lut, rd_gm))
+        fn, h = lib().ph_fused_v210_combine_multi_batch, self.h
+        if prepare_only:
+
+            def job(_keep=(arr, jobs_layers, jobs_outputs, outs)):
                 check(fn(*args), h)
             return job
         check(fn(*args), h)

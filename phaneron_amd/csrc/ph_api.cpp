@@ -951,6 +951,10 @@ int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value) {
     if (value < 0) return fail(PH_E_INVALID, "fused_multi_wgs: a number of workgroups, or 0 for no cap");
     return ctx->fused_multi_wgs = value, PH_OK;
   }
+  if (0 == strcmp(name, "fused_multi_batch")) {
+    if (value != 0 && value != 1) return fail(PH_E_INVALID, "fused_multi_batch: 0 (a launch per such job) or 1 (shared launches)");
+    return ctx->fused_multi_batch = value, PH_OK;
+  }
   if (0 == strcmp(name, "host_pool_mb")) {
     if (value < 0) return fail(PH_E_INVALID, "host_pool_mb: a size in MiB");
     std::vector<ph_ctx::HostBlock> drop;
@@ -1883,6 +1887,91 @@ int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const
   const int rc = set_device(ctx);
   if (rc) return rc;
   const hipError_t e = ph::launch_fused_v210_combine_multi(stream_of(ctx, queue), n, m, (uint32_t)ctx->props.multiProcessorCount, (uint32_t)ctx->fused_multi_wgs);
+  if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  return PH_OK;
+}
+
+/* Several channels' plain-layer composites, each for the same consumers, in one launch: see include/phaneron_hip.h.  The call IS the `jobs`
+ * calls of ph_fused_v210_combine_multi in order; every check - those calls' own, per job and output - is made before anything is launched. */
+int ph_fused_v210_combine_multi_batch(ph_ctx *ctx, int queue, int jobs, int n, const void *const *layers, int n_out, const ph_chan_output *outs,
+                                      uint32_t width, uint32_t height, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  const char *const fn = "ph_fused_v210_combine_multi_batch";
+  if (!ctx || !layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (jobs < 1 || jobs > ph::kMaxBatch) return fail(PH_E_INVALID, "%s: 1..%d jobs (%d)", fn, ph::kMaxBatch, jobs);
+  if (jobs == 1) return ph_fused_v210_combine_multi(ctx, queue, n, layers, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  if (n_out < 1 || n_out > ph::kMaxFusedOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxFusedOuts, n_out);
+  for (int j = 0; j < jobs; ++j)
+    for (int i = 0; i < n; ++i)
+      if (!layers[(size_t)j * n + i]) return fail(PH_E_INVALID, "%s: job %d: layer %d is NULL", fn, j, i);
+  PH_QUEUE(fn, queue);
+  if (!width) return fail(PH_E_INVALID, "%s: width 0", fn);
+  bool frames_only = n_out == 1;
+  for (int j = 0; j < jobs; ++j) {
+    char where[16];
+    snprintf(where, sizeof where, "job %d: ", j);
+    for (int k = 0; k < n_out; ++k) {
+      const ph_chan_output &o = outs[(size_t)j * n_out + k], &o0 = outs[k];
+      if (const int bad = chan_output_check(fn, where, k, o, width, height)) return bad;
+      if (o.format != o0.format || o.interlace != o0.interlace || o.wr_col_matrix12 != o0.wr_col_matrix12 || o.wr_gamma_lut != o0.wr_gamma_lut)
+        return fail(PH_E_INVALID, "%s: job %d: output %d differs from job 0's in more than its planes (format, interlace, writer matrix, writer table)", fn, j, k);
+      for (int e = 0; e < j * n_out + k; ++e)
+        if (outs[e].planes[0] == o.planes[0])
+          return fail(PH_E_INVALID, "%s: job %d output %d and job %d output %d name the same plane", fn, e / n_out, e % n_out, j, k);
+      frames_only = frames_only && o.format == PH_FMT_V210 && o.interlace == 0;
+    }
+  }
+  if (frames_only) {  // every job one v210 frame: the headline kernel's own batch, same route
+    void *frames[ph::kMaxBatch];
+    for (int j = 0; j < jobs; ++j) frames[j] = outs[j].planes[0];
+    return ph_fused_v210_combine_batch(ctx, queue, jobs, n, layers, frames, width, height, rd_cm, rd_lut, rd_gm, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
+  }
+  // the shared launch: what ph_fused_v210_combine_multi's own asks for
+  const LutRef rref = lds_view(ctx, rd_lut);
+  LutRef wref[ph::kMaxFusedOuts];
+  bool shared = width % 48 == 0 && rref.get() && (uint64_t)(width / 6) * height * (width / 6) < (1ull << 32);
+  for (int k = 0; k < n_out && shared; ++k) {
+    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
+    shared = wref[k].get() != nullptr;
+  }
+  if (!shared) {
+    for (int j = 0; j < jobs; ++j)
+      if (const int rc = ph_fused_v210_combine_multi(ctx, queue, n, layers + (size_t)j * n, n_out, outs + (size_t)j * n_out, width, height, rd_cm, rd_lut, rd_gm)) return rc;
+    return PH_OK;
+  }
+  if (!height) return PH_OK;
+  ph::FusedMultiBatchArgs b{};
+  ph::FusedMultiArgs &m = b.m;
+  m.quads_per_line = width / 6, m.total_quads = m.quads_per_line * height;
+  m.rd_cm = (const float *)rd_cm, m.rd_gm = (const float *)rd_gm, m.rd = *rref.get();
+  // the outputs grouped by writer table, in the order the tables first appear (every job's list is job 0's: one order for all)
+  int order[ph::kMaxFusedOuts], placed = 0;
+  for (int k = 0; k < n_out; ++k) {
+    bool seen = false;
+    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    if (seen) continue;
+    for (int j = k; j < n_out; ++j)
+      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) order[placed++] = j;
+  }
+  m.n_out = (uint32_t)n_out;
+  for (int i = 0; i < n_out; ++i) {
+    const ph_chan_output &o = outs[order[i]];
+    ph::FusedOut &d = m.out[i];
+    d.fmt = (uint32_t)o.format;
+    d.takes = !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
+    d.line_end = o.interlace ? 2u * (height / 2u) : height;
+    d.field = o.interlace ? 1u : 0u;
+    d.wr_cm = (const float *)(o.wr_col_matrix12 ? o.wr_col_matrix12 : rd_cm);
+    d.wr = *wref[order[i]].get();
+  }
+  for (int j = 0; j < jobs; ++j) {
+    for (int i = 0; i < n; ++i) b.layers[j][i] = layers[(size_t)j * n + i];
+    for (int i = 0; i < n_out; ++i)
+      for (int p = 0; p < 3; ++p) b.plane[j][i][p] = outs[(size_t)j * n_out + order[i]].planes[p];
+  }
+  const int rc = set_device(ctx);
+  if (rc) return rc;
+  const hipError_t e = ph::launch_fused_v210_combine_multi_batch(stream_of(ctx, queue), n, (uint32_t)jobs, b, (uint32_t)ctx->props.multiProcessorCount, (uint32_t)ctx->fused_multi_wgs);
   if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   return PH_OK;
 }

@@ -66,6 +66,8 @@ struct ph_ctx {
   int chan_batch_outs = 0;
   // option "fused_multi_wgs" (default 0 = no cap): the most workgroups a ph_fused_v210_combine_multi launch may have (tests, A/B runs)
   int fused_multi_wgs = 0;
+  // option "fused_multi_batch" (default 0): ph_run_programs puts consecutive fused_v210_combine_multi_<n> jobs into shared launches (ph_fused_v210_combine_multi_batch)
+  int fused_multi_batch = 0;
   std::atomic<int> fail_launches{0};  // option "fail_launches" (a TEST hook): > 0 every launch through ph_run_program(s) fails; -k: the next k go through, then every one fails
   int host_pool_mb = 4096;
   size_t host_live_bytes = 0, host_peak_bytes = 0;  // mirrors attached to buffers now / at most

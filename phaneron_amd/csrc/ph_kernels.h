@@ -75,6 +75,17 @@ struct FusedMultiArgs {
 // named "fused_v210_combine_multi x<outputs>" in a route trace; n = 1..8 layers; one workgroup per CU, never more than slices and - a test
 // and A/B hook, 0 = no cap - never more than max_wgs
 hipError_t launch_fused_v210_combine_multi(hipStream_t s, int n, const FusedMultiArgs &a, uint32_t num_cus, uint32_t max_wgs);
+// The same for `jobs` = 2..kMaxBatch frames of one geometry, layer count, reader recipe and output descriptors in one launch
+// (ph_fused_v210_combine_multi_batch): the jobs differ in their layers and in their outputs' planes only.  m: what the jobs share
+// (m.layers and m.out[k].plane are not read); layers[j] / plane[j][k]: job j's, k in m.out's order.
+struct FusedMultiBatchArgs {
+  FusedMultiArgs m;
+  const void *layers[kMaxBatch][kMaxLayers];
+  void *plane[kMaxBatch][kMaxFusedOuts][3];
+};
+// named "fused_v210_combine_multi x<outputs>j<jobs>"; max(1, num_cus / jobs) workgroups per job, never more than a job's slices and - 0 = no
+// cap - never more than max_wgs; workgroups [j * per job, (j + 1) * per job) work on job j
+hipError_t launch_fused_v210_combine_multi_batch(hipStream_t s, int n, uint32_t jobs, const FusedMultiBatchArgs &a, uint32_t num_cus, uint32_t max_wgs);
 
 struct ComposeArgs {
   const void *layers[kMaxLayers];

@@ -1,0 +1,142 @@
+// ph_kernels_fused_multi_body.h - the body of ph_kernels_fused_multi.hip's kernels, included once per kernel: the single frame's
+// (PH_FM_BATCH 0; `a`: its FusedMultiArgs) and the batched launch's (PH_FM_BATCH 1; `a`: what the jobs share, FusedMultiBatchArgs::m).
+// One text, so the two cannot drift apart - and the single frame's kernel is compiled from the tokens it always had: a body shared
+// through a function, even an inlined one, reaches the scheduler as other IR and comes out in another instruction order.
+// A batched launch is gridDim.y frames side by side: the workgroups (x, j), x = 0..gridDim.x - 1 - in the order workgroups are numbered,
+// [j * gridDim.x, (j + 1) * gridDim.x) - own job j and divide ITS quads among them as the workgroups of a single frame do.  The job is
+// uniform per workgroup: its layer and plane pointers are scalar loads from the argument block at an offset made from blockIdx.y.
+// Everything else - geometry, the reader recipe, the output descriptors but for their planes - is the launch's.
+  constexpr int P = 6, BS = kLdsBlock;
+  // The output descriptors are walked by run-time index (table groups, the outputs of a group).  Read through the argument struct
+  // that would put a private copy of all of it in scratch; read where they are - the explicit arguments lie at the start of the
+  // kernel-argument segment - they stay scalar loads at a computed offset.
+#if PH_FM_BATCH
+  typedef const __attribute__((address_space(4))) FusedMultiBatchArgs *fm_kernarg_ptr;
+  const auto *const karg = (fm_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  const auto *const outs = karg->m.out;
+#else
+  typedef const __attribute__((address_space(4))) FusedMultiArgs *fm_kernarg_ptr;
+  const auto *const outs = ((fm_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr())->out;
+#endif
+  const ReadK rk = load_read_k(a.rd_cm, a.rd_gm);
+  const LutK rlut = make_lut_k(a.rd);
+  const bool std_matrix = ycbcr_matrix_is_standard(rk);  // uniform
+#if PH_FM_BATCH
+  auto layer_ptr = [&](int l) { return reinterpret_cast<const uint4 *>(karg->layers[blockIdx.y][l]); };
+#else
+  auto layer_ptr = [&](int l) { return reinterpret_cast<const uint4 *>(a.layers[l]); };
+#endif
+  // every workgroup owns one contiguous, equally sized range of quads - it begins and ends wherever that falls, in mid-line too -
+  // and walks it in tiles of BS * P quads; only the last tile of a range is partially filled
+  const uint32_t per_wg = (a.total_quads + gridDim.x - 1) / gridDim.x;
+  const uint32_t wg_begin = blockIdx.x * per_wg;
+  const uint32_t wg_end = wg_begin + per_wg < a.total_quads ? wg_begin + per_wg : a.total_quads;
+  const uint32_t tile_quads = BS * P;
+  for (uint32_t tile_begin = wg_begin; tile_begin < wg_end; tile_begin += tile_quads) {
+    uint32_t st[P][9];
+    // (pinned per tile, like the reader table's place below: what the lanes derive from them is made in the tile, not kept in
+    // registers through it for a next tile that a frame-sized share does not have)
+    uint32_t last_quad = wg_end - 1;
+    asm volatile("" : "+s"(last_quad));
+    auto quad_of = [&](int p) {
+      const uint32_t f = tile_begin + p * BS + threadIdx.x;  // width % 48 == 0: flat index == offset
+      return f < wg_end ? f : last_quad;                      // tail lanes recompute the last quad
+    };
+    // one-deep prefetch through layers and slices; the very first word is requested before the table load
+    uint4 w = load_stream(layer_ptr(0) + quad_of(0));
+    auto phase1_slice = [&](auto tag, uint4 w, uint32_t f, uint32_t f_next, bool more, uint32_t(&st)[9]) -> uint4 {
+      float acc[18];
+#pragma unroll
+      for (int i = 0; i < 18; ++i) acc[i] = 0.0f;
+#pragma unroll 1  // rolled: one copy of the per-layer code whatever N is
+      for (int l = 0; l < N; ++l) {
+        uint4 nxt = w;
+        if (l + 1 < N) nxt = load_stream(layer_ptr(l + 1) + f);
+        else if (more) nxt = load_stream(layer_ptr(0) + f_next);
+        const Yuv6 q = unpack_quad(w);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          const float4 t = read_px_lds<decltype(tag)::value>(q.y[j], q.cb[j >> 1], q.cr[j >> 1], rk, rlut, 1.0f);
+          const float kk = 1.0f - t.w;
+          // acc = fma(acc, kk, t), acc as destination (combine.ts:45-65; layer 0: fma(0, k, t) == t)
+          asm volatile("v_fma_f32 %0, %0, %3, %4\n\tv_fma_f32 %1, %1, %3, %5\n\tv_fma_f32 %2, %2, %3, %6"
+                       : "+v"(acc[3 * j]), "+v"(acc[3 * j + 1]), "+v"(acc[3 * j + 2])
+                       : "v"(kk), "v"(t.x), "v"(t.y), "v"(t.z));
+        }
+        w = nxt;
+      }
+#pragma unroll
+      for (int i = 0; i < 9; ++i) {  // the writers' first step needs no table: the 16-bit indices, two per register
+        const uint32_t lo = __float_as_uint(lds_lut_index_unit(acc[2 * i]));
+        const uint32_t hi = __float_as_uint(lds_lut_index_unit(acc[2 * i + 1]));
+        st[i] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+        asm volatile("" : "+v"(st[i]));  // pinned: keeps phase 1's arithmetic in front of the barrier
+      }
+      return w;
+    };
+    {
+      LutView rd = a.rd;
+      asm volatile("" : "+s"(rd.blob), "+s"(rd.hole));
+      lds_lut_load<BS>(rd);
+    }
+    __syncthreads();
+    // a slice is skipped per WAVE: only the waves that hold quads of a partly filled slice run it
+    const uint32_t wave_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      const uint32_t f = quad_of(p);
+      if (p * BS + wave_first < wg_end - tile_begin) {
+        PH_FM_BALANCE(p);
+        const bool more = (p + 1 < P) && ((p + 1) * BS + wave_first < wg_end - tile_begin);
+        const uint32_t f_next = more ? quad_of(p + 1) : f;
+        if (std_matrix) w = phase1_slice(std::true_type{}, w, f, f_next, more, st[p]);
+        else w = phase1_slice(std::false_type{}, w, f, f_next, more, st[p]);
+      }
+    }
+    // phase 2, once per distinct writer table (the outputs arrive grouped by table)
+#pragma unroll 1
+    for (uint32_t k0 = 0; k0 < a.n_out;) {
+      const LutView wr{outs[k0].wr.blob, outs[k0].wr.bytes, outs[k0].wr.hole, outs[k0].wr.bias, outs[k0].wr.shift, outs[k0].wr.a_scale, outs[k0].wr.delta_scale, outs[k0].wr.delta_base};
+      uint32_t k1 = k0 + 1;
+      while (k1 < a.n_out && outs[k1].wr.blob == wr.blob) ++k1;  // uniform
+      __syncthreads();  // nobody reads the table in the LDS any more
+      lds_lut_load<BS>(wr);
+      __syncthreads();
+      const LutK wlut = make_lut_k(wr);
+      uint32_t lane_quad = tile_begin + threadIdx.x;
+      asm volatile("" : "+v"(lane_quad));  // (pinned: every slice's quad, line and column are made here, not kept from in front of the loop)
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const uint32_t f = lane_quad + p * BS;
+        if (p * BS + wave_first < wg_end - tile_begin) {
+          PH_FM_BALANCE(p);
+          float g[18];
+#pragma unroll
+          for (int i = 0; i < 9; ++i) {  // M + idx: the index ORed into the mantissa of 1.5 * 2^23
+            // (pinned: the expansion does not depend on the table, and left alone all 108 expanded indices of the tile are made
+            // in front of the loop over the tables and kept through it - twice the registers the packed ones take)
+            asm volatile("" : "+v"(st[p][i]));
+            g[2 * i] = lds_lut_fetch(wlut, __uint_as_float((st[p][i] & 0xFFFFu) | 0x4B400000u));
+            g[2 * i + 1] = lds_lut_fetch(wlut, __uint_as_float((st[p][i] >> 16) | 0x4B400000u));
+            // two pixels' twelve LDS reads in flight at a time: all thirty-six at once would want registers this kernel does not have
+            if (i % 3 == 2) __builtin_amdgcn_sched_barrier(0);
+          }
+          if (f < wg_end) {
+            uint32_t line = 0, col = 0;
+            if (a.need_line) {  // uniform: some output is a field or 4:2:0
+              line = __umulhi(f, a.magic_qpl);
+              col = f - line * a.quads_per_line;
+            }
+#pragma unroll 1
+#if PH_FM_BATCH
+            for (uint32_t k = k0; k < k1; ++k) fused_out_store(outs[k], karg->plane[blockIdx.y][k], g, f, line, col);
+#else
+            for (uint32_t k = k0; k < k1; ++k) fused_out_store(outs[k], outs[k].plane, g, f, line, col);
+#endif
+          }
+        }
+      }
+      k0 = k1;
+    }
+    __syncthreads();  // the next tile loads the reader's table
+  }

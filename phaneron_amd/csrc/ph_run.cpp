@@ -358,16 +358,23 @@ static int fused_call_parse(Args &a, FusedCall *call) {
 // outputs as chan_compose_multi_<n> names them (chan_output_parse: outPacking, output, outputU / V / C, outColMatrix, outGammaLut, interlace,
 // then out<k>Packing, output<k>[U|V|C], out<k>ColMatrix, out<k>GammaLut, interlace<k> while output<k> is there, k = 1..3)
 static bool fused_is_multi(const ph_program *prog) { return prog->kernel.compare(0, 25, "fused_v210_combine_multi_") == 0; }
-static int fused_multi_job(Args &a, int queue) {
-  ph_ctx *ctx = a.ctx;
-  const int n = a.prog->n_layers;
-  uint32_t width, height;
-  a.frame(&width, &height);
+// (ph_run_programs, with the context option "fused_multi_batch", puts several such calls of one shape into one launch)
+struct FusedMultiCall {
+  int n, n_out;
   const void *layers[ph::kMaxLayers];
-  for (int i = 0; i < n; ++i) layers[i] = a.buf(v210_bytes(width, height), "l%dIn", i)->dptr;
-  Recipe r;
   ph_chan_output outs[ph::kMaxFusedOuts];
-  int n_out = 1;
+  uint32_t width, height;
+  Recipe r;  // (the Loader's triple; the Saver's pair of output 0)
+};
+static int fused_multi_parse(Args &a, FusedMultiCall *call) {
+  const int n = call->n = a.prog->n_layers;
+  uint32_t &width = call->width, &height = call->height;
+  a.frame(&width, &height);
+  const void **layers = call->layers;
+  for (int i = 0; i < n; ++i) layers[i] = a.buf(v210_bytes(width, height), "l%dIn", i)->dptr;
+  Recipe &r = call->r = Recipe();
+  ph_chan_output *outs = call->outs;
+  int &n_out = call->n_out = 1;
   chan_output_parse(a, 0, width, height, &outs[0], &r.wr_cm, &r.wr_lut, &r);
   for (int k = 1; k < ph::kMaxFusedOuts && !a.rc && a.has("output%d", k); ++k) {
     ph_buf *wr_cm, *wr_lut;
@@ -382,7 +389,12 @@ static int fused_multi_job(Args &a, int queue) {
     for (int j = 0; j < k; ++j)
       if (outs[j].planes[0] == outs[k].planes[0]) return a.fail(PH_E_INVALID, "kernel argument 'output%d': the buffer is another output's too", k);
   }
-  return a.done() ? a.rc : ph_fused_v210_combine_multi(ctx, queue, n, layers, n_out, outs, width, height, r.rd_cm->dptr, r.rd_lut->dptr, r.rd_gm->dptr);
+  return a.rc;
+}
+static int fused_multi_job(Args &a, int queue) {
+  FusedMultiCall c;
+  if (const int rc = fused_multi_parse(a, &c)) return rc;
+  return a.done() ? a.rc : ph_fused_v210_combine_multi(a.ctx, queue, c.n, c.layers, c.n_out, c.outs, c.width, c.height, c.r.rd_cm->dptr, c.r.rd_lut->dptr, c.r.rd_gm->dptr);
 }
 
 // a compose_up_write_v210_<n> job's arguments (ph_run_program and ph_run_programs, which puts like jobs into one launch)
@@ -804,7 +816,9 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * fused_v210_combine_<n> frames; a job that reads or writes what an earlier job of its group writes (or writes what one reads) is
  * detected here and starts the next launch, so call order holds (include/phaneron_hip.h).  A chan_compose_multi_<n> job runs in its turn
  * as a launch of its own - it ends the group in front of it, so whatever that group writes is there for it, and all its outputs for what follows.
- * So does a pack_write_multi_<n> job (ph_pack_write_multi), and a fused_v210_combine_multi_<n> job (ph_fused_v210_combine_multi).
+ * So does a pack_write_multi_<n> job (ph_pack_write_multi), and a fused_v210_combine_multi_<n> job (ph_fused_v210_combine_multi) - unless
+ * the context option "fused_multi_batch" = 1 (default 0) lets consecutive such jobs of one shape and output list share launches
+ * (ph_fused_v210_combine_multi_batch), under the same call-order rule.
  * With the context option "chan_batch_outs" = 1 (default 0) consecutive chan_compose_multi_<n> jobs and chan_compose_v210_<n> jobs that
  * make another format than v210 (outPacking) share launches as well (ph_chan_compose_batch_out).  A call that fails after its checks
  * (a launch refused) has made the launches of the jobs before the failing group: ph_run_programs_progress says how many. */
@@ -826,8 +840,9 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
   std::vector<ChanCall> calls((size_t)n_jobs);
   std::vector<FusedCall> fused((size_t)n_jobs);
   std::vector<UpCall> ups;  // (sized when the first compose_up job shows up: most calls have none)
+  std::vector<FusedMultiCall> multis;  // (likewise)
   // 1: a v210 frame from the channel kernel, 2: fused_v210_combine, 3: compose_up_write_v210, 4: a channel's frame for other consumers
-  // (option "chan_batch_outs"), 0: whatever else, launched as it is
+  // (option "chan_batch_outs"), 5: fused_v210_combine_multi (option "fused_multi_batch"), 0: whatever else, launched as it is
   std::vector<char> kind((size_t)n_jobs, 0);
   for (int j = 0; j < n_jobs; ++j) {  // every job is checked before anything is launched: a bad one refuses the call as a whole
     if (!progs[j] || (n_args[j] > 0 && !args[j])) return fail(PH_E_INVALID, "ph_run_programs: job %d: NULL argument", j);
@@ -838,9 +853,15 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       // (a frame for another consumer, or a chan_compose_multi_<n> job: a launch of its own, in its turn - unless the context option
       // "chan_batch_outs" lets such jobs share launches too: ph_chan_compose_batch_out)
       kind[(size_t)j] = calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
-    } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j])) {  // (a fused_v210_combine_multi_<n> job: a launch of its own, in its turn)
+    } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j])) {
       if ((rc = fused_call_parse(job, &fused[(size_t)j]))) return rc;
       kind[(size_t)j] = 2;
+    } else if (progs[j]->id == K_FUSED_V210 && ctx->fused_multi_batch) {
+      // (a fused_v210_combine_multi_<n> job: a launch of its own, in its turn - unless the context option "fused_multi_batch" lets such
+      // jobs share launches: ph_fused_v210_combine_multi_batch)
+      if (multis.empty()) multis.resize((size_t)n_jobs);
+      if ((rc = fused_multi_parse(job, &multis[(size_t)j]))) return rc;
+      kind[(size_t)j] = 5;
     } else if (progs[j]->id == K_COMPOSE_UP) {
       if (ups.empty()) ups.resize((size_t)n_jobs);
       if ((rc = up_call_parse(job, &ups[(size_t)j]))) return rc;
@@ -881,6 +902,63 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       }
       rc = ph_fused_v210_combine_batch(ctx, queue, (int)outs.size(), f0.n, layers.data(), outs.data(), f0.width, f0.height, f0.r.rd_cm->dptr, f0.r.rd_lut->dptr,
                                        f0.r.rd_gm->dptr, f0.r.wr_cm->dptr, f0.r.wr_lut->dptr);
+      if (rc) return rc;
+      g_programs_done = j = k;
+      continue;
+    }
+    if (kind[(size_t)j] == 5) {
+      // plain-layer composites for one list of consumers - one size, layer count, Loader recipe and, output by output, format, field mode,
+      // writer matrix and table - in one launch of up to kMaxBatch jobs (ph_fused_v210_combine_multi_batch).  The jobs of a launch are made
+      // side by side, so a job one of whose layers overlaps a plane an earlier job of the group writes, or one of whose planes overlaps a
+      // layer an earlier job reads or a plane it writes, starts the next launch: call order is kept.  By byte range, as the headline
+      // kernel's groups: a layer is any v210_bytes, a plane what its format gives it.
+      const FusedMultiCall &m0 = multis[(size_t)j];
+      const size_t frame_bytes = v210_bytes(m0.width, m0.height);
+      auto overlap = [](const void *p, size_t p_bytes, const void *q, size_t q_bytes) {
+        const char *a0 = (const char *)p, *b0 = (const char *)q;
+        return a0 < b0 + q_bytes && b0 < a0 + p_bytes;
+      };
+      size_t plane_bytes[ph::kMaxFusedOuts][3];
+      for (int o = 0; o < m0.n_out; ++o) {
+        plane_bytes[o][0] = plane_bytes[o][1] = plane_bytes[o][2] = 0;
+        // (a format without plane sizes is one the typed call refuses: the job goes down alone and is answered there)
+        if (pack_plane_bytes(m0.outs[o].format, m0.width, m0.height + (m0.height & 1u), plane_bytes[o]) < 0) plane_bytes[o][0] = frame_bytes;
+      }
+      // does a plane of u overlap a plane (planes_too) or a layer of e; or a layer of u a plane of e?
+      auto clashes = [&](const FusedMultiCall &u, const FusedMultiCall &e) {
+        for (int o = 0; o < m0.n_out; ++o)
+          for (int p = 0; p < 3; ++p) {
+            if (u.outs[o].planes[p] && plane_bytes[o][p]) {
+              for (int l = 0; l < e.n; ++l)
+                if (overlap(u.outs[o].planes[p], plane_bytes[o][p], e.layers[l], frame_bytes)) return true;
+              for (int o2 = 0; o2 < m0.n_out; ++o2)
+                for (int p2 = 0; p2 < 3; ++p2)
+                  if (e.outs[o2].planes[p2] && plane_bytes[o2][p2] && overlap(u.outs[o].planes[p], plane_bytes[o][p], e.outs[o2].planes[p2], plane_bytes[o2][p2])) return true;
+            }
+            if (e.outs[o].planes[p] && plane_bytes[o][p])
+              for (int l = 0; l < u.n; ++l)
+                if (overlap(u.layers[l], frame_bytes, e.outs[o].planes[p], plane_bytes[o][p])) return true;
+          }
+        return false;
+      };
+      std::vector<const void *> layers;
+      std::vector<ph_chan_output> outs;
+      for (; k < n_jobs && kind[(size_t)k] == 5 && k - j < ph::kMaxBatch; ++k) {
+        const FusedMultiCall &m = multis[(size_t)k];
+        bool same = m.n == m0.n && m.width == m0.width && m.height == m0.height && m.n_out == m0.n_out && m.r.rd_cm == m0.r.rd_cm && m.r.rd_lut == m0.r.rd_lut &&
+                    m.r.rd_gm == m0.r.rd_gm;
+        for (int o = 0; o < m0.n_out && same; ++o)
+          same = m.outs[o].format == m0.outs[o].format && m.outs[o].interlace == m0.outs[o].interlace && m.outs[o].wr_col_matrix12 == m0.outs[o].wr_col_matrix12 &&
+                 m.outs[o].wr_gamma_lut == m0.outs[o].wr_gamma_lut;
+        if (!same) break;
+        bool clash = false;
+        for (int e = j; e < k && !clash; ++e) clash = clashes(m, multis[(size_t)e]);
+        if (clash) break;
+        layers.insert(layers.end(), m.layers, m.layers + m.n);
+        outs.insert(outs.end(), m.outs, m.outs + m.n_out);
+      }
+      rc = ph_fused_v210_combine_multi_batch(ctx, queue, k - j, m0.n, layers.data(), m0.n_out, outs.data(), m0.width, m0.height, m0.r.rd_cm->dptr, m0.r.rd_lut->dptr,
+                                             m0.r.rd_gm->dptr);
       if (rc) return rc;
       g_programs_done = j = k;
       continue;
