@@ -47,7 +47,8 @@ extern "C" {
  *    for up to four consumers, any pack format each, in one launch; program "pack_write_multi_<n>".  ph_fused_v210_combine_multi: the
  *    plain-layer composite (ph_fused_v210_combine's chain) for up to four consumers in one launch; program
  *    "fused_v210_combine_multi_<n>"; context option "fused_multi_wgs".  ph_fused_v210_combine_multi_batch: several channels' such frames in one
- *    launch; context option "fused_multi_batch" */
+ *    launch; context option "fused_multi_batch".  ph_compose_up_transition_multi (ph_image_trans_layer): dissolves and wipes inside the
+ *    2 x 2-block compositor's launch */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -269,6 +270,10 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * l<i>Width / l<i>Height) and chan_compose_multi_<n>'s outputs.  Its twin - the other field of a de-interlaced frame - is announced by
  * l0In2 (l<i>In2: its images), and its planes carry the first job's names behind the word twin: twinOutput (twinOutputU / V / C),
  * twinOutput<k> (twinOutput<k>U / V / C) - `output2` being output 2's frame here.
+ * A compose_up_trans_<n> job (ph_compose_up_transition_multi) takes the same arguments and, per layer, the keys chan_compose_v210_<n> has
+ * for a transition: l<i>Transition (0 cut / 1 dissolve / 2 wipe), l<i>Mix, l<i>IncomingIn, l<i>IncomingMatrix and - with packedRgb -
+ * l<i>IncomingWidth / l<i>IncomingHeight, the same with Mask for a wipe; for the twin l<i>IncomingIn2, l<i>MaskIn2 and l<i>Mix2 (default:
+ * l<i>Mix).
  * And so does a pack_write_multi_<n> job (ph_pack_write_multi; globalWorkItems [width, height]): input - the f32 RGBA image - width, and
  * its n = 1..4 outputs as chan_compose_multi_<n> names them, outPacking / out<k>Packing being any PH_FMT_* here (7 and 8 included). */
 int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_arg *const *args, const int *n_args, int queue);
@@ -605,6 +610,32 @@ int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
  * A refused call writes nothing. */
 int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, int n_out,
                               const ph_chan_output *outs, uint32_t out_width, uint32_t out_height);
+/* The same with layers in a TRANSITION (transitioner.ts:165-176): a layer may bring the transition's second source and, for a wipe, its
+ * mask - enlarged images like the layer itself, each with a size and a matrix of its own.  For every job and output the result is, bit
+ * for bit, ph_transform of each present image (src, incoming, mask) with its own matrix to the output size, then
+ * ph_transition_dissolve(src', incoming', mix) or ph_transition_wipe(src', incoming', mask') for the layers that have one, then
+ * ph_combine over the n results (n == 1: the Combiner's passthrough), then ph_pack_write with the output's format, planes, interlace,
+ * matrix and table - which is what ph_chan_compose_multi makes of the same layers given as PH_SRC_RGBA_F32 sources.
+ * jobs: 1..4 (the argument block holds four jobs of eight layers with both partners).  Job j differs from job 0 in its images' data,
+ * its outputs' planes and its `mix` values (the two fields of a tick pass the Transitioner one after the other:
+ * transitioner.ts:170-175); layer count, transition kinds, image sizes, layouts and placements are job 0's.
+ * All images of a call have one layout, PH_IMG_RGBA_F32 or PH_IMG_RGB_F32; a packed image has alpha 1 inside and the border's 0
+ * outside, a packed mask gives its red.
+ * Launches: with every layer PH_TRANSITION_CUT the call IS ph_compose_up_write_multi on the `src` layers (same routes, same trace
+ * names).  Otherwise one launch per distinct registered writer table, outputs keeping their order
+ * ("compose_up_trans<rgb|rgba>x<outputs>j<jobs>" in a trace) - a v210 output that is alone with its table included.
+ * PH_E_INVALID, decided before anything is launched (a refused call writes nothing): everything ph_compose_up_write_multi refuses, per
+ * job and output; a placement of ANY present image that does not qualify on the composed geometry; a transition outside 0..2; a
+ * missing incoming image, or a missing mask for a wipe; with any layer in a transition, a v210 output at out_width % 48 != 0 (its tail
+ * quad truncates table indices where the other writers round: send that frame to ph_chan_compose_multi).  out_height == 0 is PH_OK. */
+typedef struct ph_image_trans_layer {
+  ph_image_layer src;
+  int transition;                /* PH_TRANSITION_CUT | _DISSOLVE | _WIPE */
+  float mix;                     /* dissolve */
+  ph_image_layer incoming, mask; /* the transition's second source and (wipe) its mask; ignored for CUT (the mask: for a dissolve too) */
+} ph_image_trans_layer;
+int ph_compose_up_transition_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_trans_layer *const *layer_sets, int n_out,
+                                   const ph_chan_output *outs /* [jobs * n_out], job-major */, uint32_t out_width, uint32_t out_height);
 /* One f32 RGBA image packed for up to four CONSUMERS in one call: a frame that exists as an image (a routed channel, a Combiner
  * passthrough, a frame whose fused launch was refused) and that every consumer runs its own FromRGBA on (channel.ts:40,64-88) - v210 for
  * SDI, p010 / yuv420p10 for a Main10 encoder, rgba8 for the screen.  outs: n_out = 1..4 outputs (ph_chan_output) in ANY

@@ -56,6 +56,8 @@ const pushNew = (list, v) => { if (!list.includes(v)) list.push(v) }
 
 // what `upWriters` is where the context does not say: see the constructor
 const UP_WRITERS_DEFAULT = { alone: true, several: true } // (both measured 4 - 6 x faster than today's launches: profiles/up_out_bench.jsonl)
+// the arguments of the 2 x 2-block compositor's programs that may name a packed field image when the launch was told packedRgb
+const PACKED_IMAGE_ARG = /^l\d+(Incoming|Mask)?In2?$/
 
 class Deferral {
 	constructor(ctx) {
@@ -100,6 +102,11 @@ class Deferral {
 		// `several`: sibling writes of one image folded into the launch - on where it measured faster by more than the separate side's
 		// spread (profiles/up_out_bench.jsonl, DESIGN.md 5.1).  `upWriters: true / false` on the context sets both.
 		this.upWriters = ctx.upWriters === undefined || ctx.upWriters === null ? Object.assign({}, UP_WRITERS_DEFAULT) : { alone: !!ctx.upWriters, several: !!ctx.upWriters }
+		// A frame of enlarged images (or fields at their own size) with a layer in a dissolve or a wipe: compose_up_trans_<n>
+		// (ph_compose_up_transition_multi) ahead of the channel kernel - the layers, the incoming images and the masks all placed as the
+		// 2 x 2-block compositor takes them, packed fields staying packed when every image of the frame is one.  `upTransitions: true` on
+		// the context; off unless asked for.
+		this.upTransitions = ctx.upTransitions === true
 		// Several channels' frames of a tick for consumers other than SDI - an encoder's, the screen's - and for several consumers at once
 		// (chan_compose_multi_<n>) as ONE launch: they go down in one runPrograms call with the library's context option "chan_batch_outs"
 		// set (ph_chan_compose_batch_out).  `batchOuts: true` on the context; off unless asked for (DESIGN.md 5.1: measured through the
@@ -466,7 +473,7 @@ class Deferral {
 					else if (/^out\d*GammaLut$/.test(k) && first.outGammaLut && Deferral.same(v, first.outGammaLut)) v = first.outGammaLut
 				} else if ((k === 'colMatrix' || k === 'gammaLut' || k === 'gamutMatrix' || k === 'outColMatrix' || k === 'outGammaLut') && first[k]) v = first[k]
 				// (a packed field image as a source of a batched frame: the real image first - unless the frame is the compositor's and was told)
-				if (v && v._packed != null && !(params.packedRgb && /^l\d+In2?$/.test(k))) this._unpack(v)
+				if (v && v._packed != null && !(params.packedRgb && PACKED_IMAGE_ARG.test(k))) this._unpack(v)
 				nm.push(k)
 				vs.push(Buffer.isBuffer(v) ? v._handle : typeof v === 'boolean' ? (v ? 1 : 0) : v)
 			}
@@ -515,7 +522,7 @@ class Deferral {
 		// packed field images (see _deinterlace) are images to everybody but the 2 x 2-block compositor that was told so
 		for (let k = 0; k < names.length; ++k) {
 			const v = params[names[k]]
-			if (v && v._packed != null && !(params.packedRgb && /^l\d+In2?$/.test(names[k])) && program.name !== 'rgb_unpack') this._unpack(v)
+			if (v && v._packed != null && !(params.packedRgb && PACKED_IMAGE_ARG.test(names[k])) && program.name !== 'rgb_unpack') this._unpack(v)
 		}
 		this.stats.launched++
 		this.launchedOn.set(queue, (this.launchedOn.get(queue) || 0) + 1)
@@ -820,7 +827,7 @@ class Deferral {
 		// Will this frame be made by the 2 x 2-block compositor from de-interlaced fields alone?  Every layer [transform of] a pending yadif
 		// output, placed as that compositor takes it (decided from the matrices' host copies, as `enlarged` in _plan): then the fields may
 		// be written packed.
-		const fieldLayer = (img) => {
+		const fieldImage = (img) => {
 			const t = img._producer
 			if (!t || t.state !== 'pending' || t.program.name !== 'transform' || !t.params.input || !t.params.transformMatrix ||
 				t.program.globalWorkItems[0] !== width || t.program.globalWorkItems[1] !== height) return false
@@ -831,10 +838,21 @@ class Deferral {
 			if (!interlace && d.width === width && d.height === height && q[0] === 1 && q[4] === 1 && q[2] === 0 && q[5] === 0) return true
 			return q[0] * d.width <= 0.99 * width && q[4] * d.height * (interlace ? 2 : 1) <= 0.99 * height
 		}
+		// upTransitions: a layer in a dissolve or a wipe is its two or three images, each of them such a field; the fields under the
+		// transition are de-interlaced with the others (fieldImages: what _deinterlace is given)
+		const under = (img) => {
+			const p = this.upTransitions && img._producer
+			const kind = p && p.state === 'pending' ? p.program.name : ''
+			if (kind !== 'transition_dissolve' && kind !== 'mixer' && kind !== 'transition_wipe') return [img]
+			const parts = [p.params.input0, p.params.input1].concat(kind === 'transition_wipe' ? [p.params.maskIn] : [])
+			return parts.every((x) => x) ? parts : [img]
+		}
+		const fieldImages = this.upTransitions ? [].concat(...layerImages.map(under)) : layerImages
+		const fieldLayer = (img) => under(img).every(fieldImage)
 		// (... or by its several-outputs form, which has every writer: planar frames in widths that are multiples of 8, 4:2:0 in even heights)
 		const upOut = !outFmt || ((this.upWriters.alone || this.upWriters.several) && (outRgb8 || (width % 8 === 0 && (outFmt < 3 || height % 2 === 0))))
 		const packFields = this.packFields && upOut && width % 2 === 0 && layerImages.every(fieldLayer)
-		return { outFmt, outRgb8, image, top, width, height, interlace, output, m, layerImages, packFields }
+		return { outFmt, outRgb8, image, top, width, height, interlace, output, m, layerImages, fieldImages, packFields }
 	}
 	// The Yadif windows of ALL the frames about to be planned go to the device in shared launches (up to eight windows each): the reference's
 	// four channels are all 1080i (src/index.ts:45-71) - their windows of a tick in one or two launches of the de-interlacing reader
@@ -846,7 +864,7 @@ class Deferral {
 			if (n.state !== 'pending') continue
 			let f = null
 			try { f = this._writeFrame(n) } catch (e) { f = null }
-			if (f) (f.packFields ? packed : plain).push(...f.layerImages)
+			if (f) (f.packFields ? packed : plain).push(...f.fieldImages)
 		}
 		if (packed.length) this._deinterlace(packed, true)
 		if (plain.length) this._deinterlace(plain, false)
@@ -854,8 +872,8 @@ class Deferral {
 	_plan(node) {
 		const frame = this._writeFrame(node)
 		if (!frame) return null
-		const { outFmt, outRgb8, image, top, width, height, interlace, output, m, layerImages, packFields } = frame
-		this._deinterlace(layerImages, packFields)
+		const { outFmt, outRgb8, image, top, width, height, interlace, output, m, layerImages, fieldImages, packFields } = frame
+		this._deinterlace(fieldImages, packFields)
 
 		// what each layer is made of.  The fused kernel applies ONE gamma table and gamut matrix (`reader`: a call is one colour
 		// space) and one YCbCr matrix to its v210 sources (`packedCm`); a planar source may bring a matrix of its own (the 8-bit
@@ -1007,6 +1025,34 @@ class Deferral {
 			candidates.push([`compose_up_write_v210_${n}`, params])
 			upMulti = { params, packedLayers, twin }
 		}
+		// the same compositor with a layer in a dissolve or a wipe (upTransitions): every present image - layer, incoming, mask - placed as
+		// it takes them; a v210 frame in a width it writes without a tail quad.  One image layout per launch: packed fields stay packed
+		// when every image of the frame is one, else the packed ones become images.  Ahead of the channel kernel; refused, that follows.
+		let upTrans = null
+		if (this.upTransitions && !anyV210 && width % 2 === 0 && layers.some((l) => l.transition)) {
+			const parts = [].concat(...layers.map((l) => (l.transition ? [l, l.transition.incoming].concat(l.transition.wipe ? [l.transition.mask] : []) : [l])))
+			const outOk = outFmt ? outRgb8 || (width % 8 === 0 && (outFmt < 3 || height % 2 === 0)) : width % 48 === 0
+			if (outOk && parts.every((s) => s.matrix && enlarged(s))) {
+				const packedAll = parts.every((s) => s.source._packed != null)
+				if (!packedAll) for (const s of parts) if (s.source._packed != null) this._unpack(s.source)
+				const params = Object.assign({ output, interlace }, saver)
+				if (packedAll) params.packedRgb = 1
+				const put = (name, s) => {
+					params[`${name}In`] = s.source; params[`${name}Matrix`] = s.matrix
+					if (packedAll) { params[`${name}Width`] = s.source.imageDims.width; params[`${name}Height`] = s.source.imageDims.height }
+				}
+				layers.forEach((l, i) => {
+					put(`l${i}`, l)
+					if (!l.transition) return
+					params[`l${i}Transition`] = l.transition.wipe ? 2 : 1
+					if (!l.transition.wipe) params[`l${i}Mix`] = l.transition.mix
+					put(`l${i}Incoming`, l.transition.incoming)
+					if (l.transition.wipe) put(`l${i}Mask`, l.transition.mask)
+				})
+				upTrans = [`compose_up_trans_${n}`, params]
+				if (packedAll) frame.packedSources = parts.map((s) => s.source)
+			}
+		}
 		// the channel kernel wants a whole Loader recipe even if no layer turns out to need its YCbCr matrix (packed RGB and image layers only)
 		const anyCm = packedCm || (reader && reader.colMatrix) || (this.lastReader && this.lastReader.colMatrix)
 		const loader = reader ? (anyCm ? { colMatrix: anyCm, gammaLut: reader.gammaLut, gamutMatrix: reader.gamutMatrix } : null) : this.lastReader
@@ -1037,7 +1083,7 @@ class Deferral {
 			})
 			candidates.push([`chan_compose_v210_${n}`, params])
 		}
-		if (!candidates.length) return null
+		if (!candidates.length && !upTrans) return null
 		// the other consumers' writes of the same image go with this one, as further outputs of the channel kernel's launch - for the
 		// classes of frame where that measured faster than a launch per consumer (profiles/chan_multi_bench.jsonl, DESIGN.md 5.1): the
 		// channel kernel's own frames and the headline's plain reads.  Frames of enlarged images (the 2 x 2-block compositor's) fold into
@@ -1143,6 +1189,7 @@ class Deferral {
 		// (frames from planar / packed-RGB clips go along in the same call: the library runs those it cannot put into a shared launch in their turn,
 		// and makes the ones of enlarged clips of one shape together)
 		// ... or frames of the 2 x 2-block compositor (de-interlaced fields at their own size or enlarged: several 1080i channels in a tick)
+		if (upTrans) candidates.unshift(upTrans)
 		const up = candidates[0][0].startsWith('compose_up_write_v210_')
 		const batchable = up || (candidates[0][0].startsWith('fused_v210_combine_') && !candidates[0][0].startsWith('fused_v210_combine_multi_')) || (candidates.length === 1 && candidates[0][0].startsWith('chan_compose_v210_') && !outFmt)
 		// ... or, with batchOuts, the channel kernel's frame for another consumer than SDI, or for several consumers (ph_chan_compose_batch_out)

@@ -98,6 +98,11 @@ export class clContext {
 	 * `upWriters` (default true for both classes of frame, as measured: DESIGN.md 5.1; PHANERON_UP_WRITERS=0): frames made from de-interlaced fields or
 	 * enlarged images for a consumer that is not SDI, and the writes of several consumers on one such image, are one launch of the 2 x 2-block
 	 * compositor from the packed fields (`compose_up_multi_<n>`); `false`: the fields unpacked and the channel kernel, a launch per consumer.
+	 * `upTransitions` (default false; PHANERON_UP_TRANSITIONS=1): a frame of such images with a layer in a dissolve or a wipe - the layer, the incoming
+	 * image and a wipe's mask all enlarged (or fields at their own size), none of them a wire-format frame, an even width (a v210 frame: a multiple of
+	 * 48) - is one launch of the same compositor (`compose_up_trans_<n>`, ph_compose_up_transition_multi) ahead of the channel kernel, from the packed
+	 * fields when every image of the frame is one; `false`: the recorded stream reaches the device exactly as without the option.  The same bytes either
+	 * way.  Measured through the library (DESIGN.md 5.1), not through node.
 	 * `batchOuts` (default false; PHANERON_BATCH_OUTS=1): the frames several channels post in one tick for consumers other than SDI (an encoder's
 	 * yuv422p8, the screen's rgba8) and for several consumers at once share ONE launch of the channel kernel (the library's context option
 	 * `chan_batch_outs`, ph_chan_compose_batch_out); `false`: a launch per channel, in its turn.  The same bytes either way.
@@ -120,7 +125,7 @@ export class clContext {
 	 * `strictHandles` (default false; PHANERON_STRICT_HANDLES=1): a fresh object per takeover, so that a reference kept past release()
 	 * is refused ('... released buffer') instead of aliasing the next owner's buffer - for running an application under test. */
 	constructor(params?: { platformIndex?: number; deviceIndex?: number; overlapping?: boolean; profile?: boolean; spinWaitMicros?: number; deferred?: boolean;
-		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; batchOuts?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
+		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; upTransitions?: boolean; batchOuts?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
 	readonly queue: { load: number; process: number; unload: number }
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo

@@ -163,6 +163,9 @@ class clContext {
 		// frames of the 2 x 2-block compositor for consumers other than SDI and for several consumers at once (node/defer.js upWriters);
 		// undefined: per class of frame as measured; true / false or PHANERON_UP_WRITERS=1 / 0: for every class
 		this.upWriters = params.upWriters === undefined ? (process.env.PHANERON_UP_WRITERS === undefined ? undefined : process.env.PHANERON_UP_WRITERS !== '0') : !!params.upWriters
+		// frames with a layer in a dissolve or a wipe through the 2 x 2-block compositor (node/defer.js upTransitions): off unless asked for
+		// (upTransitions: true, or PHANERON_UP_TRANSITIONS=1)
+		this.upTransitions = params.upTransitions === undefined ? process.env.PHANERON_UP_TRANSITIONS === '1' : !!params.upTransitions
 		// several channels' frames of a tick for consumers other than SDI, or for several consumers, as one launch (node/defer.js batchOuts): off unless asked for
 		this.batchOuts = params.batchOuts === undefined ? process.env.PHANERON_BATCH_OUTS === '1' : !!params.batchOuts
 		// wire-format writes of one image that are launched as posted - a routed channel's image, a frame whose fused launch was refused, the 10-bit

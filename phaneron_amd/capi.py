@@ -38,6 +38,7 @@ EXPORTS = [
     "ph_chan_compose_multi", "ph_compose_up_write_multi", "ph_chan_compose_batch_out", "ph_pack_write_multi",
     "ph_fused_v210_combine_multi",
     "ph_fused_v210_combine_multi_batch",
+    "ph_compose_up_transition_multi",
 ]
 
 
@@ -89,6 +90,10 @@ class PhChanJobOut(C.Structure):
 
 class PhImageLayer(C.Structure):
     _fields_ = [("data", C.c_void_p), ("format", C.c_int), ("width", C.c_int), ("height", C.c_int), ("matrix9_host", C.POINTER(C.c_float))]
+
+
+class PhImageTransLayer(C.Structure):  # ph_image_trans_layer
+    _fields_ = [("src", PhImageLayer), ("transition", C.c_int), ("mix", C.c_float), ("incoming", PhImageLayer), ("mask", PhImageLayer)]
 
 
 IMG_RGBA_F32, IMG_RGB_F32 = 0, 1
@@ -210,6 +215,7 @@ def lib():
         "ph_chan_compose_batch": (ci, [vp, ci, ci, C.POINTER(PhChanJob), cu, cu, vp, vp, vp, vp, vp]),
         "ph_chan_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_compose_up_write_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
+        "ph_compose_up_transition_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageTransLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_pack_write_multi": (ci, [vp, ci, vp, ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_fused_v210_combine_multi": (ci, [vp, ci, ci, C.POINTER(C.c_void_p), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_fused_v210_combine_multi_batch": (ci, [vp, ci, ci, ci, C.POINTER(C.c_void_p), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
@@ -578,6 +584,52 @@ class Context:
                 d.wr_gamma_lut = _ptr(o["wr_lut"]).value
         args = (self.h, queue, len(layer_sets), len(layer_sets[0]), sets, n_out, outs, out_w, out_h)
         fn, h = lib().ph_compose_up_write_multi, self.h
+        if prepare_only:
+
+            def job(_keep=(keep, arrs, layer_sets, outputs, sets, outs)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
+
+    def compose_up_transition_multi(self, layer_sets, outputs, out_w, out_h, queue=QUEUE_PROCESS, rgb=False, prepare_only=False):
+        """compose_up_write_multi with layers in a transition (ph_compose_up_transition_multi).  layer_sets: 1..4 sets of layers, a layer
+        either the (tensor, width, height, matrix) tuple compose_up_write_multi takes - a cut - or a dict {"src": tuple, "transition":
+        "cut" | "dissolve" | "wipe", "mix": float, "incoming": tuple, "mask": tuple} as chan_compose_v210's layers; a further set differs from the first in its tensors and its mix
+        values only.  outputs: as compose_up_write_multi."""
+        import numpy as np
+        keep = []
+
+        def image(dst, spec):
+            t, w, h, m = spec
+            mh = np.ascontiguousarray(m, np.float32)
+            keep.append(mh)
+            dst.data, dst.width, dst.height = _ptr(t).value, w, h
+            dst.format = IMG_RGB_F32 if rgb else IMG_RGBA_F32
+            dst.matrix9_host = mh.ctypes.data_as(C.POINTER(C.c_float))
+
+        arrs = []
+        for layers in layer_sets:
+            arr = (PhImageTransLayer * len(layers))()
+            for i, spec in enumerate(layers):
+                if not isinstance(spec, dict):
+                    spec = {"src": spec}
+                image(arr[i].src, spec["src"])
+                tr = spec.get("transition", "cut")  # (a raw number: a caller that tests the refusal of a bad one)
+                arr[i].transition = tr if isinstance(tr, int) else {"cut": TRANSITION_CUT, "dissolve": TRANSITION_DISSOLVE, "wipe": TRANSITION_WIPE}[tr]
+                arr[i].mix = float(spec.get("mix", 0.0))
+                if spec.get("incoming") is not None:
+                    image(arr[i].incoming, spec["incoming"])
+                if spec.get("mask") is not None:
+                    image(arr[i].mask, spec["mask"])
+            arrs.append(arr)
+        sets = (C.POINTER(PhImageTransLayer) * len(arrs))(*[C.cast(a, C.POINTER(PhImageTransLayer)) for a in arrs])
+        n_out = len(outputs[0])
+        for per_job in outputs:
+            if len(per_job) != n_out:
+                raise PhaneronError("compose_up_transition_multi: every set of layers needs the same number of outputs")
+        outs = self._chan_outputs([o for per_job in outputs for o in per_job])
+        args = (self.h, queue, len(layer_sets), len(layer_sets[0]), sets, n_out, outs, out_w, out_h)
+        fn, h = lib().ph_compose_up_transition_multi, self.h
         if prepare_only:
 
             def job(_keep=(keep, arrs, layer_sets, outputs, sets, outs)):

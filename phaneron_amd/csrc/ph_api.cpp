@@ -2467,20 +2467,9 @@ int ph_compose_up_write_v210_batch(ph_ctx *ctx, int queue, int jobs, int n, cons
   return compose_up_common("ph_compose_up_write_v210_batch", ctx, queue, jobs, n, layer_sets, outs, out_w, out_h, interlace, wr_cm, wr_lut);
 }
 
-/* Several consumers' frames of one enlarged composition: see include/phaneron_hip.h.  Every check is made, and every launch of the call
- * is planned, before anything is launched. */
-int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, int n_out, const ph_chan_output *outs,
-                              uint32_t out_w, uint32_t out_h) {
-  const char *const fn = "ph_compose_up_write_multi";
-  if (!ctx || !layer_sets || !outs) return fail(PH_E_INVALID, "%s: NULL argument", fn);
-  if (n_out < 1 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
-  if (jobs < 1 || jobs > ph::kMaxUpJobs) return fail(PH_E_INVALID, "%s: 1..%d jobs (%d)", fn, ph::kMaxUpJobs, jobs);
-  if (jobs == 1 && n_out == 1 && outs[0].format == PH_FMT_V210)
-    return ph_compose_up_write_v210(ctx, queue, n, layer_sets[0], outs[0].planes[0], out_w, out_h, outs[0].interlace, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
-  PH_QUEUE(fn, queue);
-  for (int j = 0; j < jobs; ++j)
-    if (!layer_sets[j]) return fail(PH_E_INVALID, "%s: NULL argument", fn);
-  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+// the outputs of a several-consumers call of the 2 x 2-block compositor (jobs x n_out entries, job-major; both counts are checked by the
+// caller): every check of the frame's width and of an output that needs no context ...
+static int compose_up_outputs(const char *fn, int jobs, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h) {
   if (!out_w || out_w % 2) return fail(PH_E_INVALID, "%s: width %u is odd (a block is two pixels wide); run the separate kernels", fn, out_w);
   for (int k = 0; k < n_out; ++k) {
     const ph_chan_output &o = outs[k];
@@ -2504,23 +2493,28 @@ int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_
         if (outs[i].planes[0] == b.planes[0]) return fail(PH_E_INVALID, "%s: outputs %d and %d name the same plane", fn, i, j * n_out + k);
     }
   }
-  LutRef wref[ph::kMaxUpOuts];
+  return PH_OK;
+}
+// ... then each output's writer table in its LDS form into wref[k]
+static int compose_up_tables(const char *fn, ph_ctx *ctx, int n_out, const ph_chan_output *outs, LutRef *wref) {
   for (int k = 0; k < n_out; ++k) {
     wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
     if (!wref[k].get())
       return fail(PH_E_INVALID, "%s: output %d: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn, k);
   }
-  ph::UpArgs base{};
-  int fmt = 0;
-  int rc = compose_up_layers(fn, jobs, n, layer_sets, base, &fmt);
-  if (rc) return rc;
-  // the launches: per writer table, in the order the tables first appear, a v210 output that cannot share (its lines end in a tail quad,
-  // or nobody else names its table) through today's kernel, then the rest as one several-outputs launch
-  struct Launch {
-    bool solo;  // compose_up_write_v210_kernel: m.up alone
-    ph::UpMultiArgs m;
-  };
-  std::vector<Launch> launches;
+  return PH_OK;
+}
+
+struct UpLaunch {
+  bool solo;  // compose_up_write_v210_kernel: m.up alone
+  int table;  // the first output that names the launch's writer table (m.up.wr: the caller's to fill)
+  ph::UpMultiArgs m;
+};
+// the launches of such a call: per writer table, in the order the tables first appear, a v210 output that cannot share (its lines end in a tail quad,
+// or nobody else names its table) through the one-output kernel, then the rest as one several-outputs launch.  split_v210 == false (layers in a
+// transition, which the one-output kernel does not have): every output of a table stays in the table's launch
+static void compose_up_launches(const ph::UpArgs &base, int jobs, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h,
+                                bool split_v210, std::vector<UpLaunch> &launches) {
   for (int k = 0; k < n_out; ++k) {
     bool seen = false;
     for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
@@ -2528,13 +2522,13 @@ int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_
     int group[ph::kMaxUpOuts], members = 0;
     for (int j = k; j < n_out; ++j)
       if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) group[members++] = j;
-    Launch shared{};
-    shared.solo = false, shared.m.up = base, shared.m.up.wr = *wref[k].get();
+    UpLaunch shared{};
+    shared.solo = false, shared.table = k, shared.m.up = base;
     for (int g = 0; g < members; ++g) {
       const ph_chan_output &o = outs[group[g]];
-      if (o.format == PH_FMT_V210 && (out_w % 48 || members == 1)) {
-        Launch own{};
-        own.solo = true, own.m.up = base, own.m.up.wr = *wref[k].get(), own.m.up.wr_cm = (const float *)o.wr_col_matrix12;
+      if (split_v210 && o.format == PH_FMT_V210 && (out_w % 48 || members == 1)) {
+        UpLaunch own{};
+        own.solo = true, own.table = k, own.m.up = base, own.m.up.wr_cm = (const float *)o.wr_col_matrix12;
         own.m.up.out = o.planes[0];
         for (int j = 1; j < jobs; ++j) own.m.up.more_out[j - 1] = outs[j * n_out + group[g]].planes[0];
         compose_up_lines(own.m.up, out_w, out_h, o.interlace);
@@ -2564,16 +2558,158 @@ int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_
     }
     launches.push_back(shared);
   }
-  for (const Launch &l : launches)
+}
+
+/* Several consumers' frames of one enlarged composition: see include/phaneron_hip.h.  Every check is made, and every launch of the call
+ * is planned, before anything is launched. */
+int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, int n_out, const ph_chan_output *outs,
+                              uint32_t out_w, uint32_t out_h) {
+  const char *const fn = "ph_compose_up_write_multi";
+  if (!ctx || !layer_sets || !outs) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n_out < 1 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
+  if (jobs < 1 || jobs > ph::kMaxUpJobs) return fail(PH_E_INVALID, "%s: 1..%d jobs (%d)", fn, ph::kMaxUpJobs, jobs);
+  if (jobs == 1 && n_out == 1 && outs[0].format == PH_FMT_V210)
+    return ph_compose_up_write_v210(ctx, queue, n, layer_sets[0], outs[0].planes[0], out_w, out_h, outs[0].interlace, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
+  PH_QUEUE(fn, queue);
+  for (int j = 0; j < jobs; ++j)
+    if (!layer_sets[j]) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  LutRef wref[ph::kMaxUpOuts];
+  int rc = compose_up_outputs(fn, jobs, n_out, outs, out_w, out_h);
+  if (!rc) rc = compose_up_tables(fn, ctx, n_out, outs, wref);
+  if (rc) return rc;
+  ph::UpArgs base{};
+  int fmt = 0;
+  rc = compose_up_layers(fn, jobs, n, layer_sets, base, &fmt);
+  if (rc) return rc;
+  std::vector<UpLaunch> launches;
+  compose_up_launches(base, jobs, n_out, outs, out_w, out_h, true, launches);
+  for (UpLaunch &l : launches) {
+    l.m.up.wr = *wref[l.table].get();
     if (!ph::compose_up_eligible(l.m.up)) return compose_up_not_eligible(fn);
+  }
   rc = set_device(ctx);
   if (rc) return rc;
-  for (const Launch &l : launches) {
+  for (const UpLaunch &l : launches) {
     if (!l.m.up.lines) continue;
     hipError_t e = hipSuccess;
     if (!l.solo) e = ph::launch_compose_up_multi(stream_of(ctx, queue), l.m, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount);
     else if (!ph::trace_launch("compose_up_write_v210"))
       e = ph::launch_compose_up_write_v210(stream_of(ctx, queue), l.m.up, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount);
+    if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  }
+  return PH_OK;
+}
+
+// one image of a transition call (a layer's src, incoming or mask) into a launch's arguments
+static int compose_up_image(const char *fn, int job, int layer, const char *what, const ph_image_layer &I, int fmt, ph::UpLayer &d) {
+  if (!I.data || I.width <= 0 || I.height <= 0 || !I.matrix9_host)
+    return fail(PH_E_INVALID, "%s: job %d layer %d: the %s image is missing or incomplete", fn, job, layer, what);
+  if (I.format != fmt) return fail(PH_E_INVALID, "%s: job %d layer %d: the %s image has another image format than layer 0's src", fn, job, layer, what);
+  d.ptr = I.data, d.w = (uint32_t)I.width, d.h = (uint32_t)I.height, d.pitch = (uint32_t)I.width * (fmt == PH_IMG_RGB_F32 ? 12u : 16u);
+  for (int k = 0; k < 6; ++k) d.m[k] = I.matrix9_host[k];
+  return PH_OK;
+}
+static bool compose_up_same_shape(const ph_image_layer &a, const ph_image_layer &b) {
+  if (a.width != b.width || a.height != b.height) return false;
+  for (int k = 0; k < 9; ++k)
+    if (a.matrix9_host[k] != b.matrix9_host[k]) return false;
+  return true;
+}
+
+/* Dissolves and wipes inside the 2 x 2-block compositor's launch: see include/phaneron_hip.h.  Every check is made, and every launch of
+ * the call is planned, before anything is launched. */
+int ph_compose_up_transition_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_trans_layer *const *layer_sets, int n_out,
+                                   const ph_chan_output *outs, uint32_t out_w, uint32_t out_h) {
+  const char *const fn = "ph_compose_up_transition_multi";
+  // (what the arguments alone decide is decided first - the context is looked at last, so a caller without a device learns of its mistakes too)
+  if (!layer_sets || !outs) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n_out < 1 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
+  if (jobs < 1 || jobs > ph::kMaxUpJobs) return fail(PH_E_INVALID, "%s: 1..%d jobs (%d)", fn, ph::kMaxUpJobs, jobs);
+  for (int j = 0; j < jobs; ++j)
+    if (!layer_sets[j]) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  bool any = false;
+  for (int j = 0; j < jobs; ++j)
+    for (int i = 0; i < n; ++i) {
+      const int t = layer_sets[j][i].transition;
+      if (t != PH_TRANSITION_CUT && t != PH_TRANSITION_DISSOLVE && t != PH_TRANSITION_WIPE)
+        return fail(PH_E_INVALID, "%s: job %d layer %d: transition %d is not a PH_TRANSITION_*", fn, j, i, t);
+      if (t != layer_sets[0][i].transition) return fail(PH_E_INVALID, "%s: job %d layer %d: another transition than job 0's layer has", fn, j, i);
+      any = any || t != PH_TRANSITION_CUT;
+    }
+  if (!any) {  // every layer a cut: ph_compose_up_write_multi on the src layers
+    std::vector<ph_image_layer> flat((size_t)jobs * n);
+    const ph_image_layer *sets[ph::kMaxUpJobs];
+    for (int j = 0; j < jobs; ++j) {
+      for (int i = 0; i < n; ++i) flat[(size_t)j * n + i] = layer_sets[j][i].src;
+      sets[j] = &flat[(size_t)j * n];
+    }
+    return ph_compose_up_write_multi(ctx, queue, jobs, n, sets, n_out, outs, out_w, out_h);
+  }
+  int rc = compose_up_outputs(fn, jobs, n_out, outs, out_w, out_h);
+  if (rc) return rc;
+  for (int k = 0; k < n_out; ++k)
+    if (outs[k].format == PH_FMT_V210 && out_w % 48)
+      return fail(PH_E_INVALID, "%s: output %d: a v210 frame of width %u ends its lines in a tail quad, which this kernel does not write for layers in a "
+                                "transition (width %% 48 != 0); use ph_chan_compose_multi", fn, k, out_w);
+  // the layers: job 0 gives count, kinds, sizes, layouts and placements; a further job its images' data and its mix values
+  ph::UpTransArgs t{};
+  ph::UpArgs &base = t.multi.up;
+  base.n = n, base.jobs = (uint32_t)jobs;
+  const int fmt = layer_sets[0][0].src.format;
+  if (fmt != PH_IMG_RGBA_F32 && fmt != PH_IMG_RGB_F32) return fail(PH_E_INVALID, "%s: image format %d", fn, fmt);
+  std::vector<ph::UpLayer> partners;  // the present partner images, for the placement rule
+  for (int i = 0; i < n; ++i) {
+    const ph_image_trans_layer &L = layer_sets[0][i];
+    const bool has[2] = {L.transition != PH_TRANSITION_CUT, L.transition == PH_TRANSITION_WIPE};
+    const char *const what[2] = {"incoming", "mask"};
+    t.kind[i] = (uint32_t)L.transition;
+    for (int j = 0; j < jobs; ++j) {
+      const ph_image_trans_layer &B = layer_sets[j][i];
+      const ph_image_layer *const theirs[2] = {&B.incoming, &B.mask}, *const firsts[2] = {&L.incoming, &L.mask};
+      ph::UpLayer d{};
+      if ((rc = compose_up_image(fn, j, i, "src", B.src, fmt, d))) return rc;
+      if (j == 0) base.layer[i] = d;
+      else if (!compose_up_same_shape(B.src, L.src)) return fail(PH_E_INVALID, "%s: job %d layer %d: the src image differs from job 0's in more than its data", fn, j, i);
+      else base.more_ptr[j - 1][i] = d.ptr;
+      for (int w = 0; w < 2; ++w) {
+        if (!has[w]) continue;
+        if ((rc = compose_up_image(fn, j, i, what[w], *theirs[w], fmt, d))) return rc;
+        if (j == 0) {
+          t.partner[i][w] = d;
+          t.same[i] |= compose_up_same_shape(*theirs[w], L.src) ? 1u << w : 0u;
+          partners.push_back(d);
+        } else if (!compose_up_same_shape(*theirs[w], *firsts[w])) {
+          return fail(PH_E_INVALID, "%s: job %d layer %d: the %s image differs from job 0's in more than its data", fn, j, i, what[w]);
+        } else {
+          t.more_partner[j - 1][i][w] = d.ptr;
+        }
+      }
+      t.mix[j][i] = B.mix;
+    }
+  }
+  std::vector<UpLaunch> launches;
+  if (out_h) compose_up_launches(base, jobs, n_out, outs, out_w, out_h, false, launches);  // (no lines: nothing to compose, PH_OK)
+  for (const UpLaunch &l : launches) {  // the placement rule on the geometry each launch composes: layers and partners alike
+    if (!ph::compose_up_eligible(l.m.up)) return compose_up_not_eligible(fn);
+    ph::UpArgs p = l.m.up;
+    p.n = 1;
+    for (const ph::UpLayer &partner : partners) {
+      p.layer[0] = partner;
+      if (!ph::compose_up_eligible(p)) return compose_up_not_eligible(fn);
+    }
+  }
+  if (!ctx) return fail(PH_E_INVALID, "%s: ctx is NULL", fn);
+  PH_QUEUE(fn, queue);
+  LutRef wref[ph::kMaxUpOuts];
+  if ((rc = compose_up_tables(fn, ctx, n_out, outs, wref))) return rc;
+  rc = set_device(ctx);
+  if (rc) return rc;
+  for (const UpLaunch &l : launches) {
+    if (!l.m.up.lines) continue;
+    t.multi = l.m, t.multi.up.wr = *wref[l.table].get();
+    const hipError_t e = ph::launch_compose_up_trans(stream_of(ctx, queue), t, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount);
     if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   }
   return PH_OK;

@@ -350,6 +350,21 @@ struct UpMultiArgs {
 };
 static_assert(sizeof(UpMultiArgs) < 4096, "kernel arguments are limited to 4 KiB");
 hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb12, uint32_t num_cus);
+// The same with layers in a transition (ph_compose_up_transition_multi, compose_up_trans_kernel): a layer may bring an incoming image
+// (dissolve, wipe) and a mask (wipe), each with a size and a placement of its own.  multi.up.layer[l] is the layer's `src`; job j > 0
+// differs in the images' data, the outputs' planes and the mix values.  multi.up.shared is not used: geometry is per layer, and a
+// partner shares its layer's only where `same` says it has the layer's size and placement.
+// Every field is sized for kMaxUpJobs jobs and kMaxLayers layers: 2.6 of the argument block's 4 KiB, so the bound on jobs stays kMaxUpJobs.
+struct UpTransArgs {
+  UpMultiArgs multi;
+  UpLayer partner[kMaxLayers][2];                            // [layer][0: incoming, 1: mask]; ptr: job 0's
+  const void *more_partner[kMaxUpJobs - 1][kMaxLayers][2];   // the further jobs' partner images
+  float mix[kMaxUpJobs][kMaxLayers];                         // dissolve: per job (the two fields of a tick pass the Transitioner one after the other)
+  uint32_t kind[kMaxLayers];                                 // PH_TRANSITION_*
+  uint32_t same[kMaxLayers];                                 // bit 0: the incoming image has the layer's size and placement, bit 1: the mask has
+};
+static_assert(sizeof(UpTransArgs) < 4096, "kernel arguments are limited to 4 KiB: kMaxUpJobs jobs of kMaxLayers layers with two partners each must fit");
+hipError_t launch_compose_up_trans(hipStream_t s, const UpTransArgs &t, bool rgb12, uint32_t num_cus);
 
 struct DeintArgs {  // ph_kernels_deint.hip
   const uint4 *prev[kMaxLayers], *cur[kMaxLayers], *next[kMaxLayers];  // v210 frames, width x height

@@ -67,18 +67,19 @@ struct UpShare {  // as ChanShare (ph_kernels_chan.hip): units dealt XCD-aware i
   bool banded;
 };
 // COLS: the output columns of a wave step - 126 (63 lanes: 21 v210 quads), or 128 (all 64 lanes) in launches without a v210 output
-template <uint32_t COLS = kUpCols>
+// BLOCK: the lanes of the kernel's workgroup (compose_up_trans_kernel has fewer than the others)
+template <uint32_t COLS = kUpCols, uint32_t BLOCK = (uint32_t)kUpBlock>
 __device__ __forceinline__ UpShare up_share(const UpArgs &a) {
   UpShare s;
   s.upr = (a.cover_w + COLS - 1u) / COLS;  // wave steps per row pair
   s.units = s.upr * ((a.lines + 1u) / 2u) * a.jobs;  // a further job's row pairs follow the one before's
   s.upg = (uint32_t)(PH_UP_GROUP_ROWS / 2) * s.upr;
   s.banded = (gridDim.x & 7u) == 0;
-  s.xcd = 0, s.v0 = blockIdx.x * (kUpBlock / 64), s.vstep = gridDim.x * (kUpBlock / 64), s.vend = s.units;
+  s.xcd = 0, s.v0 = blockIdx.x * (BLOCK / 64), s.vstep = gridDim.x * (BLOCK / 64), s.vend = s.units;
   if (s.banded) {
     s.xcd = blockIdx.x & 7u;
     const uint32_t groups = (s.units + s.upg - 1u) / s.upg, mine = (groups + 7u - s.xcd) / 8u;
-    s.v0 = (blockIdx.x >> 3) * (kUpBlock / 64), s.vstep = (gridDim.x >> 3) * (kUpBlock / 64), s.vend = mine * s.upg;
+    s.v0 = (blockIdx.x >> 3) * (BLOCK / 64), s.vstep = (gridDim.x >> 3) * (BLOCK / 64), s.vend = mine * s.upg;
   }
   return s;
 }
@@ -145,10 +146,10 @@ struct UpStep {
 // usually partial (2160p: 8.2 rounds) and its units are dealt one per SIMD instead - workgroup first, wave second (the waves of a
 // workgroup go round its four SIMDs) - so that the tail runs as single waves on otherwise idle SIMDs all over the chip, not as a few
 // CUs with sixteen waves each doing a ninth step.
-template <uint32_t COLS = kUpCols>
+template <uint32_t COLS = kUpCols, uint32_t BLOCK = (uint32_t)kUpBlock>
 __device__ __forceinline__ bool up_step(const UpArgs &a, const UpShare &sh, uint32_t &base, uint32_t wave, uint32_t lane, UpStep &st) {
   while (base < sh.vend) {
-    const uint32_t left = sh.vend - base, nwg = sh.vstep / (kUpBlock / 64), wg = sh.v0 / (kUpBlock / 64);
+    const uint32_t left = sh.vend - base, nwg = sh.vstep / (BLOCK / 64), wg = sh.v0 / (BLOCK / 64);
     const uint32_t pos = left >= sh.vstep ? sh.v0 + wave : wg + nwg * wave;
     const uint32_t v = base + pos;
     base += sh.vstep;
@@ -576,6 +577,172 @@ __global__ __launch_bounds__(kUpBlock) void compose_up_multi_kernel(UpMultiArgs 
   }
 }
 
+// ---- layers in a TRANSITION: [transform -> dissolve | wipe against a second source] x N -> combine_N -> the writers, one launch --------
+// The Transitioner (transitioner.ts:165-176) puts transition.ts's dissolve or wipe between a layer's transform and the Combiner, with
+// the incoming source - and a wipe's mask - transformed by matrices of their own.  Here a layer's four block pixels are made as VALUES
+// (r, g, b and the filtered alpha: a transition mixes alpha like any channel, so the INSIDE shortcut of up_blend holds for no layer
+// that has one), the partner images are filtered one after the other into the same sixteen registers - one patch in flight at any time -
+// and the result goes over the accumulators as any layer's does.  Arithmetic and order are transition.ts's:
+//   dissolve  v = fma(src, mix, incoming * (1 - mix))           wipe  v = fma(incoming, m, src * (1 - m)),  m = the mask's red
+// with (1 - mix), (1 - m) and the products beside the fma each rounded once.  A wipe's mask is filtered BEFORE its incoming image (the
+// order of the loads is nobody's business): src * (1 - m) then replaces src, and only those sixteen values and the four m wait for the
+// incoming patch - with the incoming image first, thirty-two values would.
+template <bool RGB12, typename F>
+__device__ __forceinline__ void up_values(const UpPatch &p, const UpGeo &g, F each) {
+  UpTexel P[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      P[r][c] = p.P[r][c];
+      if (RGB12) P[r][c].a = (((g.rin >> r) & 1u) && ((g.cin >> c) & 1u)) ? 1.0f : 0.0f;  // packed RGB: alpha 1 inside, the border's 0 outside
+    }
+  auto value = [](const UpTexel &t00, const UpTexel &t10, const UpTexel &t01, const UpTexel &t11, const UpWeights &w) __attribute__((always_inline)) {
+    UpTexel v;
+    v.r = ((w.w00 * t00.r + w.w10 * t10.r) + w.w01 * t01.r) + w.w11 * t11.r;
+    v.g = ((w.w00 * t00.g + w.w10 * t10.g) + w.w01 * t01.g) + w.w11 * t11.g;
+    v.b = ((w.w00 * t00.b + w.w10 * t10.b) + w.w01 * t01.b) + w.w11 * t11.b;
+    v.a = ((w.w00 * t00.a + w.w10 * t10.a) + w.w01 * t01.a) + w.w11 * t11.a;
+    return v;
+  };
+  const bool d1 = g.d1;
+  each(0, 0, value(P[0][0], P[0][1], P[1][0], P[1][1], g.w[0][0]));
+  each(0, 1, value(up_pick(d1, P[0][0], P[0][1]), up_pick(d1, P[0][1], P[0][2]), up_pick(d1, P[1][0], P[1][1]), up_pick(d1, P[1][1], P[1][2]), g.w[0][1]));
+  UpTexel lo0, lo1;
+  if (g.dj) {  // uniform, as up_filter
+    lo0 = value(P[1][0], P[1][1], P[2][0], P[2][1], g.w[1][0]);
+    lo1 = value(up_pick(d1, P[1][0], P[1][1]), up_pick(d1, P[1][1], P[1][2]), up_pick(d1, P[2][0], P[2][1]), up_pick(d1, P[2][1], P[2][2]), g.w[1][1]);
+  } else {
+    lo0 = value(P[0][0], P[0][1], P[1][0], P[1][1], g.w[1][0]);
+    lo1 = value(up_pick(d1, P[0][0], P[0][1]), up_pick(d1, P[0][1], P[0][2]), up_pick(d1, P[1][0], P[1][1]), up_pick(d1, P[1][1], P[1][2]), g.w[1][1]);
+  }
+  each(1, 0, lo0);
+  each(1, 1, lo1);
+}
+
+// layer l of the step's job as the Combiner gets it: the block's four pixels after transform and transition
+template <bool RGB12>
+__device__ __forceinline__ void up_trans_layer(const UpTransArgs &m, const UpStep &st, int l, UpTexel (&v)[2][2]) {
+  const UpArgs &a = m.multi.up;
+  UpLayer L = a.layer[l];
+  if (st.job) L.ptr = a.more_ptr[st.job - 1u][l];
+  UpGeo geo = up_geo<RGB12>(L, st);
+  {
+    UpPatch p;
+    up_fetch<RGB12>(L, geo, p);
+    up_values<RGB12>(p, geo, [&](int dy, int dx, const UpTexel &t) __attribute__((always_inline)) { v[dy][dx] = t; });
+  }
+  const uint32_t kind = m.kind[l], same = m.same[l];  // uniform
+  if (kind == PH_TRANSITION_CUT) return;
+  // a partner of the layer's size and placement is filtered with the layer's geometry; any other brings its own, which takes the
+  // layer's place (the layer is filtered by then) - and is replaced in its turn if the next partner is like the layer again
+  bool geo_is_layers = true;
+  auto partner = [&](int which, auto each) __attribute__((always_inline)) {
+    UpLayer P = m.partner[l][which];
+    if (st.job) P.ptr = m.more_partner[st.job - 1u][l][which];
+    const bool like_layer = (same >> which) & 1u;
+    if (!(like_layer && geo_is_layers)) geo = up_geo<RGB12>(P, st);  // uniform
+    geo_is_layers = like_layer;
+    UpPatch p;
+    up_fetch<RGB12>(P, geo, p);
+    up_values<RGB12>(p, geo, each);
+  };
+  if (kind == PH_TRANSITION_WIPE) {
+    float mr[2][2];
+    partner(1, [&](int dy, int dx, const UpTexel &t) __attribute__((always_inline)) {
+      const float mk = t.r, rm = 1.0f - mk;
+      UpTexel &s = v[dy][dx];
+      mr[dy][dx] = mk, s.r = s.r * rm, s.g = s.g * rm, s.b = s.b * rm, s.a = s.a * rm;
+    });
+    partner(0, [&](int dy, int dx, const UpTexel &t) __attribute__((always_inline)) {
+      const float mk = mr[dy][dx];
+      UpTexel &s = v[dy][dx];
+      s.r = fma_rn(t.r, mk, s.r), s.g = fma_rn(t.g, mk, s.g), s.b = fma_rn(t.b, mk, s.b), s.a = fma_rn(t.a, mk, s.a);
+    });
+  } else {
+    const float mix = m.mix[st.job][l], rmix = 1.0f - mix;  // uniform
+    partner(0, [&](int dy, int dx, const UpTexel &t) __attribute__((always_inline)) {
+      UpTexel &s = v[dy][dx];
+      s.r = fma_rn(s.r, mix, t.r * rmix), s.g = fma_rn(s.g, mix, t.g * rmix), s.b = fma_rn(s.b, mix, t.b * rmix), s.a = fma_rn(s.a, mix, t.a * rmix);
+    });
+  }
+}
+
+// compose_up_multi_kernel with up_trans_layer's layers; everything behind the layer loop is that kernel's, kept in step by hand (its
+// code is pinned - profiles/up_trans_resources.txt - so the two do not share a function that it would have to be rebuilt around)
+//
+// Lanes.  A transitioning layer's sixteen values (and a wipe's four mask values) live beside the accumulators while the partner's patch
+// is fetched and filtered: at 1024 lanes (128 vector registers) 52 - 56 of them are spilled, 288 - 316 bytes of scratch per lane; at
+// 768 lanes (three waves per SIMD, 168 registers) 7 - 10 and 124 - 144 bytes (profiles/up_trans_resources.txt).  Timed, four packed 1080p
+// fields with a dissolve and a wipe on a 1080p channel: 1024 lanes 81.1 us, 768 lanes 54.2 us, 512 lanes (no spills, two waves per
+// SIMD) 65.7 us; both fields of a tick 140.9 / 100.9 / 116.4; config 3's 2160p frame with one dissolve 120.9 / 122.5 / 148.9
+// (profiles/up_transition_lanes.jsonl): 768 lanes it is.
+#ifndef PH_UP_TRANS_BLOCK
+#define PH_UP_TRANS_BLOCK 768
+#endif
+constexpr int kUpTransBlock = PH_UP_TRANS_BLOCK;
+template <bool RGB12, uint32_t COLS>
+__global__ __launch_bounds__(kUpTransBlock) void compose_up_trans_kernel(UpTransArgs tr) {
+  const UpMultiArgs &m = tr.multi;
+  const UpArgs &a = m.up;
+  const LutK lk = make_lut_k(a.wr);
+  lds_lut_load<kUpTransBlock>(a.wr);
+  __syncthreads();
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const UpShare sh = up_share<COLS, (uint32_t)kUpTransBlock>(a);
+  const uint32_t role = lane - 3u * (lane / 3u);
+  UpStep st;
+  for (uint32_t base = 0; up_step<COLS, (uint32_t)kUpTransBlock>(a, sh, base, wave, lane, st);) {
+    UpAcc acc[2][2];
+    {  // the bottom layer is taken as it is - with a transition: the transition's value as it is
+      UpTexel v[2][2];
+      up_trans_layer<RGB12>(tr, st, 0, v);
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) acc[dy][dx] = UpAcc{v[dy][dx].r, v[dy][dx].g, v[dy][dx].b};
+    }
+#pragma unroll 1
+    for (int l = 1; l < a.n; ++l) {
+      UpTexel v[2][2];
+      up_trans_layer<RGB12>(tr, st, l, v);
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) up_over<false>(UpColour{v[dy][dx].r, v[dy][dx].g, v[dy][dx].b, 1.0f - v[dy][dx].a}, acc[dy][dx]);  // combine.ts:45-65
+    }
+    float t[2][2][3];
+    {
+      PxPending pend[2][2];
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx)
+          pend[dy][dx] = write_px_issue(lds_lut_index_unit(acc[dy][dx].r), lds_lut_index_unit(acc[dy][dx].g), lds_lut_index_unit(acc[dy][dx].b), lk);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx)
+          t[dy][dx][0] = lds_lut_finish(pend[dy][dx].r), t[dy][dx][1] = lds_lut_finish(pend[dy][dx].g), t[dy][dx][2] = lds_lut_finish(pend[dy][dx].b);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kMaxUpOuts; ++k) {
+      if (k >= m.n_out) break;  // uniform
+      const UpOut &o = m.out[k];
+      switch (o.fmt) {  // uniform
+        case PH_FMT_V210: up_write_out<PH_FMT_V210>(o, st, t, role); break;
+        case PH_FMT_YUV422P10: up_write_out<PH_FMT_YUV422P10>(o, st, t, role); break;
+        case PH_FMT_YUV422P8: up_write_out<PH_FMT_YUV422P8>(o, st, t, role); break;
+        case PH_FMT_YUV420P: up_write_out<PH_FMT_YUV420P>(o, st, t, role); break;
+        case PH_FMT_NV12: up_write_out<PH_FMT_NV12>(o, st, t, role); break;
+        case PH_FMT_RGBA8: up_write_out<PH_FMT_RGBA8>(o, st, t, role); break;
+        case PH_FMT_BGRA8: up_write_out<PH_FMT_BGRA8>(o, st, t, role); break;
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------
 // Clips straight from their wire formats: [read] x N -> [transform] x N -> combine_N -> v210 write as ONE launch.
 // The two-launch route (reader of the format into an f32 image, then the kernel above) sends every clip's image out of the chip and
@@ -931,7 +1098,7 @@ bool compose_up_eligible(const UpArgs &a) {
 }
 
 // what the launcher adds to a launch's arguments; returns the number of workgroups
-static uint32_t up_plan(UpArgs &b, bool tails, uint32_t num_cus, uint32_t cols = kUpCols) {
+static uint32_t up_plan(UpArgs &b, bool tails, uint32_t num_cus, uint32_t cols = kUpCols, uint32_t block = (uint32_t)kUpBlock) {
   if (!b.jobs) b.jobs = 1;
   b.out_qpitch = v210_pitch_bytes(b.out_w) / 16u;
   b.cover_w = tails ? b.out_qpitch * 6u : b.out_w;
@@ -945,7 +1112,7 @@ static uint32_t up_plan(UpArgs &b, bool tails, uint32_t num_cus, uint32_t cols =
   // reciprocals for the kernel's uniform divisions: umulhi(v, ceil(2^32 / d)) == v / d while v * d < 2^32
   b.magic_upr = upr > 1 ? (uint32_t)(((1ull << 32) + upr - 1) / upr) : 0u;
   b.magic_upg = (uint32_t)(((1ull << 32) + upg - 1) / upg);
-  const uint32_t want = (units + kUpBlock / 64 - 1) / (kUpBlock / 64);
+  const uint32_t want = (units + block / 64 - 1) / (block / 64);
   return want < num_cus ? want : num_cus;
 }
 
@@ -993,6 +1160,33 @@ hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb
   };
   if (wide) return rgb12 ? go(compose_up_multi_kernel<true, 128u>) : go(compose_up_multi_kernel<false, 128u>);
   return rgb12 ? go(compose_up_multi_kernel<true, kUpCols>) : go(compose_up_multi_kernel<false, kUpCols>);
+}
+
+// The same with layers in a transition: named compose_up_trans<rgb|rgba>x<outputs>j<jobs> in a route trace.  A v210 output's lines end on
+// a 48-pixel block (the caller refuses the others: no TAILS instantiation here)
+hipError_t launch_compose_up_trans(hipStream_t s, const UpTransArgs &t, bool rgb12, uint32_t num_cus) {
+  const UpMultiArgs &m = t.multi;
+  if (!m.up.lines) return hipSuccess;
+  if (m.n_out < 1 || m.n_out > (uint32_t)kMaxUpOuts || m.up.jobs < 1 || m.up.jobs > (uint32_t)kMaxUpJobs || m.up.n < 1 || m.up.n > kMaxLayers) return hipErrorInvalidValue;
+  for (uint32_t k = 0; k < m.n_out; ++k)
+    if (!fmt_chan_out((int)m.out[k].fmt) || (m.out[k].fmt == PH_FMT_V210 && m.up.out_w % 48u)) return hipErrorInvalidValue;
+  for (int l = 0; l < m.up.n; ++l)
+    if (t.kind[l] > (uint32_t)PH_TRANSITION_WIPE) return hipErrorInvalidValue;
+  char name[48];
+  snprintf(name, sizeof name, "compose_up_trans<%s>x%uj%u", rgb12 ? "rgb" : "rgba", m.n_out, m.up.jobs);
+  if (trace_launch(name)) return hipSuccess;
+  bool v210 = false;
+  for (uint32_t k = 0; k < m.n_out; ++k) v210 = v210 || m.out[k].fmt == PH_FMT_V210;
+  UpTransArgs b = t;
+  const uint32_t grid = up_plan(b.multi.up, false, num_cus, v210 ? kUpCols : 128u, (uint32_t)kUpTransBlock);
+  auto go = [&](auto kernel) -> hipError_t {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
+    if (e != hipSuccess) return e;
+    kernel<<<grid, kUpTransBlock, b.multi.up.wr.bytes, s>>>(b);
+    return hipGetLastError();
+  };
+  if (!v210) return rgb12 ? go(compose_up_trans_kernel<true, 128u>) : go(compose_up_trans_kernel<false, 128u>);
+  return rgb12 ? go(compose_up_trans_kernel<true, kUpCols>) : go(compose_up_trans_kernel<false, kUpCols>);
 }
 
 }  // namespace ph

@@ -198,6 +198,7 @@ int resolve_program(const char *src, const char *name, ProgramChoice &c, std::st
   if (0 == strncmp(name, "chan_compose_multi_", 19)) return layers("chan_compose_multi_", 1, K_CHAN_COMPOSE);  // (the same program with more outputs: told apart by name, ph_run.cpp)
   if (0 == strncmp(name, "compose_up_write_v210_", 22)) return layers("compose_up_write_v210_", 1, K_COMPOSE_UP);
   if (0 == strncmp(name, "compose_up_multi_", 17)) return layers("compose_up_multi_", 1, K_COMPOSE_UP);  // (the same program with any writer and more outputs: told apart by name, ph_run.cpp)
+  if (0 == strncmp(name, "compose_up_trans_", 17)) return layers("compose_up_trans_", 1, K_COMPOSE_UP);  // (compose_up_multi_<n> with layers in a transition, ph_compose_up_transition_multi: told apart by name, ph_run.cpp)
   if (0 == strncmp(name, "pack_write_multi_", 17)) {  // (the Writers' program with several outputs: told apart by name, ph_run.cpp; no one format)
     c.format = -1;
     return layers("pack_write_multi_", 1, K_PACK_WRITE, kMaxPackOuts, "output");

@@ -406,10 +406,37 @@ struct UpCall {
   Recipe r;  // (the Saver's pair)
   uint32_t width, height, interlace;
   // compose_up_multi_<n>: every output as ph_compose_up_write_multi takes it, job-major (outs[1]: the twin's)
-  bool multi;  // the program is compose_up_multi_<n>
+  bool multi;  // the program is compose_up_multi_<n> or compose_up_trans_<n>
   int n_out;
   ph_chan_output outs[2][ph::kMaxUpOuts];
+  // compose_up_trans_<n>: the layers as ph_compose_up_transition_multi takes them (tlayers[1]: the twin's; their src: layers / layers2)
+  bool trans;  // the program is compose_up_trans_<n>
+  ph_image_trans_layer tlayers[2][ph::kMaxLayers];
 };
+// a partner image of a compose_up_trans_<n> layer: l<i><Role>In, l<i><Role>Matrix, with packedRgb l<i><Role>Width / Height, the twin's l<i><Role>In2
+static void up_partner_parse(Args &a, int i, const char *role, bool rgb, bool pair, ph_image_layer *first, ph_image_layer *twin) {
+  const ph_buf *x = a.buf(0, "l%d%sIn", i, role);
+  double w = 0, h = 0;
+  if (rgb) {
+    w = a.num("l%d%sWidth", i, role), h = a.num("l%d%sHeight", i, role);
+    if (w <= 0 || h <= 0 || x->bytes < (size_t)w * (size_t)h * 12) return (void)a.fail(PH_E_RANGE, "kernel argument 'l%d%sIn': smaller than its %gx%g packed-RGB image", i, role, w, h);
+  } else {
+    int iw, ih;
+    a.named("l%d%sIn", i, role).need_image(x, &iw, &ih);
+    w = iw, h = ih;
+  }
+  first->data = x->dptr, first->format = rgb ? PH_IMG_RGB_F32 : PH_IMG_RGBA_F32, first->width = (int)w, first->height = (int)h;
+  first->matrix9_host = a.host_matrix(a.buf(36, "l%d%sMatrix", i, role));
+  *twin = *first;
+  if (!pair) return;
+  const ph_buf *x2 = a.buf(x->bytes, "l%d%sIn2", i, role);
+  if (!rgb) {
+    int w2, h2;
+    a.need_image(x2, &w2, &h2);
+    if (!a.rc && (w2 != (int)w || h2 != (int)h)) return (void)a.fail(PH_E_INVALID, "kernel argument '%s': the second job's image is %dx%d, the first's %gx%g", a.name, w2, h2, w, h);
+  }
+  twin->data = x2->dptr;
+}
 static int up_call_parse(Args &a, UpCall *u) {
   // l<i>In: the layer's image - an RGBA image buffer, or with packedRgb = 1 a buffer of packed f32 RGB (l<i>Width / l<i>Height:
   // its size); l<i>Matrix: its placement (host mirror, as above); output: v210; outColMatrix / outGammaLut; interlace
@@ -421,7 +448,11 @@ static int up_call_parse(Args &a, UpCall *u) {
   // outputU / V / C, outColMatrix, outGammaLut, interlace, then out<k>Packing, output<k>[U|V|C], out<k>ColMatrix, out<k>GammaLut,
   // interlace<k>, k = 1..3).  There `output2` is output 2's frame, so the twin is announced by l0In2 and its planes are the first
   // job's names behind the word twin: twinOutput, twinOutputU / V / C, twinOutput<k>, twinOutput<k>U / V / C.
-  u->multi = a.prog->kernel.compare(0, 17, "compose_up_multi_") == 0;
+  // compose_up_trans_<n>: compose_up_multi_<n>'s arguments and, per layer, the keys chan_compose_v210_<n> has for a transition:
+  // l<i>Transition (0 cut / 1 dissolve / 2 wipe), l<i>Mix, l<i>Incoming(In|Matrix|Width|Height), l<i>Mask(...); the twin's
+  // l<i>IncomingIn2, l<i>MaskIn2 and l<i>Mix2 (default l<i>Mix)
+  u->trans = a.prog->kernel.compare(0, 17, "compose_up_trans_") == 0;
+  u->multi = u->trans || a.prog->kernel.compare(0, 17, "compose_up_multi_") == 0;
   u->n_out = 0;
   u->pair = u->multi ? a.has("l0In2") : a.has("output2");
   for (int i = 0; i < u->n; ++i) {
@@ -449,6 +480,17 @@ static int up_call_parse(Args &a, UpCall *u) {
     u->layers[i].width = (int)lw, u->layers[i].height = (int)lh, u->layers[i].matrix9_host = placement;
     u->layers2[i] = u->layers[i];
     if (u->pair) u->layers2[i].data = x2->dptr;
+    if (!u->trans) continue;
+    ph_image_trans_layer &t = u->tlayers[0][i], &t2 = u->tlayers[1][i];
+    t = t2 = ph_image_trans_layer{};
+    t.src = u->layers[i], t2.src = u->layers2[i];
+    const double kind = a.num_or(0, "l%dTransition", i);
+    if (kind != PH_TRANSITION_CUT && kind != PH_TRANSITION_DISSOLVE && kind != PH_TRANSITION_WIPE)
+      return a.fail(PH_E_INVALID, "kernel argument 'l%dTransition': %g (0 cut, 1 dissolve, 2 wipe)", i, kind);
+    t.transition = t2.transition = (int)kind;
+    t.mix = (float)a.num_or(0, "l%dMix", i), t2.mix = (float)a.num_or(t.mix, "l%dMix2", i);
+    if (t.transition != PH_TRANSITION_CUT) up_partner_parse(a, i, "Incoming", u->rgb, u->pair, &t.incoming, &t2.incoming);
+    if (t.transition == PH_TRANSITION_WIPE) up_partner_parse(a, i, "Mask", u->rgb, u->pair, &t.mask, &t2.mask);
   }
   if (u->multi) {
     u->o = u->o2 = nullptr, u->r = Recipe(), u->interlace = 0;
@@ -483,13 +525,17 @@ static int up_call_parse(Args &a, UpCall *u) {
   return a.rc;
 }
 
-// a compose_up_multi_<n> job as the typed call
+// a compose_up_multi_<n> / compose_up_trans_<n> job as the typed call
 static int up_call_multi(ph_ctx *ctx, int queue, const UpCall &u) {
   const ph_image_layer *sets[2] = {u.layers, u.layers2};
   ph_chan_output outs[2 * ph::kMaxUpOuts];
   const int jobs = u.pair ? 2 : 1;
   for (int j = 0; j < jobs; ++j)
     for (int k = 0; k < u.n_out; ++k) outs[j * u.n_out + k] = u.outs[j][k];
+  if (u.trans) {
+    const ph_image_trans_layer *tsets[2] = {u.tlayers[0], u.tlayers[1]};
+    return ph_compose_up_transition_multi(ctx, queue, jobs, u.n, tsets, u.n_out, outs, u.width, u.height);
+  }
   return ph_compose_up_write_multi(ctx, queue, jobs, u.n, sets, u.n_out, outs, u.width, u.height);
 }
 
