@@ -919,6 +919,23 @@ int ph_lut_layout_of(const float *host, ph_lut_layout *layout, void *lds_image, 
   return (int)info.bytes;
 }
 
+// What the host computes for the fused kernel once per launch (ph_kernels.h: fused_lut_k, fused_wg_magic, fused_job_of), device-free,
+// for tests/test_fused_args_cpu.py.  k5: the bit patterns of a_scale, a_base, delta_scale, delta_base, then a_shift; returns the
+// table's LDS footprint as ph_lut_layout_of does (0: the table stays plain).
+int ph_debug_fused_lut_k(const float *host, uint32_t k5[5]) {
+  if (!host || !k5) return fail(PH_E_INVALID, "ph_debug_fused_lut_k: NULL argument");
+  std::vector<uint32_t> blob;
+  ph::LutHostInfo info;
+  if (!ph::lut_compress(host, ph::kLutMaxLdsBytes, blob, info)) return 0;
+  const ph::FusedLutK k = ph::fused_lut_k(ph::lut_view(info, nullptr));
+  memcpy(k5, &k, 5 * sizeof(uint32_t));
+  return (int)info.bytes;
+}
+// block / wg_per_job as the kernel takes it: the high word of (2 * block + 1) * magic
+uint32_t ph_debug_fused_job_of(uint32_t wg_per_job, uint32_t block) {
+  return wg_per_job ? ph::fused_job_of(block, ph::fused_wg_magic(wg_per_job)) : 0;
+}
+
 int ph_lut_query(ph_ctx *ctx, const void *dev, uint32_t *lds_bytes, uint32_t *toe, uint32_t *shift) {
   if (!ctx) return fail(PH_E_INVALID, "ph_lut_query: ctx is NULL");
   std::lock_guard<std::mutex> lock(ctx->mu);
@@ -1109,8 +1126,7 @@ int ph_fused_v210_combine(ph_ctx *ctx, int queue, int n, const void *const *laye
     const LutRef rref = lds_view(ctx, rd_lut), wref = lds_view(ctx, wr_lut);
     const ph::LutView *rv = rref.get(), *wv = wref.get();
     if (rv && wv) {
-      ph::FusedLdsArgs la{};
-      la.f = a, la.rd = *rv, la.wr = *wv, la.jobs = 1;
+      const ph::FusedLdsArgs la = ph::fused_lds_args(a, *rv, *wv);
       PH_LAUNCH(ph::launch_fused_v210_combine_lds(stream_of(ctx, queue), n, la, (uint32_t)ctx->props.multiProcessorCount));
     }
   }
@@ -1147,15 +1163,16 @@ int ph_fused_v210_combine_batch(ph_ctx *ctx, int queue, int jobs, int n, const v
     }
     return PH_OK;
   }
-  ph::FusedLdsArgs la{};
-  for (int l = 0; l < n; ++l) la.f.layers[l] = layers[l];
-  la.f.out = outs[0];
-  la.f.quads_per_line_used = width / 6;
-  la.f.quads_per_line_pitch = ph::v210_pitch_bytes(width) / 16;
-  la.f.total_quads = la.f.quads_per_line_used * height;
-  la.f.rd_cm = (const float *)rd_cm, la.f.rd_lut = (const float *)rd_lut, la.f.rd_gm = (const float *)rd_gm;
-  la.f.wr_cm = (const float *)wr_cm, la.f.wr_lut = (const float *)wr_lut;
-  la.rd = *rv, la.wr = *wv, la.jobs = (uint32_t)jobs;
+  ph::FusedArgs f{};
+  for (int l = 0; l < n; ++l) f.layers[l] = layers[l];
+  f.out = outs[0];
+  f.quads_per_line_used = width / 6;
+  f.quads_per_line_pitch = ph::v210_pitch_bytes(width) / 16;
+  f.total_quads = f.quads_per_line_used * height;
+  f.rd_cm = (const float *)rd_cm, f.rd_lut = (const float *)rd_lut, f.rd_gm = (const float *)rd_gm;
+  f.wr_cm = (const float *)wr_cm, f.wr_lut = (const float *)wr_lut;
+  ph::FusedLdsArgs la = ph::fused_lds_args(f, *rv, *wv);
+  la.jobs = (uint32_t)jobs;
   for (int j = 1; j < jobs; ++j) {
     for (int l = 0; l < n; ++l) la.more_layers[j - 1][l] = layers[(size_t)j * n + l];
     la.more_out[j - 1] = outs[j];

@@ -36,15 +36,73 @@ struct FusedArgs {
 };
 
 constexpr int kMaxBatch = 8;
-struct FusedLdsArgs {
-  FusedArgs f;     // job 0 (and the geometry / colour parameters of every job)
-  LutView rd, wr;  // compressed reader / writer tables (ph_lut.h)
+// The lookup constants of one table (LutK of ph_ldslut.h) as the HOST finishes them: they are the same for every lane of every
+// launch that uses the table, and the fused kernel used to rebuild both records from the LutViews in front of its first memory
+// instruction.  fused_lut_k makes them with make_lut_k's float operations in make_lut_k's order (the LDS base is 0:
+// ph_lut_register checks it), so the bits are the device's; tests/test_fused_args_cpu.py compares them for every layout.
+struct FusedLutK {
+  float a_scale, a_base, delta_scale, delta_base;
+  uint32_t a_shift;
+};
+FusedLutK fused_lut_k(const LutView &v);  // ph_kernels_lds.hip (host code)
+
+// blockIdx.x / wg_per_job of the fused kernel without a division: magic = ceil(2^31 / wg_per_job) (fused_wg_magic), and the
+// high word of (2 * block + 1) * magic is the quotient - floor((block + 1/2) / d) == floor(block / d), and the half leaves room
+// for the magic's rounding as long as (block + 1) * wg_per_job <= 2^30.  (ceil(2^32 / d) needs 33 bits at d = 1.)
+static inline uint32_t fused_wg_magic(uint32_t wg_per_job) { return (uint32_t)(((1ull << 31) + wg_per_job - 1) / wg_per_job); }
+static inline __host__ __device__ uint32_t fused_job_of(uint32_t block, uint32_t magic) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umulhi(2u * block + 1u, magic);
+#else
+  return (uint32_t)(((uint64_t)(2u * block + 1u) * magic) >> 32);
+#endif
+}
+
+// The fused LDS kernel's arguments.  What the kernel needs in front of its first vector memory instruction - the job arithmetic,
+// the reader table's place, the first layers - is the first 64-byte line; the rest of what its head reads fills the next two, and
+// the kernel asks for all 192 bytes in one request and waits once (ph_kernels_lds.hip).  The listed fields take 168 bytes, so
+// 128 cannot hold them.  The launcher fills `jobs` < 1 as 1, wg_per_job, per_wg and magic_wg.
+struct alignas(64) FusedLdsArgs {
+  // ---- bytes 0 .. 63
+  const uint32_t *rd_blob;          // reader table (LutView of ph_lut.h): blob, LDS footprint, hole
+  uint32_t rd_bytes, rd_hole;
+  uint32_t total_quads;             // quads_per_line_used * height (ragged lines: quad slots of the pitch)
   // batched launch: `jobs` frames of identical geometry and colour parameters, each with its own
   // layers and output; workgroups [j * wg_per_job, (j + 1) * wg_per_job) work on job j
-  uint32_t jobs, wg_per_job;
+  uint32_t wg_per_job;
+  uint32_t per_wg;                  // ceil(total_quads / wg_per_job): a workgroup's share
+  uint32_t magic_wg;                // fused_wg_magic(wg_per_job)
+  const void *layers[kMaxLayers];   // job 0 (bytes 32 .. 95)
+  // ---- bytes 96 .. 127
+  void *out;                        // job 0
+  const float *rd_cm, *rd_gm, *wr_cm;
+  // ---- bytes 128 .. 191
+  FusedLutK rd_k, wr_k;
+  uint32_t wr_bytes, wr_hole;       // writer table
+  const uint32_t *wr_blob;
+  uint32_t jobs;
+  uint32_t quads_per_line_used;     // width / 6
+  // ---- what the head does not read
+  uint32_t quads_per_line_pitch;    // pitch bytes / 16
+  // widths that are not a multiple of 48 (the TAIL instantiation only): see FusedArgs
+  uint32_t tail_px, magic_qpp;
   const void *more_layers[kMaxBatch - 1][kMaxLayers];
   void *more_out[kMaxBatch - 1];
 };
+constexpr size_t kFusedHeadBytes = 192;
+static_assert(offsetof(FusedLdsArgs, rd_blob) == 0 && offsetof(FusedLdsArgs, rd_bytes) == 8 && offsetof(FusedLdsArgs, rd_hole) == 12 &&
+              offsetof(FusedLdsArgs, total_quads) == 16 && offsetof(FusedLdsArgs, wg_per_job) == 20 && offsetof(FusedLdsArgs, per_wg) == 24 &&
+              offsetof(FusedLdsArgs, magic_wg) == 28 && offsetof(FusedLdsArgs, layers) == 32,
+              "line 0 of the fused kernel's head: ph_kernels_lds.hip reads it by offset");
+static_assert(offsetof(FusedLdsArgs, out) == 96 && offsetof(FusedLdsArgs, rd_cm) == 104 && offsetof(FusedLdsArgs, rd_gm) == 112 &&
+              offsetof(FusedLdsArgs, wr_cm) == 120, "the head's pointers end with the first 128 bytes");
+static_assert(offsetof(FusedLdsArgs, rd_k) == 128 && offsetof(FusedLdsArgs, wr_k) == 148 && offsetof(FusedLdsArgs, wr_bytes) == 168 &&
+              offsetof(FusedLdsArgs, wr_hole) == 172 && offsetof(FusedLdsArgs, wr_blob) == 176 && offsetof(FusedLdsArgs, jobs) == 184 &&
+              offsetof(FusedLdsArgs, quads_per_line_used) == 188 && offsetof(FusedLdsArgs, quads_per_line_pitch) == kFusedHeadBytes,
+              "line 2 of the fused kernel's head");
+static_assert(offsetof(FusedLdsArgs, more_layers) >= kFusedHeadBytes, "the batch arrays lie behind the head");
+// the arguments of one frame (or of job 0 and what all jobs share) from the plain kernel's and the two tables
+FusedLdsArgs fused_lds_args(const FusedArgs &f, const LutView &rd, const LutView &wr);  // ph_kernels_lds.hip
 
 // Several consumers' frames of ONE plain-layer composite in one launch (ph_fused_v210_combine_multi; ph_kernels_fused_multi.hip): the
 // headline kernel's phase 1, then the writer's phase once per distinct writer table - the quad's 18 table reads made once, every

@@ -13,6 +13,7 @@
 #include "ph_kernels.h"
 #include "ph_ldslut.h"
 
+#include <atomic>
 #include <cstdlib>
 
 #include <type_traits>
@@ -25,20 +26,34 @@
 #ifndef PH_PROBE
 #define PH_PROBE 0
 #endif
+// Stamps 0..4 are the phase boundaries; 5 = the kernel's entry (both counters are read by the kernel's first
+// instructions, before the result of any kernel-argument load is consumed, and held in SGPRs until stamp 0 is stored -
+// so stamp 0 minus stamp 5 is the scalar head in front of the first table DMA); 6 = behind the barrier that ends the
+// tile, i.e. when the slowest wave of the workgroup has stored its last quad (stamp 4 is wave 0's own last store).
 #if PH_PROBE
-__device__ unsigned long long g_fused_probe[2048 * 12];
+constexpr int kProbeWords = 16;  // per workgroup: 7 stamps of (shader cycles, 100 MHz ticks)
+__device__ unsigned long long g_fused_probe[2048 * kProbeWords];
 extern "C" int ph_debug_fused_probe(unsigned long long *out, int n_words) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fused_probe), (size_t)n_words * 8);
 }
-#define PH_STAMP(k)                                                                  \
+#define PH_STAMP_ENTRY() \
+  const unsigned long long ph_entry_cycles = __builtin_amdgcn_s_memtime(), ph_entry_ticks = __builtin_amdgcn_s_memrealtime()
+#define PH_STAMP(k) PH_STAMP_IF(k, tile_begin == wg_begin)
+#define PH_STAMP_IF(k, first_tile)                                                   \
   do {                                                                               \
-    if (threadIdx.x == 0 && tile_begin == wg_begin) {                                \
-      g_fused_probe[blockIdx.x * 12 + 2 * (k)] = __builtin_amdgcn_s_memtime();       \
-      g_fused_probe[blockIdx.x * 12 + 2 * (k) + 1] = __builtin_amdgcn_s_memrealtime(); \
+    if (threadIdx.x == 0 && (first_tile)) {                                          \
+      g_fused_probe[blockIdx.x * kProbeWords + 2 * (k)] = __builtin_amdgcn_s_memtime();       \
+      g_fused_probe[blockIdx.x * kProbeWords + 2 * (k) + 1] = __builtin_amdgcn_s_memrealtime(); \
+      if ((k) == 0) {                                                                \
+        g_fused_probe[blockIdx.x * kProbeWords + 10] = ph_entry_cycles;              \
+        g_fused_probe[blockIdx.x * kProbeWords + 11] = ph_entry_ticks;               \
+      }                                                                              \
     }                                                                                \
   } while (0)
 #else
+#define PH_STAMP_ENTRY() do { } while (0)
 #define PH_STAMP(k) do { } while (0)
+#define PH_STAMP_IF(k, first_tile) do { } while (0)
 #endif
 
 // The four waves of a SIMD are served oldest first, so left alone the oldest wave of a workgroup races through its
@@ -95,6 +110,56 @@ __device__ __forceinline__ uint4 write_quad_lds(const float (&rgb)[18], const Wr
 #ifndef PH_FUSED_SPLIT
 #define PH_FUSED_SPLIT 0
 #endif
+// The head of FusedLdsArgs (ph_kernels.h: its first kFusedHeadBytes) in scalar registers.  Left to the compiler the kernel
+// arguments arrive in five dependent batches, each behind a wait of its own - 1.0 - 1.3 us between a wave's first instruction
+// and its first table DMA (profiles/launch_head_parent.jsonl).  Here the three 64-byte lines are asked for in one go and waited
+// for once; the compiler neither sees these loads nor counts them, so the wait is part of the statement.
+typedef uint32_t fused_head_line __attribute__((ext_vector_type(16)));
+struct FusedHead {
+  fused_head_line l0, l1, l2;
+  __device__ __forceinline__ uint32_t word(int byte) const { return byte < 64 ? l0[byte / 4] : byte < 128 ? l1[byte / 4 - 16] : l2[byte / 4 - 32]; }
+  // A pointer made from two words has lost its address space, and a load through it would be a flat VECTOR load.  P names it:
+  // global for the frames and the table, constant for the colour coefficients - uniform loads from there are scalar loads, as the
+  // compiler makes them for a pointer it has seen arrive as a kernel argument.
+  template <typename P>
+  __device__ __forceinline__ P ptr(int byte) const { return (P)((uintptr_t)word(byte) | ((uintptr_t)word(byte + 4) << 32)); }
+  __device__ __forceinline__ LutK lut_k(int byte) const {
+    return LutK{__uint_as_float(word(byte)), __uint_as_float(word(byte + 4)), __uint_as_float(word(byte + 8)), __uint_as_float(word(byte + 12)), word(byte + 16)};
+  }
+};
+typedef const __attribute__((address_space(1))) ph_u4v *global_quad_ptr;
+typedef const __attribute__((address_space(1))) uint32_t *global_u32_ptr;
+typedef const __attribute__((address_space(4))) float *const_f32_ptr;
+__device__ __forceinline__ uint4 load_stream(global_quad_ptr p) {
+  const ph_u4v v = __builtin_nontemporal_load(p);
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ ReadK load_read_k(const_f32_ptr cm, const_f32_ptr gm) {  // (ph_device.h's, through constant pointers)
+  ReadK k;
+  k.r = make_float4(cm[0], cm[1], cm[2], cm[3]);
+  k.g = make_float4(cm[4], cm[5], cm[6], cm[7]);
+  k.b = make_float4(cm[8], cm[9], cm[10], cm[11]);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) k.gm[i] = gm[i];
+  return k;
+}
+__device__ __forceinline__ WriteK load_write_k(const_f32_ptr cm) {
+  WriteK k;
+  k.y = make_float4(cm[0], cm[1], cm[2], cm[3]);
+  k.u = make_float4(cm[4], cm[5], cm[6], cm[7]);
+  k.v = make_float4(cm[8], cm[9], cm[10], cm[11]);
+  return k;
+}
+static_assert(kFusedHeadBytes == 3 * sizeof(fused_head_line), "fused_head_load asks for three lines");
+__device__ __forceinline__ FusedHead fused_head_load() {
+  FusedHead h;
+  const auto *args = __builtin_amdgcn_kernarg_segment_ptr();  // FusedLdsArgs is the kernel's first argument: offset 0
+  asm volatile("s_load_dwordx16 %0, %3, 0x0\n\ts_load_dwordx16 %1, %3, 0x40\n\ts_load_dwordx16 %2, %3, 0x80\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(h.l0), "=&s"(h.l1), "=&s"(h.l2)
+               : "s"(args));
+  return h;
+}
+
 // TAIL: lines that do not end on a 48-pixel block (1280 x 720, src/config.ts:43-54).  The flat index then runs over the quad SLOTS
 // of the pitch - the layers' words and the output's are at the same offsets - and a lane's slot is a whole quad, the line's tail
 // quad (its 2 or 4 pixels read without the matrix's offset column, v210.ts:88-93, written from truncated indices with round(),
@@ -102,40 +167,66 @@ __device__ __forceinline__ uint4 write_quad_lds(const float (&rgb)[18], const Wr
 template <int N, int P, int BS, bool PIPE = false, int MODE = 0, bool TAIL = false>
 __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs a, uint32_t *handoff = nullptr) {
   static_assert(!TAIL || (!PIPE && MODE == 0), "the tail instantiation exists for the shipped form only");
-  const ReadK rk = load_read_k(a.f.rd_cm, a.f.rd_gm);
-  const WriteK wk = load_write_k(a.f.wr_cm);
-  const LutK rlut = make_lut_k(a.rd), wlut = make_lut_k(a.wr);
-  const bool std_matrix = ycbcr_matrix_is_standard(rk);  // uniform
+  PH_STAMP_ENTRY();
+  // The head, ordered by hand: one request and one wait for everything in front of the first vector memory instruction; then the
+  // first input word and the reader table's DMA; the colour coefficients are asked for behind them and arrive under the DMA.
+  const FusedHead head = fused_head_load();
+  const uint32_t total_quads = head.word(offsetof(FusedLdsArgs, total_quads)), wg_per_job = head.word(offsetof(FusedLdsArgs, wg_per_job));
+  const uint32_t per_wg = head.word(offsetof(FusedLdsArgs, per_wg));
   // Every workgroup owns one contiguous, equally sized range of quads (all CUs finish together)
   // and walks it in tiles of BS*P quads; only the last tile of a range is partially filled.
   // Batched launches give every job its own group of workgroups (uniform per workgroup, so the layer
   // pointers stay scalar loads from the kernel arguments).
-  const uint32_t job = blockIdx.x / a.wg_per_job, wg_in_job = blockIdx.x - job * a.wg_per_job;
-  auto layer_ptr = [&](int l) { return reinterpret_cast<const uint4 *>(job ? a.more_layers[job - 1][l] : a.f.layers[l]); };
-  uint4 *const out_ptr = reinterpret_cast<uint4 *>(job ? a.more_out[job - 1] : a.f.out);
-  const uint32_t per_wg = (a.f.total_quads + a.wg_per_job - 1) / a.wg_per_job;
+  uint32_t job = fused_job_of(blockIdx.x, head.word(offsetof(FusedLdsArgs, magic_wg)));
+  asm("" : "+s"(job));  // (or `job != 0` becomes a 64-bit vector compare of the whole product)
+  const uint32_t wg_in_job = blockIdx.x - job * wg_per_job;
+  auto layer_ptr = [&](int l) { return reinterpret_cast<const uint4 *>(job ? a.more_layers[job - 1][l] : a.layers[l]); };
   const uint32_t wg_begin = wg_in_job * per_wg;
-  const uint32_t wg_end = wg_begin + per_wg < a.f.total_quads ? wg_begin + per_wg : a.f.total_quads;
+  const uint32_t wg_end = wg_begin + per_wg < total_quads ? wg_begin + per_wg : total_quads;
+  if (wg_begin >= wg_end) return;  // (uniform per workgroup)
   const uint32_t tile_quads = BS * P;
+  // Input words are streamed with a one-deep prefetch that runs THROUGH the slices: while layer l
+  // of slice p is being decoded the next word (layer l+1, or layer 0 of slice p+1) is in flight -
+  // 8 VGPRs of input instead of 4*N*P, and no slice starts by waiting for HBM.  The very first word
+  // is requested before the table load so its latency hides behind the DMA.
+  auto quad_at = [&](uint32_t tile_begin, int p) {
+    const uint32_t f = tile_begin + p * BS + threadIdx.x;  // width % 48 == 0: flat index == offset
+    return f < wg_end ? f : wg_end - 1;                     // tail lanes recompute the last quad
+  };
+  // (job 0's first layer is in the head; a later job's comes from the batch arrays: one more scalar load)
+  uint4 w;
+  if (job) w = load_stream(layer_ptr(0) + quad_at(wg_begin, 0));
+  else w = load_stream(head.ptr<global_quad_ptr>(offsetof(FusedLdsArgs, layers)) + quad_at(wg_begin, 0));
+  const uint32_t *const rd_blob = (const uint32_t *)head.ptr<global_u32_ptr>(offsetof(FusedLdsArgs, rd_blob));
+  const uint32_t rd_bytes = head.word(offsetof(FusedLdsArgs, rd_bytes)), rd_hole = head.word(offsetof(FusedLdsArgs, rd_hole));
+  PH_STAMP_IF(0, true);
+  if (MODE != 2) lds_lut_load<BS, false>(rd_blob, rd_bytes, rd_hole);
+  __builtin_amdgcn_sched_barrier(0);  // what follows is asked for behind the DMA, not in front of it
+  const ReadK rk = load_read_k(head.ptr<const_f32_ptr>(offsetof(FusedLdsArgs, rd_cm)), head.ptr<const_f32_ptr>(offsetof(FusedLdsArgs, rd_gm)));
+  const WriteK wk = load_write_k(head.ptr<const_f32_ptr>(offsetof(FusedLdsArgs, wr_cm)));
+  LutK rlut = head.lut_k(offsetof(FusedLdsArgs, rd_k)), wlut = head.lut_k(offsetof(FusedLdsArgs, wr_k));
+  // The two fma of a lookup take a scale and a base.  An instruction reads one scalar register, so with both in SGPRs the base is
+  // copied to a VGPR inside the layer loop; the bases live in VGPRs from here on, where make_lut_k's arithmetic used to leave them.
+  asm("" : "+v"(rlut.a_base), "+v"(rlut.delta_base), "+v"(wlut.a_base), "+v"(wlut.delta_base));
+  const uint32_t *const wr_blob = (const uint32_t *)head.ptr<global_u32_ptr>(offsetof(FusedLdsArgs, wr_blob));
+  const uint32_t wr_bytes = head.word(offsetof(FusedLdsArgs, wr_bytes)), wr_hole = head.word(offsetof(FusedLdsArgs, wr_hole));
+  uint4 *const out_ptr = reinterpret_cast<uint4 *>(job ? a.more_out[job - 1] : a.out);
+  const bool std_matrix = ycbcr_matrix_is_standard(rk);  // uniform
   for (uint32_t tile_begin = wg_begin; tile_begin < wg_end; tile_begin += tile_quads) {
     uint32_t st[P][9];
-    // Input words are streamed with a one-deep prefetch that runs THROUGH the slices: while layer l
-    // of slice p is being decoded the next word (layer l+1, or layer 0 of slice p+1) is in flight -
-    // 8 VGPRs of input instead of 4*N*P, and no slice starts by waiting for HBM.  The very first word
-    // is requested before the table load so its latency hides behind the DMA.
-    auto quad_of = [&](int p) {
-      const uint32_t f = tile_begin + p * BS + threadIdx.x;  // width % 48 == 0: flat index == offset
-      return f < wg_end ? f : wg_end - 1;                     // tail lanes recompute the last quad
-    };
-    uint4 w = load_stream(layer_ptr(0) + quad_of(0));
+    auto quad_of = [&](int p) { return quad_at(tile_begin, p); };
+    if (tile_begin != wg_begin) {  // (the first tile's word and table are on their way)
+      w = load_stream(layer_ptr(0) + quad_of(0));
+      if (MODE == 0) lds_lut_load<BS, false>(rd_blob, rd_bytes, rd_hole);
+    }
     // Phase 1 of one slice: N layers of one quad per lane -> combine -> the 18 writer-LUT indices,
     // packed.  Takes the slice's layer-0 word and returns the next slice's (prefetch chain).  A
     // generic lambda instantiated for both matrix shapes; everything it touches stays in registers
     // (a by-reference `w` or argument struct ends up in scratch).
     // slot f of a TAIL frame: 0 = a whole quad, 1 = the line's tail quad, 2 = past the line's pixels
     auto slot_kind = [&](uint32_t f) -> uint32_t {
-      const uint32_t g = f - __umulhi(f, a.f.magic_qpp) * a.f.quads_per_line_pitch;
-      return g < a.f.quads_per_line_used ? 0u : (g == a.f.quads_per_line_used && a.f.tail_px) ? 1u : 2u;
+      const uint32_t g = f - __umulhi(f, a.magic_qpp) * a.quads_per_line_pitch;
+      return g < a.quads_per_line_used ? 0u : (g == a.quads_per_line_used && a.tail_px) ? 1u : 2u;
     };
     auto phase1_slice = [&](auto tag, uint4 w, uint32_t f, uint32_t f_next, bool more, uint32_t(&st)[9]) -> uint4 {
       const bool in_tail = TAIL && slot_kind(f) == 1u;
@@ -178,9 +269,8 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
       }
       return w;
     };
-    PH_STAMP(0);
     if (MODE == 0 || (MODE == 1 && tile_begin == wg_begin)) {  // a half keeps its one table over all its tiles
-      lds_lut_load<BS>(a.rd);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
     }
     PH_STAMP(1);
@@ -260,7 +350,7 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
       else phase1_all(std::false_type{});
       PH_STAMP(2);
       __syncthreads();
-      lds_lut_load<BS>(a.wr);
+      lds_lut_load<BS>(wr_blob, wr_bytes, wr_hole);
       __syncthreads();
       PH_STAMP(3);
       // phase 2, pipelined the same way: indices -> writer table -> matrix -> codes -> packed words
@@ -320,7 +410,7 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
         if (p * BS + wave_first < wg_end - tile_begin) {
           const uint32_t f = quad_of(p);
 #pragma unroll
-          for (int i = 0; i < 9; ++i) handoff[(size_t)i * a.f.total_quads + f] = st[p][i];
+          for (int i = 0; i < 9; ++i) handoff[(size_t)i * a.total_quads + f] = st[p][i];
         }
       continue;
     }
@@ -330,13 +420,13 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
         if (p * BS + wave_first < wg_end - tile_begin) {
           const uint32_t f = quad_of(p);
 #pragma unroll
-          for (int i = 0; i < 9; ++i) st[p][i] = __builtin_nontemporal_load(handoff + (size_t)i * a.f.total_quads + f);
+          for (int i = 0; i < 9; ++i) st[p][i] = __builtin_nontemporal_load(handoff + (size_t)i * a.total_quads + f);
         }
     }
     PH_STAMP(2);
     if (MODE == 0 || tile_begin == wg_begin) {
       __syncthreads();
-      lds_lut_load<BS>(a.wr);
+      lds_lut_load<BS>(wr_blob, wr_bytes, wr_hole);
       __syncthreads();
     }
     PH_STAMP(3);
@@ -355,7 +445,7 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
         if (TAIL) {
           const uint32_t kind = slot_kind(f < wg_end ? f : wg_end - 1);
           if (kind == 0u) packed = write_quad_idx_lds(yi, wk, wlut);
-          else if (kind == 1u) packed = write_quad_idx_lds_tail(yi, wk, wlut, a.f.tail_px);
+          else if (kind == 1u) packed = write_quad_idx_lds_tail(yi, wk, wlut, a.tail_px);
           else packed = make_uint4(0u, 0u, 0u, 0u);
         } else {
           packed = write_quad_idx_lds(yi, wk, wlut);
@@ -365,7 +455,10 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
     }
     }
     PH_STAMP(4);
-    __syncthreads();
+    // The barrier orders the NEXT tile's reader-table DMA behind this tile's last writer-table read, and nothing else: behind the
+    // last tile of the range (the only one of a 2160p share) a wave that has stored its quads ends without waiting for the slowest.
+    if (PIPE || MODE != 0 || tile_begin + tile_quads < wg_end) __syncthreads();
+    PH_STAMP(6);
   }
 }
 
@@ -935,18 +1028,61 @@ template <typename K>
 static hipError_t allow_lds(K kernel, uint32_t bytes) {
   return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
 }
+// The same once per kernel and device, not per launch (the attribute is per-function state and always kMaxDynamicLds): `done` is
+// the caller's static flag word for this instantiation, one bit per device.
+template <typename K>
+static hipError_t allow_lds_once(K kernel, std::atomic<uint64_t> &done) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const uint64_t bit = 1ull << (dev & 63);
+  if (dev < 64 && (done.load(std::memory_order_acquire) & bit)) return hipSuccess;
+  e = allow_lds(kernel, kMaxDynamicLds);
+  if (e == hipSuccess && dev < 64) done.fetch_or(bit, std::memory_order_release);
+  return e;
+}
+
+// make_lut_k of ph_ldslut.h on the host: the same float operations in the same order (the kernels' g_lds is at LDS address 0).
+// The sums are denormals, so a thread that runs with flush-to-zero set computes them with it cleared.
+FusedLutK fused_lut_k(const LutView &v) {
+#if defined(__x86_64__)
+  const unsigned csr = __builtin_ia32_stmxcsr();
+  __builtin_ia32_ldmxcsr(csr & ~0x8040u);  // FTZ, DAZ
+#endif
+  const volatile float lds0 = 0.0f, magic = 12582912.0f;  // kRoundMagic; volatile: no operation is folded or reassociated
+  const float small = (v.delta_base + lds0) + v.bias * v.delta_scale;
+  const float b = small - magic * v.delta_scale;
+  const FusedLutK k{v.a_scale, -((magic - v.bias) * v.a_scale), v.delta_scale, b, v.shift - 2u};
+#if defined(__x86_64__)
+  __builtin_ia32_ldmxcsr(csr);
+#endif
+  return k;
+}
+
+FusedLdsArgs fused_lds_args(const FusedArgs &f, const LutView &rd, const LutView &wr) {
+  FusedLdsArgs a{};
+  a.rd_blob = rd.blob, a.rd_bytes = rd.bytes, a.rd_hole = rd.hole;
+  a.wr_blob = wr.blob, a.wr_bytes = wr.bytes, a.wr_hole = wr.hole;
+  a.rd_k = fused_lut_k(rd), a.wr_k = fused_lut_k(wr);
+  for (int l = 0; l < kMaxLayers; ++l) a.layers[l] = f.layers[l];
+  a.out = f.out, a.rd_cm = f.rd_cm, a.rd_gm = f.rd_gm, a.wr_cm = f.wr_cm;
+  a.total_quads = f.total_quads, a.quads_per_line_used = f.quads_per_line_used, a.quads_per_line_pitch = f.quads_per_line_pitch;
+  a.tail_px = f.tail_px, a.magic_qpp = f.magic_qpp, a.jobs = 1;
+  return a;
+}
 
 #if PH_FUSED_SPLIT
 template <int N, int P, int BS, int MODE>
 static hipError_t launch_fused_half(hipStream_t s, FusedLdsArgs b, uint32_t lds) {
   static uint32_t *handoff = nullptr;
   static size_t handoff_quads = 0;
-  if (handoff_quads < b.f.total_quads) {
+  if (handoff_quads < b.total_quads) {
     if (handoff) hipFree(handoff);
-    if (hipMalloc(&handoff, (size_t)b.f.total_quads * 36) != hipSuccess) return hipErrorOutOfMemory;
-    handoff_quads = b.f.total_quads;
+    if (hipMalloc(&handoff, (size_t)b.total_quads * 36) != hipSuccess) return hipErrorOutOfMemory;
+    handoff_quads = b.total_quads;
   }
-  hipError_t e = allow_lds(fused_v210_combine_lds_kernel<N, P, BS, false, MODE>, lds);
+  static std::atomic<uint64_t> lds_allowed{0};
+  hipError_t e = allow_lds_once(fused_v210_combine_lds_kernel<N, P, BS, false, MODE>, lds_allowed);
   if (e != hipSuccess) return e;
   fused_v210_combine_lds_kernel<N, P, BS, false, MODE><<<b.wg_per_job * b.jobs, BS, lds, s>>>(b, handoff);
   return hipGetLastError();
@@ -963,13 +1099,17 @@ static hipError_t launch_fused_npb(hipStream_t s, const FusedLdsArgs &a, uint32_
   }();
   if (cus_env > 0 && (uint32_t)cus_env < grid) grid = (uint32_t)cus_env;
 #endif
-  hipError_t e = allow_lds(fused_v210_combine_lds_kernel<N, P, BS, PIPE, 0, TAIL>, lds);
+  static std::atomic<uint64_t> lds_allowed{0};
+  hipError_t e = allow_lds_once(fused_v210_combine_lds_kernel<N, P, BS, PIPE, 0, TAIL>, lds_allowed);
   if (e != hipSuccess) return e;
-  const uint32_t slices = (a.f.total_quads + BS - 1) / BS;  // never more workgroups per job than slices
+  const uint32_t slices = (a.total_quads + BS - 1) / BS;  // never more workgroups per job than slices
   FusedLdsArgs b = a;
   if (b.jobs < 1) b.jobs = 1;
   b.wg_per_job = grid / b.jobs ? grid / b.jobs : 1;
   if (b.wg_per_job > slices) b.wg_per_job = slices;
+  // what every workgroup of the launch would otherwise derive for itself: its share, and the reciprocal of the job division
+  b.per_wg = (b.total_quads + b.wg_per_job - 1) / b.wg_per_job;
+  b.magic_wg = fused_wg_magic(b.wg_per_job);
 #if PH_FUSED_SPLIT
   if (!PIPE && N == 4) {
     static const int mode_env = [] {
@@ -998,7 +1138,7 @@ static hipError_t launch_fused_n(hipStream_t s, const FusedLdsArgs &a, uint32_t 
     const char *e = getenv("PH_FUSED_GEOM");
     return e ? atoi(e) : 0;
   }();
-  if (a.f.quads_per_line_used != a.f.quads_per_line_pitch) return launch_fused_npb<N, 6, 1024, false, true>(s, a, grid, lds);  // ragged lines
+  if (a.quads_per_line_used != a.quads_per_line_pitch) return launch_fused_npb<N, 6, 1024, false, true>(s, a, grid, lds);  // ragged lines
   int geom = geom_env ? geom_env : 6;
   static const int pipe_env = [] {
     const char *e = getenv("PH_FUSED_PIPE");  // 1 = the software-pipelined phases (measured 3 % SLOWER: DESIGN.md 4)
@@ -1019,7 +1159,7 @@ static hipError_t launch_fused_n(hipStream_t s, const FusedLdsArgs &a, uint32_t 
 }
 
 hipError_t launch_fused_v210_combine_lds(hipStream_t s, int n, const FusedLdsArgs &a, uint32_t num_cus) {
-  const uint32_t lds = a.rd.bytes > a.wr.bytes ? a.rd.bytes : a.wr.bytes;
+  const uint32_t lds = a.rd_bytes > a.wr_bytes ? a.rd_bytes : a.wr_bytes;
   switch (n) {
     case 1: return launch_fused_n<1>(s, a, num_cus, lds);
     case 2: return launch_fused_n<2>(s, a, num_cus, lds);

@@ -22,17 +22,18 @@ extern __shared__ __attribute__((aligned(16))) unsigned char g_lds[];
 
 // all lanes of the workgroup copy the table blob global -> LDS (16 bytes per lane per step)
 // WAIT = false: the caller waits (s_waitcnt vmcnt(0)) and synchronises itself, having done something else meanwhile
+// (the three fields of the LutView it needs, for a caller that holds them in registers already: the fused kernel's head)
 template <int BS = kLdsBlock, bool WAIT = true>
-__device__ __forceinline__ void lds_lut_load(const LutView &v) {
+__device__ __forceinline__ void lds_lut_load(const uint32_t *blob, uint32_t bytes, uint32_t hole) {
 #if PH_ABLATE & 2  // timing experiment only: no table loads
   return;
 #endif
-  const uint32_t n = (v.bytes - v.hole) / 16;
-  unsigned char *const dst = g_lds + v.hole;
+  const uint32_t n = (bytes - hole) / 16;
+  unsigned char *const dst = g_lds + hole;
   // LDS-DMA: each wave instruction moves 1 KiB global -> LDS (wave-uniform LDS base + lane*16)
   // without touching VGPRs; all of a wave's pieces are in flight before the single wait.
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint4 *src = reinterpret_cast<const uint4 *>(v.blob);
+  const uint4 *src = reinterpret_cast<const uint4 *>(blob);
   for (uint32_t base = wave * 64; base < n; base += BS) {
     const uint32_t i = base + lane;
     if (i < n)
@@ -40,6 +41,10 @@ __device__ __forceinline__ void lds_lut_load(const LutView &v) {
                                        (__attribute__((address_space(3))) void *)(dst + 16 * base), 16, 0, 0);
   }
   if (WAIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+template <int BS = kLdsBlock, bool WAIT = true>
+__device__ __forceinline__ void lds_lut_load(const LutView &v) {
+  lds_lut_load<BS, WAIT>(v.blob, v.bytes, v.hole);
 }
 
 // table[clamp(rint(x), 0, 65535)] for x = (gamma- or linear-domain value) * 65535, see ph_lut.h:
