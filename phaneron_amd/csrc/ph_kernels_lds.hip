@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include <type_traits>
+#include <utility>
 
 #pragma clang fp contract(off)
 
@@ -118,6 +119,11 @@ typedef uint32_t fused_head_line __attribute__((ext_vector_type(16)));
 struct FusedHead {
   fused_head_line l0, l1, l2;
   __device__ __forceinline__ uint32_t word(int byte) const { return byte < 64 ? l0[byte / 4] : byte < 128 ? l1[byte / 4 - 16] : l2[byte / 4 - 32]; }
+  __device__ __forceinline__ void set_word(int byte, uint32_t v) {
+    if (byte < 64) l0[byte / 4] = v;
+    else if (byte < 128) l1[byte / 4 - 16] = v;
+    else l2[byte / 4 - 32] = v;
+  }
   // A pointer made from two words has lost its address space, and a load through it would be a flat VECTOR load.  P names it:
   // global for the frames and the table, constant for the colour coefficients - uniform loads from there are scalar loads, as the
   // compiler makes them for a pointer it has seen arrive as a kernel argument.
@@ -160,6 +166,68 @@ __device__ __forceinline__ FusedHead fused_head_load() {
   return h;
 }
 
+// One layer of one quad in phase 1 of the shipped fused kernel: decode the word, reader table, gamut, and the combine into the
+// quad's eighteen accumulators (combine.ts:45-65).  The layer's place in the stack is a compile-time property, so that neither
+// end of the stack pays for what only the middle needs:
+//  - the FIRST layer has nothing below it: acc = t, no zero to start from and no fma.  That is fma(0, kk, t) for every t, Inf
+//    and NaN included, except that t = -0 stays -0 where the fma gives +0 - and the sign of a zero can never reach the packed
+//    output: the clamp and x 65535 + M behind the last layer map both zeros to index 0;
+//  - a MIDDLE layer is acc = fma(acc, kk, t), written as the three-operand v_fma_f32 with acc as destination.  Left to itself
+//    LLVM picks v_fmac (d = a*b + d, so the result lands in t's register) and pays for it with a v_mov per accumulator per
+//    layer to get the loop-carried value back;
+//  - the LAST layer is the same instruction with the clamp modifier: the writer's clamp to [0, 1] (v210.ts:148-150) rides on
+//    it for nothing, where a v_max_f32 ... clamp per accumulator used to follow the loop.  Only here: on a lower layer the
+//    clamp would turn an Inf or NaN of the stack below into a number, and the layers above would hide that it was ever there.
+// A one-layer stack is first and last at once: its clamp goes on the value itself.
+constexpr int kLayerFirst = 1, kLayerLast = 2;
+// f(0) ... f(COUNT - 1) with the index a compile-time constant: straight-line code whatever its size
+template <int... I, typename F>
+__device__ __forceinline__ void static_for_each(std::integer_sequence<int, I...>, F &&f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int COUNT, typename F>
+__device__ __forceinline__ void static_for(F &&f) {
+  static_for_each(std::make_integer_sequence<int, COUNT>{}, f);
+}
+template <int PLACE, bool STD>
+__device__ __forceinline__ void fused_layer_combine(float (&acc)[18], const uint4 w, const ReadK &rk, const LutK &rlut, float last) {
+  // A layer is scheduled on its own, as an iteration of the rolled loop was: nothing of the next layer's decode moves up into
+  // this one's.  Within the layer the asm statements (the first layer has an empty one per pixel) keep the pixels in order;
+  // without that order the eighteen lookups of a quad are all started at once and a lane runs out of registers (spills).
+  __builtin_amdgcn_sched_barrier(0);
+  const Yuv6 q = unpack_quad(w);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const float4 t = read_px_lds<STD>(q.y[j], q.cb[j >> 1], q.cr[j >> 1], rk, rlut, last);
+    if (PLACE & kLayerFirst) {
+      acc[3 * j] = t.x, acc[3 * j + 1] = t.y, acc[3 * j + 2] = t.z;
+      if (PLACE & kLayerLast) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[3 * j + c] = __builtin_fminf(__builtin_fmaxf(acc[3 * j + c], 0.0f), 1.0f);
+      }
+      // (no instruction: the place in the pixel order that the combine's asm statement holds in the other layers)
+      asm volatile("" : "+v"(acc[3 * j]), "+v"(acc[3 * j + 1]), "+v"(acc[3 * j + 2]));
+    } else {
+      const float kk = 1.0f - t.w;
+      if (PLACE & kLayerLast)
+        asm volatile("v_fma_f32 %0, %0, %3, %4 clamp\n\tv_fma_f32 %1, %1, %3, %5 clamp\n\tv_fma_f32 %2, %2, %3, %6 clamp"
+                     : "+v"(acc[3 * j]), "+v"(acc[3 * j + 1]), "+v"(acc[3 * j + 2])
+                     : "v"(kk), "v"(t.x), "v"(t.y), "v"(t.z));
+      else
+        asm volatile("v_fma_f32 %0, %0, %3, %4\n\tv_fma_f32 %1, %1, %3, %5\n\tv_fma_f32 %2, %2, %3, %6"
+                     : "+v"(acc[3 * j]), "+v"(acc[3 * j + 1]), "+v"(acc[3 * j + 2])
+                     : "v"(kk), "v"(t.x), "v"(t.y), "v"(t.z));
+    }
+  }
+}
+// The writer's first step behind a stack whose last layer has clamped (v210.ts:148-150 index = sat_rte(rgb * 65535)): what
+// lds_lut_index_unit / lds_lut_index_unit_tail (ph_ldslut.h) do behind their own clamp.
+__device__ __forceinline__ float lds_lut_index_clamped(float t) { return t * 65535.0f + kRoundMagic; }
+__device__ __forceinline__ float lds_lut_index_clamped_tail(float t, bool trunc) {
+  const float x = t * 65535.0f;
+  return (trunc ? __builtin_floorf(x) : x) + kRoundMagic;
+}
+
 // TAIL: lines that do not end on a 48-pixel block (1280 x 720, src/config.ts:43-54).  The flat index then runs over the quad SLOTS
 // of the pitch - the layers' words and the output's are at the same offsets - and a lane's slot is a whole quad, the line's tail
 // quad (its 2 or 4 pixels read without the matrix's offset column, v210.ts:88-93, written from truncated indices with round(),
@@ -170,7 +238,7 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
   PH_STAMP_ENTRY();
   // The head, ordered by hand: one request and one wait for everything in front of the first vector memory instruction; then the
   // first input word and the reader table's DMA; the colour coefficients are asked for behind them and arrive under the DMA.
-  const FusedHead head = fused_head_load();
+  FusedHead head = fused_head_load();
   const uint32_t total_quads = head.word(offsetof(FusedLdsArgs, total_quads)), wg_per_job = head.word(offsetof(FusedLdsArgs, wg_per_job));
   const uint32_t per_wg = head.word(offsetof(FusedLdsArgs, per_wg));
   // Every workgroup owns one contiguous, equally sized range of quads (all CUs finish together)
@@ -194,8 +262,43 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
     return f < wg_end ? f : wg_end - 1;                     // tail lanes recompute the last quad
   };
   // (job 0's first layer is in the head; a later job's comes from the batch arrays: one more scalar load)
+  // The shipped form never asks for a layer pointer again: job 0's N pointers are in the head, and a later job of a batch puts
+  // its own in their place here, once per workgroup - no scalar load and no wait for one inside a slice.  A word's address is
+  // that scalar base plus a 32-bit byte offset per lane (16 * quad: launch_fused_v210_combine_lds refuses frames of 4 GiB), the
+  // same for all N layers of a slice.
+  constexpr bool kSplitLayers = !PIPE && MODE == 0;
+  // (every index into the head below is a literal, so each word is a register by name from the first compiler pass on)
+  if (kSplitLayers && job) {
+    auto own_layer = [&](int l) {
+      const uintptr_t p = (uintptr_t)a.more_layers[job - 1][l];
+      head.set_word(offsetof(FusedLdsArgs, layers) + 8 * l, (uint32_t)p);
+      head.set_word(offsetof(FusedLdsArgs, layers) + 8 * l + 4, (uint32_t)(p >> 32));
+    };
+    own_layer(0);
+    if (N > 1) own_layer(1);
+    if (N > 2) own_layer(2);
+    if (N > 3) own_layer(3);
+    if (N > 4) own_layer(4);
+    if (N > 5) own_layer(5);
+    if (N > 6) own_layer(6);
+    if (N > 7) own_layer(7);
+  }
+  static_assert(N <= 8, "the layers' pointers are named one by one");
+  typedef const __attribute__((address_space(1))) char *global_byte_ptr;
+  auto layer_base = [&](int l) { return (global_byte_ptr)head.ptr<global_quad_ptr>(offsetof(FusedLdsArgs, layers) + 8 * l); };
+  auto layer_word = [&](int l, uint32_t at) { return load_stream((global_quad_ptr)(layer_base(l) + at)); };  // l: a literal, at: bytes
+  auto layer_word_any = [&](int l, uint32_t at) {  // l in 2 .. N-1, uniform: the base picked by scalar selects
+    global_byte_ptr base = layer_base(N - 1);
+    if (N > 3 && l == 2) base = layer_base(2);
+    if (N > 4 && l == 3) base = layer_base(3);
+    if (N > 5 && l == 4) base = layer_base(4);
+    if (N > 6 && l == 5) base = layer_base(5);
+    if (N > 7 && l == 6) base = layer_base(6);
+    return load_stream((global_quad_ptr)(base + at));
+  };
   uint4 w;
-  if (job) w = load_stream(layer_ptr(0) + quad_at(wg_begin, 0));
+  if (kSplitLayers) w = layer_word(0, quad_at(wg_begin, 0) << 4);
+  else if (job) w = load_stream(layer_ptr(0) + quad_at(wg_begin, 0));
   else w = load_stream(head.ptr<global_quad_ptr>(offsetof(FusedLdsArgs, layers)) + quad_at(wg_begin, 0));
   const uint32_t *const rd_blob = (const uint32_t *)head.ptr<global_u32_ptr>(offsetof(FusedLdsArgs, rd_blob));
   const uint32_t rd_bytes = head.word(offsetof(FusedLdsArgs, rd_bytes)), rd_hole = head.word(offsetof(FusedLdsArgs, rd_hole));
@@ -216,7 +319,7 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
     uint32_t st[P][9];
     auto quad_of = [&](int p) { return quad_at(tile_begin, p); };
     if (tile_begin != wg_begin) {  // (the first tile's word and table are on their way)
-      w = load_stream(layer_ptr(0) + quad_of(0));
+      w = kSplitLayers ? layer_word(0, quad_of(0) << 4) : load_stream(layer_ptr(0) + quad_of(0));
       if (MODE == 0) lds_lut_load<BS, false>(rd_blob, rd_bytes, rd_hole);
     }
     // Phase 1 of one slice: N layers of one quad per lane -> combine -> the 18 writer-LUT indices,
@@ -266,6 +369,76 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
         // arithmetic to its first use in phase 2 (past the barrier and the table swap) and keeps
         // the raw LDS words of every lookup alive instead: hundreds of spilled VGPRs.
         asm volatile("" : "+v"(st[i]));
+      }
+      return w;
+    };
+    // The same slice in the shipped form (PIPE off, MODE 0), with the layer loop split by a layer's place in the stack
+    // (fused_layer_combine): first, middle, last.  The prefetch chain is the one above - while a layer is decoded the word
+    // behind it is in flight - but the words are named, not copied: straight-line code for up to two middle layers, and a loop
+    // of PAIRS beyond that (N > 4) in which the two word registers take turns, so no `w = nxt` is left in it.  One copy
+    // remains per slice: the `nxt = w` in front of the last layer, for a wave's last slice, where nothing is prefetched (four
+    // v_mov_b32, which the compiler puts in front of the branch on `more`, not behind it).
+    // (inlined by order: as a call of its own it gets `st` by address, and the packed state of the whole tile lives in scratch)
+    auto phase1_slice_split = [&](auto tag, uint4 w, uint32_t f, uint32_t f_next, bool more, uint32_t(&st)[9]) __attribute__((always_inline)) -> uint4 {
+      constexpr int MID = N > 2 ? N - 2 : 0;  // layers 1 .. N-2
+      const bool in_tail = TAIL && slot_kind(f) == 1u;
+      const float last = TAIL ? (in_tail ? 0.0f : 1.0f) : 1.0f;
+      float acc[18];
+      constexpr bool STD = decltype(tag)::value;
+      auto combine = [&](auto place, const uint4 word) __attribute__((always_inline)) {
+        fused_layer_combine<decltype(place)::value, STD>(acc, word, rk, rlut, last);
+      };
+      constexpr std::integral_constant<int, N == 1 ? (kLayerFirst | kLayerLast) : kLayerFirst> first_layer{};
+      constexpr std::integral_constant<int, 0> middle_layer{};
+      constexpr std::integral_constant<int, kLayerLast> last_layer{};
+      // A quad's byte offset, the same in all N layers.  The statement is no instruction; its text differs between the two
+      // matrix shapes so that their address arithmetic is not one expression, which the compiler would hoist in front of the
+      // branch between them - and a load whose address was formed in another block gets it as a 64-bit sum, not as base + offset.
+      uint32_t at = f << 4;
+      if (STD) asm volatile("; standard matrix" : "+v"(at));
+      else asm volatile("; any matrix" : "+v"(at));
+      uint4 nxt = w;
+      if (N > 1) nxt = layer_word(1, at);
+      else if (more) nxt = layer_word(0, f_next << 4);
+      combine(first_layer, w);
+      w = nxt;
+      if constexpr (MID > 0 && MID <= 2) {
+        nxt = layer_word(2, at);
+        combine(middle_layer, w);
+        w = nxt;
+        if constexpr (MID == 2) {
+          nxt = layer_word(3, at);
+          combine(middle_layer, w);
+          w = nxt;
+        }
+      } else if constexpr (MID > 2) {
+#pragma unroll 1  // rolled: two copies of the per-layer code whatever N is (I-cache, compile time)
+        for (int l = 1; l + 1 <= MID; l += 2) {  // w holds layer l; l + 2 <= N - 1
+          const uint4 w2 = layer_word_any(l + 1, at);
+          combine(middle_layer, w);
+          w = layer_word_any(l + 2, at);
+          combine(middle_layer, w2);
+        }
+        if (MID & 1) {  // the odd one: layer N-2
+          nxt = layer_word(N - 1, at);
+          combine(middle_layer, w);
+          w = nxt;
+        }
+      }
+      if constexpr (N > 1) {
+        nxt = w;
+        if (more) nxt = layer_word(0, f_next << 4);
+        combine(last_layer, w);
+        w = nxt;
+      }
+      // the writer's first step needs no table: do it here and keep only the 16-bit indices, two per register (v_perm_b32).
+      // The last layer has clamped, so v_mul, v_add, v_perm is all that is left of it
+#pragma unroll
+      for (int i = 0; i < 9; ++i) {
+        const uint32_t lo = __float_as_uint(TAIL ? lds_lut_index_clamped_tail(acc[2 * i], in_tail) : lds_lut_index_clamped(acc[2 * i]));
+        const uint32_t hi = __float_as_uint(TAIL ? lds_lut_index_clamped_tail(acc[2 * i + 1], in_tail) : lds_lut_index_clamped(acc[2 * i + 1]));
+        st[i] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+        asm volatile("" : "+v"(st[i]));  // pinned, as above
       }
       return w;
     };
@@ -391,7 +564,21 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
     // at 1080p, 1350 quads per CU, ten of thirty-two)
     const uint32_t wave_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
     // (a wave's priority by the slices it has LEFT, so that the waves with one slice more run one slice ahead, measured slower: 49.4 against 48.8 us)
-    if (MODE != 2) {
+    if constexpr (kSplitLayers) {
+      // The slices are written out one by one, not unrolled from a loop: with three or four copies of the layer code per slice
+      // and matrix shape the loop is more than `#pragma unroll` unrolls in full, and `st` indexed by a live p lives in scratch.
+      static_for<P>([&](auto slice) __attribute__((always_inline)) {
+        constexpr int p = decltype(slice)::value;
+        const uint32_t f = quad_of(p);
+        if (p * BS + wave_first < wg_end - tile_begin) {  // uniform per WAVE: skip the slices in which this wave holds no quad
+          PH_BALANCE(p);
+          const bool more = (p + 1 < P) && ((p + 1) * BS + wave_first < wg_end - tile_begin);  // uniform per wave
+          const uint32_t f_next = more ? quad_of(p + 1) : f;
+          if (std_matrix) w = phase1_slice_split(std::true_type{}, w, f, f_next, more, st[p]);
+          else w = phase1_slice_split(std::false_type{}, w, f, f_next, more, st[p]);
+        }
+      });
+    } else if (MODE != 2) {
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       const uint32_t f = quad_of(p);
@@ -1160,6 +1347,7 @@ static hipError_t launch_fused_n(hipStream_t s, const FusedLdsArgs &a, uint32_t 
 
 hipError_t launch_fused_v210_combine_lds(hipStream_t s, int n, const FusedLdsArgs &a, uint32_t num_cus) {
   const uint32_t lds = a.rd_bytes > a.wr_bytes ? a.rd_bytes : a.wr_bytes;
+  if (a.total_quads > (1u << 28)) return hipErrorInvalidValue;  // the kernel's byte offsets into a layer are 32 bits wide
   switch (n) {
     case 1: return launch_fused_n<1>(s, a, num_cus, lds);
     case 2: return launch_fused_n<2>(s, a, num_cus, lds);
