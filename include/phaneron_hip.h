@@ -48,7 +48,8 @@ extern "C" {
  *    plain-layer composite (ph_fused_v210_combine's chain) for up to four consumers in one launch; program
  *    "fused_v210_combine_multi_<n>"; context option "fused_multi_wgs".  ph_fused_v210_combine_multi_batch: several channels' such frames in one
  *    launch; context option "fused_multi_batch".  ph_compose_up_transition_multi (ph_image_trans_layer): dissolves and wipes inside the
- *    2 x 2-block compositor's launch */
+ *    2 x 2-block compositor's launch.  ph_fused_v210_transition_multi (ph_fused_layer): dissolves and wipes between the plain v210 layers
+ *    of ph_fused_v210_combine_multi's launch; program "fused_v210_trans_<n>" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -274,6 +275,10 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * for a transition: l<i>Transition (0 cut / 1 dissolve / 2 wipe), l<i>Mix, l<i>IncomingIn, l<i>IncomingMatrix and - with packedRgb -
  * l<i>IncomingWidth / l<i>IncomingHeight, the same with Mask for a wipe; for the twin l<i>IncomingIn2, l<i>MaskIn2 and l<i>Mix2 (default:
  * l<i>Mix).
+ * A fused_v210_trans_<n> job (ph_fused_v210_transition_multi) takes fused_v210_combine_multi_<n>'s arguments and, per layer, l<i>Transition (0
+ * cut / 1 dissolve / 2 wipe, default 0), l<i>Mix, l<i>IncomingIn - a v210 frame of the output's size - and for a wipe l<i>MaskIn with
+ * l<i>MaskPacking: 0 (PH_FMT_V210) the buffer is a v210 frame, absent it is an f32 RGBA image of the output's size.  A launch of its own,
+ * in its turn.
  * And so does a pack_write_multi_<n> job (ph_pack_write_multi; globalWorkItems [width, height]): input - the f32 RGBA image - width, and
  * its n = 1..4 outputs as chan_compose_multi_<n> names them, outPacking / out<k>Packing being any PH_FMT_* here (7 and 8 included). */
 int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_arg *const *args, const int *n_args, int queue);
@@ -691,6 +696,35 @@ int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const
 int ph_fused_v210_combine_multi_batch(ph_ctx *ctx, int queue, int jobs, int n, const void *const *layers /* [jobs * n], job-major */,
                                       int n_out, const ph_chan_output *outs /* [jobs * n_out], job-major */, uint32_t width, uint32_t height,
                                       const void *rd_col_matrix12, const void *rd_gamma_lut, const void *rd_gamut9);
+/* ph_fused_v210_combine_multi with layers in a TRANSITION (transitioner.ts:165-176: a MIX or WIPE between two clips): a layer may bring
+ * the transition's second source - a v210 frame of the output's size - and, for a wipe, its mask of that size, a v210 frame or an f32
+ * RGBA image.  Exactly, bit for bit and in order, the n_out calls of ph_chan_compose on these ph_chan_layers: src = the v210 frame taken
+ * 1:1 (matrix9_host == NULL); transition, mix; incoming = the v210 frame taken 1:1; mask = a 1:1 source in its format - and therefore
+ * ph_v210_read (of every frame) -> ph_transition_dissolve / ph_transition_wipe -> ph_combine -> ph_pack_write.  A v210 mask goes through the
+ * reader (the call's Loader recipe) like any layer, and its .r is the factor.
+ * Arithmetic: dissolve fma(src.c, mix, incoming.c * (1 - mix)), wipe fma(incoming.c, m, src.c * (1 - m)) on all four channels, each
+ * difference and product rounded once; alpha is a value - a dissolve's is fma(1, mix, 1 * (1 - mix)), not always 1, a wipe's is per
+ * pixel.  The bottom layer is taken as it is (a mask value of Inf or NaN does not reach it through a factor); above it k = 1 - v.a,
+ * acc = fma(acc, k, v); n == 1 is the passthrough of the mixed image.
+ * Routes: every layer PH_TRANSITION_CUT IS ph_fused_v210_combine_multi, same route and trace name.  Otherwise one launch
+ * ("fused_v210_trans_multi x<outputs>" in a trace) of that call's kernel with the transitions inside its phase 1 - a v210 frame output
+ * that is alone included.  The launch needs what ph_fused_v210_combine_multi's needs (width % 48 == 0, every table registered, "lds_lut"
+ * = 1, a frame within the kernel's division by reciprocal); a call that does not qualify runs ph_chan_compose_multi on the equivalent
+ * layers inside the call, under that call's trace name.  "fused_multi_wgs" caps the workgroups as it does there.
+ * PH_E_INVALID, decided before anything is launched and before the context is looked at (a refused call writes nothing): everything
+ * ph_fused_v210_combine_multi refuses (yuv420p10 / p010 outputs included); a transition outside 0..2; a dissolve or a wipe without
+ * incoming_v210; a wipe without mask; a wipe whose mask_format is neither PH_SRC_V210 nor PH_SRC_RGBA_F32.  height == 0 is PH_OK. */
+typedef struct ph_fused_layer {
+  const void *v210;           /* device: the layer's frame, width x height */
+  int transition;             /* PH_TRANSITION_CUT | _DISSOLVE | _WIPE */
+  float mix;                  /* dissolve */
+  const void *incoming_v210;  /* dissolve, wipe: the second source, a v210 frame of the same size */
+  const void *mask;           /* wipe: the mask, of the same size, taken 1:1 */
+  int mask_format;            /* PH_SRC_V210 (read with the call's Loader recipe, .r used) | PH_SRC_RGBA_F32 */
+} ph_fused_layer;
+int ph_fused_v210_transition_multi(ph_ctx *ctx, int queue, int n, const ph_fused_layer *layers, int n_out, const ph_chan_output *outs,
+                                   uint32_t width, uint32_t height, const void *rd_col_matrix12, const void *rd_gamma_lut,
+                                   const void *rd_gamut9);
 
 /* ---- gamma LUT placement.  The reference hands its kernels a 65536-entry f32 `gammaLut` buffer
  *      (loadSave.ts:65-73,152-160) and gathers from it 3x per pixel.  Registering the table's

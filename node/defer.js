@@ -124,6 +124,12 @@ class Deferral {
 		// quad for all outputs) ahead of the channel kernel's candidates.  `fusedWriters: true` on the context; off unless asked for
 		// (DESIGN.md 5.1 has what it measured through the library) - with it off the recorded stream reaches the device exactly as before.
 		this.fusedWriters = ctx.fusedWriters === true
+		// The same chain with a layer in a dissolve or a wipe - the layer, its incoming source and a wipe's mask plain v210 reads of the
+		// output's size under one Loader recipe (the mask may be an f32 image of that size instead), no transform or yadif anywhere: ONE
+		// fused_v210_trans_<n> launch (ph_fused_v210_transition_multi) ahead of the channel kernel's candidates, sibling writes folded in as
+		// `fusedWriters` folds them.  `fusedTransitions: true` on the context; off unless asked for (DESIGN.md 5.1: measured through the
+		// library, not through node) - with it off the recorded stream reaches the device exactly as before.
+		this.fusedTransitions = ctx.fusedTransitions === true
 		// Several channels' such frames of a tick - one size, layer count, Loader recipe and list of consumers - as ONE launch: they go down
 		// in one runPrograms call with the library's context option "fused_multi_batch" set (ph_fused_v210_combine_multi_batch).
 		// `fusedBatch: true` on the context, with `fusedWriters`; off unless asked for (DESIGN.md 5.1: measured through the library, not
@@ -1127,6 +1133,35 @@ class Deferral {
 				params[`interlace${k}`] = f.interlace
 			})
 			candidates.unshift([`fused_v210_combine_multi_${n}`, params, null, found.length ? found.map((v) => v.node) : null])
+		}
+		// fusedTransitions: the same with a layer in a dissolve or a wipe - every read a plain v210 frame of the output's size (a wipe's mask:
+		// that, or an f32 image of the frame's size), nothing placed.  Ahead of the channel kernel's candidates; refused, they follow.
+		const plainV210 = (s) => s.v210 && !s.planar && !s.matrix
+		if (this.fusedTransitions && reader && reader.colMatrix && layers.some((l) => l.transition) &&
+			layers.every((l) => plainV210(l) && (!l.transition || (plainV210(l.transition.incoming) &&
+				(!l.transition.wipe || plainV210(l.transition.mask) || (!l.transition.mask.v210 && !l.transition.mask.matrix && l.transition.mask.source._packed == null)))))) {
+			const params = Object.assign({ output, interlace }, reader, saver)
+			layers.forEach((l, i) => {
+				params[`l${i}In`] = l.source
+				if (!l.transition) return
+				params[`l${i}Transition`] = l.transition.wipe ? 2 : 1
+				if (!l.transition.wipe) params[`l${i}Mix`] = l.transition.mix
+				params[`l${i}IncomingIn`] = l.transition.incoming.source
+				if (!l.transition.wipe) return
+				params[`l${i}MaskIn`] = l.transition.mask.source
+				if (l.transition.mask.v210) params[`l${i}MaskPacking`] = 0 // PH_FMT_V210; absent: an f32 image
+			})
+			found.forEach(({ frame: f, node: w }, i) => {
+				const k = i + 1
+				if (f.outFmt) params[`out${k}Packing`] = f.outFmt
+				params[`output${k}`] = f.output
+				if (f.outFmt === 4) params[`output${k}C`] = w.params.outputC
+				else if (f.outFmt >= 1 && f.outFmt < 5) { params[`output${k}U`] = w.params.outputU; params[`output${k}V`] = w.params.outputV }
+				if (!f.outRgb8) params[`out${k}ColMatrix`] = w.params.colMatrix
+				params[`out${k}GammaLut`] = w.params.gammaLut
+				params[`interlace${k}`] = f.interlace
+			})
+			candidates.unshift([`fused_v210_trans_${n}`, params, null, found.length ? found.map((v) => v.node) : null])
 		}
 		// the 2 x 2-block compositor's several-outputs form, ahead of all of these: the frame of a consumer that is not SDI, and the other
 		// consumers' writes of the same image as further outputs - with the frame's other field (the twin) where every one of these

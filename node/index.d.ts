@@ -103,6 +103,12 @@ export class clContext {
 	 * 48) - is one launch of the same compositor (`compose_up_trans_<n>`, ph_compose_up_transition_multi) ahead of the channel kernel, from the packed
 	 * fields when every image of the frame is one; `false`: the recorded stream reaches the device exactly as without the option.  The same bytes either
 	 * way.  Measured through the library (DESIGN.md 5.1), not through node.
+	 * `fusedTransitions` (default false; PHANERON_FUSED_TRANSITIONS=1): a frame of plain v210 layers of the output's size with a layer in a dissolve
+	 * or a wipe - the layer, its incoming frame and a wipe's mask plain v210 reads under one Loader recipe (the mask may be an f32 image of the
+	 * frame's size), no transform or yadif in the chain - is one launch of the headline kernel's several-outputs form (`fused_v210_trans_<n>`,
+	 * ph_fused_v210_transition_multi) ahead of the channel kernel, the other consumers' writes of the image folded in; `false`: the recorded
+	 * stream reaches the device exactly as without the option.  The same bytes either way.  Measured through the library (DESIGN.md 5.1), not
+	 * through node.
 	 * `batchOuts` (default false; PHANERON_BATCH_OUTS=1): the frames several channels post in one tick for consumers other than SDI (an encoder's
 	 * yuv422p8, the screen's rgba8) and for several consumers at once share ONE launch of the channel kernel (the library's context option
 	 * `chan_batch_outs`, ph_chan_compose_batch_out); `false`: a launch per channel, in its turn.  The same bytes either way.
@@ -125,7 +131,7 @@ export class clContext {
 	 * `strictHandles` (default false; PHANERON_STRICT_HANDLES=1): a fresh object per takeover, so that a reference kept past release()
 	 * is refused ('... released buffer') instead of aliasing the next owner's buffer - for running an application under test. */
 	constructor(params?: { platformIndex?: number; deviceIndex?: number; overlapping?: boolean; profile?: boolean; spinWaitMicros?: number; deferred?: boolean;
-		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; upTransitions?: boolean; batchOuts?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
+		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; upTransitions?: boolean; fusedTransitions?: boolean; batchOuts?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
 	readonly queue: { load: number; process: number; unload: number }
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo

@@ -166,6 +166,9 @@ class clContext {
 		// frames with a layer in a dissolve or a wipe through the 2 x 2-block compositor (node/defer.js upTransitions): off unless asked for
 		// (upTransitions: true, or PHANERON_UP_TRANSITIONS=1)
 		this.upTransitions = params.upTransitions === undefined ? process.env.PHANERON_UP_TRANSITIONS === '1' : !!params.upTransitions
+		// frames of plain v210 layers with a layer in a dissolve or a wipe through the headline kernel's several-outputs form (node/defer.js
+		// fusedTransitions): off unless asked for (fusedTransitions: true, or PHANERON_FUSED_TRANSITIONS=1)
+		this.fusedTransitions = params.fusedTransitions === undefined ? process.env.PHANERON_FUSED_TRANSITIONS === '1' : !!params.fusedTransitions
 		// several channels' frames of a tick for consumers other than SDI, or for several consumers, as one launch (node/defer.js batchOuts): off unless asked for
 		this.batchOuts = params.batchOuts === undefined ? process.env.PHANERON_BATCH_OUTS === '1' : !!params.batchOuts
 		// wire-format writes of one image that are launched as posted - a routed channel's image, a frame whose fused launch was refused, the 10-bit

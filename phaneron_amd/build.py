@@ -15,8 +15,8 @@ LIB = os.path.join(LIB_DIR, "libphaneron_hip.so")
 VARIANT_DIR = os.path.normpath(os.path.join(HERE, "..", "tools", "_variants"))
 ARCH = "gfx950"
 
-SOURCES = ["ph_kernels.hip", "ph_kernels_lds.hip", "ph_kernels_fused_multi.hip", "ph_kernels_fmt.hip", "ph_kernels_deint.hip", "ph_kernels_chan.hip", "ph_kernels_up.hip", "ph_api.cpp", "ph_run.cpp", "ph_program.cpp", "ph_colour.cpp", "ph_lut.cpp"]
-HEADERS = ["ph_device.h", "ph_formats.h", "ph_internal.h", "ph_kernels.h", "ph_kernels_fused_multi_body.h", "ph_lut.h", "ph_lut_host.h", "ph_ldslut.h", "ph_program.h", "ph_yadif.h", os.path.join("..", "..", "include", "phaneron_hip.h")]
+SOURCES = ["ph_kernels.hip", "ph_kernels_lds.hip", "ph_kernels_fused_multi.hip", "ph_kernels_fused_trans.hip", "ph_kernels_fmt.hip", "ph_kernels_deint.hip", "ph_kernels_chan.hip", "ph_kernels_up.hip", "ph_api.cpp", "ph_run.cpp", "ph_program.cpp", "ph_colour.cpp", "ph_lut.cpp"]
+HEADERS = ["ph_device.h", "ph_formats.h", "ph_internal.h", "ph_kernels.h", "ph_kernels_fused_multi_body.h", "ph_kernels_fused_out.h", "ph_lut.h", "ph_lut_host.h", "ph_ldslut.h", "ph_program.h", "ph_yadif.h", os.path.join("..", "..", "include", "phaneron_hip.h")]
 # -ffp-contract=off: every fused multiply-add in the kernels is explicit (parity with the
 # reference's OpenCL arithmetic); no fast-math anywhere.
 # -fno-slp-vectorize: the SLP vectoriser pairs independent f32 operations into v_pk_add / v_pk_fma_f32.  On gfx950 a
@@ -28,6 +28,11 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "
           # loads only if it can walk all its users - at most 300 by default.  The channel compositor indexes its op list
           # in several inlined places and crossed that line: the whole 1.7 KiB struct went to scratch (1792 B per lane, 4x slower).
           "-mllvm", "-instcombine-max-copied-from-constant-users=8000"]
+
+# Flags of one source.  ph_kernels_fused_trans.hip: the shared body's slice loop must be unrolled in full (the tile's packed indices
+# st[p][9] are registers only then), and with a transition layer's code inside it the loop is larger than the size up to which
+# "#pragma unroll" is obeyed - left rolled, st goes to scratch (224 bytes per lane).
+PER_SOURCE = {"ph_kernels_fused_trans.hip": ["-mllvm", "-pragma-unroll-threshold=100000"]}
 
 
 def hipcc():
@@ -67,7 +72,7 @@ def build(force=False, verbose=False, extra_flags=(), variant=None):
         # an object is rebuilt when its source, any header or this script is newer (force: always)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(hdr_time, os.path.getmtime(os.path.join(CSRC, src))):
             continue
-        cmd = [cc, "--offload-arch=" + ARCH, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj] + COMMON + list(extra_flags)
+        cmd = [cc, "--offload-arch=" + ARCH, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj] + COMMON + PER_SOURCE.get(src, []) + list(extra_flags)
         if verbose:
             print(" ".join(cmd))
         jobs.append((src, subprocess.Popen(cmd)))  # the sources compile side by side

@@ -39,6 +39,7 @@ EXPORTS = [
     "ph_fused_v210_combine_multi",
     "ph_fused_v210_combine_multi_batch",
     "ph_compose_up_transition_multi",
+    "ph_fused_v210_transition_multi",
 ]
 
 
@@ -94,6 +95,10 @@ class PhImageLayer(C.Structure):
 
 class PhImageTransLayer(C.Structure):  # ph_image_trans_layer
     _fields_ = [("src", PhImageLayer), ("transition", C.c_int), ("mix", C.c_float), ("incoming", PhImageLayer), ("mask", PhImageLayer)]
+
+
+class PhFusedLayer(C.Structure):  # ph_fused_layer
+    _fields_ = [("v210", C.c_void_p), ("transition", C.c_int), ("mix", C.c_float), ("incoming_v210", C.c_void_p), ("mask", C.c_void_p), ("mask_format", C.c_int)]
 
 
 IMG_RGBA_F32, IMG_RGB_F32 = 0, 1
@@ -218,6 +223,7 @@ def lib():
         "ph_compose_up_transition_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageTransLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_pack_write_multi": (ci, [vp, ci, vp, ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_fused_v210_combine_multi": (ci, [vp, ci, ci, C.POINTER(C.c_void_p), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
+        "ph_fused_v210_transition_multi": (ci, [vp, ci, ci, C.POINTER(PhFusedLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_fused_v210_combine_multi_batch": (ci, [vp, ci, ci, ci, C.POINTER(C.c_void_p), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_chan_compose_batch_out": (ci, [vp, ci, ci, C.POINTER(PhChanJobOut), cu, cu, vp, vp, vp]),
         "ph_ctx_host_pool_stats": (ci, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
@@ -865,6 +871,32 @@ class Context:
         outs = self._chan_outputs(outputs)
         args = (self.h, queue, len(layers), arr, len(outputs), outs, width, height) + tuple(None if t is None else _ptr(t) for t in (rd_cm, rd_lut, rd_gm))
         fn, h = lib().ph_fused_v210_combine_multi, self.h
+        if prepare_only:
+
+            def job(_keep=(arr, layers, outputs, outs)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
+
+    def fused_v210_transition_multi(self, layers, outputs, width, height, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
+        """fused_v210_combine_multi with layers in a dissolve or a wipe (ph_fused_v210_transition_multi).  layers: a v210 frame tensor - a
+        cut - or a dict {"v210": tensor, "transition": "cut" | "dissolve" | "wipe" (or a raw number), "mix": float, "incoming": v210
+        tensor, "mask": tensor, "mask_format": "v210" | "rgba" (or a raw number; default "rgba": an f32 RGBA image)}, every frame of the
+        output's size; outputs: dicts as chan_compose_multi takes them."""
+        arr = (PhFusedLayer * max(len(layers), 1))()
+        for i, spec in enumerate(layers):
+            if not isinstance(spec, dict):
+                spec = {"v210": spec}
+            tr, mf = spec.get("transition", "cut"), spec.get("mask_format", "rgba")
+            arr[i].v210 = None if spec.get("v210") is None else _ptr(spec["v210"]).value
+            arr[i].transition = tr if isinstance(tr, int) else {"cut": TRANSITION_CUT, "dissolve": TRANSITION_DISSOLVE, "wipe": TRANSITION_WIPE}[tr]
+            arr[i].mix = float(spec.get("mix", 0.0))
+            arr[i].incoming_v210 = None if spec.get("incoming") is None else _ptr(spec["incoming"]).value
+            arr[i].mask = None if spec.get("mask") is None else _ptr(spec["mask"]).value
+            arr[i].mask_format = mf if isinstance(mf, int) else {"v210": SRC_V210, "rgba": SRC_RGBA_F32}[mf]
+        outs = self._chan_outputs(outputs)
+        args = (self.h, queue, len(layers), arr, len(outputs), outs, width, height) + tuple(None if t is None else _ptr(t) for t in (rd_cm, rd_lut, rd_gm))
+        fn, h = lib().ph_fused_v210_transition_multi, self.h
         if prepare_only:
 
             def job(_keep=(arr, layers, outputs, outs)):

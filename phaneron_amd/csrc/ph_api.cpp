@@ -1836,17 +1836,9 @@ int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
   return PH_OK;
 }
 
-/* The plain-layer composite for several consumers: see include/phaneron_hip.h.  The call IS the n_out calls of ph_chan_compose on the layers
- * taken 1:1; every check is made before anything is launched, with ph_chan_compose_multi's texts per output.  A call the shared kernel
- * does not take runs ph_chan_compose_multi on those layers, which answers for everything else. */
-int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const *layers, int n_out, const ph_chan_output *outs, uint32_t width,
-                                uint32_t height, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
-  const char *const fn = "ph_fused_v210_combine_multi";
-  if (!ctx || !layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
-  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
-  if (n_out < 1 || n_out > ph::kMaxFusedOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxFusedOuts, n_out);
-  for (int i = 0; i < n; ++i)
-    if (!layers[i]) return fail(PH_E_INVALID, "%s: layer %d is NULL", fn, i);
+// What ph_fused_v210_combine_multi and ph_fused_v210_transition_multi refuse about their outputs and geometry - everything but the layers and
+// the context, which each entry sees to itself
+static int fused_multi_outputs_check(const char *fn, int queue, int n_out, const ph_chan_output *outs, uint32_t width, uint32_t height) {
   PH_QUEUE(fn, queue);
   if (!width) return fail(PH_E_INVALID, "%s: width 0", fn);
   for (int k = 0; k < n_out; ++k) {
@@ -1854,11 +1846,12 @@ int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const
     for (int j = 0; j < k; ++j)
       if (outs[j].planes[0] == outs[k].planes[0]) return fail(PH_E_INVALID, "%s: outputs %d and %d name the same plane", fn, j, k);
   }
-  // one v210 frame: the headline kernel itself, same route
-  if (n_out == 1 && outs[0].format == PH_FMT_V210 && outs[0].interlace == 0)
-    return ph_fused_v210_combine(ctx, queue, n, layers, outs[0].planes[0], width, height, rd_cm, rd_lut, rd_gm, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
-  // the shared launch: lines of whole 48-pixel blocks, every table in its LDS form (none is with the option "lds_lut" = 0), a frame
-  // small enough for the kernel's quad -> line division by reciprocal
+  return PH_OK;
+}
+// The shared launch's arguments but for the layers - or false: the call does not qualify.  It needs lines of whole 48-pixel blocks, every
+// table in its LDS form (none is with the option "lds_lut" = 0), a frame small enough for the kernel's quad -> line division by reciprocal.
+static bool fused_multi_shared(ph_ctx *ctx, int n_out, const ph_chan_output *outs, uint32_t width, uint32_t height, const void *rd_cm, const void *rd_lut,
+                               const void *rd_gm, ph::FusedMultiArgs &m) {
   const LutRef rref = lds_view(ctx, rd_lut);
   LutRef wref[ph::kMaxFusedOuts];
   bool shared = width % 48 == 0 && rref.get() && (uint64_t)(width / 6) * height * (width / 6) < (1ull << 32);
@@ -1866,18 +1859,7 @@ int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const
     wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
     shared = wref[k].get() != nullptr;
   }
-  if (!shared) {
-    ph_chan_layer cl[ph::kMaxLayers];
-    memset(cl, 0, sizeof cl);
-    for (int i = 0; i < n; ++i) {
-      cl[i].src.data = layers[i], cl[i].src.format = PH_SRC_V210, cl[i].src.width = (int)width, cl[i].src.height = (int)height;
-      cl[i].transition = PH_TRANSITION_CUT;
-    }
-    return ph_chan_compose_multi(ctx, queue, n, cl, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
-  }
-  if (!height) return PH_OK;
-  ph::FusedMultiArgs m{};
-  for (int i = 0; i < n; ++i) m.layers[i] = layers[i];
+  if (!shared) return false;
   m.quads_per_line = width / 6, m.total_quads = m.quads_per_line * height;
   m.rd_cm = (const float *)rd_cm, m.rd_gm = (const float *)rd_gm, m.rd = *rref.get();
   // the outputs grouped by writer table, in the order the tables first appear
@@ -1901,9 +1883,101 @@ int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const
     d.plane[0] = o.planes[0], d.plane[1] = o.planes[1], d.plane[2] = o.planes[2];
     d.wr = *wref[order[i]].get();
   }
+  return true;
+}
+
+/* The plain-layer composite for several consumers: see include/phaneron_hip.h.  The call IS the n_out calls of ph_chan_compose on the layers
+ * taken 1:1; every check is made before anything is launched, with ph_chan_compose_multi's texts per output.  A call the shared kernel
+ * does not take runs ph_chan_compose_multi on those layers, which answers for everything else. */
+int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const *layers, int n_out, const ph_chan_output *outs, uint32_t width,
+                                uint32_t height, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  const char *const fn = "ph_fused_v210_combine_multi";
+  if (!ctx || !layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  if (n_out < 1 || n_out > ph::kMaxFusedOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxFusedOuts, n_out);
+  for (int i = 0; i < n; ++i)
+    if (!layers[i]) return fail(PH_E_INVALID, "%s: layer %d is NULL", fn, i);
+  if (const int bad = fused_multi_outputs_check(fn, queue, n_out, outs, width, height)) return bad;
+  // one v210 frame: the headline kernel itself, same route
+  if (n_out == 1 && outs[0].format == PH_FMT_V210 && outs[0].interlace == 0)
+    return ph_fused_v210_combine(ctx, queue, n, layers, outs[0].planes[0], width, height, rd_cm, rd_lut, rd_gm, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
+  ph::FusedMultiArgs m{};
+  if (!fused_multi_shared(ctx, n_out, outs, width, height, rd_cm, rd_lut, rd_gm, m)) {
+    ph_chan_layer cl[ph::kMaxLayers];
+    memset(cl, 0, sizeof cl);
+    for (int i = 0; i < n; ++i) {
+      cl[i].src.data = layers[i], cl[i].src.format = PH_SRC_V210, cl[i].src.width = (int)width, cl[i].src.height = (int)height;
+      cl[i].transition = PH_TRANSITION_CUT;
+    }
+    return ph_chan_compose_multi(ctx, queue, n, cl, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
+  }
+  if (!height) return PH_OK;
+  for (int i = 0; i < n; ++i) m.layers[i] = layers[i];
   const int rc = set_device(ctx);
   if (rc) return rc;
   const hipError_t e = ph::launch_fused_v210_combine_multi(stream_of(ctx, queue), n, m, (uint32_t)ctx->props.multiProcessorCount, (uint32_t)ctx->fused_multi_wgs);
+  if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  return PH_OK;
+}
+
+/* The same with layers in a dissolve or a wipe: see include/phaneron_hip.h.  What the arguments alone decide is decided first - the context is
+ * looked at last, so a caller without a device learns of its mistakes too. */
+int ph_fused_v210_transition_multi(ph_ctx *ctx, int queue, int n, const ph_fused_layer *layers, int n_out, const ph_chan_output *outs, uint32_t width,
+                                   uint32_t height, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  const char *const fn = "ph_fused_v210_transition_multi";
+  if (!layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  if (n_out < 1 || n_out > ph::kMaxFusedOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxFusedOuts, n_out);
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    const ph_fused_layer &L = layers[i];
+    if (!L.v210) return fail(PH_E_INVALID, "%s: layer %d is NULL", fn, i);
+    if (L.transition != PH_TRANSITION_CUT && L.transition != PH_TRANSITION_DISSOLVE && L.transition != PH_TRANSITION_WIPE)
+      return fail(PH_E_INVALID, "%s: layer %d: transition %d is not a PH_TRANSITION_*", fn, i, L.transition);
+    if (L.transition == PH_TRANSITION_CUT) continue;
+    any = true;
+    if (!L.incoming_v210) return fail(PH_E_INVALID, "%s: layer %d: a layer in a transition needs its incoming frame", fn, i);
+    if (L.transition != PH_TRANSITION_WIPE) continue;
+    if (!L.mask) return fail(PH_E_INVALID, "%s: layer %d: a wipe needs its mask", fn, i);
+    if (L.mask_format != PH_SRC_V210 && L.mask_format != PH_SRC_RGBA_F32)
+      return fail(PH_E_INVALID, "%s: layer %d: mask format %d (a v210 frame, PH_SRC_V210, or an f32 RGBA image, PH_SRC_RGBA_F32)", fn, i, L.mask_format);
+  }
+  if (const int bad = fused_multi_outputs_check(fn, queue, n_out, outs, width, height)) return bad;
+  if (!ctx) return fail(PH_E_INVALID, "%s: ctx is NULL", fn);
+  if (!any) {  // every layer a cut: ph_fused_v210_combine_multi on the layers' frames
+    const void *plain[ph::kMaxLayers];
+    for (int i = 0; i < n; ++i) plain[i] = layers[i].v210;
+    return ph_fused_v210_combine_multi(ctx, queue, n, plain, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
+  }
+  ph::FusedTransArgs t{};
+  if (!fused_multi_shared(ctx, n_out, outs, width, height, rd_cm, rd_lut, rd_gm, t.m)) {
+    ph_chan_layer cl[ph::kMaxLayers];
+    memset(cl, 0, sizeof cl);
+    auto source = [&](ph_chan_source &s, const void *data, int format) { s.data = data, s.format = format, s.width = (int)width, s.height = (int)height; };
+    for (int i = 0; i < n; ++i) {
+      const ph_fused_layer &L = layers[i];
+      source(cl[i].src, L.v210, PH_SRC_V210);
+      cl[i].transition = L.transition, cl[i].mix = L.mix;
+      if (L.transition != PH_TRANSITION_CUT) source(cl[i].incoming, L.incoming_v210, PH_SRC_V210);
+      if (L.transition == PH_TRANSITION_WIPE) source(cl[i].mask, L.mask, L.mask_format);
+    }
+    return ph_chan_compose_multi(ctx, queue, n, cl, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
+  }
+  if (!height) return PH_OK;
+  for (int i = 0; i < n; ++i) {
+    const ph_fused_layer &L = layers[i];
+    t.m.layers[i] = L.v210;
+    if (L.transition == PH_TRANSITION_CUT) continue;  // (kFusedCut: what a cut layer says beside its frame is not looked at)
+    t.incoming[i] = L.incoming_v210;
+    if (L.transition == PH_TRANSITION_DISSOLVE) {
+      t.kind[i] = ph::kFusedDissolve, t.mix[i] = L.mix;
+    } else {
+      t.kind[i] = L.mask_format == PH_SRC_V210 ? ph::kFusedWipeV210 : ph::kFusedWipeF32, t.mask[i] = L.mask;
+    }
+  }
+  const int rc = set_device(ctx);
+  if (rc) return rc;
+  const hipError_t e = ph::launch_fused_v210_trans_multi(stream_of(ctx, queue), n, t, (uint32_t)ctx->props.multiProcessorCount, (uint32_t)ctx->fused_multi_wgs);
   if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   return PH_OK;
 }

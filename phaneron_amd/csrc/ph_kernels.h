@@ -133,6 +133,8 @@ struct FusedMultiArgs {
 // named "fused_v210_combine_multi x<outputs>" in a route trace; n = 1..8 layers; one workgroup per CU, never more than slices and - a test
 // and A/B hook, 0 = no cap - never more than max_wgs
 hipError_t launch_fused_v210_combine_multi(hipStream_t s, int n, const FusedMultiArgs &a, uint32_t num_cus, uint32_t max_wgs);
+// (the launcher's checks and planning, for the launchers of the single frame's kernels: ph_kernels_fused_multi.hip)
+hipError_t fused_multi_plan(const FusedMultiArgs &a, uint32_t num_cus, uint32_t max_wgs, FusedMultiArgs &b, uint32_t &grid, uint32_t &lds);
 // The same for `jobs` = 2..kMaxBatch frames of one geometry, layer count, reader recipe and output descriptors in one launch
 // (ph_fused_v210_combine_multi_batch): the jobs differ in their layers and in their outputs' planes only.  m: what the jobs share
 // (m.layers and m.out[k].plane are not read); layers[j] / plane[j][k]: job j's, k in m.out's order.
@@ -144,6 +146,19 @@ struct FusedMultiBatchArgs {
 // named "fused_v210_combine_multi x<outputs>j<jobs>"; max(1, num_cus / jobs) workgroups per job, never more than a job's slices and - 0 = no
 // cap - never more than max_wgs; workgroups [j * per job, (j + 1) * per job) work on job j
 hipError_t launch_fused_v210_combine_multi_batch(hipStream_t s, int n, uint32_t jobs, const FusedMultiBatchArgs &a, uint32_t num_cus, uint32_t max_wgs);
+// The single frame's launch with layers in a TRANSITION (ph_fused_v210_transition_multi; ph_kernels_fused_trans.hip): a layer may bring a
+// second v210 frame and, for a wipe, a mask - a v210 frame read like a layer (its red is the factor) or an f32 RGBA image (the red of
+// pixel x, 16 bytes apart) - all of the output's size.  m: as launch_fused_v210_combine_multi takes it.
+enum : uint32_t { kFusedCut = 0, kFusedDissolve = 1, kFusedWipeV210 = 2, kFusedWipeF32 = 3 };
+struct FusedTransArgs {
+  FusedMultiArgs m;
+  const void *incoming[kMaxLayers];  // dissolve, wipe
+  const void *mask[kMaxLayers];      // wipe
+  uint32_t kind[kMaxLayers];         // kFused*
+  float mix[kMaxLayers];             // dissolve
+};
+// named "fused_v210_trans_multi x<outputs>"; workgroups as launch_fused_v210_combine_multi
+hipError_t launch_fused_v210_trans_multi(hipStream_t s, int n, const FusedTransArgs &a, uint32_t num_cus, uint32_t max_wgs);
 
 struct ComposeArgs {
   const void *layers[kMaxLayers];

@@ -6,11 +6,22 @@
 // [j * gridDim.x, (j + 1) * gridDim.x) - own job j and divide ITS quads among them as the workgroups of a single frame do.  The job is
 // uniform per workgroup: its layer and plane pointers are scalar loads from the argument block at an offset made from blockIdx.y.
 // Everything else - geometry, the reader recipe, the output descriptors but for their planes - is the launch's.
+// PH_FM_TRANS 1 (ph_kernels_fused_trans.hip; `a`: FusedTransArgs::m): the single frame's kernel with layers that may be in a dissolve or a
+// wipe - such a layer leaves the rolled loop's plain path for fm_trans_layer; everything else, phase 2 included, is the text below.
   constexpr int P = 6, BS = kLdsBlock;
+#if PH_FM_TRANS
+#define PH_FM_LUT_LOAD(v) fm_lut_load<BS>(v)  // (lds_lut_load with the lane's place made at the load: ph_kernels_fused_trans.hip)
+#else
+#define PH_FM_LUT_LOAD(v) lds_lut_load<BS>(v)
+#endif
   // The output descriptors are walked by run-time index (table groups, the outputs of a group).  Read through the argument struct
   // that would put a private copy of all of it in scratch; read where they are - the explicit arguments lie at the start of the
   // kernel-argument segment - they stay scalar loads at a computed offset.
-#if PH_FM_BATCH
+#if PH_FM_TRANS
+  typedef const __attribute__((address_space(4))) FusedTransArgs *fm_kernarg_ptr;
+  const auto *const karg = (fm_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  const auto *const outs = karg->m.out;
+#elif PH_FM_BATCH
   typedef const __attribute__((address_space(4))) FusedMultiBatchArgs *fm_kernarg_ptr;
   const auto *const karg = (fm_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
   const auto *const outs = karg->m.out;
@@ -21,7 +32,9 @@
   const ReadK rk = load_read_k(a.rd_cm, a.rd_gm);
   const LutK rlut = make_lut_k(a.rd);
   const bool std_matrix = ycbcr_matrix_is_standard(rk);  // uniform
-#if PH_FM_BATCH
+#if PH_FM_TRANS
+  auto layer_ptr = [&](int l) { return reinterpret_cast<const uint4 *>(karg->m.layers[l]); };
+#elif PH_FM_BATCH
   auto layer_ptr = [&](int l) { return reinterpret_cast<const uint4 *>(karg->layers[blockIdx.y][l]); };
 #else
   auto layer_ptr = [&](int l) { return reinterpret_cast<const uint4 *>(a.layers[l]); };
@@ -53,6 +66,13 @@
         uint4 nxt = w;
         if (l + 1 < N) nxt = load_stream(layer_ptr(l + 1) + f);
         else if (more) nxt = load_stream(layer_ptr(0) + f_next);
+#if PH_FM_TRANS
+        if (karg->kind[l] != kFusedCut) {  // uniform: the layer is in a transition
+          fm_trans_layer<decltype(tag)::value>(acc, w, karg, l, f, rk, rlut);
+          w = nxt;
+          continue;
+        }
+#endif
         const Yuv6 q = unpack_quad(w);
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
@@ -77,7 +97,7 @@
     {
       LutView rd = a.rd;
       asm volatile("" : "+s"(rd.blob), "+s"(rd.hole));
-      lds_lut_load<BS>(rd);
+      PH_FM_LUT_LOAD(rd);
     }
     __syncthreads();
     // a slice is skipped per WAVE: only the waves that hold quads of a partly filled slice run it
@@ -100,7 +120,7 @@
       uint32_t k1 = k0 + 1;
       while (k1 < a.n_out && outs[k1].wr.blob == wr.blob) ++k1;  // uniform
       __syncthreads();  // nobody reads the table in the LDS any more
-      lds_lut_load<BS>(wr);
+      PH_FM_LUT_LOAD(wr);
       __syncthreads();
       const LutK wlut = make_lut_k(wr);
       uint32_t lane_quad = tile_begin + threadIdx.x;
@@ -140,3 +160,4 @@
     }
     __syncthreads();  // the next tile loads the reader's table
   }
+#undef PH_FM_LUT_LOAD

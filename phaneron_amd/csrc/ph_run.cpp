@@ -396,6 +396,35 @@ static int fused_multi_job(Args &a, int queue) {
   if (const int rc = fused_multi_parse(a, &c)) return rc;
   return a.done() ? a.rc : ph_fused_v210_combine_multi(a.ctx, queue, c.n, c.layers, c.n_out, c.outs, c.width, c.height, c.r.rd_cm->dptr, c.r.rd_lut->dptr, c.r.rd_gm->dptr);
 }
+// fused_v210_trans_<n> (K_FUSED_V210, told apart by its name; ph_fused_v210_transition_multi): fused_v210_combine_multi_<n>'s arguments and,
+// per layer, the keys compose_up_trans_<n> has for a transition - l<i>Transition (0 cut / 1 dissolve / 2 wipe, default 0), l<i>Mix,
+// l<i>IncomingIn: a v210 frame of the output's size; a wipe's l<i>MaskIn with l<i>MaskPacking: 0 (PH_FMT_V210) a v210 frame, absent an f32
+// RGBA image of the output's size.  A launch of its own, in its turn (ph_run_programs does not group it).
+static bool fused_is_trans(const ph_program *prog) { return prog->kernel.compare(0, 17, "fused_v210_trans_") == 0; }
+static int fused_trans_job(Args &a, int queue) {
+  FusedMultiCall c;
+  if (const int rc = fused_multi_parse(a, &c)) return rc;
+  ph_fused_layer layers[ph::kMaxLayers];
+  for (int i = 0; i < c.n; ++i) {
+    ph_fused_layer &L = layers[i] = ph_fused_layer{};
+    L.v210 = c.layers[i];
+    const double kind = a.num_or(0, "l%dTransition", i);
+    if (kind != PH_TRANSITION_CUT && kind != PH_TRANSITION_DISSOLVE && kind != PH_TRANSITION_WIPE)
+      return a.fail(PH_E_INVALID, "kernel argument 'l%dTransition': %g (0 cut, 1 dissolve, 2 wipe)", i, kind);
+    L.transition = (int)kind;
+    L.mix = (float)a.num_or(0, "l%dMix", i);
+    if (L.transition != PH_TRANSITION_CUT) L.incoming_v210 = a.buf(v210_bytes(c.width, c.height), "l%dIncomingIn", i)->dptr;
+    if (L.transition != PH_TRANSITION_WIPE) continue;
+    if (a.has("l%dMaskPacking", i)) {
+      const double packing = a.num("l%dMaskPacking", i);
+      if (packing != PH_FMT_V210) return a.fail(PH_E_INVALID, "kernel argument 'l%dMaskPacking': %g (0: a v210 frame; absent: an f32 RGBA image)", i, packing);
+      L.mask = a.buf(v210_bytes(c.width, c.height), "l%dMaskIn", i)->dptr, L.mask_format = PH_SRC_V210;
+    } else {
+      L.mask = a.buf(image_bytes(c.width, c.height), "l%dMaskIn", i)->dptr, L.mask_format = PH_SRC_RGBA_F32;
+    }
+  }
+  return a.done() ? a.rc : ph_fused_v210_transition_multi(a.ctx, queue, c.n, layers, c.n_out, c.outs, c.width, c.height, c.r.rd_cm->dptr, c.r.rd_lut->dptr, c.r.rd_gm->dptr);
+}
 
 // a compose_up_write_v210_<n> job's arguments (ph_run_program and ph_run_programs, which puts like jobs into one launch)
 struct UpCall {
@@ -734,6 +763,7 @@ static int dispatch_compose(Args &a, int queue) {
       return a.done() ? a.rc : ph_combine(ctx, queue, prog->n_layers, layers, w, h, out->dptr);
     }
     case K_FUSED_V210: {
+      if (fused_is_trans(prog)) return fused_trans_job(a, queue);
       if (fused_is_multi(prog)) return fused_multi_job(a, queue);
       FusedCall f;
       fused_call_parse(a, &f);
@@ -899,10 +929,10 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       // (a frame for another consumer, or a chan_compose_multi_<n> job: a launch of its own, in its turn - unless the context option
       // "chan_batch_outs" lets such jobs share launches too: ph_chan_compose_batch_out)
       kind[(size_t)j] = calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
-    } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j])) {
+    } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j]) && !fused_is_trans(progs[j])) {
       if ((rc = fused_call_parse(job, &fused[(size_t)j]))) return rc;
       kind[(size_t)j] = 2;
-    } else if (progs[j]->id == K_FUSED_V210 && ctx->fused_multi_batch) {
+    } else if (progs[j]->id == K_FUSED_V210 && ctx->fused_multi_batch && !fused_is_trans(progs[j])) {  // (a fused_v210_trans_<n> job: a launch of its own, in its turn)
       // (a fused_v210_combine_multi_<n> job: a launch of its own, in its turn - unless the context option "fused_multi_batch" lets such
       // jobs share launches: ph_fused_v210_combine_multi_batch)
       if (multis.empty()) multis.resize((size_t)n_jobs);
