@@ -49,7 +49,8 @@ extern "C" {
  *    "fused_v210_combine_multi_<n>"; context option "fused_multi_wgs".  ph_fused_v210_combine_multi_batch: several channels' such frames in one
  *    launch; context option "fused_multi_batch".  ph_compose_up_transition_multi (ph_image_trans_layer): dissolves and wipes inside the
  *    2 x 2-block compositor's launch.  ph_fused_v210_transition_multi (ph_fused_layer): dissolves and wipes between the plain v210 layers
- *    of ph_fused_v210_combine_multi's launch; program "fused_v210_trans_<n>" */
+ *    of ph_fused_v210_combine_multi's launch; program "fused_v210_trans_<n>".  ph_fused_v210_route_multi (ph_route_layer): a routed f32 RGBA
+ *    image among that launch's layers and the combined image among its outputs; program "fused_v210_route_<n>" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -279,6 +280,9 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * cut / 1 dissolve / 2 wipe, default 0), l<i>Mix, l<i>IncomingIn - a v210 frame of the output's size - and for a wipe l<i>MaskIn with
  * l<i>MaskPacking: 0 (PH_FMT_V210) the buffer is a v210 frame, absent it is an f32 RGBA image of the output's size.  A launch of its own,
  * in its turn.
+ * A fused_v210_route_<n> job (ph_fused_v210_route_multi) takes fused_v210_combine_multi_<n>'s arguments and l<i>Image: 1 marks l<i>In as
+ * an f32 RGBA image of width x height x 16 bytes (absent or 0: a v210 frame); the optional buffer imageOut receives the combined image,
+ * and `output` may be absent only when imageOut is there (no packed frame at all).  A launch of its own, in its turn.
  * And so does a pack_write_multi_<n> job (ph_pack_write_multi; globalWorkItems [width, height]): input - the f32 RGBA image - width, and
  * its n = 1..4 outputs as chan_compose_multi_<n> names them, outPacking / out<k>Packing being any PH_FMT_* here (7 and 8 included). */
 int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_arg *const *args, const int *n_args, int queue);
@@ -725,8 +729,37 @@ typedef struct ph_fused_layer {
 int ph_fused_v210_transition_multi(ph_ctx *ctx, int queue, int n, const ph_fused_layer *layers, int n_out, const ph_chan_output *outs,
                                    uint32_t width, uint32_t height, const void *rd_col_matrix12, const void *rd_gamma_lut,
                                    const void *rd_gamut9);
+/* ph_fused_v210_combine_multi for a ROUTED channel (routeProducer.ts:63-126, combiner.ts:219-254): a layer may be a finished f32 RGBA
+ * image of the output's size - another channel's combined frame - and the combined image is an output, image_out, beside the n_out =
+ * 0..4 packed frames.  Exactly, bit for bit and in order: ph_v210_read of every v210 layer; ph_combine of the n images in layer order
+ * into image_out (n == 1: the Combiner's passthrough - image_out is that one image); ph_pack_write(image_out, ...) for each output with
+ * its format, planes, interlace, matrix and table.  The packed outputs are therefore also ph_chan_compose_multi's on the same layers,
+ * v210 and PH_SRC_RGBA_F32 sources both taken 1:1 (matrix9_host == NULL, PH_TRANSITION_CUT).
+ * Arithmetic (ph_combine's): the bottom layer is taken as it is - its -0 and its alpha reach image_out unchanged; above it k = 1 - l.a,
+ * rgb = fma(acc, k, l), a = fma(acc.a, 0, l.a).  Alpha is a value of its own: NaN above an image pixel whose alpha is Inf or NaN.  An
+ * image layer's alpha is arbitrary, a v210 layer's is 1.  Only a NaN's payload is not pinned.
+ * Routes: no image layer and image_out == NULL (n_out >= 1) IS ph_fused_v210_combine_multi, same route and trace name.  Otherwise one
+ * launch ("fused_v210_route_multi x<n_out>i<0|1>" in a trace, i1: the image is written) of that call's kernel, the image layers loaded
+ * and image_out stored inside its phase 1; with n_out == 0 no writer table is touched.  image_out is stored as ph_combine stores its
+ * image (context option "stream_images").  The launch needs what ph_fused_v210_combine_multi's needs (width % 48 == 0, the reader's
+ * table and every writer's table registered, "lds_lut" = 1, a frame within the kernel's division by reciprocal).  A call that does not
+ * qualify and has image_out == NULL runs ph_chan_compose_multi on the equivalent layers inside the call, under that call's trace name
+ * and with its errors; one that wants image_out is PH_E_INVALID - nothing else makes the image in one call: run ph_v210_read,
+ * ph_combine and ph_pack_write_multi.  "fused_multi_wgs" caps the workgroups as it does for ph_fused_v210_combine_multi.
+ * PH_E_INVALID, decided from the arguments before the context is looked at (a refused call writes nothing): everything
+ * ph_fused_v210_combine_multi refuses about outputs and geometry (yuv420p10 / p010 outputs included); n outside 1..8; a layer with NULL
+ * data; a layer format that is neither PH_SRC_V210 nor PH_SRC_RGBA_F32; n_out outside 0..4; n_out == 0 with image_out == NULL;
+ * image_out equal to a layer's data (tail lanes read the range's last quad again, which another lane may just have written) or to an
+ * output's first plane.  height == 0 is PH_OK and launches nothing. */
+typedef struct ph_route_layer {
+  const void *data;  /* device: a v210 frame, or an f32 RGBA image (16 B per pixel, rows unpadded), width x height */
+  int format;        /* PH_SRC_V210 | PH_SRC_RGBA_F32 */
+} ph_route_layer;
+int ph_fused_v210_route_multi(ph_ctx *ctx, int queue, int n, const ph_route_layer *layers, void *image_out /* f32 RGBA, width x height, or NULL */,
+                              int n_out /* 0..4 */, const ph_chan_output *outs, uint32_t width, uint32_t height, const void *rd_col_matrix12,
+                              const void *rd_gamma_lut, const void *rd_gamut9);
 
-/* ---- gamma LUT placement.  The reference hands its kernels a 65536-entry f32 `gammaLut` buffer
+/* ---- gamma LUT placement. The reference hands its kernels a 65536-entry f32 `gammaLut` buffer
  *      (loadSave.ts:65-73,152-160) and gathers from it 3x per pixel.  Registering the table's
  *      host contents lets the library keep an exact compressed copy for the CU's LDS
  *      (DESIGN.md "LUT placement"); kernels given a registered device pointer then use the LDS

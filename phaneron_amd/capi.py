@@ -40,6 +40,7 @@ EXPORTS = [
     "ph_fused_v210_combine_multi_batch",
     "ph_compose_up_transition_multi",
     "ph_fused_v210_transition_multi",
+    "ph_fused_v210_route_multi",
 ]
 
 
@@ -95,6 +96,10 @@ class PhImageLayer(C.Structure):
 
 class PhImageTransLayer(C.Structure):  # ph_image_trans_layer
     _fields_ = [("src", PhImageLayer), ("transition", C.c_int), ("mix", C.c_float), ("incoming", PhImageLayer), ("mask", PhImageLayer)]
+
+
+class PhRouteLayer(C.Structure):  # ph_route_layer
+    _fields_ = [("data", C.c_void_p), ("format", C.c_int)]
 
 
 class PhFusedLayer(C.Structure):  # ph_fused_layer
@@ -224,6 +229,7 @@ def lib():
         "ph_pack_write_multi": (ci, [vp, ci, vp, ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_fused_v210_combine_multi": (ci, [vp, ci, ci, C.POINTER(C.c_void_p), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_fused_v210_transition_multi": (ci, [vp, ci, ci, C.POINTER(PhFusedLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
+        "ph_fused_v210_route_multi": (ci, [vp, ci, ci, C.POINTER(PhRouteLayer), vp, ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_fused_v210_combine_multi_batch": (ci, [vp, ci, ci, ci, C.POINTER(C.c_void_p), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_chan_compose_batch_out": (ci, [vp, ci, ci, C.POINTER(PhChanJobOut), cu, cu, vp, vp, vp]),
         "ph_ctx_host_pool_stats": (ci, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
@@ -900,6 +906,28 @@ class Context:
         if prepare_only:
 
             def job(_keep=(arr, layers, outputs, outs)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
+
+    def fused_v210_route_multi(self, layers, image_out, outputs, width, height, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
+        """fused_v210_combine_multi for a routed channel (ph_fused_v210_route_multi): a layer may be an f32 RGBA image, and image_out -
+        a tensor, or None - receives the combined image.  layers: a v210 frame tensor, or a dict {"data": tensor, "format": "v210" |
+        "rgba" (or a raw number)}, every one of the output's size; outputs: 0..4 dicts as chan_compose_multi takes them."""
+        arr = (PhRouteLayer * max(len(layers), 1))()
+        for i, spec in enumerate(layers):
+            if not isinstance(spec, dict):
+                spec = {"data": spec}
+            fmt = spec.get("format", "v210")
+            arr[i].data = None if spec.get("data") is None else _ptr(spec["data"]).value
+            arr[i].format = fmt if isinstance(fmt, int) else {"v210": SRC_V210, "rgba": SRC_RGBA_F32}[fmt]
+        outs = self._chan_outputs(outputs)
+        args = (self.h, queue, len(layers), arr, None if image_out is None else _ptr(image_out), len(outputs), outs, width, height) + tuple(
+            None if t is None else _ptr(t) for t in (rd_cm, rd_lut, rd_gm))
+        fn, h = lib().ph_fused_v210_route_multi, self.h
+        if prepare_only:
+
+            def job(_keep=(arr, layers, image_out, outputs, outs)):
                 check(fn(*args), h)
             return job
         check(fn(*args), h)

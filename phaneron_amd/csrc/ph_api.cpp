@@ -1982,6 +1982,59 @@ int ph_fused_v210_transition_multi(ph_ctx *ctx, int queue, int n, const ph_fused
   return PH_OK;
 }
 
+/* The same for a routed channel - an f32 RGBA image among the layers, the combined image among the outputs: see include/phaneron_hip.h.
+ * What the arguments alone decide is decided first; the context is looked at last. */
+int ph_fused_v210_route_multi(ph_ctx *ctx, int queue, int n, const ph_route_layer *layers, void *image_out, int n_out, const ph_chan_output *outs,
+                              uint32_t width, uint32_t height, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  const char *const fn = "ph_fused_v210_route_multi";
+  if (n_out < 0 || n_out > ph::kMaxFusedOuts) return fail(PH_E_INVALID, "%s: 0..%d outputs (%d)", fn, ph::kMaxFusedOuts, n_out);
+  if (!layers || (n_out && !outs) || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  if (!n_out && !image_out) return fail(PH_E_INVALID, "%s: nothing to make: no output and image_out is NULL", fn);
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    const ph_route_layer &L = layers[i];
+    if (!L.data) return fail(PH_E_INVALID, "%s: layer %d is NULL", fn, i);
+    if (L.format != PH_SRC_V210 && L.format != PH_SRC_RGBA_F32)
+      return fail(PH_E_INVALID, "%s: layer %d: format %d (a v210 frame, PH_SRC_V210, or an f32 RGBA image, PH_SRC_RGBA_F32)", fn, i, L.format);
+    any = any || L.format == PH_SRC_RGBA_F32;
+    // (tail lanes recompute the last quad of a range: they would read what another lane has just written)
+    if (L.data == image_out) return fail(PH_E_INVALID, "%s: image_out is layer %d's data", fn, i);
+  }
+  if (const int bad = fused_multi_outputs_check(fn, queue, n_out, outs, width, height)) return bad;
+  for (int k = 0; k < n_out; ++k)
+    if (image_out && outs[k].planes[0] == image_out) return fail(PH_E_INVALID, "%s: image_out is output %d's first plane", fn, k);
+  if (!ctx) return fail(PH_E_INVALID, "%s: ctx is NULL", fn);
+  if (!any && !image_out) {  // plain layers, packed frames only: ph_fused_v210_combine_multi on the layers' frames
+    const void *plain[ph::kMaxLayers];
+    for (int i = 0; i < n; ++i) plain[i] = layers[i].data;
+    return ph_fused_v210_combine_multi(ctx, queue, n, plain, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
+  }
+  ph::FusedRouteArgs t{};
+  if (!fused_multi_shared(ctx, n_out, outs, width, height, rd_cm, rd_lut, rd_gm, t.m)) {
+    if (image_out)
+      return fail(PH_E_INVALID,
+                  "%s: the one-launch route does not take this frame (it needs width %% 48 == 0, the reader's and every writer's table registered, \"lds_lut\" = 1 and a "
+                  "frame within the kernel's division by reciprocal) and nothing else makes image_out: run ph_v210_read, ph_combine and ph_pack_write_multi",
+                  fn);
+    ph_chan_layer cl[ph::kMaxLayers];
+    memset(cl, 0, sizeof cl);
+    for (int i = 0; i < n; ++i) {
+      cl[i].src.data = layers[i].data, cl[i].src.format = layers[i].format, cl[i].src.width = (int)width, cl[i].src.height = (int)height;
+      cl[i].transition = PH_TRANSITION_CUT;
+    }
+    return ph_chan_compose_multi(ctx, queue, n, cl, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
+  }
+  if (!height) return PH_OK;
+  for (int i = 0; i < n; ++i) t.m.layers[i] = layers[i].data, t.is_image[i] = layers[i].format == PH_SRC_RGBA_F32 ? 1u : 0u;
+  t.image_out = image_out;
+  const int rc = set_device(ctx);
+  if (rc) return rc;
+  const hipError_t e = ph::launch_fused_v210_route_multi(stream_of(ctx, queue), n, t, (uint32_t)ctx->props.multiProcessorCount, (uint32_t)ctx->fused_multi_wgs);
+  if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  return PH_OK;
+}
+
 /* Several channels' plain-layer composites, each for the same consumers, in one launch: see include/phaneron_hip.h.  The call IS the `jobs`
  * calls of ph_fused_v210_combine_multi in order; every check - those calls' own, per job and output - is made before anything is launched. */
 int ph_fused_v210_combine_multi_batch(ph_ctx *ctx, int queue, int jobs, int n, const void *const *layers, int n_out, const ph_chan_output *outs,

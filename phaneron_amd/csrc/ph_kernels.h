@@ -159,6 +159,18 @@ struct FusedTransArgs {
 };
 // named "fused_v210_trans_multi x<outputs>"; workgroups as launch_fused_v210_combine_multi
 hipError_t launch_fused_v210_trans_multi(hipStream_t s, int n, const FusedTransArgs &a, uint32_t num_cus, uint32_t max_wgs);
+// The single frame's launch with a ROUTED IMAGE among the layers and the combined image as an output (ph_fused_v210_route_multi;
+// ph_kernels_fused_route.hip): a layer may be an f32 RGBA image of the output's size (16 bytes per pixel, rows unpadded) instead of a
+// v210 frame, and image_out - or NULL - receives what ph_combine makes of the layers' images, to the bit.  m: as
+// launch_fused_v210_combine_multi takes it, but m.n_out may be 0 with an image_out: the image alone, no writer table touched.
+struct FusedRouteArgs {
+  FusedMultiArgs m;
+  uint32_t is_image[kMaxLayers];  // 1: m.layers[l] is an f32 RGBA image
+  void *image_out;
+  uint32_t nt;                    // launcher: image_out's store policy (image_nt)
+};
+// named "fused_v210_route_multi x<outputs>i<0|1>" (i1: the image is written); workgroups as launch_fused_v210_combine_multi
+hipError_t launch_fused_v210_route_multi(hipStream_t s, int n, const FusedRouteArgs &a, uint32_t num_cus, uint32_t max_wgs);
 
 struct ComposeArgs {
   const void *layers[kMaxLayers];

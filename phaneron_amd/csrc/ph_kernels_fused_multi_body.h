@@ -8,9 +8,17 @@
 // Everything else - geometry, the reader recipe, the output descriptors but for their planes - is the launch's.
 // PH_FM_TRANS 1 (ph_kernels_fused_trans.hip; `a`: FusedTransArgs::m): the single frame's kernel with layers that may be in a dissolve or a
 // wipe - such a layer leaves the rolled loop's plain path for fm_trans_layer; everything else, phase 2 included, is the text below.
+// PH_FM_ROUTE 1 (ph_kernels_fused_route.hip; `a`: FusedRouteArgs::m; IMG: the launch has an image layer): the single frame's kernel with
+// layers that may be f32 RGBA images - such a layer leaves the plain path for fm_route_image_layer - and the combined image as an output
+// (karg->image_out, stored at the end of phase 1).  There the combine is ph_combine's to the bit: the bottom layer is assigned, and with
+// IMG the six alphas are carried.  n_out may be 0: no phase 2.
+#if PH_FM_ROUTE
+  constexpr int P = PH_FM_ROUTE_P, BS = kLdsBlock;
+#else
   constexpr int P = 6, BS = kLdsBlock;
-#if PH_FM_TRANS
-#define PH_FM_LUT_LOAD(v) fm_lut_load<BS>(v)  // (lds_lut_load with the lane's place made at the load: ph_kernels_fused_trans.hip)
+#endif
+#if PH_FM_TRANS || PH_FM_ROUTE
+#define PH_FM_LUT_LOAD(v) fm_lut_load<BS>(v)  // (lds_lut_load with the lane's place made at the load: ph_kernels_fused_out.h)
 #else
 #define PH_FM_LUT_LOAD(v) lds_lut_load<BS>(v)
 #endif
@@ -19,6 +27,10 @@
   // kernel-argument segment - they stay scalar loads at a computed offset.
 #if PH_FM_TRANS
   typedef const __attribute__((address_space(4))) FusedTransArgs *fm_kernarg_ptr;
+  const auto *const karg = (fm_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  const auto *const outs = karg->m.out;
+#elif PH_FM_ROUTE
+  typedef const __attribute__((address_space(4))) FusedRouteArgs *fm_kernarg_ptr;
   const auto *const karg = (fm_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
   const auto *const outs = karg->m.out;
 #elif PH_FM_BATCH
@@ -32,7 +44,7 @@
   const ReadK rk = load_read_k(a.rd_cm, a.rd_gm);
   const LutK rlut = make_lut_k(a.rd);
   const bool std_matrix = ycbcr_matrix_is_standard(rk);  // uniform
-#if PH_FM_TRANS
+#if PH_FM_TRANS || PH_FM_ROUTE
   auto layer_ptr = [&](int l) { return reinterpret_cast<const uint4 *>(karg->m.layers[l]); };
 #elif PH_FM_BATCH
   auto layer_ptr = [&](int l) { return reinterpret_cast<const uint4 *>(karg->layers[blockIdx.y][l]); };
@@ -56,16 +68,42 @@
       return f < wg_end ? f : last_quad;                      // tail lanes recompute the last quad
     };
     // one-deep prefetch through layers and slices; the very first word is requested before the table load
+#if PH_FM_ROUTE
+    // (an image layer's slot in the chain stays empty: its v210 word is not loaded, its texels are fm_route_image_layer's)
+    auto is_image = [&](int l) { return IMG && karg->is_image[l] != 0; };  // uniform
+    uint4 w = make_uint4(0u, 0u, 0u, 0u);
+    if (!is_image(0)) w = load_stream(layer_ptr(0) + quad_of(0));
+    bool own = false;  // the lane's quad of the slice is its own, not a tail lane's copy of the last one: set per slice
+#else
     uint4 w = load_stream(layer_ptr(0) + quad_of(0));
+#endif
     auto phase1_slice = [&](auto tag, uint4 w, uint32_t f, uint32_t f_next, bool more, uint32_t(&st)[9]) -> uint4 {
       float acc[18];
 #pragma unroll
       for (int i = 0; i < 18; ++i) acc[i] = 0.0f;
+#if PH_FM_ROUTE
+      float al[IMG ? 6 : 1];  // the six alphas: carried only where a layer's can differ from 1
+#pragma unroll
+      for (int j = 0; j < (IMG ? 6 : 1); ++j) al[j] = 1.0f;
+#endif
 #pragma unroll 1  // rolled: one copy of the per-layer code whatever N is
       for (int l = 0; l < N; ++l) {
         uint4 nxt = w;
+#if PH_FM_ROUTE
+        if (l + 1 < N) {
+          if (!is_image(l + 1)) nxt = load_stream(layer_ptr(l + 1) + f);
+        } else if (more) {
+          if (!is_image(0)) nxt = load_stream(layer_ptr(0) + f_next);
+        }
+        if (is_image(l)) {
+          fm_route_image_layer(acc, al, karg->m.layers[l], l, f);
+          w = nxt;
+          continue;
+        }
+#else
         if (l + 1 < N) nxt = load_stream(layer_ptr(l + 1) + f);
         else if (more) nxt = load_stream(layer_ptr(0) + f_next);
+#endif
 #if PH_FM_TRANS
         if (karg->kind[l] != kFusedCut) {  // uniform: the layer is in a transition
           fm_trans_layer<decltype(tag)::value>(acc, w, karg, l, f, rk, rlut);
@@ -78,6 +116,13 @@
         for (int j = 0; j < 6; ++j) {
           const float4 t = read_px_lds<decltype(tag)::value>(q.y[j], q.cb[j >> 1], q.cr[j >> 1], rk, rlut, 1.0f);
           const float kk = 1.0f - t.w;
+#if PH_FM_ROUTE
+          if (l == 0) {  // uniform: the bottom layer is taken as it is, its -0 included (ph_combine)
+            acc[3 * j] = t.x, acc[3 * j + 1] = t.y, acc[3 * j + 2] = t.z;
+            continue;
+          }
+          if (IMG) al[j] = fma_rn(al[j], 0.0f, t.w);  // NaN above an image pixel whose alpha is Inf or NaN
+#endif
           // acc = fma(acc, kk, t), acc as destination (combine.ts:45-65; layer 0: fma(0, k, t) == t)
           asm volatile("v_fma_f32 %0, %0, %3, %4\n\tv_fma_f32 %1, %1, %3, %5\n\tv_fma_f32 %2, %2, %3, %6"
                        : "+v"(acc[3 * j]), "+v"(acc[3 * j + 1]), "+v"(acc[3 * j + 2])
@@ -85,6 +130,14 @@
         }
         w = nxt;
       }
+#if PH_FM_ROUTE
+      if (karg->image_out && own) {  // the combined image, as ph_combine stores it (without an image layer its alpha is the chain's fma(1, 0, 1))
+        float4 *const po = reinterpret_cast<float4 *>(karg->image_out) + (size_t)f * 6u;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) store_image(po + j, make_float4(acc[3 * j], acc[3 * j + 1], acc[3 * j + 2], al[IMG ? j : 0]), karg->nt);
+      }
+      if (a.n_out)  // uniform
+#endif
 #pragma unroll
       for (int i = 0; i < 9; ++i) {  // the writers' first step needs no table: the 16-bit indices, two per register
         const uint32_t lo = __float_as_uint(lds_lut_index_unit(acc[2 * i]));
@@ -109,6 +162,9 @@
         PH_FM_BALANCE(p);
         const bool more = (p + 1 < P) && ((p + 1) * BS + wave_first < wg_end - tile_begin);
         const uint32_t f_next = more ? quad_of(p + 1) : f;
+#if PH_FM_ROUTE
+        own = tile_begin + p * BS + threadIdx.x < wg_end;
+#endif
         if (std_matrix) w = phase1_slice(std::true_type{}, w, f, f_next, more, st[p]);
         else w = phase1_slice(std::false_type{}, w, f, f_next, more, st[p]);
       }

@@ -1,7 +1,8 @@
 // ph_kernels_fused_out.h - what the kernels of ph_kernels_fused_multi_body.h share beside the body itself: the wave-priority ladder
-// and one output's share of one quad.  Included by ph_kernels_fused_multi.hip and ph_kernels_fused_trans.hip, each inside its own
-// unnamed namespace; the text is the one ph_kernels_fused_multi.hip always had, and its kernels compile to the same assembly,
-// instruction for instruction (profiles/fused_trans_resources.txt).
+// the table load of the kernels with more in their layer loop, and one output's share of one quad.  Included by
+// ph_kernels_fused_multi.hip, ph_kernels_fused_trans.hip and ph_kernels_fused_route.hip, each inside its own unnamed namespace; the
+// text is the one ph_kernels_fused_multi.hip always had, and its kernels compile to the same assembly, instruction for instruction
+// (profiles/fused_trans_resources.txt, profiles/fused_route_resources.txt).
 
 // as ph_kernels_lds.hip PH_BALANCE: a wave lowers its priority as it advances through its slices, so the waves of a SIMD
 // reach the phase barrier together (s_setprio takes an immediate: the switch folds once the slice loop is unrolled)
@@ -22,6 +23,27 @@ __device__ __forceinline__ void store_stream8(uint2 *p, const uint2 v) {
 #else
   *p = v;
 #endif
+}
+
+// lds_lut_load (ph_ldslut.h: its text, its s_waitcnt included) with the lane's place in the copy made at the load, from a pinned copy of
+// threadIdx.x.  Made from threadIdx.x as it stands, the wave's and the lane's offsets are loop invariants that the compiler carries
+// through both phases of every tile - in registers the kernels with more in their layer loop (ph_kernels_fused_trans.hip,
+// ph_kernels_fused_route.hip) do not have: four vector spills (profiles/fused_trans_resources.txt).
+template <int BS>
+__device__ __forceinline__ void fm_lut_load(const LutView &v) {
+  uint32_t tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const uint32_t n = (v.bytes - v.hole) / 16;
+  unsigned char *const dst = g_lds + v.hole;
+  const uint32_t wave = tid >> 6, lane = tid & 63;
+  const uint4 *src = reinterpret_cast<const uint4 *>(v.blob);
+  for (uint32_t base = wave * 64; base < n; base += BS) {
+    const uint32_t i = base + lane;
+    if (i < n)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + i),
+                                       (__attribute__((address_space(3))) void *)(dst + 16 * base), 16, 0, 0);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // One output's share of one quad: the six pixels' table values g[3 j + c] packed with the output's own writer matrix and stored.

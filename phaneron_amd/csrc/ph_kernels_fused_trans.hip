@@ -22,26 +22,6 @@ namespace {
 
 #include "ph_kernels_fused_out.h"
 
-// lds_lut_load (ph_ldslut.h: its text, its s_waitcnt included) with the lane's place in the copy made at the load, from a pinned copy of
-// threadIdx.x.  Made from threadIdx.x as it stands, the wave's and the lane's offsets are loop invariants that the compiler carries
-// through both phases of every tile - in registers this kernel does not have: four vector spills (profiles/fused_trans_resources.txt).
-template <int BS>
-__device__ __forceinline__ void fm_lut_load(const LutView &v) {
-  uint32_t tid = threadIdx.x;
-  asm volatile("" : "+v"(tid));
-  const uint32_t n = (v.bytes - v.hole) / 16;
-  unsigned char *const dst = g_lds + v.hole;
-  const uint32_t wave = tid >> 6, lane = tid & 63;
-  const uint4 *src = reinterpret_cast<const uint4 *>(v.blob);
-  for (uint32_t base = wave * 64; base < n; base += BS) {
-    const uint32_t i = base + lane;
-    if (i < n)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + i),
-                                       (__attribute__((address_space(3))) void *)(dst + 16 * base), 16, 0, 0);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
 // pixel J of a word quad as unpack_quad gives it (v210.ts:58-63): the fields are taken where the pixel is used, pixel by pixel -
 // unpacked up front, three quads' 36 values stand beside the accumulators and the tile's packed indices, and registers spill
 struct Yuv1f {

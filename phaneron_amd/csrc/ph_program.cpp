@@ -14,6 +14,7 @@
 // pack_write_multi_<n> (not a reference kernel): one image packed for n = 1..4 consumers (ph_pack_write_multi).
 // fused_v210_combine_multi_<n> (not a reference kernel): n plain v210 layers composited for 1..4 consumers (ph_fused_v210_combine_multi).
 // fused_v210_trans_<n> (not a reference kernel): the same with layers in a dissolve or a wipe (ph_fused_v210_transition_multi).
+// fused_v210_route_<n> (not a reference kernel): the same with f32 RGBA images among the layers and the combined image as an output (ph_fused_v210_route_multi).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -209,6 +210,7 @@ int resolve_program(const char *src, const char *name, ProgramChoice &c, std::st
   if (0 == strncmp(name, "combine_", 8)) return layers("combine_", 2, K_COMBINE);
   // not reference kernels: the headline chain / the field pipeline as one program
   if (0 == strncmp(name, "fused_v210_trans_", 17)) return layers("fused_v210_trans_", 1, K_FUSED_V210);  // (fused_v210_combine_multi_<n> with layers in a transition: told apart by name, ph_run.cpp)
+  if (0 == strncmp(name, "fused_v210_route_", 17)) return layers("fused_v210_route_", 1, K_FUSED_V210);  // (fused_v210_combine_multi_<n> with image layers and the image out: told apart by name, ph_run.cpp)
   if (0 == strncmp(name, "fused_v210_combine_multi_", 25)) return layers("fused_v210_combine_multi_", 1, K_FUSED_V210);  // (the same chain for several consumers: told apart by name, ph_run.cpp)
   if (0 == strncmp(name, "fused_v210_combine_", 19)) return layers("fused_v210_combine_", 1, K_FUSED_V210);
   if (0 == strcmp(name, "transition_dissolve")) return set(c, K_DISSOLVE, name, how);

@@ -365,16 +365,36 @@ struct FusedMultiCall {
   ph_chan_output outs[ph::kMaxFusedOuts];
   uint32_t width, height;
   Recipe r;  // (the Loader's triple; the Saver's pair of output 0)
+  // fused_v210_route_<n>: which layers are f32 RGBA images, and the combined image's buffer (or NULL)
+  int format[ph::kMaxLayers];
+  void *image_out;
 };
-static int fused_multi_parse(Args &a, FusedMultiCall *call) {
+// route: the program is fused_v210_route_<n> - l<i>Image, imageOut, and no `output` at all where imageOut is there
+static int fused_multi_parse(Args &a, FusedMultiCall *call, bool route = false) {
   const int n = call->n = a.prog->n_layers;
   uint32_t &width = call->width, &height = call->height;
   a.frame(&width, &height);
   const void **layers = call->layers;
-  for (int i = 0; i < n; ++i) layers[i] = a.buf(v210_bytes(width, height), "l%dIn", i)->dptr;
+  for (int i = 0; i < n; ++i) {
+    const double image = route ? a.num_or(0, "l%dImage", i) : 0;
+    if (image != 0 && image != 1) return a.fail(PH_E_INVALID, "kernel argument 'l%dImage': %g (0: l%dIn is a v210 frame, 1: an f32 RGBA image)", i, image, i);
+    call->format[i] = image != 0 ? PH_SRC_RGBA_F32 : PH_SRC_V210;
+    layers[i] = a.buf(image != 0 ? image_bytes(width, height) : v210_bytes(width, height), "l%dIn", i)->dptr;
+  }
   Recipe &r = call->r = Recipe();
   ph_chan_output *outs = call->outs;
   int &n_out = call->n_out = 1;
+  call->image_out = nullptr;
+  if (route) {
+    if (const ph_buf *image = a.buf_or_null(image_bytes(width, height), "imageOut")) call->image_out = image->dptr;
+    for (int i = 0; i < n && !a.rc && call->image_out; ++i)
+      if (layers[i] == call->image_out) return a.fail(PH_E_INVALID, "kernel argument 'imageOut': the buffer is layer %d's too", i);
+  }
+  if (call->image_out && !a.has("output")) {  // the image alone
+    n_out = 0;
+    a.loader(&r);
+    return a.rc;
+  }
   chan_output_parse(a, 0, width, height, &outs[0], &r.wr_cm, &r.wr_lut, &r);
   for (int k = 1; k < ph::kMaxFusedOuts && !a.rc && a.has("output%d", k); ++k) {
     ph_buf *wr_cm, *wr_lut;
@@ -388,6 +408,7 @@ static int fused_multi_parse(Args &a, FusedMultiCall *call) {
     if (fmt_v420(outs[k].format) && (height & 1)) return a.fail(PH_E_INVALID, "kernel argument 'out%sPacking': a 4:2:0 frame needs an even height (%u)", num, height);
     for (int j = 0; j < k; ++j)
       if (outs[j].planes[0] == outs[k].planes[0]) return a.fail(PH_E_INVALID, "kernel argument 'output%d': the buffer is another output's too", k);
+    if (call->image_out && outs[k].planes[0] == call->image_out) return a.fail(PH_E_INVALID, "kernel argument 'imageOut': the buffer is output %d's too", k);
   }
   return a.rc;
 }
@@ -424,6 +445,19 @@ static int fused_trans_job(Args &a, int queue) {
     }
   }
   return a.done() ? a.rc : ph_fused_v210_transition_multi(a.ctx, queue, c.n, layers, c.n_out, c.outs, c.width, c.height, c.r.rd_cm->dptr, c.r.rd_lut->dptr, c.r.rd_gm->dptr);
+}
+// fused_v210_route_<n> (K_FUSED_V210, told apart by its name; ph_fused_v210_route_multi): fused_v210_combine_multi_<n>'s arguments and
+// l<i>Image: 1 marks l<i>In as an f32 RGBA image of width x height x 16 bytes (absent or 0: a v210 frame); imageOut (optional): the
+// buffer that receives the combined image; `output` may be absent only when imageOut is there - no packed frame at all.  A launch of
+// its own, in its turn (ph_run_programs does not group it).
+static bool fused_is_route(const ph_program *prog) { return prog->kernel.compare(0, 17, "fused_v210_route_") == 0; }
+static int fused_route_job(Args &a, int queue) {
+  FusedMultiCall c;
+  if (const int rc = fused_multi_parse(a, &c, true)) return rc;
+  ph_route_layer layers[ph::kMaxLayers];
+  for (int i = 0; i < c.n; ++i) layers[i] = ph_route_layer{c.layers[i], c.format[i]};
+  return a.done() ? a.rc
+                  : ph_fused_v210_route_multi(a.ctx, queue, c.n, layers, c.image_out, c.n_out, c.outs, c.width, c.height, c.r.rd_cm->dptr, c.r.rd_lut->dptr, c.r.rd_gm->dptr);
 }
 
 // a compose_up_write_v210_<n> job's arguments (ph_run_program and ph_run_programs, which puts like jobs into one launch)
@@ -764,6 +798,7 @@ static int dispatch_compose(Args &a, int queue) {
     }
     case K_FUSED_V210: {
       if (fused_is_trans(prog)) return fused_trans_job(a, queue);
+      if (fused_is_route(prog)) return fused_route_job(a, queue);
       if (fused_is_multi(prog)) return fused_multi_job(a, queue);
       FusedCall f;
       fused_call_parse(a, &f);
@@ -929,10 +964,10 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       // (a frame for another consumer, or a chan_compose_multi_<n> job: a launch of its own, in its turn - unless the context option
       // "chan_batch_outs" lets such jobs share launches too: ph_chan_compose_batch_out)
       kind[(size_t)j] = calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
-    } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j]) && !fused_is_trans(progs[j])) {
+    } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j]) && !fused_is_trans(progs[j]) && !fused_is_route(progs[j])) {
       if ((rc = fused_call_parse(job, &fused[(size_t)j]))) return rc;
       kind[(size_t)j] = 2;
-    } else if (progs[j]->id == K_FUSED_V210 && ctx->fused_multi_batch && !fused_is_trans(progs[j])) {  // (a fused_v210_trans_<n> job: a launch of its own, in its turn)
+    } else if (progs[j]->id == K_FUSED_V210 && ctx->fused_multi_batch && !fused_is_trans(progs[j]) && !fused_is_route(progs[j])) {  // (a fused_v210_trans_<n> or fused_v210_route_<n> job: a launch of its own, in its turn)
       // (a fused_v210_combine_multi_<n> job: a launch of its own, in its turn - unless the context option "fused_multi_batch" lets such
       // jobs share launches: ph_fused_v210_combine_multi_batch)
       if (multis.empty()) multis.resize((size_t)n_jobs);

@@ -6,6 +6,7 @@ over xGMI, phaneron_amd/multigpu.py).  Per channel and frame: v210 read x3 -> co
 frame of the PREVIOUS step (a route is one frame late in the reference too) -> v210 write.
 
   python tools/route_bench.py                                       # one GPU: both routes are local aliases
+  python tools/route_bench.py --fused                               # the same frames, a channel's step in ONE launch (ph_fused_v210_route_multi)
   python tools/route_bench.py --loopback --check                    # one GPU, routes through RCCL to the own rank
   torchrun --nproc-per-node 8 tools/route_bench.py                  # 16 channels on 8 GPUs (RCCL over xGMI)
   torchrun --nproc-per-node 2 tools/route_bench.py --backend gloo --same-gpu --check   # functional test on one GPU
@@ -38,6 +39,8 @@ def parse(argv=None):
     ap.add_argument("--check", action="store_true", help="verify (bit for bit) that a routed layer is the source channel's output")
     ap.add_argument("--print-fingerprints", action="store_true", help="print a fingerprint of every channel's final v210 output")
     ap.add_argument("--loopback", action="store_true", help="send same-rank routes through RCCL too (peer = own rank)")
+    ap.add_argument("--fused", action="store_true", help="a channel's step is ONE ph_fused_v210_route_multi call (three v210 layers + the routed frame on top, "
+                    "the combined image out, one v210 output) instead of v210 read x3, combine_4 and v210 write")
     args = ap.parse_args(argv)
     if args.loopback:  # the one-device rehearsal of the hand-off always verifies what arrived (profiles/r05_route_loopback.jsonl said "not run")
         args.check = True
@@ -105,7 +108,29 @@ def measure(args, ctx, dist, rank, world, device, log=lambda m: print(m, flush=T
     torch.cuda.synchronize()
     exch_s = [0.0]
 
+    fused = getattr(args, "fused", False)
+
+    def fused_step(i):
+        # one launch per channel: nothing of this step can run before the routed frames are there
+        if on_device:
+            ex.start({ch: chan[ch]["out"][0] for ch in mine})
+            routed = ex.finish()
+        else:
+            ctx.wait()
+            t0 = time.perf_counter()
+            routed = ex.exchange({ch: chan[ch]["out"][0] for ch in mine})
+            torch.cuda.synchronize()
+            exch_s[0] += time.perf_counter() - t0
+        for ch in mine:
+            c = chan[ch]
+            ctx.fused_v210_route_multi(c["layers"] + [dict(data=routed[ch], format="rgba")], c["out"][1],
+                                       [dict(fmt="v210", planes=[c["v210"]], interlace=0, wr_cm=wr[0], wr_lut=wr[1])], w, h, *rd)
+        for ch in mine:
+            chan[ch]["out"].reverse()
+
     def step(i):
+        if fused:
+            return fused_step(i)
         if on_device:
             # the routed frames of the previous step travel on the communication stream WHILE this step's reads run;
             # nothing waits on the host
@@ -189,6 +214,7 @@ def measure(args, ctx, dist, rank, world, device, log=lambda m: print(m, flush=T
         "hop_GBps_unoverlapped": round(ex.traffic_bytes() / (hop_ms * 1e-3) / 1e9, 1) if hop_ms else None,
         "rccl_ranks_in_communicator": ex.route.comm_count() if on_device else None,
         "fingerprint_check": "ok" if checked else "not run",
+        **({"channel_step": "one fused_v210_route_multi launch"} if fused else {}),
         "exchange_ms_per_step_rank0": round(1e3 * per_step_exch, 3),
         "exchange_GBps_rank0": round(ex.traffic_bytes() / per_step_exch / 1e9, 1) if per_step_exch > 0 and ex.traffic_bytes() else None,
         "path": "ph_route: RCCL on its own stream, event-ordered, overlapped with the v210 reads" if on_device else
