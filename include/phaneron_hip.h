@@ -50,7 +50,8 @@ extern "C" {
  *    launch; context option "fused_multi_batch".  ph_compose_up_transition_multi (ph_image_trans_layer): dissolves and wipes inside the
  *    2 x 2-block compositor's launch.  ph_fused_v210_transition_multi (ph_fused_layer): dissolves and wipes between the plain v210 layers
  *    of ph_fused_v210_combine_multi's launch; program "fused_v210_trans_<n>".  ph_fused_v210_route_multi (ph_route_layer): a routed f32 RGBA
- *    image among that launch's layers and the combined image among its outputs; program "fused_v210_route_<n>" */
+ *    image among that launch's layers and the combined image among its outputs; program "fused_v210_route_<n>".  ph_debug_image_nt
+ *    (tests): which store policy the next launch would be given */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -792,7 +793,9 @@ int ph_lut_layout_of(const float *host_lut65536, ph_lut_layout *layout, void *ld
  *          caches, for a caller that knows nothing on the device reads the image soon; 2 does so only for images
  *          larger than "stream_threshold_mb" MiB (default 64; measured neutral on the reference-shaped chains).  By
  *          default an image is treated as what it is in a channel, an intermediate the next operator reads back;
- *          wire-format outputs always stream;
+ *          wire-format outputs always stream.  The policy applies to f32 RGBA images: the packed-RGB (12 bytes per pixel)
+ *          outputs of the de-interlacing reader (ph_yadif_pair_packed with PH_IMG_RGB_F32) are always stored plainly - the
+ *          2 x 2-block compositor reads them back at once;
  *          "host_pool_mb" (default 4096): how much pinned host memory released buffers' mirrors may keep for the next
  *          buffer of the same size (the reference creates its destinations per job and frame: io.ts:64-72) - this much,
  *          or as much as was ever attached to live buffers at once if that is more (a pool smaller than the working set
@@ -817,6 +820,10 @@ int ph_lut_layout_of(const float *host_lut65536, ph_lut_layout *layout, void *ld
  *          up to 8 jobs each (ph_fused_v210_combine_multi_batch); 0: each such job a launch of its own, in its turn.  The same bits
  *          either way.  Any other value is PH_E_INVALID. */
 int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value);
+/* TESTS: the store policy a launch issued next on the calling thread for `ctx` would be given for an f32 RGBA image of `bytes` bytes -
+ * 0 through the caches, 1 streamed - from "stream_images" and "stream_threshold_mb" (2: 1 for bytes > threshold << 20, strictly).
+ * Selects the context's device as a launch does; negative on error (a NULL or destroyed context). */
+int ph_debug_image_nt(ph_ctx *ctx, size_t bytes);
 
 /* ---- host colour maths (src/process/colourMaths.ts, run by Loader/Saver constructors
  *      loadSave.ts:50-63,139-149): outputs are HOST arrays the caller uploads. ------------------ */

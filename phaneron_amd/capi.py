@@ -41,6 +41,7 @@ EXPORTS = [
     "ph_compose_up_transition_multi",
     "ph_fused_v210_transition_multi",
     "ph_fused_v210_route_multi",
+    "ph_debug_image_nt",
 ]
 
 
@@ -253,6 +254,7 @@ def lib():
         "ph_image_unpack_rgb": (ci, [vp, ci, vp, ci, ci]),
         "ph_trace_begin": (ci, [ci]),
         "ph_trace_end": (ci, [C.c_char_p, cs]),
+        "ph_debug_image_nt": (ci, [vp, cs]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(l, name)  # AttributeError here = the header and the library disagree
@@ -440,6 +442,13 @@ class Context:
 
     def set_option(self, name, value):
         check(lib().ph_ctx_set_option(self.h, name.encode(), int(value)), self.h)
+
+    def debug_image_nt(self, nbytes):
+        """0 / 1: the store policy a launch issued next on this thread for this context would be given for an image of nbytes bytes"""
+        rc = lib().ph_debug_image_nt(self.h, int(nbytes))
+        if rc < 0:
+            check(rc, self.h)
+        return rc
 
     # typed kernels on torch tensors / raw pointers ------------------------------------------------
     def v210_read(self, src, dst, width, height, col_matrix, lut, gamut, queue=QUEUE_PROCESS):

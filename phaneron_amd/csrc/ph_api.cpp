@@ -935,6 +935,13 @@ int ph_debug_fused_lut_k(const float *host, uint32_t k5[5]) {
 uint32_t ph_debug_fused_job_of(uint32_t wg_per_job, uint32_t block) {
   return wg_per_job ? ph::fused_job_of(block, ph::fused_wg_magic(wg_per_job)) : 0;
 }
+// The store policy (ph_kernels.h image_nt) a launch issued next on the calling thread for `ctx` would be given for an image of `bytes`
+// bytes: the context's "stream_images" / "stream_threshold_mb" as set_device hands them to the launchers.  0 cached, 1 streamed.
+int ph_debug_image_nt(ph_ctx *ctx, size_t bytes) {
+  if (!ctx) return fail(PH_E_INVALID, "ph_debug_image_nt: ctx is NULL");
+  if (int rc = set_device(ctx)) return rc;
+  return (int)ph::image_nt(bytes);
+}
 
 int ph_lut_query(ph_ctx *ctx, const void *dev, uint32_t *lds_bytes, uint32_t *toe, uint32_t *shift) {
   if (!ctx) return fail(PH_E_INVALID, "ph_lut_query: ctx is NULL");

@@ -456,8 +456,8 @@ struct DeintArgs {  // ph_kernels_deint.hip
   float4 *out0[kMaxLayers], *out1[kMaxLayers];                         // RGBA f32: yadif parity 0 / parity 1
   int n, skip;
   uint32_t width, height, quads_pitch;
-  uint32_t rows_per_strip, strips, col_blocks, nt;  // filled in by the launcher
-  uint32_t rgb12;  // 1: the outputs are packed f32 RGB (12 bytes per pixel, the reader's alpha == 1 left out)
+  uint32_t rows_per_strip, strips, col_blocks, nt;  // filled in by the launcher; nt (image_nt) is the RGBA outputs' store policy only
+  uint32_t rgb12;  // 1: the outputs are packed f32 RGB (12 bytes per pixel, the reader's alpha == 1 left out); always stored plainly, nt or not
   const float *cm, *gm;
   LutView lut;
   // the windows' PH_FMT_* (one the fused reader takes: fmt_deint); planar frames: prev / cur / next are the Y planes, these the

@@ -190,15 +190,17 @@ __device__ __forceinline__ void v210_yadif_pair_body(const DeintArgs &a, const R
           ph_f3v *const pc = reinterpret_cast<ph_f3v *>(reinterpret_cast<char *>(out_copy) + ((size_t)y * w + xr) * 12);
           ph_f3v *const pi = reinterpret_cast<ph_f3v *>(reinterpret_cast<char *>(out_interp) + ((size_t)y * w + xr) * 12);
           const ph_f3v vc = {PH_W(C, 2).r, PH_W(C, 2).g, PH_W(C, 2).b}, vi = {res[0], res[1], res[2]};
+          // Stored plainly whatever a.nt says: a 12-byte store does not keep a nontemporal hint with this compiler (an `if (a.nt)`
+          // around __builtin_nontemporal_store came out as one global_store_dwordx3 without it: profiles/deint_store_policy_resources.txt),
+          // and the 2 x 2-block compositor reads these images back at once, so streaming them is not wanted anyway.  The store policy
+          // ("stream_images") is the RGBA form's, below.
 #if PH_DEINT_PRICE_INDEX  // timing only (tools/config3_price.py): the kept line stored as three 16-bit values - half the bytes
           typedef uint16_t ph_h3v __attribute__((ext_vector_type(3)));
           *reinterpret_cast<ph_h3v *>(reinterpret_cast<char *>(out_copy) + ((size_t)y * w + xr) * 6) =
               ph_h3v{(uint16_t)__float_as_uint(vc.x), (uint16_t)__float_as_uint(vc.y), (uint16_t)__float_as_uint(vc.z)};
-          if (a.nt) __builtin_nontemporal_store(vi, pi);
-          else *pi = vi;
+          *pi = vi;
 #else
-          if (a.nt) __builtin_nontemporal_store(vc, pc), __builtin_nontemporal_store(vi, pi);
-          else *pc = vc, *pi = vi;
+          *pc = vc, *pi = vi;
 #endif
         } else {
           store_image(out_copy + (size_t)y * w + xr, make_float4(PH_W(C, 2).r, PH_W(C, 2).g, PH_W(C, 2).b, 1.0f), a.nt);  // yadifCl.ts:117-121

@@ -115,6 +115,15 @@ def test_argument_validation_needs_no_device():
     assert l.ph_fused_v210_combine(None, 1, 2, arr3, one, 1920, 0, one, one, one, one, one) == 0
 
 
+def test_debug_image_nt_is_bound_and_refuses_a_null_context():
+    """the store-policy query of tests/test_store_policy_gpu.py: additive within ABI 8; it selects the context's device, so without one
+    it answers only for no context at all"""
+    l = capi.lib()
+    assert "ph_debug_image_nt" in capi.EXPORTS and l.ph_abi_version() == 8
+    assert l.ph_debug_image_nt(None, 16) < 0
+    assert "ph_debug_image_nt: ctx is NULL" in l.ph_last_error(None).decode()
+
+
 def test_pack_geometry():
     want = {"yuv422p10": [1920 * 2 * 1080, 1920 * 1080, 1920 * 1080], "yuv422p8": [1920 * 1080, 960 * 1080, 960 * 1080],
             "yuv420p": [1920 * 1080, 960 * 540, 960 * 540], "nv12": [1920 * 1080, 1920 * 540], "rgba8": [1920 * 4 * 1080],
