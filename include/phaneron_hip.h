@@ -51,7 +51,9 @@ extern "C" {
  *    2 x 2-block compositor's launch.  ph_fused_v210_transition_multi (ph_fused_layer): dissolves and wipes between the plain v210 layers
  *    of ph_fused_v210_combine_multi's launch; program "fused_v210_trans_<n>".  ph_fused_v210_route_multi (ph_route_layer): a routed f32 RGBA
  *    image among that launch's layers and the combined image among its outputs; program "fused_v210_route_<n>".  ph_debug_image_nt
- *    (tests): which store policy the next launch would be given */
+ *    (tests): which store policy the next launch would be given.  ph_clip_compose_multi: file playback - enlarged clips, decoders' frames
+ *    under the default fill - for up to four consumers of any format the channel kernel writes, read once per source pixel; program
+ *    "clip_compose_multi_<n>" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -269,6 +271,7 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * image format and sizes, placements, frame size, field mode, Saver - each one frame or a frame's two fields (ph_compose_up_write_v210_batch, up to four frames
  * per launch).  A chan_compose_multi_<n> job - chan_compose_v210_<n>'s arguments for output 0 and, for outputs k = 1..3, out<k>Packing,
  * output<k> (output<k>U / V / C), out<k>ColMatrix, out<k>GammaLut, interlace<k>: ph_chan_compose_multi - runs in its turn as a launch of its own.
+ * So does a clip_compose_multi_<n> job: the same arguments, name for name, through ph_clip_compose_multi (never grouped across jobs).
  * So does a compose_up_multi_<n> job (ph_compose_up_write_multi): compose_up_write_v210_<n>'s layers (l<i>In, l<i>Matrix, packedRgb,
  * l<i>Width / l<i>Height) and chan_compose_multi_<n>'s outputs.  Its twin - the other field of a de-interlaced frame - is announced by
  * l0In2 (l<i>In2: its images), and its planes carry the first job's names behind the word twin: twinOutput (twinOutputU / V / C),
@@ -579,6 +582,27 @@ typedef struct ph_chan_output {
   const void *wr_gamma_lut;     /* registered (LDS form) */
 } ph_chan_output;
 int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs,
+                          uint32_t out_width, uint32_t out_height, const void *rd_col_matrix12, const void *rd_gamma_lut,
+                          const void *rd_gamut9);
+/* FILE PLAYBACK for any consumer, up to four per call.  A decoder's frame is uploaded at the clip's own size and the Mixer's transform
+ * fills the channel with it (ffmpegProducer.ts:395-442, mixer.ts:189-228); for one v210 frame ph_chan_compose then reads every source
+ * pixel once (its enlarged-clip routes) instead of converting four taps per output pixel.  This entry does the same for an encoder's
+ * yuv422p10 / yuv422p8 / yuv420p / nv12 frame and the screen's rgba8 / bgra8, beside SDI's v210 or instead of it.  ph_chan_compose_multi's
+ * signature and contract: exactly, bit for bit and in order, the `n_out` calls of ph_chan_compose with each output's format, planes,
+ * interlace, matrix and table; it takes everything ph_chan_compose_multi takes and answers its errors (yuv420p10 / p010 outputs
+ * included); every check of the arguments is made before the context is looked at, and a refused call writes nothing.
+ * Routes, decided in this order.  (1) n_out == 1 with PH_FMT_V210 IS ph_chan_compose: same routes, same trace names.  (2) The lines
+ * composed are the field every output wants, else the whole frame, of which a field output takes the rows of its parity.  (3) A call
+ * whose layers are not all enlarged without rotation or mirroring (or decoders' frames of the channel's size under the default fill; no
+ * transition), with the context option "chan_enlarged" = 0, or with a table that has no LDS form, runs ph_chan_compose_multi on the same
+ * arguments inside the call, under that call's trace name.  (4) The outputs are grouped by registered writer table, in the order the
+ * tables first appear; a v210 output at out_width % 48 != 0 (its tail quad truncates table indices where the other writers round) is
+ * made by a ph_chan_compose call of its own.  (5) A group is ONE launch ("clip_up_multi<rgb|rgba>x<outputs>" in a trace: the format's
+ * reader into an L2-resident rectangle per workgroup tile, the writer's table swapped in, the 2 x 2-block compositor, every output's
+ * writer) where the frame is a single clip in a wire format - any PH_SRC_* but PH_SRC_RGBA_F32; a 4:2:0 one of an even height - and
+ * "chan_enlarged" = 1; else two stages: each clip through its format's reader into the queue's scratch images (finished f32 images are
+ * taken as they are), then "compose_up_multi<rgba>x<outputs>j1".  out_height == 0 is PH_OK. */
+int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs,
                           uint32_t out_width, uint32_t out_height, const void *rd_col_matrix12, const void *rd_gamma_lut,
                           const void *rd_gamut9);
 /* Several CHANNELS' frames for any consumers in one launch: ph_chan_compose_batch's sharing (the tables loaded once, the wave steps of

@@ -136,6 +136,9 @@ export class clContext {
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo
 	createBuffer(numBytes: number, bufDir: BufDir, bufType: BufSVMType, imageDims?: ImageDims, owner?: string): Promise<OpenCLBuffer>
+	/** extension: `name` may be `clip_compose_multi_<n>` (n = layers): `chan_compose_multi_<n>`'s arguments, name for name, through
+	 * ph_clip_compose_multi - file playback (an enlarged clip, a decoder's frame under the default fill) for up to four consumers with the clip
+	 * read once per source pixel; same bytes as `chan_compose_multi_<n>`.  Reached by name only: the recording context (defer.js) does not plan it. */
 	createProgram(kernel: string, options: { name: string; globalWorkItems?: number | Uint32Array | number[]; workItemsPerGroup?: number }): Promise<OpenCLProgram>
 	runProgram(program: OpenCLProgram, params: KernelParams, queue?: number): Promise<RunTimings>
 	/** Recording contexts only: runProgram without the promise (node/jobs.js uses it per job of a batch).  null = not a recording

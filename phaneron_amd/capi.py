@@ -42,6 +42,7 @@ EXPORTS = [
     "ph_fused_v210_transition_multi",
     "ph_fused_v210_route_multi",
     "ph_debug_image_nt",
+    "ph_clip_compose_multi",
 ]
 
 
@@ -225,6 +226,7 @@ def lib():
         "ph_chan_compose": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(C.c_void_p), cu, cu, cu, vp, vp, vp, vp, vp]),
         "ph_chan_compose_batch": (ci, [vp, ci, ci, C.POINTER(PhChanJob), cu, cu, vp, vp, vp, vp, vp]),
         "ph_chan_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
+        "ph_clip_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_compose_up_write_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_compose_up_transition_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageTransLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_pack_write_multi": (ci, [vp, ci, vp, ci, C.POINTER(PhChanOutput), cu, cu]),
@@ -860,6 +862,20 @@ class Context:
         outs = self._chan_outputs(outputs)
         args = (self.h, queue, len(layers), arr, len(outputs), outs, out_w, out_h, _ptr(rd_cm), _ptr(rd_lut), _ptr(rd_gm))
         fn, h = lib().ph_chan_compose_multi, self.h
+        if prepare_only:
+
+            def job(_keep=(keep, layers, outputs, outs)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
+
+    def clip_compose_multi(self, layers, outputs, out_w, out_h, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
+        """File playback for 1..4 consumers (ph_clip_compose_multi): chan_compose_multi's arguments and frames, with enlarged clips and
+        decoders' frames under the default fill read once per source pixel - one launch per writer table for a single wire-format clip."""
+        arr, keep = self._chan_layers(layers)
+        outs = self._chan_outputs(outputs)
+        args = (self.h, queue, len(layers), arr, len(outputs), outs, out_w, out_h, _ptr(rd_cm), _ptr(rd_lut), _ptr(rd_gm))
+        fn, h = lib().ph_clip_compose_multi, self.h
         if prepare_only:
 
             def job(_keep=(keep, layers, outputs, outs)):

@@ -1545,6 +1545,83 @@ static bool chan_enlarged_same_shape(int n, const ph_chan_layer *a, const ph_cha
   }
   return true;
 }
+// The reading half of the two-stage route, for `jobs` frames of one shape: every clip through its format's reader - as few launches as
+// their sizes allow - into the queue's scratch images (finished f32 images are taken as they are); il / sets: the images as the 2 x 2-block
+// compositor's entries take them.  The caller holds ctx->chan_scratch_mu[queue], and keeps it until its compositor launch is enqueued.
+static int chan_enlarged_read(ph_ctx *ctx, int queue, int jobs, int n, const ph_chan_layer *const *layers, const void *rd_cm, const void *rd_lut, const void *rd_gm,
+                              ph_image_layer (*il)[ph::kMaxLayers], const ph_image_layer **sets) {
+  // the images live in the channel compositor's scratch area of the queue (launches on one queue are in order)
+  size_t off[ph::kMaxLayers], per_job = 0;
+  bool one_size = true;
+  for (int i = 0; i < n; ++i) {
+    off[i] = per_job;
+    per_job += ((size_t)layers[0][i].src.width * layers[0][i].src.height * 16u + 255u) & ~(size_t)255u;
+    one_size = one_size && layers[0][i].src.width == layers[0][0].src.width && layers[0][i].src.height == layers[0][0].src.height;
+  }
+  const size_t total = per_job * (size_t)jobs;
+  // Three sets of images taken in turn: a frame's read kernel overwriting the very lines the previous frame's compositor has just read
+  // (still cached, in several XCDs' L2s) measured 11.7 us against 7.9 us into lines nobody holds (tools/enlarge_bench.py, PH_ENLARGE_RING)
+  // - while the sets together stay inside the 256 MB of last-level cache: four 1080p images (132 MB) in three sets measured 109 us per
+  // 2160p frame against 94 in one set that stays cached
+  const unsigned kTurns = total <= ((size_t)64 << 20) ? 3u : 1u;
+  char *base;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    int rc = chan_index_reserve(ctx, queue, total * kTurns);
+    if (rc) return rc;
+    base = (char *)ctx->chan_index[queue] + total * (ctx->chan_scratch_turn[queue]++ % kTurns);
+  }
+  const void *ins[ph::kMaxUpJobs * ph::kMaxLayers];
+  void *imgs[ph::kMaxUpJobs * ph::kMaxLayers];
+  for (int j = 0; j < jobs; ++j) {
+    for (int i = 0; i < n; ++i) {
+      const ph_chan_source &S = layers[j][i].src;
+      ins[j * n + i] = S.data, imgs[j * n + i] = S.format == PH_SRC_RGBA_F32 ? const_cast<void *>(S.data) : base + per_job * (size_t)j + off[i];
+      il[j][i] = ph_image_layer{imgs[j * n + i], PH_IMG_RGBA_F32, S.width, S.height, S.matrix9_host};
+    }
+    sets[j] = il[j];
+  }
+  int rc = PH_OK;
+  const int frames = jobs * n;
+  bool all_v210 = true;
+  for (int f = 0; f < frames; ++f) all_v210 = all_v210 && layers[f / n][f % n].src.format == PH_SRC_V210;
+  bool one_reader = !all_v210 && one_size && frames > 1;  // every frame a decoder's frame of ONE format, size and Loader matrix: one launch reads them all
+  for (int f = 0; f < frames && one_reader; ++f) {
+    const ph_chan_source &S = layers[f / n][f % n].src, &S0 = layers[0][0].src;
+    one_reader = S.format == S0.format && fmt_of_src(S.format) > PH_FMT_V210 && S.col_matrix12 == S0.col_matrix12;
+  }
+  if (one_reader) {
+    const void *planes[ph::kMaxUpJobs * ph::kMaxLayers][3];
+    for (int f = 0; f < frames; ++f) {
+      const ph_chan_source &S = layers[f / n][f % n].src;
+      planes[f][0] = S.data, planes[f][1] = S.data_u, planes[f][2] = S.data_v;
+    }
+    const ph_chan_source &S0 = layers[0][0].src;
+    for (int f = 0; f < frames && rc == PH_OK; f += ph::kMaxLayers)
+      rc = ph_pack_read_batch(ctx, queue, fmt_of_src(S0.format), frames - f < ph::kMaxLayers ? frames - f : ph::kMaxLayers, planes + f, imgs + f,
+                              (uint32_t)S0.width, (uint32_t)S0.height, S0.col_matrix12 ? S0.col_matrix12 : rd_cm, rd_lut, rd_gm);
+  } else if (!all_v210) {  // each clip through the reader of its format (a source with code ranges of its own brings its Loader matrix)
+    for (int f = 0; f < frames && rc == PH_OK; ++f) {
+      const ph_chan_source &S = layers[f / n][f % n].src;
+      if (S.format == PH_SRC_RGBA_F32) continue;  // an image: nothing to read
+      if (S.format == PH_SRC_V210) {
+        rc = ph_v210_read(ctx, queue, S.data, imgs[f], (uint32_t)S.width, (uint32_t)S.height, rd_cm, rd_lut, rd_gm);
+      } else {
+        const void *planes[3] = {S.data, S.data_u, S.data_v};
+        rc = ph_pack_read(ctx, queue, fmt_of_src(S.format), planes, imgs[f], (uint32_t)S.width, (uint32_t)S.height,
+                          S.col_matrix12 ? S.col_matrix12 : rd_cm, rd_lut, rd_gm);
+      }
+    }
+  } else if (one_size && frames > 1) {
+    for (int f = 0; f < frames && rc == PH_OK; f += ph::kMaxLayers)
+      rc = ph_v210_read_batch(ctx, queue, frames - f < ph::kMaxLayers ? frames - f : ph::kMaxLayers, ins + f, imgs + f, (uint32_t)layers[0][0].src.width,
+                              (uint32_t)layers[0][0].src.height, rd_cm, rd_lut, rd_gm);
+  } else {
+    for (int f = 0; f < frames && rc == PH_OK; ++f)
+      rc = ph_v210_read(ctx, queue, ins[f], imgs[f], (uint32_t)layers[f / n][f % n].src.width, (uint32_t)layers[f / n][f % n].src.height, rd_cm, rd_lut, rd_gm);
+  }
+  return rc;
+}
 // `jobs` frames of one shape and field mode (1 .. kMaxUpJobs, different outputs): the clips read - as few launches as their sizes allow -
 // and ONE compositor launch (ph_compose_up_write_v210_batch)
 static int chan_compose_enlarged(ph_ctx *ctx, int queue, int jobs, int n, const ph_chan_layer *const *layers, void *const *outs, uint32_t out_w, uint32_t out_h,
@@ -1599,79 +1676,10 @@ static int chan_compose_enlarged(ph_ctx *ctx, int queue, int jobs, int n, const 
       }
     }
   }
-  // the images live in the channel compositor's scratch area of the queue (launches on one queue are in order)
-  size_t off[ph::kMaxLayers], per_job = 0;
-  bool one_size = true;
-  for (int i = 0; i < n; ++i) {
-    off[i] = per_job;
-    per_job += ((size_t)layers[0][i].src.width * layers[0][i].src.height * 16u + 255u) & ~(size_t)255u;
-    one_size = one_size && layers[0][i].src.width == layers[0][0].src.width && layers[0][i].src.height == layers[0][0].src.height;
-  }
-  const size_t total = per_job * (size_t)jobs;
-  // Three sets of images taken in turn: a frame's read kernel overwriting the very lines the previous frame's compositor has just read
-  // (still cached, in several XCDs' L2s) measured 11.7 us against 7.9 us into lines nobody holds (tools/enlarge_bench.py, PH_ENLARGE_RING)
-  // - while the sets together stay inside the 256 MB of last-level cache: four 1080p images (132 MB) in three sets measured 109 us per
-  // 2160p frame against 94 in one set that stays cached
-  const unsigned kTurns = total <= ((size_t)64 << 20) ? 3u : 1u;
-  std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);  // until the compositor's launch is enqueued
-  char *base;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    int rc = chan_index_reserve(ctx, queue, total * kTurns);
-    if (rc) return rc;
-    base = (char *)ctx->chan_index[queue] + total * (ctx->chan_scratch_turn[queue]++ % kTurns);
-  }
-  const void *ins[ph::kMaxUpJobs * ph::kMaxLayers];
-  void *imgs[ph::kMaxUpJobs * ph::kMaxLayers];
   ph_image_layer il[ph::kMaxUpJobs][ph::kMaxLayers];
   const ph_image_layer *sets[ph::kMaxUpJobs];
-  for (int j = 0; j < jobs; ++j) {
-    for (int i = 0; i < n; ++i) {
-      const ph_chan_source &S = layers[j][i].src;
-      ins[j * n + i] = S.data, imgs[j * n + i] = S.format == PH_SRC_RGBA_F32 ? const_cast<void *>(S.data) : base + per_job * (size_t)j + off[i];
-      il[j][i] = ph_image_layer{imgs[j * n + i], PH_IMG_RGBA_F32, S.width, S.height, S.matrix9_host};
-    }
-    sets[j] = il[j];
-  }
-  int rc = PH_OK;
-  const int frames = jobs * n;
-  bool all_v210 = true;
-  for (int f = 0; f < frames; ++f) all_v210 = all_v210 && layers[f / n][f % n].src.format == PH_SRC_V210;
-  bool one_reader = !all_v210 && one_size && frames > 1;  // every frame a decoder's frame of ONE format, size and Loader matrix: one launch reads them all
-  for (int f = 0; f < frames && one_reader; ++f) {
-    const ph_chan_source &S = layers[f / n][f % n].src, &S0 = layers[0][0].src;
-    one_reader = S.format == S0.format && fmt_of_src(S.format) > PH_FMT_V210 && S.col_matrix12 == S0.col_matrix12;
-  }
-  if (one_reader) {
-    const void *planes[ph::kMaxUpJobs * ph::kMaxLayers][3];
-    for (int f = 0; f < frames; ++f) {
-      const ph_chan_source &S = layers[f / n][f % n].src;
-      planes[f][0] = S.data, planes[f][1] = S.data_u, planes[f][2] = S.data_v;
-    }
-    const ph_chan_source &S0 = layers[0][0].src;
-    for (int f = 0; f < frames && rc == PH_OK; f += ph::kMaxLayers)
-      rc = ph_pack_read_batch(ctx, queue, fmt_of_src(S0.format), frames - f < ph::kMaxLayers ? frames - f : ph::kMaxLayers, planes + f, imgs + f,
-                              (uint32_t)S0.width, (uint32_t)S0.height, S0.col_matrix12 ? S0.col_matrix12 : rd_cm, rd_lut, rd_gm);
-  } else if (!all_v210) {  // each clip through the reader of its format (a source with code ranges of its own brings its Loader matrix)
-    for (int f = 0; f < frames && rc == PH_OK; ++f) {
-      const ph_chan_source &S = layers[f / n][f % n].src;
-      if (S.format == PH_SRC_RGBA_F32) continue;  // an image: nothing to read
-      if (S.format == PH_SRC_V210) {
-        rc = ph_v210_read(ctx, queue, S.data, imgs[f], (uint32_t)S.width, (uint32_t)S.height, rd_cm, rd_lut, rd_gm);
-      } else {
-        const void *planes[3] = {S.data, S.data_u, S.data_v};
-        rc = ph_pack_read(ctx, queue, fmt_of_src(S.format), planes, imgs[f], (uint32_t)S.width, (uint32_t)S.height,
-                          S.col_matrix12 ? S.col_matrix12 : rd_cm, rd_lut, rd_gm);
-      }
-    }
-  } else if (one_size && frames > 1) {
-    for (int f = 0; f < frames && rc == PH_OK; f += ph::kMaxLayers)
-      rc = ph_v210_read_batch(ctx, queue, frames - f < ph::kMaxLayers ? frames - f : ph::kMaxLayers, ins + f, imgs + f, (uint32_t)layers[0][0].src.width,
-                              (uint32_t)layers[0][0].src.height, rd_cm, rd_lut, rd_gm);
-  } else {
-    for (int f = 0; f < frames && rc == PH_OK; ++f)
-      rc = ph_v210_read(ctx, queue, ins[f], imgs[f], (uint32_t)layers[f / n][f % n].src.width, (uint32_t)layers[f / n][f % n].src.height, rd_cm, rd_lut, rd_gm);
-  }
+  std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);  // until the compositor's launch is enqueued
+  const int rc = chan_enlarged_read(ctx, queue, jobs, n, layers, rd_cm, rd_lut, rd_gm, il, sets);
   if (rc) return rc;
   return ph_compose_up_write_v210_batch(ctx, queue, jobs, n, sets, outs, out_w, out_h, interlace, wr_cm, wr_lut);
 }
@@ -2747,6 +2755,134 @@ int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_
     if (!l.solo) e = ph::launch_compose_up_multi(stream_of(ctx, queue), l.m, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount);
     else if (!ph::trace_launch("compose_up_write_v210"))
       e = ph::launch_compose_up_write_v210(stream_of(ctx, queue), l.m.up, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount);
+    if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  }
+  return PH_OK;
+}
+
+/* File playback for any consumer, up to four per call: see include/phaneron_hip.h.  Exactly the n_out calls of ph_chan_compose in order,
+ * bit for bit; every check is made before the context is looked at, and a refused call writes nothing.  An enlarged clip (or a decoder's
+ * frame under the default fill) is read ONCE per source pixel instead of four times per output pixel: one launch of clip_up_multi_kernel
+ * per writer table where the frame is a single wire-format clip, else the format readers into the queue's scratch images and one
+ * compose_up_multi launch per table (n > 1: measured for v210 frames only - chan_compose_enlarged - tools/clip_multi_bench.py records
+ * n = 2 both ways).  Whatever these routes do not take runs ph_chan_compose_multi on the same arguments inside the call. */
+int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h,
+                          const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  const char *const fn = "ph_clip_compose_multi";
+  if (!layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n_out < 1 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  if (const int bad = fused_multi_outputs_check(fn, queue, n_out, outs, out_w, out_h)) return bad;
+  {  // the layers, as the channel kernel's entries check them (their texts)
+    ph::ChanArgs probe{};
+    int n_ops = 0;
+    if (const int bad = chan_ops(n, layers, out_w, out_h, probe.op, probe.plane_u, probe.plane_v, probe.cm_op, &probe.planar, &n_ops)) return bad;
+  }
+  if (!ctx) return fail(PH_E_INVALID, "%s: ctx is NULL", fn);
+  // 1. a single v210 frame IS ph_chan_compose: today's routes under today's names
+  if (n_out == 1 && outs[0].format == PH_FMT_V210)
+    return ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, outs[0].planes, out_w, out_h, outs[0].interlace, rd_cm, rd_lut, rd_gm, outs[0].wr_col_matrix12,
+                           outs[0].wr_gamma_lut);
+  // 2. the lines composed: the field every output wants, or the whole frame (a field output then takes the rows of its parity)
+  bool same_lines = true;
+  for (int k = 1; k < n_out; ++k) same_lines = same_lines && outs[k].interlace == outs[0].interlace;
+  const uint32_t interlace = same_lines ? outs[0].interlace : 0u;
+  // 3. not for these routes: the channel kernel, under its own trace name
+  const LutRef rref = lds_view(ctx, rd_lut);
+  LutRef wref[ph::kMaxUpOuts];
+  bool takes = ctx->chan_enlarged != 0 && rref.get() && chan_layers_enlarged(n, layers, out_w, out_h, interlace, /*v210_fill*/ true);
+  for (int k = 0; k < n_out && takes; ++k) {
+    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
+    takes = wref[k].get() && !(fmt_planar(outs[k].format) && out_w % 8);
+  }
+  ph::UpArgs base{};
+  if (takes) {
+    base.n = n, base.jobs = 1;
+    for (int i = 0; i < n; ++i) {
+      const ph_chan_source &S = layers[i].src;
+      base.layer[i].w = (uint32_t)S.width, base.layer[i].h = (uint32_t)S.height, base.layer[i].pitch = (uint32_t)S.width * 16u;
+      for (int k = 0; k < 6; ++k) base.layer[i].m[k] = S.matrix9_host[k];
+    }
+    compose_up_lines(base, out_w, out_h, interlace);
+    takes = ph::compose_up_eligible(base);
+  }
+  if (!takes) return ph_chan_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm);
+  if (!base.lines) return PH_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  // one launch of the clip kernel per table?  A single clip in a wire format (v210 included), a 4:2:0 one of an even height
+  bool one_launch = ctx->chan_enlarged == 1 && n == 1, alpha = false;
+  if (one_launch) {
+    const ph_chan_source &S = layers[0].src;
+    const int fmt = fmt_of_src(S.format);
+    one_launch = fmt >= 0 && !(fmt_v420(fmt) && (S.height & 1));
+    alpha = fmt_rgb8(fmt);
+  }
+  // 4. the outputs by writer table, in the order the tables first appear; a v210 output whose lines end in a tail quad truncates its table
+  // indices there where the other writers round: through ph_chan_compose, alone
+  // (the two stages: the clips are read once for all the call's tables; the queue's scratch area is held until the last compositor launch
+  // that takes the images is enqueued - and given up in front of a ph_chan_compose call, which takes the area itself)
+  ph_image_layer il[1][ph::kMaxLayers];
+  const ph_image_layer *sets[1];
+  std::unique_lock<std::mutex> images;
+  for (int k = 0; k < n_out; ++k) {
+    bool seen = false;
+    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    if (seen) continue;
+    ph::UpMultiArgs m{};
+    m.up = base, m.up.wr = *wref[k].get();
+    for (int j = k; j < n_out; ++j) {
+      const ph_chan_output &o = outs[j];
+      if (o.wr_gamma_lut != outs[k].wr_gamma_lut) continue;
+      if (o.format == PH_FMT_V210 && out_w % 48) {
+        if (images.owns_lock()) images.unlock();
+        rc = ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, o.planes, out_w, out_h, o.interlace, rd_cm, rd_lut, rd_gm, o.wr_col_matrix12, o.wr_gamma_lut);
+        if (rc) return rc;
+        continue;
+      }
+      ph::UpOut &d = m.out[m.n_out++];
+      d.fmt = (uint32_t)o.format;
+      d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48)
+      d.wr_cm = (const float *)o.wr_col_matrix12;
+      for (int i = 0; i < 3; ++i) d.plane[0][i] = o.planes[i];
+      d.takes = same_lines || !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
+      d.line_end = o.interlace ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as ph_chan_compose writes it)
+      d.field = o.interlace ? 1u : 0u;
+    }
+    if (!m.n_out) continue;
+    // 5. the group's launch
+    if (one_launch) {
+      ph::ClipUpMultiArgs c{};
+      c.clip.up = m.up, c.n_out = m.n_out;
+      for (uint32_t i = 0; i < m.n_out; ++i) c.out[i] = m.out[i];
+      c.clip.rd = *rref.get(), c.clip.rd_gm = (const float *)rd_gm;
+      const ph_chan_source &S = layers[0].src;
+      const int fmt = fmt_of_src(S.format);
+      c.clip.src[0] = ph::ClipSrc{S.data, S.data_u, S.data_v, (const float *)(S.col_matrix12 ? S.col_matrix12 : rd_cm), (uint32_t)fmt,
+                                  fmt == PH_FMT_V210 ? ph_v210_pitch_bytes((uint32_t)S.width) / 16u : ph::pack_pitch(fmt, (uint32_t)S.width)};
+      const uint32_t grid = ph::clip_up_plan(c.clip, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ false);
+      if (grid) {
+        if (images.owns_lock()) images.unlock();
+        std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);  // until the launch is enqueued
+        {
+          std::lock_guard<std::mutex> lock(ctx->mu);
+          rc = chan_index_reserve(ctx, queue, (size_t)c.clip.wg_bytes * grid + 4096u);
+          if (rc) return rc;
+          c.clip.scratch = (char *)ctx->chan_index[queue];
+        }
+        const hipError_t e = ph::launch_clip_up_multi(stream_of(ctx, queue), c, !alpha, grid);
+        if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+        continue;
+      }
+    }
+    // the two stages: every clip through its format's reader into the queue's scratch images, then the 2 x 2-block compositor's launch
+    if (!images.owns_lock()) {
+      images = std::unique_lock<std::mutex>(ctx->chan_scratch_mu[queue]);
+      rc = chan_enlarged_read(ctx, queue, 1, n, &layers, rd_cm, rd_lut, rd_gm, il, sets);
+      if (rc) return rc;
+    }
+    for (int i = 0; i < n; ++i) m.up.layer[i].ptr = il[0][i].data;
+    const hipError_t e = ph::launch_compose_up_multi(stream_of(ctx, queue), m, false, (uint32_t)ctx->props.multiProcessorCount);
     if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   }
   return PH_OK;

@@ -408,7 +408,8 @@ struct ClipUpArgs {
   uint32_t info_off;         // LDS offset of the per-layer rectangle descriptors (behind the larger table)
 };
 // picks the tiling and fills rect_off / rect_cap / wg_bytes / tcu / trp / gx / info_off; returns the number of workgroups (0: not for this kernel)
-uint32_t clip_up_plan(ClipUpArgs &a, bool rgb12, uint32_t num_cus);
+// (v210_tails == false: for clip_up_multi_kernel, which writes no v210 line tails - its wave steps cover the frame's columns, not the pitch)
+uint32_t clip_up_plan(ClipUpArgs &a, bool rgb12, uint32_t num_cus, bool v210_tails = true);
 hipError_t launch_clip_up_write_v210(hipStream_t s, const ClipUpArgs &a, bool rgb12, uint32_t grid);
 bool compose_up_eligible(const UpArgs &a);
 hipError_t launch_compose_up_write_v210(hipStream_t s, const UpArgs &a, bool rgb12, uint32_t num_cus);
@@ -435,6 +436,18 @@ struct UpMultiArgs {
 };
 static_assert(sizeof(UpMultiArgs) < 4096, "kernel arguments are limited to 4 KiB");
 hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb12, uint32_t num_cus);
+// Clips straight from their wire formats for ANY consumer, up to kMaxUpOuts per launch (ph_clip_compose_multi, clip_up_multi_kernel):
+// clip describes the composition as for clip_up_write_v210_kernel - clip.up.out / more_out / wr_cm are unused, clip.up.wr is the ONE
+// writer table of the launch, clip.up.jobs is 1 - and every output brings its format, job 0's planes and its writer matrix, as in
+// UpMultiArgs.  A v210 output's lines end on a 48-pixel block.
+struct ClipUpMultiArgs {
+  ClipUpArgs clip;
+  uint32_t n_out;
+  UpOut out[kMaxUpOuts];
+};
+static_assert(sizeof(ClipUpMultiArgs) < 4096, "kernel arguments are limited to 4 KiB");
+// grid: clip_up_plan(clip, rgb12, num_cus, false); named clip_up_multi<rgb|rgba>x<outputs> in a route trace
+hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rgb12, uint32_t grid);
 // The same with layers in a transition (ph_compose_up_transition_multi, compose_up_trans_kernel): a layer may bring an incoming image
 // (dissolve, wipe) and a mask (wipe), each with a size and a placement of its own.  multi.up.layer[l] is the layer's `src`; job j > 0
 // differs in the images' data, the outputs' planes and the mix values.  multi.up.shared is not used: geometry is per layer, and a

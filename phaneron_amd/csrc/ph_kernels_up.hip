@@ -1008,15 +1008,170 @@ __global__ __launch_bounds__(kUpBlock) void clip_up_write_v210_kernel(ClipUpArgs
   }
 }
 
+// ---- the same clips for ANY consumer, up to four per launch -----------------------------------------------------------------------------
+// File playback that feeds an encoder or the screen beside SDI (or instead of it): clip_up_write_v210_kernel's phase 1 and table swap,
+// its wave-step loop up to the block's four accumulators, and from there compose_up_multi_kernel's tail - the twelve writer-table reads
+// made once, then every output packing the same twelve values with its own matrix (up_write_out).  Both kernels keep their own text
+// (their code is pinned: profiles/up_out_resources.txt, profiles/clip_multi_resources.txt), so the two halves are copies kept in step by
+// hand.  One frame per launch (job 0's planes of every output: clip_step's job is 0); the wave step is the clip kernel's 126 columns for
+// every launch, a v210 output or not, so the tiling and the rectangle bounds of clip_up_plan hold as they are.  A v210 output's lines end
+// on a 48-pixel block here (the caller sends the others through the one-output routes: their tail quads truncate table indices).
+template <bool RGB12>
+__global__ __launch_bounds__(kUpBlock) void clip_up_multi_kernel(ClipUpMultiArgs cm) {
+  const ClipUpArgs &c = cm.clip;
+  const UpArgs &a = c.up;
+  constexpr uint32_t kTexel = RGB12 ? 12u : 16u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  // the tile
+  const uint32_t upr = (a.cover_w + kUpCols - 1u) / kUpCols, rps = (a.lines + 1u) / 2u;
+  const uint32_t ty = blockIdx.x / c.gx, tx = blockIdx.x - ty * c.gx;
+  const uint32_t cu0 = tx * c.tcu, rp0 = ty * c.trp;
+  const uint32_t ncu = cu0 + c.tcu <= upr ? c.tcu : upr - cu0, nrp = rp0 + c.trp <= rps ? c.trp : rps - rp0;
+  char *const mine = c.scratch + (size_t)blockIdx.x * c.wg_bytes;
+  // ---- phase 1: the reader's table; every layer's rectangle converted
+  const LutK rlk = make_lut_k(c.rd);
+  uint4 *const info = reinterpret_cast<uint4 *>(g_lds + c.info_off);
+#pragma unroll 1
+  for (int l = 0; l < a.n; ++l) {
+    const UpLayer L = a.layer[l];
+    const ClipSrc S = c.src[l];
+    const uint32_t x_first = cu0 * kUpCols, x_end = (cu0 + ncu) * kUpCols < a.out_w ? (cu0 + ncu) * kUpCols : a.out_w;
+    const uint32_t li_last = 2u * (rp0 + nrp) < a.lines ? 2u * (rp0 + nrp) - 1u : a.lines - 1u;
+    ClipRect R{0, 0, 0, 0};
+    if (x_first < x_end) {
+      int c_lo = clip_tap_col(L, x_first, a.out_w), c_hi = clip_tap_col(L, x_end - 1u, a.out_w) + 2;
+      int r_lo = clip_tap_row(L, a.first_line + 2u * rp0 * a.line_step, a.out_h), r_hi = clip_tap_row(L, a.first_line + li_last * a.line_step, a.out_h) + 2;
+      c_lo = c_lo < 0 ? 0 : c_lo, r_lo = r_lo < 0 ? 0 : r_lo;
+      c_hi = c_hi >= (int)L.w ? (int)L.w - 1 : c_hi, r_hi = r_hi >= (int)L.h ? (int)L.h - 1 : r_hi;
+      if (c_hi >= c_lo && r_hi >= r_lo) R = ClipRect{(uint32_t)c_lo, (uint32_t)r_lo, (uint32_t)(c_hi - c_lo + 1), (uint32_t)(r_hi - r_lo + 1)};
+    }
+    R.c0 = __builtin_amdgcn_readfirstlane(R.c0), R.r0 = __builtin_amdgcn_readfirstlane(R.r0);
+    R.w = __builtin_amdgcn_readfirstlane(R.w), R.h = __builtin_amdgcn_readfirstlane(R.h);
+    const uint32_t ppitch = R.w * kTexel;
+    if (ppitch && R.h * ppitch > c.rect_cap[l]) R.h = c.rect_cap[l] / ppitch;  // (the launcher's bound holds: never taken)
+    char *const dst = mine + c.rect_off[l];
+#define PH_CLIP_CASE(F)                                                                                   \
+  case F:                                                                                                  \
+    if (l == 0) clip_convert<F, RGB12, true>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);                    \
+    else clip_convert<F, RGB12, false>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);                          \
+    break;
+    switch (S.fmt) {  // uniform
+      PH_CLIP_CASE(PH_FMT_V210)
+      PH_CLIP_CASE(PH_FMT_YUV422P10)
+      PH_CLIP_CASE(PH_FMT_YUV422P8)
+      PH_CLIP_CASE(PH_FMT_YUV420P)
+      PH_CLIP_CASE(PH_FMT_NV12)
+      PH_CLIP_CASE(PH_FMT_YUV420P10)
+      PH_CLIP_CASE(PH_FMT_P010)
+      PH_CLIP_CASE(PH_FMT_RGBA8)
+      default:
+        if (l == 0) clip_convert<PH_FMT_BGRA8, RGB12, true>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);
+        else clip_convert<PH_FMT_BGRA8, RGB12, false>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);
+        break;
+    }
+#undef PH_CLIP_CASE
+    if (threadIdx.x == 0) {  // the layer as phase 2 sees it (clip_up_write_v210_kernel)
+      const uint64_t base = (uint64_t)(uintptr_t)dst - ((uint64_t)R.r0 * ppitch + (uint64_t)R.c0 * kTexel);
+      info[l] = make_uint4((uint32_t)base, (uint32_t)(base >> 32), ppitch ? ppitch : kTexel, 0u);
+    }
+  }
+  // ---- the swap: every wave's rectangle rows are in L2, the writer's table comes in
+  __threadfence_block();
+  __syncthreads();
+  const LutK lk = make_lut_k(a.wr);
+  lds_lut_load<kUpBlock>(a.wr);
+  __syncthreads();
+  // ---- phase 2: the 2 x 2-block compositor on the tile's wave steps, every output's writer behind it
+  const uint32_t role = lane - 3u * (lane / 3u);
+  auto layer_of = [&](int l) __attribute__((always_inline)) {
+    UpLayer L = a.layer[l];
+    const uint4 d = info[l];  // uniform address: one broadcast read
+    const uint64_t base = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)d.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)d.y) << 32;
+    L.ptr = reinterpret_cast<const void *>((uintptr_t)base);
+    L.pitch = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.z);
+    L.pad = kUpOutside - 16u;
+    return L;
+  };
+  const uint32_t units = ncu * nrp;
+  for (uint32_t u = wave; u < units; u += kUpBlock / 64) {
+    const uint32_t rp_in = ncu == 1u ? u : u / ncu, cu_in = u - rp_in * ncu;
+    UpStep st;
+    clip_step(a, 0u, cu0 + cu_in, rp0 + rp_in, lane, st);
+    UpAcc acc[2][2];
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) acc[dy][dx] = UpAcc{0.0f, 0.0f, 0.0f};
+    UpGeo geo;
+    auto layers = [&](auto inside_tag, auto shared_tag) __attribute__((always_inline)) {
+      constexpr bool INSIDE = decltype(inside_tag)::value, SHARED = decltype(shared_tag)::value;
+      {
+        const UpLayer L = layer_of(0);
+        if (!SHARED) geo = up_geo<RGB12>(L, st);
+        UpPatch p;
+        up_fetch<RGB12>(L, geo, p);
+        up_filter<RGB12, INSIDE, true>(p, geo, acc, lk);
+      }
+#pragma unroll 1
+      for (int l = 1; l < a.n; ++l) {
+        const UpLayer L = layer_of(l);
+        if (!SHARED) geo = up_geo<RGB12>(L, st);
+        UpPatch p;
+        up_fetch<RGB12>(L, geo, p);
+        up_filter<RGB12, INSIDE, false>(p, geo, acc, lk);
+      }
+    };
+    if (a.shared) {  // uniform
+      geo = up_geo<RGB12>(layer_of(0), st);
+      if (RGB12 && geo.all_inside) layers(std::true_type{}, std::true_type{});
+      else layers(std::false_type{}, std::true_type{});
+    } else {
+      layers(std::false_type{}, std::false_type{});
+    }
+    // the twelve table reads of the block's four pixels, started together - once for all outputs (compose_up_multi_kernel)
+    float t[2][2][3];
+    {
+      PxPending pend[2][2];
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx)
+          pend[dy][dx] = write_px_issue(lds_lut_index_unit(acc[dy][dx].r), lds_lut_index_unit(acc[dy][dx].g), lds_lut_index_unit(acc[dy][dx].b), lk);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx)
+          t[dy][dx][0] = lds_lut_finish(pend[dy][dx].r), t[dy][dx][1] = lds_lut_finish(pend[dy][dx].g), t[dy][dx][2] = lds_lut_finish(pend[dy][dx].b);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kMaxUpOuts; ++k) {
+      if (k >= cm.n_out) break;  // uniform
+      const UpOut &o = cm.out[k];
+      switch (o.fmt) {  // uniform
+        case PH_FMT_V210: up_write_out<PH_FMT_V210>(o, st, t, role); break;
+        case PH_FMT_YUV422P10: up_write_out<PH_FMT_YUV422P10>(o, st, t, role); break;
+        case PH_FMT_YUV422P8: up_write_out<PH_FMT_YUV422P8>(o, st, t, role); break;
+        case PH_FMT_YUV420P: up_write_out<PH_FMT_YUV420P>(o, st, t, role); break;
+        case PH_FMT_NV12: up_write_out<PH_FMT_NV12>(o, st, t, role); break;
+        case PH_FMT_RGBA8: up_write_out<PH_FMT_RGBA8>(o, st, t, role); break;
+        case PH_FMT_BGRA8: up_write_out<PH_FMT_BGRA8>(o, st, t, role); break;
+      }
+    }
+  }
+}
+
 // The tiling: tiles of tcu wave-step columns x trp row pairs, one per workgroup, as even as the frame allows (a workgroup's sixteen waves
 // share its tile's wave steps); then every layer's rectangle bound - the taps of (tcu * 126) columns x (2 * trp) written rows span that
 // many source texels times the magnification, + the patch's third column / row, + one for the rounding of the coordinates.
-uint32_t clip_up_plan(ClipUpArgs &c, bool rgb12, uint32_t num_cus) {
+// v210_tails: the launch's kernel writes a v210 line's tail quad and cleared slots (clip_up_write_v210_kernel<.., TAILS>), so the wave
+// steps cover the whole pitch; clip_up_multi_kernel has no such output and covers the frame's columns.
+uint32_t clip_up_plan(ClipUpArgs &c, bool rgb12, uint32_t num_cus, bool v210_tails) {
   UpArgs &a = c.up;
   if (!a.lines || !a.n || !num_cus) return 0;
   if (!a.jobs) a.jobs = 1;
   if (a.jobs > (uint32_t)kMaxUpJobs || (a.jobs > 1u && a.n != 1)) return 0;
-  const bool tails = a.out_w % 48u != 0;
+  const bool tails = v210_tails && a.out_w % 48u != 0;
   a.out_qpitch = v210_pitch_bytes(a.out_w) / 16u;
   a.cover_w = tails ? a.out_qpitch * 6u : a.out_w;
   a.shared = 1;
@@ -1073,6 +1228,26 @@ hipError_t launch_clip_up_write_v210(hipStream_t s, const ClipUpArgs &c, bool rg
   }
   if (tails) return rgb12 ? go(clip_up_write_v210_kernel<true, true, false>) : go(clip_up_write_v210_kernel<false, true, false>);
   return rgb12 ? go(clip_up_write_v210_kernel<true, false, false>) : go(clip_up_write_v210_kernel<false, false, false>);
+}
+
+// Several outputs of one clip composition: named clip_up_multi<rgb|rgba>x<outputs> in a route trace.  grid: clip_up_plan's, asked with
+// v210_tails == false.  Refuses what launch_compose_up_multi refuses.
+hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rgb12, uint32_t grid) {
+  const UpArgs &a = m.clip.up;
+  if (!grid || m.n_out < 1 || m.n_out > (uint32_t)kMaxUpOuts || a.jobs != 1u || a.n < 1 || a.n > kMaxLayers || a.cover_w != a.out_w) return hipErrorInvalidValue;
+  for (uint32_t k = 0; k < m.n_out; ++k)
+    if (!fmt_chan_out((int)m.out[k].fmt) || (m.out[k].fmt == PH_FMT_V210 && a.out_w % 48u)) return hipErrorInvalidValue;
+  char name[48];
+  snprintf(name, sizeof name, "clip_up_multi<%s>x%u", rgb12 ? "rgb" : "rgba", m.n_out);
+  if (trace_launch(name)) return hipSuccess;
+  const uint32_t lds = m.clip.info_off + 16u * (uint32_t)a.n;
+  auto go = [&](auto kernel) -> hipError_t {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
+    if (e != hipSuccess) return e;
+    kernel<<<grid, kUpBlock, lds, s>>>(m);
+    return hipGetLastError();
+  };
+  return rgb12 ? go(clip_up_multi_kernel<true>) : go(clip_up_multi_kernel<false>);
 }
 
 // Does the 2 x 2 block scheme apply?  Unrotated, unmirrored, MAGNIFIED in both directions (then the first taps of the two

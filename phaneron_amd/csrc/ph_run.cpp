@@ -235,7 +235,8 @@ struct ChanCall {
   void *out_planes[3];
   Recipe r;
   // chan_compose_multi_<n>: every output as ph_chan_compose_multi takes it (outs[0]: the one above)
-  bool multi;  // the program is chan_compose_multi_<n>
+  bool multi;  // the program is chan_compose_multi_<n> - or clip_compose_multi_<n>, which names its arguments the same
+  bool clip;   // the program is clip_compose_multi_<n>: ph_clip_compose_multi, a launch of its own in its turn
   int n_out;
   ph_chan_output outs[ph::kMaxChanOuts];
 };
@@ -320,7 +321,8 @@ static int chan_call_parse(Args &a, ChanCall *call) {
   call->r = Recipe();
   chan_output_parse(a, 0, width, height, &call->outs[0], &call->r.wr_cm, &call->r.wr_lut, &call->r);
   call->n_out = 1;
-  call->multi = a.prog->kernel.compare(0, 19, "chan_compose_multi_") == 0;
+  call->clip = a.prog->kernel.compare(0, 19, "clip_compose_multi_") == 0;
+  call->multi = call->clip || a.prog->kernel.compare(0, 19, "chan_compose_multi_") == 0;
   if (call->multi) {  // the outputs named, in turn
     ph_buf *wr_cm, *wr_lut;
     for (int k = 1; k < ph::kMaxChanOuts && !a.rc && a.has("output%d", k); ++k) chan_output_parse(a, k, width, height, &call->outs[call->n_out++], &wr_cm, &wr_lut);
@@ -748,6 +750,9 @@ static int dispatch_compose(Args &a, int queue) {
       ChanCall call;
       chan_call_parse(a, &call);
       if (a.done()) return a.rc;
+      if (call.clip)  // clip_compose_multi_<n>: chan_compose_multi_<n>'s arguments, name for name
+        return ph_clip_compose_multi(ctx, queue, call.n_layers, call.layers, call.n_out, call.outs, call.width, call.height, call.r.rd_cm->dptr, call.r.rd_lut->dptr,
+                                     call.r.rd_gm->dptr);
       if (call.multi)  // chan_compose_multi_<n>: chan_compose_v210_<n>'s arguments (output 0) and up to three more outputs (chan_output_parse)
         return ph_chan_compose_multi(ctx, queue, call.n_layers, call.layers, call.n_out, call.outs, call.width, call.height, call.r.rd_cm->dptr, call.r.rd_lut->dptr,
                                      call.r.rd_gm->dptr);
@@ -963,7 +968,8 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       if ((rc = chan_call_parse(job, &calls[(size_t)j]))) return rc;
       // (a frame for another consumer, or a chan_compose_multi_<n> job: a launch of its own, in its turn - unless the context option
       // "chan_batch_outs" lets such jobs share launches too: ph_chan_compose_batch_out)
-      kind[(size_t)j] = calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
+      // (a clip_compose_multi_<n> job: always a launch of its own, in its turn - no grouping across jobs)
+      kind[(size_t)j] = calls[(size_t)j].clip ? 0 : calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
     } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j]) && !fused_is_trans(progs[j]) && !fused_is_route(progs[j])) {
       if ((rc = fused_call_parse(job, &fused[(size_t)j]))) return rc;
       kind[(size_t)j] = 2;
