@@ -53,7 +53,8 @@ extern "C" {
  *    image among that launch's layers and the combined image among its outputs; program "fused_v210_route_<n>".  ph_debug_image_nt
  *    (tests): which store policy the next launch would be given.  ph_clip_compose_multi: file playback - enlarged clips, decoders' frames
  *    under the default fill - for up to four consumers of any format the channel kernel writes, read once per source pixel; program
- *    "clip_compose_multi_<n>" */
+ *    "clip_compose_multi_<n>".  ph_clip_compose_batch_out (ph_chan_job_out): several channels' such frames in one launch; context
+ *    option "clip_batch" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -271,7 +272,8 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * image format and sizes, placements, frame size, field mode, Saver - each one frame or a frame's two fields (ph_compose_up_write_v210_batch, up to four frames
  * per launch).  A chan_compose_multi_<n> job - chan_compose_v210_<n>'s arguments for output 0 and, for outputs k = 1..3, out<k>Packing,
  * output<k> (output<k>U / V / C), out<k>ColMatrix, out<k>GammaLut, interlace<k>: ph_chan_compose_multi - runs in its turn as a launch of its own.
- * So does a clip_compose_multi_<n> job: the same arguments, name for name, through ph_clip_compose_multi (never grouped across jobs).
+ * So does a clip_compose_multi_<n> job: the same arguments, name for name, through ph_clip_compose_multi (grouped across jobs only with the
+ * context option "clip_batch" = 1: consecutive such jobs of one geometry and Loader recipe in one ph_clip_compose_batch_out call).
  * So does a compose_up_multi_<n> job (ph_compose_up_write_multi): compose_up_write_v210_<n>'s layers (l<i>In, l<i>Matrix, packedRgb,
  * l<i>Width / l<i>Height) and chan_compose_multi_<n>'s outputs.  Its twin - the other field of a de-interlaced frame - is announced by
  * l0In2 (l<i>In2: its images), and its planes carry the first job's names behind the word twin: twinOutput (twinOutputU / V / C),
@@ -622,6 +624,22 @@ typedef struct ph_chan_job_out {
 } ph_chan_job_out;
 int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job_out *jobs, uint32_t out_width, uint32_t out_height,
                               const void *rd_col_matrix12, const void *rd_gamma_lut, const void *rd_gamut9);
+/* Several CHANNELS' FILE PLAYBACK for any consumers in one launch: ph_chan_compose_batch_out's signature, struct and contract with
+ * ph_clip_compose_multi's frames.  Exactly, in order and bit for bit, the `n_jobs` calls of ph_clip_compose_multi (n_jobs == 1 IS that
+ * call).  Every check of the arguments is made before the context is looked at; every job is checked and every launch planned before
+ * anything is launched: a refused call writes nothing.  out_height == 0 is PH_OK.  Errors as ph_chan_compose_batch_out, per job and
+ * output, under this entry's name (every table needs its LDS form).
+ * Consecutive jobs share ONE launch of the clip kernel ("clip_up_multi<rgb|rgba>x<outputs>j<jobs>" in a trace; a workgroup's tile belongs
+ * to one job) where each of them is a single clip in a wire format that ph_clip_compose_multi would make with one launch of that kernel
+ * (route 5 there, "chan_enlarged" = 1, all its outputs naming one writer table, no v210 output at out_width % 48 != 0, not a lone v210
+ * output), and all of them have one clip size and placement matrix, one alpha-ness (rgba8 / bgra8 clips against the others) and, output
+ * by output, one format, interlace, writer matrix and writer table.  The clips' wire formats and Loader matrices may differ from job to
+ * job.  A launch holds up to 4 jobs of up to 4 outputs; longer runs are split.  The entry point itself sees to it that no job of a
+ * launch reads or writes what another job of it writes, or writes what one reads (by byte range): such a job starts the next launch.
+ * Every other job - several layers, f32 images, the two-stage shapes, several writer tables, a lone v210 output, a v210 tail width - and
+ * a group of one job run in their turn through ph_clip_compose_multi, under that call's trace names. */
+int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job_out *jobs, uint32_t out_width, uint32_t out_height,
+                              const void *rd_col_matrix12, const void *rd_gamma_lut, const void *rd_gamut9);
 /* Several consumers' frames of one ENLARGED composition in one launch: the 2 x 2-block compositor (ph_compose_up_write_v210) with any
  * writer the channel kernel has - v210, yuv422p10, yuv422p8, yuv420p, nv12, rgba8, bgra8 - and up to four outputs.  The composition
  * runs once; the block's twelve writer-table reads are made once, and every output packs the same twelve values with its own writer
@@ -842,7 +860,10 @@ int ph_lut_layout_of(const float *host_lut65536, ph_lut_layout *layout, void *ld
  *          "fused_multi_batch" (default 0): 1 lets ph_run_programs put consecutive fused_v210_combine_multi_<n> jobs of one geometry,
  *          layer count, Loader recipe and output list (formats, field modes, writer matrices and tables, in order) into shared launches,
  *          up to 8 jobs each (ph_fused_v210_combine_multi_batch); 0: each such job a launch of its own, in its turn.  The same bits
- *          either way.  Any other value is PH_E_INVALID. */
+ *          either way.  Any other value is PH_E_INVALID;
+ *          "clip_batch" (default 0): 1 lets ph_run_programs put consecutive clip_compose_multi_<n> jobs of one geometry and Loader recipe
+ *          into one ph_clip_compose_batch_out call, which shares launches among those of one clip shape and output list; 0: each such
+ *          job a launch of its own, in its turn.  The same bits either way.  Any other value is PH_E_INVALID. */
 int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value);
 /* TESTS: the store policy a launch issued next on the calling thread for `ctx` would be given for an f32 RGBA image of `bytes` bytes -
  * 0 through the caches, 1 streamed - from "stream_images" and "stream_threshold_mb" (2: 1 for bytes > threshold << 20, strictly).

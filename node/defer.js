@@ -58,6 +58,7 @@ const pushNew = (list, v) => { if (!list.includes(v)) list.push(v) }
 const UP_WRITERS_DEFAULT = { alone: true, several: true } // (both measured 4 - 6 x faster than today's launches: profiles/up_out_bench.jsonl)
 // the arguments of the 2 x 2-block compositor's programs that may name a packed field image when the launch was told packedRgb
 const PACKED_IMAGE_ARG = /^l\d+(Incoming|Mask)?In2?$/
+const CLIP_JOB = /^clip_compose_multi_\d+$/ // (file playback posted by name: clipBatch)
 
 class Deferral {
 	constructor(ctx) {
@@ -135,8 +136,14 @@ class Deferral {
 		// `fusedBatch: true` on the context, with `fusedWriters`; off unless asked for (DESIGN.md 5.1: measured through the library, not
 		// yet through node).
 		this.fusedBatch = ctx.fusedBatch === true
+		// Several channels' file playback of a tick - clip_compose_multi_<n> jobs the application posts by name (no route is planned here) -
+		// go down in ONE runPrograms call with the library's context option "clip_batch" set (ph_clip_compose_batch_out: jobs of one clip
+		// shape and output list share a launch).  `clipBatch: true` on the context; off unless asked for - with it off every such job is
+		// launched as posted, in its turn.
+		this.clipBatch = ctx.clipBatch === true
 		this.batchOutsSet = false
 		this.fusedBatchSet = false
+		this.clipBatchSet = false
 	}
 
 	// ---- bookkeeping on buffers -----------------------------------------------------------------------------
@@ -375,7 +382,54 @@ class Deferral {
 			this.terminals = this.terminals.filter((n) => n.state === 'pending' && n !== node && n.queue !== node.queue)
 			if (others.length) return this._runMany([node, ...others], node)
 		}
+		if (!this.running && this.clipBatch && CLIP_JOB.test(node.program.name) && this.ctx._native.runPrograms && this._clipJobs(node)) return
 		if (!this._fused(node)) this._asPosted(node)
+	}
+	// clipBatch: somebody needs this clip_compose_multi_<n> job now - the other recorded jobs of that kind, geometry and queue whose operands
+	// are real go with it, in the order they were posted, as ONE runPrograms call (the library keeps call order among them and puts like
+	// jobs into shared launches).  false: nothing was launched for `node` (it is alone, or its operands failed) - it runs as posted.
+	_clipJobs(node) {
+		const ready = (n) => n.ins.every((i) => (!i._producer || i._producer === n || i._producer.state !== 'pending') && !i._failed)
+		try { for (const i of node.ins) if (i._producer && i._producer !== node) this.force(i) } catch (e) { return false } // (_plain tells the failure)
+		if (node.state !== 'pending' || !ready(node)) return node.state !== 'pending'
+		const gw = node.program.globalWorkItems
+		const jobs = Array.from(this.pending).filter((n) => n === node || (n.state === 'pending' && n.queue === node.queue && CLIP_JOB.test(n.program.name) &&
+			n.program.globalWorkItems[0] === gw[0] && n.program.globalWorkItems[1] === gw[1] && ready(n) && !Object.values(n.params).some((v) => v && v._packed != null)))
+		if (jobs.length < 2 || Object.values(node.params).some((v) => v && v._packed != null)) return false
+		const progs = []
+		const names = []
+		const values = []
+		for (const n of jobs) {
+			const nm = []
+			const vs = []
+			for (const k of Object.keys(n.params)) {
+				const v = n.params[k]
+				if (v === undefined || v === null) continue
+				nm.push(k)
+				vs.push(Buffer.isBuffer(v) ? v._handle : typeof v === 'boolean' ? (v ? 1 : 0) : v)
+			}
+			progs.push(n.program._handle), names.push(nm), values.push(vs)
+		}
+		if (!this.clipBatchSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'clip_batch', 1); this.clipBatchSet = true }
+		let made = jobs.length
+		let failure = null
+		try {
+			this.ctx._native.runPrograms(this.ctx._ctx, progs, names, values, node.queue)
+		} catch (e) {
+			// a call refused at a launch has made the launches of the jobs before the failing group (ph_run_programs_progress): those are done,
+			// the rest stay recorded and run as posted when somebody asks
+			failure = e
+			made = this.ctx._native.runProgramsProgress ? this.ctx._native.runProgramsProgress() : 0
+			this.stats.fallbacks++
+			this.stats.lastFallback = `clip batch of ${jobs.length}: ${e && e.message || e}`
+		}
+		if (made > 0) {
+			this.stats.launched++
+			this.stats.batched = (this.stats.batched || 0) + made
+			this.launchedOn.set(node.queue, (this.launchedOn.get(node.queue) || 0) + 1)
+			for (const n of jobs.slice(0, made)) { if (this.timed) this.timed.push(n); this._retire(n, 'done') }
+		}
+		return !failure || node.state !== 'pending'
 	}
 	// Several terminal writes at once.  `must` (or null) has to be done when this returns - fused, or as recorded; the others are
 	// launched only if their chain folds (what does not fold stays recorded until somebody asks).  Frames the channel kernel (or the

@@ -112,6 +112,11 @@ export class clContext {
 	 * `batchOuts` (default false; PHANERON_BATCH_OUTS=1): the frames several channels post in one tick for consumers other than SDI (an encoder's
 	 * yuv422p8, the screen's rgba8) and for several consumers at once share ONE launch of the channel kernel (the library's context option
 	 * `chan_batch_outs`, ph_chan_compose_batch_out); `false`: a launch per channel, in its turn.  The same bytes either way.
+	 * `clipBatch` (default false; PHANERON_CLIP_BATCH=1): the `clip_compose_multi_<n>` jobs (file playback, posted by name) that several channels
+	 * post in one tick go down in ONE runPrograms call with the library's context option `clip_batch` set, where jobs of one clip shape and list
+	 * of consumers share ONE launch (ph_clip_compose_batch_out, `clip_up_multi<rgb|rgba>x<outputs>j<jobs>` in a trace; counted under
+	 * `deferredStats().batched`); `false`: a launch per job, in its turn.  The same bytes either way.  No route is planned for it: the programs
+	 * are those the caller names.
 	 * `imageWriters` (default false; PHANERON_IMAGE_WRITERS=1): wire-format `write` jobs that are launched as posted (no fused plan, or every fused
 	 * candidate refused) take the pending writes of the other consumers of the same image - any of the nine formats, yuv420p10 / p010 included -
 	 * with them as ONE `pack_write_multi_<n>` launch (ph_pack_write_multi: the image read and looked up once); `false`: a launch per write.
@@ -131,14 +136,15 @@ export class clContext {
 	 * `strictHandles` (default false; PHANERON_STRICT_HANDLES=1): a fresh object per takeover, so that a reference kept past release()
 	 * is refused ('... released buffer') instead of aliasing the next owner's buffer - for running an application under test. */
 	constructor(params?: { platformIndex?: number; deviceIndex?: number; overlapping?: boolean; profile?: boolean; spinWaitMicros?: number; deferred?: boolean;
-		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; upTransitions?: boolean; fusedTransitions?: boolean; batchOuts?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
+		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; upTransitions?: boolean; fusedTransitions?: boolean; batchOuts?: boolean; clipBatch?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
 	readonly queue: { load: number; process: number; unload: number }
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo
 	createBuffer(numBytes: number, bufDir: BufDir, bufType: BufSVMType, imageDims?: ImageDims, owner?: string): Promise<OpenCLBuffer>
 	/** extension: `name` may be `clip_compose_multi_<n>` (n = layers): `chan_compose_multi_<n>`'s arguments, name for name, through
 	 * ph_clip_compose_multi - file playback (an enlarged clip, a decoder's frame under the default fill) for up to four consumers with the clip
-	 * read once per source pixel; same bytes as `chan_compose_multi_<n>`.  Reached by name only: the recording context (defer.js) does not plan it. */
+	 * read once per source pixel; same bytes as `chan_compose_multi_<n>`.  Reached by name only: the recording context (defer.js) does not plan it
+	 * (`clipBatch` lets the jobs of a tick share launches). */
 	createProgram(kernel: string, options: { name: string; globalWorkItems?: number | Uint32Array | number[]; workItemsPerGroup?: number }): Promise<OpenCLProgram>
 	runProgram(program: OpenCLProgram, params: KernelParams, queue?: number): Promise<RunTimings>
 	/** Recording contexts only: runProgram without the promise (node/jobs.js uses it per job of a batch).  null = not a recording

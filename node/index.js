@@ -171,6 +171,9 @@ class clContext {
 		this.fusedTransitions = params.fusedTransitions === undefined ? process.env.PHANERON_FUSED_TRANSITIONS === '1' : !!params.fusedTransitions
 		// several channels' frames of a tick for consumers other than SDI, or for several consumers, as one launch (node/defer.js batchOuts): off unless asked for
 		this.batchOuts = params.batchOuts === undefined ? process.env.PHANERON_BATCH_OUTS === '1' : !!params.batchOuts
+		// several channels' file playback of a tick - clip_compose_multi_<n> jobs posted by name - in one runPrograms call with the library's
+		// "clip_batch" set (node/defer.js clipBatch): off unless asked for (clipBatch: true, or PHANERON_CLIP_BATCH=1)
+		this.clipBatch = params.clipBatch === undefined ? process.env.PHANERON_CLIP_BATCH === '1' : !!params.clipBatch
 		// wire-format writes of one image that are launched as posted - a routed channel's image, a frame whose fused launch was refused, the 10-bit
 		// 4:2:0 consumers - as ONE pack_write_multi_<n> launch (node/defer.js imageWriters): off unless asked for (DESIGN.md 5.1: v210 + rgba8 alone measured slower)
 		this.imageWriters = params.imageWriters === undefined ? process.env.PHANERON_IMAGE_WRITERS === '1' : !!params.imageWriters

@@ -43,6 +43,7 @@ EXPORTS = [
     "ph_fused_v210_route_multi",
     "ph_debug_image_nt",
     "ph_clip_compose_multi",
+    "ph_clip_compose_batch_out",
 ]
 
 
@@ -235,6 +236,7 @@ def lib():
         "ph_fused_v210_route_multi": (ci, [vp, ci, ci, C.POINTER(PhRouteLayer), vp, ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_fused_v210_combine_multi_batch": (ci, [vp, ci, ci, ci, C.POINTER(C.c_void_p), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_chan_compose_batch_out": (ci, [vp, ci, ci, C.POINTER(PhChanJobOut), cu, cu, vp, vp, vp]),
+        "ph_clip_compose_batch_out": (ci, [vp, ci, ci, C.POINTER(PhChanJobOut), cu, cu, vp, vp, vp]),
         "ph_ctx_host_pool_stats": (ci, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
         "ph_event_record_timed": (ci, [vp, ci, C.POINTER(vp)]),
         "ph_event_elapsed_us": (ci, [vp, vp, C.POINTER(cu)]),
@@ -879,6 +881,25 @@ class Context:
         if prepare_only:
 
             def job(_keep=(keep, layers, outputs, outs)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
+
+    def clip_compose_batch_out(self, jobs, out_w, out_h, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
+        """Several channels' file playback for any consumers (ph_clip_compose_batch_out): chan_compose_batch_out's arguments, the frames of
+        one clip_compose_multi call per job - consecutive single-clip jobs of one shape and output list in one launch of the clip kernel."""
+        arr = (PhChanJobOut * max(len(jobs), 1))()
+        keep = []
+        for j, (layers, outputs) in enumerate(jobs):
+            la, k = self._chan_layers(layers)
+            outs = self._chan_outputs(outputs)
+            keep.append((la, k, layers, outputs, outs))
+            arr[j].n, arr[j].layers, arr[j].n_out, arr[j].outs = len(layers), la, len(outputs), outs
+        args = (self.h, queue, len(jobs), arr, out_w, out_h, _ptr(rd_cm), _ptr(rd_lut), _ptr(rd_gm))
+        fn, h = lib().ph_clip_compose_batch_out, self.h
+        if prepare_only:
+
+            def job(_keep=(keep, arr)):
                 check(fn(*args), h)
             return job
         check(fn(*args), h)

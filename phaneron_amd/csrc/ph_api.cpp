@@ -971,6 +971,10 @@ int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value) {
     if (value != 0 && value != 1) return fail(PH_E_INVALID, "chan_batch_outs: 0 (a launch per such job) or 1 (shared launches)");
     return ctx->chan_batch_outs = value, PH_OK;
   }
+  if (0 == strcmp(name, "clip_batch")) {
+    if (value != 0 && value != 1) return fail(PH_E_INVALID, "clip_batch: 0 (a launch per such job) or 1 (shared launches)");
+    return ctx->clip_batch = value, PH_OK;
+  }
   if (0 == strcmp(name, "fused_multi_wgs")) {
     if (value < 0) return fail(PH_E_INVALID, "fused_multi_wgs: a number of workgroups, or 0 for no cap");
     return ctx->fused_multi_wgs = value, PH_OK;
@@ -2883,6 +2887,199 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
     }
     for (int i = 0; i < n; ++i) m.up.layer[i].ptr = il[0][i].data;
     const hipError_t e = ph::launch_compose_up_multi(stream_of(ctx, queue), m, false, (uint32_t)ctx->props.multiProcessorCount);
+    if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  }
+  return PH_OK;
+}
+
+namespace {
+struct ClipOutJob {
+  bool joins = false, alpha = false, same_lines = true;
+  uint32_t interlace = 0;  // the lines the job composes: the field every output wants, or the frame
+  std::vector<ChanSpan> reads, writes;
+};
+struct ClipBatchStep {  // what the call does in its turn: a shared launch of jobs [first, first + m.clip.up.jobs), or job `first` handed on
+  int first = 0;
+  bool shared = false, alpha = false;
+  uint32_t grid = 0;
+  ph::ClipUpMultiArgs m{};
+};
+}  // namespace
+
+/* Several CHANNELS' file playback for any consumers in one launch: see include/phaneron_hip.h.  Exactly, in order and bit for bit, the
+ * n_jobs calls of ph_clip_compose_multi.  Every check of the arguments is made before the context is looked at; every job is checked and
+ * every launch planned before anything is launched.  Consecutive jobs that ph_clip_compose_multi would make with ONE launch of the clip
+ * kernel each, of one clip size, placement and alpha-ness and of one output list (format, interlace, writer matrix and table, output by
+ * output; one table for all), share a launch of clip_up_multi_kernel<.., MULTI>: a tile belongs to one job.  The clips' wire formats may
+ * differ (ClipSrc::fmt is per job - as in the v210 form, chan_compose_enlarged).  Everything else runs ph_clip_compose_multi in its turn. */
+int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job_out *jobs, uint32_t out_w, uint32_t out_h, const void *rd_cm,
+                              const void *rd_lut, const void *rd_gm) {
+  static const char *const fn = "ph_clip_compose_batch_out";
+  if (!jobs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  PH_QUEUE(fn, queue);
+  if (n_jobs < 1) return fail(PH_E_INVALID, "%s: no jobs", fn);
+  if (!out_w) return fail(PH_E_INVALID, "%s: width 0", fn);
+  std::vector<ClipOutJob> plan((size_t)n_jobs);
+  for (int j = 0; j < n_jobs; ++j) {
+    const ph_chan_job_out &J = jobs[j];
+    ClipOutJob &P = plan[(size_t)j];
+    char where[24];
+    snprintf(where, sizeof where, "job %d: ", j);
+    if (!J.layers || !J.outs) return fail(PH_E_INVALID, "%s: %sNULL argument", fn, where);
+    if (J.n_out < 1 || J.n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: %s1..%d outputs (%d)", fn, where, ph::kMaxUpOuts, J.n_out);
+    if (J.n < 1 || J.n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: %s1..%d layers", fn, where, ph::kMaxLayers);
+    for (int k = 0; k < J.n_out; ++k) {
+      const ph_chan_output &o = J.outs[k];
+      if (const int bad = chan_output_check(fn, where, k, o, out_w, out_h)) return bad;
+      for (int i = 0; i < k; ++i)
+        if (J.outs[i].planes[0] == o.planes[0]) return fail(PH_E_INVALID, "%s: %soutputs %d and %d name the same plane", fn, where, i, k);
+      P.same_lines = P.same_lines && o.interlace == J.outs[0].interlace;
+      size_t bytes[3];
+      const int planes = ph::pack_plane_bytes(o.format, out_w, out_h, bytes);
+      for (int i = 0; i < planes; ++i) P.writes.push_back(ChanSpan{(const char *)o.planes[i], bytes[i], o.format, o.interlace});
+    }
+    P.interlace = P.same_lines ? J.outs[0].interlace : 0u;
+    ph::ChanArgs one{};  // the layers, as the channel kernel's entries check them (their texts); what the job reads
+    int n_ops = 0;
+    if (const int bad = chan_ops(J.n, J.layers, out_w, out_h, one.op, one.plane_u, one.plane_v, one.cm_op, &one.planar, &n_ops)) return bad;
+    for (int i = 0; i < n_ops; ++i) {
+      const ph::ChanSrc &src = one.op[i].src;
+      P.reads.push_back(ChanSpan{(const char *)src.ptr, (size_t)src.pitch * src.h, -1, 0u});
+      // a planar frame's chroma planes, sized as the kernel sizes them (ph_kernels_chan.hip planes_of)
+      const bool v420 = src.kind == ph::kChanP8x420 || src.kind == ph::kChanNv12 || src.kind == ph::kChanP10x420 || src.kind == ph::kChanP010;
+      const bool cbcr = src.kind == ph::kChanNv12 || src.kind == ph::kChanP010;
+      const size_t chroma = (size_t)(cbcr ? src.pitch : src.pitch >> 1) * (v420 ? (src.h + 1u) >> 1 : src.h);
+      if (one.plane_u[i]) P.reads.push_back(ChanSpan{(const char *)one.plane_u[i], chroma, -1, 0u});
+      if (one.plane_v[i]) P.reads.push_back(ChanSpan{(const char *)one.plane_v[i], chroma, -1, 0u});
+    }
+  }
+  if (!ctx) return fail(PH_E_INVALID, "%s: ctx is NULL", fn);
+  if (n_jobs == 1)  // a group of one job is that call
+    return ph_clip_compose_multi(ctx, queue, jobs[0].n, jobs[0].layers, jobs[0].n_out, jobs[0].outs, out_w, out_h, rd_cm, rd_lut, rd_gm);
+  const LutRef rref = lds_view(ctx, rd_lut);
+  if (!rref.get()) return fail(PH_E_INVALID, "%s: the reader gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn);
+  for (int j = 0; j < n_jobs; ++j)
+    for (int k = 0; k < jobs[j].n_out; ++k)
+      if (!lds_view(ctx, jobs[j].outs[k].wr_gamma_lut).found)
+        return fail(PH_E_INVALID, "%s: job %d: output %d: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn, j, k);
+  const uint32_t num_cus = (uint32_t)ctx->props.multiProcessorCount;
+  // one job's launch arguments as ph_clip_compose_multi makes them for its one-launch route (false: the job is not for that route as a whole)
+  auto clip_args = [&](int j, ph::ClipUpMultiArgs &c, bool &alpha) {
+    const ph_chan_job_out &J = jobs[j];
+    const ClipOutJob &P = plan[(size_t)j];
+    if (ctx->chan_enlarged != 1 || J.n != 1) return false;
+    if (J.n_out == 1 && J.outs[0].format == PH_FMT_V210) return false;  // (ph_chan_compose, under its names)
+    const ph_chan_source &S = J.layers[0].src;
+    const int fmt = fmt_of_src(S.format);
+    if (fmt < 0 || (fmt_v420(fmt) && (S.height & 1))) return false;
+    for (int k = 0; k < J.n_out; ++k)
+      if (J.outs[k].wr_gamma_lut != J.outs[0].wr_gamma_lut || (J.outs[k].format == PH_FMT_V210 && out_w % 48)) return false;  // (several launches there)
+    if (!chan_layers_enlarged(1, J.layers, out_w, out_h, P.interlace, /*v210_fill*/ true)) return false;
+    c = ph::ClipUpMultiArgs{};
+    ph::UpArgs &a = c.clip.up;
+    a.n = 1, a.jobs = 1;
+    a.layer[0].w = (uint32_t)S.width, a.layer[0].h = (uint32_t)S.height, a.layer[0].pitch = (uint32_t)S.width * 16u;
+    for (int k = 0; k < 6; ++k) a.layer[0].m[k] = S.matrix9_host[k];
+    compose_up_lines(a, out_w, out_h, P.interlace);
+    if (!ph::compose_up_eligible(a) || !a.lines) return false;
+    a.wr = lds_view(ctx, J.outs[0].wr_gamma_lut).view;
+    alpha = fmt_rgb8(fmt);
+    c.n_out = (uint32_t)J.n_out;
+    for (int k = 0; k < J.n_out; ++k) {
+      const ph_chan_output &o = J.outs[k];
+      ph::UpOut &d = c.out[k];
+      d.fmt = (uint32_t)o.format;
+      d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48)
+      d.wr_cm = (const float *)o.wr_col_matrix12;
+      for (int i = 0; i < 3; ++i) d.plane[0][i] = o.planes[i];
+      d.takes = P.same_lines || !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
+      d.line_end = o.interlace ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as ph_chan_compose writes it)
+      d.field = o.interlace ? 1u : 0u;
+    }
+    c.clip.rd = rref.view, c.clip.rd_gm = (const float *)rd_gm;
+    c.clip.src[0] = ph::ClipSrc{S.data, S.data_u, S.data_v, (const float *)(S.col_matrix12 ? S.col_matrix12 : rd_cm), (uint32_t)fmt,
+                                fmt == PH_FMT_V210 ? ph_v210_pitch_bytes((uint32_t)S.width) / 16u : ph::pack_pitch(fmt, (uint32_t)S.width)};
+    ph::ClipUpArgs probe = c.clip;
+    return ph::clip_up_plan(probe, !alpha, num_cus, /*v210_tails*/ false) != 0;
+  };
+  // the plan: the steps of the call, in the jobs' order
+  std::vector<ClipBatchStep> steps;
+  ClipBatchStep cur;  // the launch being collected
+  auto flush = [&]() {
+    if (!cur.shared) return;
+    ph::ClipUpArgs &c = cur.m.clip;
+    if (c.up.jobs > 1u) cur.grid = ph::clip_up_plan(c, !cur.alpha, num_cus, /*v210_tails*/ false);
+    if (c.up.jobs > 1u && cur.grid) {
+      steps.push_back(cur);
+    } else {  // a group of one job (or a tiling the kernel does not take): ph_clip_compose_multi, job by job
+      for (uint32_t i = 0; i < c.up.jobs; ++i) {
+        ClipBatchStep own;
+        own.first = cur.first + (int)i;
+        steps.push_back(own);
+      }
+    }
+    cur = ClipBatchStep{};
+  };
+  for (int j = 0; j < n_jobs; ++j) {
+    const ph_chan_job_out &J = jobs[j];
+    const ClipOutJob &P = plan[(size_t)j];
+    ph::ClipUpMultiArgs c;
+    bool alpha = false;
+    if (!clip_args(j, c, alpha)) {  // in its turn, on its own
+      flush();
+      ClipBatchStep own;
+      own.first = j;
+      steps.push_back(own);
+      continue;
+    }
+    if (cur.shared) {
+      const ph::UpArgs &a = cur.m.clip.up;
+      const ph_chan_job_out &J0 = jobs[cur.first];
+      // no job of a launch reads or writes what another job of it writes: such a job starts the next launch
+      bool apart = a.jobs >= (uint32_t)ph::kMaxUpJobs || alpha != cur.alpha || J.n_out != J0.n_out || plan[(size_t)cur.first].interlace != P.interlace ||
+                   !chan_enlarged_same_shape(1, J0.layers, J.layers);
+      for (int k = 0; k < J.n_out && !apart; ++k) {
+        const ph_chan_output &o = J.outs[k], &o0 = J0.outs[k];
+        apart = o.format != o0.format || o.interlace != o0.interlace || o.wr_col_matrix12 != o0.wr_col_matrix12 || o.wr_gamma_lut != o0.wr_gamma_lut;
+      }
+      for (int i = cur.first; i < cur.first + (int)a.jobs && !apart; ++i) {
+        const ClipOutJob &Q = plan[(size_t)i];
+        for (const ChanSpan &w : P.writes) {
+          for (const ChanSpan &r : Q.reads) apart = apart || spans_meet(w, r);
+          for (const ChanSpan &v : Q.writes) apart = apart || spans_meet(w, v);
+        }
+        for (const ChanSpan &r : P.reads)
+          for (const ChanSpan &v : Q.writes) apart = apart || spans_meet(r, v);
+      }
+      if (apart) flush();
+    }
+    if (!cur.shared) {
+      cur.shared = true, cur.first = j, cur.alpha = alpha, cur.m = c;
+      continue;
+    }
+    const uint32_t at = cur.m.clip.up.jobs++;
+    cur.m.clip.src[at] = c.clip.src[0];
+    for (int k = 0; k < J.n_out; ++k)
+      for (int i = 0; i < 3; ++i) cur.m.out[k].plane[at][i] = c.out[k].plane[0][i];
+  }
+  flush();
+  // the launches
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  for (ClipBatchStep &s : steps) {
+    if (!s.shared) {
+      const ph_chan_job_out &J = jobs[s.first];
+      if ((rc = ph_clip_compose_multi(ctx, queue, J.n, J.layers, J.n_out, J.outs, out_w, out_h, rd_cm, rd_lut, rd_gm))) return rc;
+      continue;
+    }
+    std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);  // until the launch is enqueued
+    {
+      std::lock_guard<std::mutex> lock(ctx->mu);
+      rc = chan_index_reserve(ctx, queue, (size_t)s.m.clip.wg_bytes * s.grid + 4096u);
+      if (rc) return rc;
+      s.m.clip.scratch = (char *)ctx->chan_index[queue];
+    }
+    const hipError_t e = ph::launch_clip_up_multi(stream_of(ctx, queue), s.m, !s.alpha, s.grid);
     if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   }
   return PH_OK;

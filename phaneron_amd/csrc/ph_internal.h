@@ -64,6 +64,8 @@ struct ph_ctx {
   int chan_enlarged = !(getenv("PH_CHAN_ENLARGED") && getenv("PH_CHAN_ENLARGED")[0] == '0');
   // option "chan_batch_outs" (default 0): ph_run_programs puts channel frames for other consumers than SDI into shared launches (ph_chan_compose_batch_out)
   int chan_batch_outs = 0;
+  // option "clip_batch" (default 0): ph_run_programs puts consecutive clip_compose_multi_<n> jobs into shared launches (ph_clip_compose_batch_out)
+  int clip_batch = 0;
   // option "fused_multi_wgs" (default 0 = no cap): the most workgroups a ph_fused_v210_combine_multi launch may have (tests, A/B runs)
   int fused_multi_wgs = 0;
   // option "fused_multi_batch" (default 0): ph_run_programs puts consecutive fused_v210_combine_multi_<n> jobs into shared launches (ph_fused_v210_combine_multi_batch)

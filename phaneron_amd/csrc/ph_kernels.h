@@ -438,15 +438,17 @@ static_assert(sizeof(UpMultiArgs) < 4096, "kernel arguments are limited to 4 KiB
 hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb12, uint32_t num_cus);
 // Clips straight from their wire formats for ANY consumer, up to kMaxUpOuts per launch (ph_clip_compose_multi, clip_up_multi_kernel):
 // clip describes the composition as for clip_up_write_v210_kernel - clip.up.out / more_out / wr_cm are unused, clip.up.wr is the ONE
-// writer table of the launch, clip.up.jobs is 1 - and every output brings its format, job 0's planes and its writer matrix, as in
-// UpMultiArgs.  A v210 output's lines end on a 48-pixel block.
+// writer table of the launch - and every output brings its format, its planes per job and its writer matrix, as in UpMultiArgs.  A v210
+// output's lines end on a 48-pixel block.  clip.up.jobs = 2 .. kMaxUpJobs (ph_clip_compose_batch_out): single-layer frames of one shape,
+// job j's clip in clip.src[j] and its planes in out[k].plane[j], as ClipUpArgs says for the v210 kernel.
 struct ClipUpMultiArgs {
   ClipUpArgs clip;
   uint32_t n_out;
   UpOut out[kMaxUpOuts];
 };
 static_assert(sizeof(ClipUpMultiArgs) < 4096, "kernel arguments are limited to 4 KiB");
-// grid: clip_up_plan(clip, rgb12, num_cus, false); named clip_up_multi<rgb|rgba>x<outputs> in a route trace
+// grid: clip_up_plan(clip, rgb12, num_cus, false); named clip_up_multi<rgb|rgba>x<outputs> in a route trace, with several jobs
+// clip_up_multi<rgb|rgba>x<outputs>j<jobs>
 hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rgb12, uint32_t grid);
 // The same with layers in a transition (ph_compose_up_transition_multi, compose_up_trans_kernel): a layer may bring an incoming image
 // (dissolve, wipe) and a mask (wipe), each with a size and a placement of its own.  multi.up.layer[l] is the layer's `src`; job j > 0

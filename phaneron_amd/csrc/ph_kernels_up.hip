@@ -1013,10 +1013,13 @@ __global__ __launch_bounds__(kUpBlock) void clip_up_write_v210_kernel(ClipUpArgs
 // its wave-step loop up to the block's four accumulators, and from there compose_up_multi_kernel's tail - the twelve writer-table reads
 // made once, then every output packing the same twelve values with its own matrix (up_write_out).  Both kernels keep their own text
 // (their code is pinned: profiles/up_out_resources.txt, profiles/clip_multi_resources.txt), so the two halves are copies kept in step by
-// hand.  One frame per launch (job 0's planes of every output: clip_step's job is 0); the wave step is the clip kernel's 126 columns for
+// hand.  One frame per launch unless MULTI (job 0's planes of every output: clip_step's job is 0); the wave step is the clip kernel's 126 columns for
 // every launch, a v210 output or not, so the tiling and the rectangle bounds of clip_up_plan hold as they are.  A v210 output's lines end
 // on a 48-pixel block here (the caller sends the others through the one-output routes: their tail quads truncate table indices).
-template <bool RGB12>
+// MULTI: several frames of one shape in the launch, as clip_up_write_v210_kernel's MULTI - rows of tiles job after job, job j's clip in
+// src[j], its planes o.plane[j] of every output (an instantiation of its own: the one-frame forms keep their text and their registers,
+// profiles/clip_multi_batch_resources.txt)
+template <bool RGB12, bool MULTI = false>
 __global__ __launch_bounds__(kUpBlock) void clip_up_multi_kernel(ClipUpMultiArgs cm) {
   const ClipUpArgs &c = cm.clip;
   const UpArgs &a = c.up;
@@ -1024,7 +1027,8 @@ __global__ __launch_bounds__(kUpBlock) void clip_up_multi_kernel(ClipUpMultiArgs
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   // the tile
   const uint32_t upr = (a.cover_w + kUpCols - 1u) / kUpCols, rps = (a.lines + 1u) / 2u;
-  const uint32_t ty = blockIdx.x / c.gx, tx = blockIdx.x - ty * c.gx;
+  const uint32_t tyj = blockIdx.x / c.gx, tx = blockIdx.x - tyj * c.gx;
+  const uint32_t job = MULTI ? tyj / c.gy : 0u, ty = tyj - job * c.gy;  // (uniform) several frames of one shape: rows of tiles job after job
   const uint32_t cu0 = tx * c.tcu, rp0 = ty * c.trp;
   const uint32_t ncu = cu0 + c.tcu <= upr ? c.tcu : upr - cu0, nrp = rp0 + c.trp <= rps ? c.trp : rps - rp0;
   char *const mine = c.scratch + (size_t)blockIdx.x * c.wg_bytes;
@@ -1034,7 +1038,7 @@ __global__ __launch_bounds__(kUpBlock) void clip_up_multi_kernel(ClipUpMultiArgs
 #pragma unroll 1
   for (int l = 0; l < a.n; ++l) {
     const UpLayer L = a.layer[l];
-    const ClipSrc S = c.src[l];
+    const ClipSrc S = c.src[MULTI ? job : (uint32_t)l];  // (several jobs: single-layer frames, job j's clip in src[j])
     const uint32_t x_first = cu0 * kUpCols, x_end = (cu0 + ncu) * kUpCols < a.out_w ? (cu0 + ncu) * kUpCols : a.out_w;
     const uint32_t li_last = 2u * (rp0 + nrp) < a.lines ? 2u * (rp0 + nrp) - 1u : a.lines - 1u;
     ClipRect R{0, 0, 0, 0};
@@ -1096,7 +1100,7 @@ __global__ __launch_bounds__(kUpBlock) void clip_up_multi_kernel(ClipUpMultiArgs
   for (uint32_t u = wave; u < units; u += kUpBlock / 64) {
     const uint32_t rp_in = ncu == 1u ? u : u / ncu, cu_in = u - rp_in * ncu;
     UpStep st;
-    clip_step(a, 0u, cu0 + cu_in, rp0 + rp_in, lane, st);
+    clip_step(a, job, cu0 + cu_in, rp0 + rp_in, lane, st);  // (up_write_out writes o.plane[st.job])
     UpAcc acc[2][2];
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy)
@@ -1231,14 +1235,19 @@ hipError_t launch_clip_up_write_v210(hipStream_t s, const ClipUpArgs &c, bool rg
 }
 
 // Several outputs of one clip composition: named clip_up_multi<rgb|rgba>x<outputs> in a route trace.  grid: clip_up_plan's, asked with
-// v210_tails == false.  Refuses what launch_compose_up_multi refuses.
+// v210_tails == false.  Refuses what launch_compose_up_multi refuses.  Several jobs (single-layer frames of one shape, job j's clip in
+// clip.src[j] and its planes in out[k].plane[j]): named clip_up_multi<rgb|rgba>x<outputs>j<jobs>, the MULTI instantiation.
 hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rgb12, uint32_t grid) {
   const UpArgs &a = m.clip.up;
-  if (!grid || m.n_out < 1 || m.n_out > (uint32_t)kMaxUpOuts || a.jobs != 1u || a.n < 1 || a.n > kMaxLayers || a.cover_w != a.out_w) return hipErrorInvalidValue;
+  if (!grid || m.n_out < 1 || m.n_out > (uint32_t)kMaxUpOuts || a.jobs < 1u || a.jobs > (uint32_t)kMaxUpJobs || a.n < 1 || a.n > kMaxLayers || a.cover_w != a.out_w)
+    return hipErrorInvalidValue;
+  const bool multi = a.jobs > 1u;
+  if (multi && (a.n != 1 || !m.clip.gy || grid != m.clip.gx * m.clip.gy * a.jobs)) return hipErrorInvalidValue;  // (a tile's job is its row of tiles / gy: within jobs)
   for (uint32_t k = 0; k < m.n_out; ++k)
     if (!fmt_chan_out((int)m.out[k].fmt) || (m.out[k].fmt == PH_FMT_V210 && a.out_w % 48u)) return hipErrorInvalidValue;
   char name[48];
-  snprintf(name, sizeof name, "clip_up_multi<%s>x%u", rgb12 ? "rgb" : "rgba", m.n_out);
+  if (multi) snprintf(name, sizeof name, "clip_up_multi<%s>x%uj%u", rgb12 ? "rgb" : "rgba", m.n_out, a.jobs);
+  else snprintf(name, sizeof name, "clip_up_multi<%s>x%u", rgb12 ? "rgb" : "rgba", m.n_out);
   if (trace_launch(name)) return hipSuccess;
   const uint32_t lds = m.clip.info_off + 16u * (uint32_t)a.n;
   auto go = [&](auto kernel) -> hipError_t {
@@ -1247,6 +1256,7 @@ hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rg
     kernel<<<grid, kUpBlock, lds, s>>>(m);
     return hipGetLastError();
   };
+  if (multi) return rgb12 ? go(clip_up_multi_kernel<true, true>) : go(clip_up_multi_kernel<false, true>);
   return rgb12 ? go(clip_up_multi_kernel<true>) : go(clip_up_multi_kernel<false>);
 }
 

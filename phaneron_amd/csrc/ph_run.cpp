@@ -236,7 +236,7 @@ struct ChanCall {
   Recipe r;
   // chan_compose_multi_<n>: every output as ph_chan_compose_multi takes it (outs[0]: the one above)
   bool multi;  // the program is chan_compose_multi_<n> - or clip_compose_multi_<n>, which names its arguments the same
-  bool clip;   // the program is clip_compose_multi_<n>: ph_clip_compose_multi, a launch of its own in its turn
+  bool clip;   // the program is clip_compose_multi_<n>: ph_clip_compose_multi, a launch of its own in its turn (option "clip_batch": grouped, ph_clip_compose_batch_out)
   int n_out;
   ph_chan_output outs[ph::kMaxChanOuts];
 };
@@ -936,7 +936,9 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * the context option "fused_multi_batch" = 1 (default 0) lets consecutive such jobs of one shape and output list share launches
  * (ph_fused_v210_combine_multi_batch), under the same call-order rule.
  * With the context option "chan_batch_outs" = 1 (default 0) consecutive chan_compose_multi_<n> jobs and chan_compose_v210_<n> jobs that
- * make another format than v210 (outPacking) share launches as well (ph_chan_compose_batch_out).  A call that fails after its checks
+ * make another format than v210 (outPacking) share launches as well (ph_chan_compose_batch_out).  A clip_compose_multi_<n> job
+ * (ph_clip_compose_multi) is a launch of its own in its turn too - unless the context option "clip_batch" = 1 (default 0) lets consecutive
+ * such jobs of one geometry and Loader recipe go down in one ph_clip_compose_batch_out call, under the same call-order rule.  A call that fails after its checks
  * (a launch refused) has made the launches of the jobs before the failing group: ph_run_programs_progress says how many. */
 namespace {
 thread_local int g_programs_done = 0;  // jobs of the calling thread's last ph_run_programs call whose launches were made
@@ -958,7 +960,8 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
   std::vector<UpCall> ups;  // (sized when the first compose_up job shows up: most calls have none)
   std::vector<FusedMultiCall> multis;  // (likewise)
   // 1: a v210 frame from the channel kernel, 2: fused_v210_combine, 3: compose_up_write_v210, 4: a channel's frame for other consumers
-  // (option "chan_batch_outs"), 5: fused_v210_combine_multi (option "fused_multi_batch"), 0: whatever else, launched as it is
+  // (option "chan_batch_outs"), 5: fused_v210_combine_multi (option "fused_multi_batch"), 6: clip_compose_multi (option "clip_batch"),
+  // 0: whatever else, launched as it is
   std::vector<char> kind((size_t)n_jobs, 0);
   for (int j = 0; j < n_jobs; ++j) {  // every job is checked before anything is launched: a bad one refuses the call as a whole
     if (!progs[j] || (n_args[j] > 0 && !args[j])) return fail(PH_E_INVALID, "ph_run_programs: job %d: NULL argument", j);
@@ -968,8 +971,9 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       if ((rc = chan_call_parse(job, &calls[(size_t)j]))) return rc;
       // (a frame for another consumer, or a chan_compose_multi_<n> job: a launch of its own, in its turn - unless the context option
       // "chan_batch_outs" lets such jobs share launches too: ph_chan_compose_batch_out)
-      // (a clip_compose_multi_<n> job: always a launch of its own, in its turn - no grouping across jobs)
-      kind[(size_t)j] = calls[(size_t)j].clip ? 0 : calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
+      // (a clip_compose_multi_<n> job: a launch of its own, in its turn - unless the context option "clip_batch" lets such jobs share
+      // launches: ph_clip_compose_batch_out)
+      kind[(size_t)j] = calls[(size_t)j].clip ? (ctx->clip_batch ? 6 : 0) : calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
     } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j]) && !fused_is_trans(progs[j]) && !fused_is_route(progs[j])) {
       if ((rc = fused_call_parse(job, &fused[(size_t)j]))) return rc;
       kind[(size_t)j] = 2;
@@ -1130,18 +1134,21 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       g_programs_done = j = k;
       continue;
     }
-    if (kind[(size_t)j] == 4) {
+    if (kind[(size_t)j] == 4 || kind[(size_t)j] == 6) {
       // channels' frames for consumers other than SDI, or for several consumers, of one geometry and one Loader recipe: one call of
       // ph_chan_compose_batch_out, which itself starts the next launch where a job reads or writes what an earlier one writes, and runs
-      // the jobs that name another Saver table in their turn
+      // the jobs that name another Saver table in their turn.  6: the same for clip_compose_multi_<n> jobs (file playback) through
+      // ph_clip_compose_batch_out, which runs whatever its shared launch does not take through ph_clip_compose_multi in its turn
       const ChanCall &c0 = calls[(size_t)j];
+      const char group = kind[(size_t)j];
       std::vector<ph_chan_job_out> batch;
-      for (; k < n_jobs && kind[(size_t)k] == 4; ++k) {
+      for (; k < n_jobs && kind[(size_t)k] == group; ++k) {
         const ChanCall &c = calls[(size_t)k];
         if (c.width != c0.width || c.height != c0.height || c.r.rd_cm != c0.r.rd_cm || c.r.rd_lut != c0.r.rd_lut || c.r.rd_gm != c0.r.rd_gm) break;
         batch.push_back(ph_chan_job_out{c.n_layers, c.layers, c.n_out, c.outs});
       }
-      rc = ph_chan_compose_batch_out(ctx, queue, (int)batch.size(), batch.data(), c0.width, c0.height, c0.r.rd_cm->dptr, c0.r.rd_lut->dptr, c0.r.rd_gm->dptr);
+      rc = (group == 6 ? ph_clip_compose_batch_out : ph_chan_compose_batch_out)(ctx, queue, (int)batch.size(), batch.data(), c0.width, c0.height, c0.r.rd_cm->dptr,
+                                                                                 c0.r.rd_lut->dptr, c0.r.rd_gm->dptr);
       if (rc) return rc;
       g_programs_done = j = k;
       continue;
