@@ -16,7 +16,7 @@ VARIANT_DIR = os.path.normpath(os.path.join(HERE, "..", "tools", "_variants"))
 ARCH = "gfx950"
 
 SOURCES = ["ph_kernels.hip", "ph_kernels_lds.hip", "ph_kernels_fused_multi.hip", "ph_kernels_fused_trans.hip", "ph_kernels_fused_route.hip", "ph_kernels_fmt.hip", "ph_kernels_deint.hip", "ph_kernels_chan.hip", "ph_kernels_up.hip", "ph_api.cpp", "ph_run.cpp", "ph_program.cpp", "ph_colour.cpp", "ph_lut.cpp"]
-HEADERS = ["ph_device.h", "ph_formats.h", "ph_internal.h", "ph_kernels.h", "ph_kernels_fused_multi_body.h", "ph_kernels_fused_out.h", "ph_lut.h", "ph_lut_host.h", "ph_ldslut.h", "ph_program.h", "ph_yadif.h", os.path.join("..", "..", "include", "phaneron_hip.h")]
+HEADERS = ["ph_device.h", "ph_formats.h", "ph_internal.h", "ph_kernels.h", "ph_kernels_fused_multi_body.h", "ph_kernels_fused_out.h", "ph_lut.h", "ph_lut_host.h", "ph_ldslut.h", "ph_program.h", "ph_spans.h", "ph_yadif.h", os.path.join("..", "..", "include", "phaneron_hip.h")]
 # -ffp-contract=off: every fused multiply-add in the kernels is explicit (parity with the
 # reference's OpenCL arithmetic); no fast-math anywhere.
 # -fno-slp-vectorize: the SLP vectoriser pairs independent f32 operations into v_pk_add / v_pk_fma_f32.  On gfx950 a

@@ -1457,22 +1457,32 @@ static int chan_index_reserve(ph_ctx *ctx, int queue, size_t need) {
   ctx->chan_index_bytes[queue] = need;
   return PH_OK;
 }
+// One launch that uses the queue's area: the area is held until the launch is enqueued, so the launches of two calls on one queue do not
+// interleave around it.  launch(stream, area) enqueues; what it answers is fn's "launch failed"
+extern "C++" template <class Launch>
+static int with_scratch(const char *fn, ph_ctx *ctx, int queue, size_t bytes, Launch launch) {
+  const hipStream_t s = stream_of(ctx, queue);
+  std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);
+  void *area = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (const int rc = chan_index_reserve(ctx, queue, bytes)) return rc;
+    area = ctx->chan_index[queue];
+  }
+  const hipError_t e = launch(s, area);
+  if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  return PH_OK;
+}
 // one launch of the batch kernel: b holds the jobs and their ops, g the geometry, colour recipe and tables (set_device done)
 static int chan_batch_launch(ph_ctx *ctx, int queue, ph::ChanBatchArgs &b, const ph::ChanArgs &g) {
   b.out_w = g.out_w, b.out_h = g.out_h, b.lines = g.lines, b.line_step = g.line_step;
   b.rd_cm = g.rd_cm, b.rd_gm = g.rd_gm, b.wr_cm = g.wr_cm, b.rd = g.rd, b.wr = g.wr;
   b.tails = g.planar >= 1 ? 1u : 0u, b.planar = g.planar == 2 ? 1u : 0u, b.out_qpitch = g.out_qpitch, b.out_tail_from = g.out_tail_from;
   const size_t each = (ph::chan_index_bytes(g.out_w, g.lines) + 255u) & ~(size_t)255u;
-  std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);
-  {
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    int rc = chan_index_reserve(ctx, queue, each * b.jobs);
-    if (rc) return rc;
-    for (uint32_t j = 0; j < b.jobs; ++j) b.job[j].index = (char *)ctx->chan_index[queue] + each * j;
-  }
-  hipError_t e = ph::launch_chan_compose_batch(stream_of(ctx, queue), b, (uint32_t)ctx->props.multiProcessorCount);
-  if (e != hipSuccess) return fail(PH_E_HIP, "ph_chan_compose_batch: launch failed: %s", hipGetErrorString(e));
-  return PH_OK;
+  return with_scratch("ph_chan_compose_batch", ctx, queue, each * b.jobs, [&](hipStream_t s, void *area) {
+    for (uint32_t j = 0; j < b.jobs; ++j) b.job[j].index = (char *)area + each * j;
+    return ph::launch_chan_compose_batch(s, b, (uint32_t)ctx->props.multiProcessorCount);
+  });
 }
 
 // a channel's layers as the kernel's flat program: one op per source to sample (ph_kernels.h ChanOp)
@@ -1666,16 +1676,10 @@ static int chan_compose_enlarged(ph_ctx *ctx, int queue, int jobs, int n, const 
       if (a.lines && ph::compose_up_eligible(a)) {
         const uint32_t grid = ph::clip_up_plan(c, !alpha, (uint32_t)ctx->props.multiProcessorCount);
         if (grid) {
-          std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);  // until the launch is enqueued
-          {
-            std::lock_guard<std::mutex> lock(ctx->mu);
-            int rc = chan_index_reserve(ctx, queue, (size_t)c.wg_bytes * grid + 4096u);
-            if (rc) return rc;
-            c.scratch = (char *)ctx->chan_index[queue];
-          }
-          hipError_t e = ph::launch_clip_up_write_v210(stream_of(ctx, queue), c, !alpha, grid);
-          if (e != hipSuccess) return fail(PH_E_HIP, "ph_chan_compose_v210: launch failed: %s", hipGetErrorString(e));
-          return PH_OK;
+          return with_scratch("ph_chan_compose_v210", ctx, queue, (size_t)c.wg_bytes * grid + 4096u, [&](hipStream_t s, void *area) {
+            c.scratch = (char *)area;
+            return ph::launch_clip_up_write_v210(s, c, !alpha, grid);
+          });
         }
       }
     }
@@ -1742,16 +1746,10 @@ int ph_chan_compose(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, 
   if (out_format == PH_FMT_V210 && wr_cm && ctx->chan_enlarged && chan_layers_enlarged(n, layers, out_w, out_h, interlace))
     return chan_compose_enlarged(ctx, queue, 1, n, &layers, &out, out_w, out_h, interlace, rd_cm, rd_lut, rd_gm, wr_cm, wr_lut);
   // the index frame between the phases: one per queue (launches on one queue are in order), grown on demand
-  std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);
-  {
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    rc = chan_index_reserve(ctx, queue, ph::chan_index_bytes(out_w, a.lines));
-    if (rc) return rc;
-    a.index = ctx->chan_index[queue];
-  }
-  hipError_t e = ph::launch_chan_compose_v210(stream_of(ctx, queue), a, (uint32_t)ctx->props.multiProcessorCount);
-  if (e != hipSuccess) return fail(PH_E_HIP, "ph_chan_compose_v210: launch failed: %s", hipGetErrorString(e));
-  return PH_OK;
+  return with_scratch("ph_chan_compose_v210", ctx, queue, ph::chan_index_bytes(out_w, a.lines), [&](hipStream_t s, void *area) {
+    a.index = area;
+    return ph::launch_chan_compose_v210(s, a, (uint32_t)ctx->props.multiProcessorCount);
+  });
 }
 
 // One output of a several-outputs call, checked as ph_chan_compose checks its only one.  where: "" or "job <j>: " (ph_chan_compose_batch_out)
@@ -1767,6 +1765,26 @@ static int chan_output_check(const char *fn, const char *where, int k, const ph_
     return fail(PH_E_INVALID, "%s: %soutput %d: width %u (a v210 frame needs an even width, a planar one a multiple of 8); run the separate kernels", fn, where, k, out_w);
   if (o.interlace != 0 && o.interlace != 1 && o.interlace != 3) return fail(PH_E_INVALID, "%s: %soutput %d: interlace must be 0, 1 or 3", fn, where, k);
   return PH_OK;
+}
+
+// An output's field mode as the several-outputs kernels take it (d: a ChanOut, ChanBatchOut, FusedOut or UpOut).  same_lines: the launch
+// composes just the lines every output wants; else it composes the whole frame, and a field output takes the lines of its parity
+extern "C++" template <class Out>
+static void out_lines(const ph_chan_output &o, bool same_lines, uint32_t out_h, Out &d) {
+  d.takes = same_lines || !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
+  d.line_end = o.interlace ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as ph_chan_compose writes it)
+  d.field = o.interlace ? 1u : 0u;
+}
+// the outputs grouped by writer table, in the order the tables first appear
+static void by_writer_table(int n_out, const ph_chan_output *outs, int *order) {
+  int placed = 0;
+  for (int k = 0; k < n_out; ++k) {
+    bool seen = false;
+    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    if (seen) continue;
+    for (int j = k; j < n_out; ++j)
+      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) order[placed++] = j;
+  }
 }
 
 /* Several consumers' frames of one composition in one launch: see include/phaneron_hip.h.  Every check is made before anything is
@@ -1815,15 +1833,8 @@ int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
     if (a.planar < 1) a.planar = 1;
     if (out_w % 6) a.out_tail_from = out_w - out_w % 6u;
   }
-  // the outputs grouped by writer table, in the order the tables first appear
-  int order[ph::kMaxChanOuts], placed = 0;
-  for (int k = 0; k < n_out; ++k) {
-    bool seen = false;
-    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
-    if (seen) continue;
-    for (int j = k; j < n_out; ++j)
-      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) order[placed++] = j;
-  }
+  int order[ph::kMaxChanOuts];
+  by_writer_table(n_out, outs, order);
   m.n_out = (uint32_t)n_out;
   for (int i = 0; i < n_out; ++i) {
     const ph_chan_output &o = outs[order[i]];
@@ -1832,9 +1843,7 @@ int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
     d.pitch = o.format == PH_FMT_V210 ? ph_v210_pitch_bytes(out_w) / 16u : out_w;
     d.plane[0] = o.planes[0], d.plane[1] = o.planes[1], d.plane[2] = o.planes[2];
     d.tail_from = o.format == PH_FMT_V210 ? a.out_tail_from : 0xFFFFFFFFu;
-    d.takes = same_lines || !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
-    d.line_end = o.interlace ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as ph_chan_compose writes it)
-    d.field = o.interlace ? 1u : 0u;
+    out_lines(o, same_lines, out_h, d);
     d.round = o.format != PH_FMT_V210 && a.out_tail_from != 0xFFFFFFFFu ? 1u : 0u;
     d.wr_cm = (const float *)(o.wr_col_matrix12 ? o.wr_col_matrix12 : rd_cm);
     d.wr = *wref[order[i]].get();
@@ -1843,16 +1852,10 @@ int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
   if (!a.lines) return PH_OK;
   rc = set_device(ctx);
   if (rc) return rc;
-  std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);
-  {
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    rc = chan_index_reserve(ctx, queue, ph::chan_index_bytes(out_w, a.lines));
-    if (rc) return rc;
-    a.index = ctx->chan_index[queue];
-  }
-  hipError_t e = ph::launch_chan_compose_multi(stream_of(ctx, queue), m, (uint32_t)ctx->props.multiProcessorCount);
-  if (e != hipSuccess) return fail(PH_E_HIP, "ph_chan_compose_multi: launch failed: %s", hipGetErrorString(e));
-  return PH_OK;
+  return with_scratch("ph_chan_compose_multi", ctx, queue, ph::chan_index_bytes(out_w, a.lines), [&](hipStream_t s, void *area) {
+    a.index = area;
+    return ph::launch_chan_compose_multi(s, m, (uint32_t)ctx->props.multiProcessorCount);
+  });
 }
 
 // What ph_fused_v210_combine_multi and ph_fused_v210_transition_multi refuse about their outputs and geometry - everything but the layers and
@@ -1869,8 +1872,9 @@ static int fused_multi_outputs_check(const char *fn, int queue, int n_out, const
 }
 // The shared launch's arguments but for the layers - or false: the call does not qualify.  It needs lines of whole 48-pixel blocks, every
 // table in its LDS form (none is with the option "lds_lut" = 0), a frame small enough for the kernel's quad -> line division by reciprocal.
+// order (kMaxFusedOuts entries, or NULL): m.out[i] is outs[order[i]]
 static bool fused_multi_shared(ph_ctx *ctx, int n_out, const ph_chan_output *outs, uint32_t width, uint32_t height, const void *rd_cm, const void *rd_lut,
-                               const void *rd_gm, ph::FusedMultiArgs &m) {
+                               const void *rd_gm, ph::FusedMultiArgs &m, int *order = nullptr) {
   const LutRef rref = lds_view(ctx, rd_lut);
   LutRef wref[ph::kMaxFusedOuts];
   bool shared = width % 48 == 0 && rref.get() && (uint64_t)(width / 6) * height * (width / 6) < (1ull << 32);
@@ -1881,23 +1885,15 @@ static bool fused_multi_shared(ph_ctx *ctx, int n_out, const ph_chan_output *out
   if (!shared) return false;
   m.quads_per_line = width / 6, m.total_quads = m.quads_per_line * height;
   m.rd_cm = (const float *)rd_cm, m.rd_gm = (const float *)rd_gm, m.rd = *rref.get();
-  // the outputs grouped by writer table, in the order the tables first appear
-  int order[ph::kMaxFusedOuts], placed = 0;
-  for (int k = 0; k < n_out; ++k) {
-    bool seen = false;
-    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
-    if (seen) continue;
-    for (int j = k; j < n_out; ++j)
-      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) order[placed++] = j;
-  }
+  int own[ph::kMaxFusedOuts];
+  if (!order) order = own;
+  by_writer_table(n_out, outs, order);
   m.n_out = (uint32_t)n_out;
   for (int i = 0; i < n_out; ++i) {
     const ph_chan_output &o = outs[order[i]];
     ph::FusedOut &d = m.out[i];
     d.fmt = (uint32_t)o.format;
-    d.takes = !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;  // the whole frame is composed: a field output takes the lines of its parity
-    d.line_end = o.interlace ? 2u * (height / 2u) : height;    // (a field of an odd height: height / 2 lines, as ph_chan_compose writes it)
-    d.field = o.interlace ? 1u : 0u;
+    out_lines(o, /*same_lines*/ false, height, d);  // the whole frame is composed: a field output takes the lines of its parity
     d.wr_cm = (const float *)(o.wr_col_matrix12 ? o.wr_col_matrix12 : rd_cm);
     d.plane[0] = o.planes[0], d.plane[1] = o.planes[1], d.plane[2] = o.planes[2];
     d.wr = *wref[order[i]].get();
@@ -2089,45 +2085,16 @@ int ph_fused_v210_combine_multi_batch(ph_ctx *ctx, int queue, int jobs, int n, c
     for (int j = 0; j < jobs; ++j) frames[j] = outs[j].planes[0];
     return ph_fused_v210_combine_batch(ctx, queue, jobs, n, layers, frames, width, height, rd_cm, rd_lut, rd_gm, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
   }
-  // the shared launch: what ph_fused_v210_combine_multi's own asks for
-  const LutRef rref = lds_view(ctx, rd_lut);
-  LutRef wref[ph::kMaxFusedOuts];
-  bool shared = width % 48 == 0 && rref.get() && (uint64_t)(width / 6) * height * (width / 6) < (1ull << 32);
-  for (int k = 0; k < n_out && shared; ++k) {
-    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
-    shared = wref[k].get() != nullptr;
-  }
-  if (!shared) {
+  // the shared launch: what ph_fused_v210_combine_multi's own asks for, with its arguments (every job's output list is job 0's: one order for all)
+  ph::FusedMultiBatchArgs b{};
+  int order[ph::kMaxFusedOuts];
+  if (!fused_multi_shared(ctx, n_out, outs, width, height, rd_cm, rd_lut, rd_gm, b.m, order)) {
     for (int j = 0; j < jobs; ++j)
       if (const int rc = ph_fused_v210_combine_multi(ctx, queue, n, layers + (size_t)j * n, n_out, outs + (size_t)j * n_out, width, height, rd_cm, rd_lut, rd_gm)) return rc;
     return PH_OK;
   }
   if (!height) return PH_OK;
-  ph::FusedMultiBatchArgs b{};
-  ph::FusedMultiArgs &m = b.m;
-  m.quads_per_line = width / 6, m.total_quads = m.quads_per_line * height;
-  m.rd_cm = (const float *)rd_cm, m.rd_gm = (const float *)rd_gm, m.rd = *rref.get();
-  // the outputs grouped by writer table, in the order the tables first appear (every job's list is job 0's: one order for all)
-  int order[ph::kMaxFusedOuts], placed = 0;
-  for (int k = 0; k < n_out; ++k) {
-    bool seen = false;
-    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
-    if (seen) continue;
-    for (int j = k; j < n_out; ++j)
-      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) order[placed++] = j;
-  }
-  m.n_out = (uint32_t)n_out;
-  for (int i = 0; i < n_out; ++i) {
-    const ph_chan_output &o = outs[order[i]];
-    ph::FusedOut &d = m.out[i];
-    d.fmt = (uint32_t)o.format;
-    d.takes = !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
-    d.line_end = o.interlace ? 2u * (height / 2u) : height;
-    d.field = o.interlace ? 1u : 0u;
-    d.wr_cm = (const float *)(o.wr_col_matrix12 ? o.wr_col_matrix12 : rd_cm);
-    d.wr = *wref[order[i]].get();
-  }
-  for (int j = 0; j < jobs; ++j) {
+  for (int j = 0; j < jobs; ++j) {  // (b.m.out[i].plane, job 0's, is not read: each job's planes are b.plane's)
     for (int i = 0; i < n; ++i) b.layers[j][i] = layers[(size_t)j * n + i];
     for (int i = 0; i < n_out; ++i)
       for (int p = 0; p < 3; ++p) b.plane[j][i][p] = outs[(size_t)j * n_out + order[i]].planes[p];
@@ -2137,6 +2104,23 @@ int ph_fused_v210_combine_multi_batch(ph_ctx *ctx, int queue, int jobs, int n, c
   const hipError_t e = ph::launch_fused_v210_combine_multi_batch(stream_of(ctx, queue), n, (uint32_t)jobs, b, (uint32_t)ctx->props.multiProcessorCount, (uint32_t)ctx->fused_multi_wgs);
   if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   return PH_OK;
+}
+
+// A job's Loader matrices as indices into a launch's small table: cm_of[i] = 1 .. 8, or 0 for the call's own matrix.  tab: the launch's
+// table with the job's matrices in it - those already there are found again, new ones appended in the order they first appear - for
+// the caller to make the launch's if the job joins it.  false: the table does not hold them all
+static bool place_cms(int n_ops, const float *const *cm_op, const void *rd_cm, const float *const *launch_tab, const float **tab, uint8_t *cm_of) {
+  for (int t = 0; t < 8; ++t) tab[t] = launch_tab[t];
+  for (int i = 0; i < n_ops; ++i) {
+    cm_of[i] = 0;
+    const float *cm = cm_op[i];
+    if (!cm || cm == (const float *)rd_cm) continue;
+    int at = 0;
+    while (at < 8 && tab[at] && tab[at] != cm) ++at;
+    if (at == 8) return false;
+    tab[at] = cm, cm_of[i] = (uint8_t)(at + 1);
+  }
+  return true;
 }
 
 /* Several channels' frames in one launch: see include/phaneron_hip.h.  Jobs the batch kernel does not take (planar / packed-RGB sources,
@@ -2248,32 +2232,11 @@ int ph_chan_compose_batch(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job 
       continue;
     }
     if ((rc = flush_enlarged())) return rc;
-    // a planar job's Loader matrices as indices into the launch's small table (those already there are found again)
+    // a planar job's Loader matrices against the launch's table as it stands: a job they do not fit runs on its own
     uint8_t cm_of[ph::kMaxChanOps];
-    const float *cm_new[8];
-    int n_cm_new = 0;
-    bool cm_fits = true;
-    auto cm_known = [&](const float *cm) -> int {  // 1 .. 8, or 0
-      for (uint32_t t = 0; t < 8 && b.cm_tab[t]; ++t)
-        if (b.cm_tab[t] == cm) return (int)t + 1;
-      return 0;
-    };
-    uint32_t tab_used = 0;
-    while (tab_used < 8 && b.cm_tab[tab_used]) ++tab_used;
-    for (int i = 0; i < k && one.planar == 2; ++i) {
-      cm_of[i] = 0;
-      const float *cm = one.cm_op[i];
-      if (!cm || cm == (const float *)rd_cm) continue;
-      int at = cm_known(cm);
-      for (int t = 0; t < n_cm_new && !at; ++t)
-        if (cm_new[t] == cm) at = (int)tab_used + t + 1;
-      if (!at) {
-        if (tab_used + (uint32_t)n_cm_new >= 8u) { cm_fits = false; break; }
-        cm_new[n_cm_new] = cm, at = (int)tab_used + (++n_cm_new);
-      }
-      cm_of[i] = (uint8_t)at;
-    }
-    if ((one.planar == 2 && !cm_fits) || k > ph::kMaxChanBatchOps || fit < 1 || !lines) {  // not for the batch kernel: in its turn, on its own
+    const float *tab[8];
+    const bool cm_fits = one.planar != 2 || place_cms(k, one.cm_op, rd_cm, b.cm_tab, tab, cm_of);
+    if (!cm_fits || k > ph::kMaxChanBatchOps || fit < 1 || !lines) {  // not for the batch kernel: in its turn, on its own
       if ((rc = flush())) return rc;
       if ((rc = ph_chan_compose_v210(ctx, queue, J.n, J.layers, J.out, out_w, out_h, J.interlace, rd_cm, rd_lut, rd_gm, wr_cm, wr_lut))) return rc;
       continue;
@@ -2290,21 +2253,9 @@ int ph_chan_compose_batch(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job 
     jb.out = J.out, jb.first_op = b.n_ops, jb.n_ops = (uint32_t)k, jb.first_line = J.interlace == 3 ? 1u : 0u;
     for (int i = 0; i < k; ++i) b.op[b.n_ops + i] = one.op[i], b.op_job[b.n_ops + i] = (uint8_t)b.jobs;
     if (one.planar == 2) {
-      // (a flush above has emptied the launch: the table then starts again - indices made against the old one are made again)
-      if (!b.cm_tab[0] && tab_used) {
-        int renum = 0;
-        for (int i = 0; i < k; ++i)
-          if (cm_of[i]) {
-            const float *cm = one.cm_op[i];
-            int at = 0;
-            for (int t = 0; t < renum && !at; ++t)
-              if (b.cm_tab[t] == cm) at = t + 1;
-            if (!at) b.cm_tab[renum] = cm, at = ++renum;
-            cm_of[i] = (uint8_t)at;
-          }
-      } else {
-        for (int t = 0; t < n_cm_new; ++t) b.cm_tab[tab_used + (uint32_t)t] = cm_new[t];
-      }
+      // (a flush above has emptied the launch: the table then starts again, and what fitted the old one fits an empty one)
+      place_cms(k, one.cm_op, rd_cm, b.cm_tab, tab, cm_of);
+      for (int t = 0; t < 8; ++t) b.cm_tab[t] = tab[t];
       for (int i = 0; i < k; ++i) {
         b.plane_u[b.n_ops + i] = one.plane_u[i], b.plane_v[b.n_ops + i] = one.plane_v[i], b.cm_idx[b.n_ops + i] = cm_of[i];
         b.any_cm |= cm_of[i] ? 1u : 0u;
@@ -2320,27 +2271,48 @@ int ph_chan_compose_batch(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job 
  * is launched.  Jobs the shared launch does not take run through ph_chan_compose_multi in their turn; a launch that ends up with one job
  * is that call too, so a job on its own keeps the routes it has today. */
 namespace {
-struct ChanSpan {  // bytes a job reads or writes; for an output's planes also what lets two fields of one frame share a launch
-  const char *p;
-  size_t n;
-  int fmt;             // an output's PH_FMT_* (-1: a source)
-  uint32_t interlace;
-};
-bool spans_meet(const ChanSpan &a, const ChanSpan &b) { return a.n && b.n && a.p < b.p + b.n && b.p < a.p + a.n; }
-// two outputs that may be written side by side although their bytes meet: the two fields of one frame (not 4:2:0: both fields of a
-// line pair write the pair's chroma line, and the later call has to win)
-bool spans_interleave(const ChanSpan &a, const ChanSpan &b) {
-  return a.p == b.p && a.fmt >= 0 && a.fmt == b.fmt && !fmt_v420(a.fmt) && a.interlace && b.interlace && a.interlace != b.interlace;
-}
-struct ChanOutJob {
+struct ChanJobPlan {  // what ph_chan_compose_batch_out and ph_clip_compose_batch_out learn of a job while they check it
   ph::ChanArgs one{};  // the job's program (op, plane_u / plane_v, cm_op, planar)
   int n_ops = 0;
   uint32_t interlace = 0;  // the lines the job composes: the field every output wants, or the frame
   bool same_lines = true, any_v210 = false, joins = false;
   const void *table = nullptr;  // the writer table all its outputs name (NULL: they name several)
-  std::vector<ChanSpan> reads, writes;
+  Footprint print;              // what it reads and writes
+  ChanJobPlan() {}              // (user-provided, as Footprint's: a vector of plans does not clear the spans)
 };
 }  // namespace
+// One job of those two entries, checked as ph_chan_compose_multi checks its call, fault by fault in that order, and described in P.
+// max_outs: the entry's limit; ctx: where an output's writer table is looked up between that output's checks and the next output's
+// (NULL: the caller looks the tables up later, after every check of the arguments)
+static int chan_job_check(const char *fn, int j, const ph_chan_job_out &J, int max_outs, ph_ctx *ctx, uint32_t out_w, uint32_t out_h, ChanJobPlan &P) {
+  char where[24];
+  snprintf(where, sizeof where, "job %d: ", j);
+  if (!J.layers || !J.outs) return fail(PH_E_INVALID, "%s: %sNULL argument", fn, where);
+  if (J.n_out < 1 || J.n_out > max_outs) return fail(PH_E_INVALID, "%s: %s1..%d outputs (%d)", fn, where, max_outs, J.n_out);
+  if (J.n < 1 || J.n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: %s1..%d layers", fn, where, ph::kMaxLayers);
+  P.table = J.outs[0].wr_gamma_lut;
+  for (int k = 0; k < J.n_out; ++k) {
+    const ph_chan_output &o = J.outs[k];
+    if (const int bad = chan_output_check(fn, where, k, o, out_w, out_h)) return bad;
+    for (int i = 0; i < k; ++i)
+      if (J.outs[i].planes[0] == o.planes[0]) return fail(PH_E_INVALID, "%s: %soutputs %d and %d name the same plane", fn, where, i, k);
+    if (ctx && !lds_view(ctx, o.wr_gamma_lut).found)
+      return fail(PH_E_INVALID, "%s: %soutput %d: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn, where, k);
+    P.any_v210 = P.any_v210 || o.format == PH_FMT_V210;
+    P.same_lines = P.same_lines && o.interlace == J.outs[0].interlace;
+    if (o.wr_gamma_lut != P.table) P.table = nullptr;
+    span_write_output(P.print, o, out_w, out_h);
+  }
+  P.interlace = P.same_lines ? J.outs[0].interlace : 0u;
+  // the layers, as the channel kernel's entries check them (their texts); what the job reads
+  if (const int bad = chan_ops(J.n, J.layers, out_w, out_h, P.one.op, P.one.plane_u, P.one.plane_v, P.one.cm_op, &P.one.planar, &P.n_ops)) return bad;
+  for (int i = 0; i < P.n_ops; ++i) {
+    const ph::ChanSrc &src = P.one.op[i].src;
+    const bool v420 = src.kind == ph::kChanP8x420 || src.kind == ph::kChanNv12 || src.kind == ph::kChanP10x420 || src.kind == ph::kChanP010;
+    span_read_planes(P.print, src.ptr, src.pitch, src.h, v420, /*cbcr*/ src.kind == ph::kChanNv12 || src.kind == ph::kChanP010, P.one.plane_u[i], P.one.plane_v[i]);
+  }
+  return PH_OK;
+}
 
 int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job_out *jobs, uint32_t out_w, uint32_t out_h, const void *rd_cm,
                               const void *rd_lut, const void *rd_gm) {
@@ -2355,43 +2327,12 @@ int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
   if (!out_w) return fail(PH_E_INVALID, "%s: width 0", fn);
   const LutRef rref = lds_view(ctx, rd_lut);
   if (!rref.get()) return fail(PH_E_INVALID, "%s: the reader gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn);
-  std::vector<ChanOutJob> plan((size_t)n_jobs);
+  std::vector<ChanJobPlan> plan((size_t)n_jobs);
   uint32_t plan_jobs = 0, plan_ops = 0, plan_outs = 0;
   for (int j = 0; j < n_jobs; ++j) {
     const ph_chan_job_out &J = jobs[j];
-    ChanOutJob &P = plan[(size_t)j];
-    char where[24];
-    snprintf(where, sizeof where, "job %d: ", j);
-    if (!J.layers || !J.outs) return fail(PH_E_INVALID, "%s: %sNULL argument", fn, where);
-    if (J.n_out < 1 || J.n_out > ph::kMaxChanOuts) return fail(PH_E_INVALID, "%s: %s1..%d outputs (%d)", fn, where, ph::kMaxChanOuts, J.n_out);
-    if (J.n < 1 || J.n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: %s1..%d layers", fn, where, ph::kMaxLayers);
-    P.table = J.outs[0].wr_gamma_lut;
-    for (int k = 0; k < J.n_out; ++k) {
-      const ph_chan_output &o = J.outs[k];
-      if (const int bad = chan_output_check(fn, where, k, o, out_w, out_h)) return bad;
-      for (int i = 0; i < k; ++i)
-        if (J.outs[i].planes[0] == o.planes[0]) return fail(PH_E_INVALID, "%s: %soutputs %d and %d name the same plane", fn, where, i, k);
-      if (!lds_view(ctx, o.wr_gamma_lut).found)
-        return fail(PH_E_INVALID, "%s: %soutput %d: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn, where, k);
-      P.any_v210 = P.any_v210 || o.format == PH_FMT_V210;
-      P.same_lines = P.same_lines && o.interlace == J.outs[0].interlace;
-      if (o.wr_gamma_lut != P.table) P.table = nullptr;
-      size_t bytes[3];
-      const int planes = ph::pack_plane_bytes(o.format, out_w, out_h, bytes);
-      for (int i = 0; i < planes; ++i) P.writes.push_back(ChanSpan{(const char *)o.planes[i], bytes[i], o.format, o.interlace});  // (every plane of a 4:2:2 or packed frame has a row per line: fields interleave in all of them)
-    }
-    P.interlace = P.same_lines ? J.outs[0].interlace : 0u;
-    if (const int bad = chan_ops(J.n, J.layers, out_w, out_h, P.one.op, P.one.plane_u, P.one.plane_v, P.one.cm_op, &P.one.planar, &P.n_ops)) return bad;
-    for (int i = 0; i < P.n_ops; ++i) {
-      const ph::ChanSrc &src = P.one.op[i].src;
-      P.reads.push_back(ChanSpan{(const char *)src.ptr, (size_t)src.pitch * src.h, -1, 0u});
-      // a planar frame's chroma planes, sized as the kernel sizes them (ph_kernels_chan.hip planes_of)
-      const bool v420 = src.kind == ph::kChanP8x420 || src.kind == ph::kChanNv12 || src.kind == ph::kChanP10x420 || src.kind == ph::kChanP010;
-      const bool cbcr = src.kind == ph::kChanNv12 || src.kind == ph::kChanP010;
-      const size_t chroma = (size_t)(cbcr ? src.pitch : src.pitch >> 1) * (v420 ? (src.h + 1u) >> 1 : src.h);
-      if (P.one.plane_u[i]) P.reads.push_back(ChanSpan{(const char *)P.one.plane_u[i], chroma, -1, 0u});
-      if (P.one.plane_v[i]) P.reads.push_back(ChanSpan{(const char *)P.one.plane_v[i], chroma, -1, 0u});
-    }
+    ChanJobPlan &P = plan[(size_t)j];
+    if (const int bad = chan_job_check(fn, j, J, ph::kMaxChanOuts, ctx, out_w, out_h, P)) return bad;
     // what the shared launch takes: one writer table, a program and outputs that fit, lines to compose - and not the one v210 frame
     // that the enlarged-clip routes make better (ph_chan_compose takes them; with several outputs nobody does)
     const ph_chan_output &o0 = J.outs[0];
@@ -2440,25 +2381,16 @@ int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
       d.round = d.fmt != PH_FMT_V210 && b.out_tail_from != 0xFFFFFFFFu ? 1u : 0u;
     }
     const size_t each = (ph::chan_index_bytes(out_w, b.lines) + 255u) & ~(size_t)255u;
-    int r = PH_OK;
-    {
-      std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);
-      {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        r = chan_index_reserve(ctx, queue, each * b.jobs);
-        for (uint32_t j = 0; j < b.jobs && !r; ++j) b.job[j].index = (char *)ctx->chan_index[queue] + each * j;
-      }
-      if (!r) {
-        hipError_t e = ph::launch_chan_compose_batch_out(stream_of(ctx, queue), b, (uint32_t)ctx->props.multiProcessorCount);
-        if (e != hipSuccess) r = fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-      }
-    }
+    const int r = with_scratch(fn, ctx, queue, each * b.jobs, [&](hipStream_t s, void *area) {
+      for (uint32_t j = 0; j < b.jobs; ++j) b.job[j].index = (char *)area + each * j;
+      return ph::launch_chan_compose_batch_out(s, b, (uint32_t)ctx->props.multiProcessorCount);
+    });
     b = ph::ChanBatchOutArgs{};
     return r;
   };
   for (int j = 0; j < n_jobs; ++j) {
     const ph_chan_job_out &J = jobs[j];
-    const ChanOutJob &P = plan[(size_t)j];
+    const ChanJobPlan &P = plan[(size_t)j];
     if (!P.joins) {  // in its turn, on its own
       if ((rc = flush())) return rc;
       if ((rc = hand_on(j))) return rc;
@@ -2466,39 +2398,18 @@ int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
     }
     // no job of a launch reads or writes what another job of it writes (two fields of one frame excepted): such a job starts the next launch
     bool clash = false;
-    for (int i = first_job; i < first_job + (int)b.jobs && !clash; ++i) {
-      const ChanOutJob &Q = plan[(size_t)i];
-      for (const ChanSpan &w : P.writes) {
-        for (const ChanSpan &r : Q.reads) clash = clash || spans_meet(w, r);
-        for (const ChanSpan &v : Q.writes) clash = clash || (spans_meet(w, v) && !spans_interleave(w, v));
-      }
-      for (const ChanSpan &r : P.reads)
-        for (const ChanSpan &v : Q.writes) clash = clash || spans_meet(r, v);
-    }
-    // the job's Loader matrices as indices into the launch's small table (those already there are found again)
+    for (int i = first_job; i < first_job + (int)b.jobs && !clash; ++i) clash = clashes(P.print, plan[(size_t)i].print, kAllHazards, /*fields_interleave*/ true);
+    // the job's Loader matrices as indices into the launch's small table
     uint8_t cm_of[ph::kMaxChanOps] = {};
     const float *tab[8];
-    auto place_cms = [&]() {
-      for (int t = 0; t < 8; ++t) tab[t] = b.cm_tab[t];
-      for (int i = 0; i < P.n_ops; ++i) {
-        cm_of[i] = 0;
-        const float *cm = P.one.cm_op[i];
-        if (!cm || cm == (const float *)rd_cm) continue;
-        int at = 0;
-        while (at < 8 && tab[at] && tab[at] != cm) ++at;
-        if (at == 8) return false;
-        tab[at] = cm, cm_of[i] = (uint8_t)(at + 1);
-      }
-      return true;
-    };
     if (b.jobs && (clash || P.table != table || (P.interlace != 0) != fields || b.jobs >= jobs_per_launch || b.n_ops + (uint32_t)P.n_ops > (uint32_t)ph::kMaxChanOutOps ||
-                   b.n_out + (uint32_t)J.n_out > (uint32_t)ph::kMaxChanBatchOuts || !place_cms()))
+                   b.n_out + (uint32_t)J.n_out > (uint32_t)ph::kMaxChanBatchOuts || !place_cms(P.n_ops, P.one.cm_op, rd_cm, b.cm_tab, tab, cm_of)))
       if ((rc = flush())) return rc;
     if (!b.jobs) {
       first_job = j, table = P.table, wref = lds_view(ctx, table), fields = P.interlace != 0, planar = 0, any_v210 = false;
       if (!wref.found) return fail(PH_E_INVALID, "%s: job %d: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn, j);
     }
-    place_cms();  // (fits an empty table: the job has at most eight matrices of its own)
+    place_cms(P.n_ops, P.one.cm_op, rd_cm, b.cm_tab, tab, cm_of);  // (fits an empty table: the job has at most eight matrices of its own)
     for (int t = 0; t < 8; ++t) b.cm_tab[t] = tab[t];
     planar = std::max(planar, P.one.planar), any_v210 = any_v210 || P.any_v210;
     ph::ChanJob &jb = b.job[b.jobs];
@@ -2515,9 +2426,7 @@ int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
       d.fmt = (uint32_t)o.format;
       d.pitch = o.format == PH_FMT_V210 ? ph_v210_pitch_bytes(out_w) / 16u : out_w;
       d.plane[0] = o.planes[0], d.plane[1] = o.planes[1], d.plane[2] = o.planes[2];
-      d.takes = P.same_lines || !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
-      d.line_end = o.interlace ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as ph_chan_compose writes it)
-      d.field = o.interlace ? 1u : 0u;
+      out_lines(o, P.same_lines, out_h, d);
       d.job = b.jobs;
       d.wr_cm = (const float *)(o.wr_col_matrix12 ? o.wr_col_matrix12 : rd_cm);
     }
@@ -2686,6 +2595,7 @@ static void compose_up_launches(const ph::UpArgs &base, int jobs, int n_out, con
     for (int j = k; j < n_out; ++j)
       if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) group[members++] = j;
     UpLaunch shared{};
+    const ph_chan_output *stays[ph::kMaxUpOuts];  // the outputs of shared.m.out
     shared.solo = false, shared.table = k, shared.m.up = base;
     for (int g = 0; g < members; ++g) {
       const ph_chan_output &o = outs[group[g]];
@@ -2704,21 +2614,14 @@ static void compose_up_launches(const ph::UpArgs &base, int jobs, int n_out, con
       d.wr_cm = (const float *)o.wr_col_matrix12;
       for (int j = 0; j < jobs; ++j)
         for (int i = 0; i < 3; ++i) d.plane[j][i] = outs[j * n_out + group[g]].planes[i];
-      d.takes = o.interlace, ++shared.m.n_out;  // (takes: settled below, once the launch's lines are known)
+      stays[shared.m.n_out++] = &o;  // (takes / line_end / field: settled below, once the launch's lines are known)
     }
     if (!shared.m.n_out) continue;
     // a split-off v210 output does not count: the first output that stays decides what "the same" is
-    const uint32_t first_il = shared.m.out[0].takes;
     bool same_lines = true;
-    for (uint32_t i = 0; i < shared.m.n_out; ++i) same_lines = same_lines && shared.m.out[i].takes == first_il;
-    compose_up_lines(shared.m.up, out_w, out_h, same_lines ? first_il : 0u);
-    for (uint32_t i = 0; i < shared.m.n_out; ++i) {
-      ph::UpOut &d = shared.m.out[i];
-      const uint32_t il = d.takes;
-      d.takes = same_lines || !il ? 0u : il == 1 ? 1u : 2u;
-      d.line_end = il ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as the one-output kernels write it)
-      d.field = il ? 1u : 0u;
-    }
+    for (uint32_t i = 0; i < shared.m.n_out; ++i) same_lines = same_lines && stays[i]->interlace == stays[0]->interlace;
+    compose_up_lines(shared.m.up, out_w, out_h, same_lines ? stays[0]->interlace : 0u);
+    for (uint32_t i = 0; i < shared.m.n_out; ++i) out_lines(*stays[i], same_lines, out_h, shared.m.out[i]);
     launches.push_back(shared);
   }
 }
@@ -2764,6 +2667,30 @@ int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_
   return PH_OK;
 }
 
+// What ph_clip_compose_multi's one-launch route and ph_clip_compose_batch_out's planner make of a clip and of an output: a clip's size and
+// placement as a compositor layer (ptr: the launch's own), ...
+static ph::UpLayer up_layer_of(const ph_chan_source &S) {
+  ph::UpLayer d{};
+  d.w = (uint32_t)S.width, d.h = (uint32_t)S.height, d.pitch = (uint32_t)S.width * 16u;
+  for (int k = 0; k < 6; ++k) d.m[k] = S.matrix9_host[k];
+  return d;
+}
+// ... an output of a one-job launch of the several-outputs kernels, ...
+static ph::UpOut up_out_of(const ph_chan_output &o, bool same_lines, uint32_t out_w, uint32_t out_h) {
+  ph::UpOut d{};
+  d.fmt = (uint32_t)o.format;
+  d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48)
+  d.wr_cm = (const float *)o.wr_col_matrix12;
+  for (int i = 0; i < 3; ++i) d.plane[0][i] = o.planes[i];
+  out_lines(o, same_lines, out_h, d);
+  return d;
+}
+// ... and a clip in its wire format fmt, as the clip kernel reads it
+static ph::ClipSrc clip_src_of(const ph_chan_source &S, int fmt, const void *rd_cm) {
+  return ph::ClipSrc{S.data, S.data_u, S.data_v, (const float *)(S.col_matrix12 ? S.col_matrix12 : rd_cm), (uint32_t)fmt,
+                     fmt == PH_FMT_V210 ? ph_v210_pitch_bytes((uint32_t)S.width) / 16u : ph::pack_pitch(fmt, (uint32_t)S.width)};
+}
+
 /* File playback for any consumer, up to four per call: see include/phaneron_hip.h.  Exactly the n_out calls of ph_chan_compose in order,
  * bit for bit; every check is made before the context is looked at, and a refused call writes nothing.  An enlarged clip (or a decoder's
  * frame under the default fill) is read ONCE per source pixel instead of four times per output pixel: one launch of clip_up_multi_kernel
@@ -2802,11 +2729,7 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
   ph::UpArgs base{};
   if (takes) {
     base.n = n, base.jobs = 1;
-    for (int i = 0; i < n; ++i) {
-      const ph_chan_source &S = layers[i].src;
-      base.layer[i].w = (uint32_t)S.width, base.layer[i].h = (uint32_t)S.height, base.layer[i].pitch = (uint32_t)S.width * 16u;
-      for (int k = 0; k < 6; ++k) base.layer[i].m[k] = S.matrix9_host[k];
-    }
+    for (int i = 0; i < n; ++i) base.layer[i] = up_layer_of(layers[i].src);
     compose_up_lines(base, out_w, out_h, interlace);
     takes = ph::compose_up_eligible(base);
   }
@@ -2844,14 +2767,7 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
         if (rc) return rc;
         continue;
       }
-      ph::UpOut &d = m.out[m.n_out++];
-      d.fmt = (uint32_t)o.format;
-      d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48)
-      d.wr_cm = (const float *)o.wr_col_matrix12;
-      for (int i = 0; i < 3; ++i) d.plane[0][i] = o.planes[i];
-      d.takes = same_lines || !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
-      d.line_end = o.interlace ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as ph_chan_compose writes it)
-      d.field = o.interlace ? 1u : 0u;
+      m.out[m.n_out++] = up_out_of(o, same_lines, out_w, out_h);
     }
     if (!m.n_out) continue;
     // 5. the group's launch
@@ -2860,22 +2776,15 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
       c.clip.up = m.up, c.n_out = m.n_out;
       for (uint32_t i = 0; i < m.n_out; ++i) c.out[i] = m.out[i];
       c.clip.rd = *rref.get(), c.clip.rd_gm = (const float *)rd_gm;
-      const ph_chan_source &S = layers[0].src;
-      const int fmt = fmt_of_src(S.format);
-      c.clip.src[0] = ph::ClipSrc{S.data, S.data_u, S.data_v, (const float *)(S.col_matrix12 ? S.col_matrix12 : rd_cm), (uint32_t)fmt,
-                                  fmt == PH_FMT_V210 ? ph_v210_pitch_bytes((uint32_t)S.width) / 16u : ph::pack_pitch(fmt, (uint32_t)S.width)};
+      c.clip.src[0] = clip_src_of(layers[0].src, fmt_of_src(layers[0].src.format), rd_cm);
       const uint32_t grid = ph::clip_up_plan(c.clip, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ false);
       if (grid) {
         if (images.owns_lock()) images.unlock();
-        std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);  // until the launch is enqueued
-        {
-          std::lock_guard<std::mutex> lock(ctx->mu);
-          rc = chan_index_reserve(ctx, queue, (size_t)c.clip.wg_bytes * grid + 4096u);
-          if (rc) return rc;
-          c.clip.scratch = (char *)ctx->chan_index[queue];
-        }
-        const hipError_t e = ph::launch_clip_up_multi(stream_of(ctx, queue), c, !alpha, grid);
-        if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+        rc = with_scratch(fn, ctx, queue, (size_t)c.clip.wg_bytes * grid + 4096u, [&](hipStream_t s, void *area) {
+          c.clip.scratch = (char *)area;
+          return ph::launch_clip_up_multi(s, c, !alpha, grid);
+        });
+        if (rc) return rc;
         continue;
       }
     }
@@ -2893,11 +2802,6 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
 }
 
 namespace {
-struct ClipOutJob {
-  bool joins = false, alpha = false, same_lines = true;
-  uint32_t interlace = 0;  // the lines the job composes: the field every output wants, or the frame
-  std::vector<ChanSpan> reads, writes;
-};
 struct ClipBatchStep {  // what the call does in its turn: a shared launch of jobs [first, first + m.clip.up.jobs), or job `first` handed on
   int first = 0;
   bool shared = false, alpha = false;
@@ -2905,6 +2809,31 @@ struct ClipBatchStep {  // what the call does in its turn: a shared launch of jo
   ph::ClipUpMultiArgs m{};
 };
 }  // namespace
+// one job's launch arguments as ph_clip_compose_multi makes them for its one-launch route (false: the job is not for that route as a whole)
+static bool clip_job_args(ph_ctx *ctx, const ph_chan_job_out &J, const ChanJobPlan &P, uint32_t out_w, uint32_t out_h, const void *rd_cm, const void *rd_gm,
+                          const ph::LutView &rd, ph::ClipUpMultiArgs &c, bool &alpha) {
+  if (ctx->chan_enlarged != 1 || J.n != 1) return false;
+  if (J.n_out == 1 && J.outs[0].format == PH_FMT_V210) return false;  // (ph_chan_compose, under its names)
+  const ph_chan_source &S = J.layers[0].src;
+  const int fmt = fmt_of_src(S.format);
+  if (fmt < 0 || (fmt_v420(fmt) && (S.height & 1))) return false;
+  for (int k = 0; k < J.n_out; ++k)
+    if (J.outs[k].wr_gamma_lut != J.outs[0].wr_gamma_lut || (J.outs[k].format == PH_FMT_V210 && out_w % 48)) return false;  // (several launches there)
+  if (!chan_layers_enlarged(1, J.layers, out_w, out_h, P.interlace, /*v210_fill*/ true)) return false;
+  c = ph::ClipUpMultiArgs{};
+  ph::UpArgs &a = c.clip.up;
+  a.n = 1, a.jobs = 1, a.layer[0] = up_layer_of(S);
+  compose_up_lines(a, out_w, out_h, P.interlace);
+  if (!ph::compose_up_eligible(a) || !a.lines) return false;
+  a.wr = lds_view(ctx, J.outs[0].wr_gamma_lut).view;
+  alpha = fmt_rgb8(fmt);
+  c.n_out = (uint32_t)J.n_out;
+  for (int k = 0; k < J.n_out; ++k) c.out[k] = up_out_of(J.outs[k], P.same_lines, out_w, out_h);
+  c.clip.rd = rd, c.clip.rd_gm = (const float *)rd_gm;
+  c.clip.src[0] = clip_src_of(S, fmt, rd_cm);
+  ph::ClipUpArgs probe = c.clip;
+  return ph::clip_up_plan(probe, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ false) != 0;
+}
 
 /* Several CHANNELS' file playback for any consumers in one launch: see include/phaneron_hip.h.  Exactly, in order and bit for bit, the
  * n_jobs calls of ph_clip_compose_multi.  Every check of the arguments is made before the context is looked at; every job is checked and
@@ -2919,40 +2848,9 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
   PH_QUEUE(fn, queue);
   if (n_jobs < 1) return fail(PH_E_INVALID, "%s: no jobs", fn);
   if (!out_w) return fail(PH_E_INVALID, "%s: width 0", fn);
-  std::vector<ClipOutJob> plan((size_t)n_jobs);
-  for (int j = 0; j < n_jobs; ++j) {
-    const ph_chan_job_out &J = jobs[j];
-    ClipOutJob &P = plan[(size_t)j];
-    char where[24];
-    snprintf(where, sizeof where, "job %d: ", j);
-    if (!J.layers || !J.outs) return fail(PH_E_INVALID, "%s: %sNULL argument", fn, where);
-    if (J.n_out < 1 || J.n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: %s1..%d outputs (%d)", fn, where, ph::kMaxUpOuts, J.n_out);
-    if (J.n < 1 || J.n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: %s1..%d layers", fn, where, ph::kMaxLayers);
-    for (int k = 0; k < J.n_out; ++k) {
-      const ph_chan_output &o = J.outs[k];
-      if (const int bad = chan_output_check(fn, where, k, o, out_w, out_h)) return bad;
-      for (int i = 0; i < k; ++i)
-        if (J.outs[i].planes[0] == o.planes[0]) return fail(PH_E_INVALID, "%s: %soutputs %d and %d name the same plane", fn, where, i, k);
-      P.same_lines = P.same_lines && o.interlace == J.outs[0].interlace;
-      size_t bytes[3];
-      const int planes = ph::pack_plane_bytes(o.format, out_w, out_h, bytes);
-      for (int i = 0; i < planes; ++i) P.writes.push_back(ChanSpan{(const char *)o.planes[i], bytes[i], o.format, o.interlace});
-    }
-    P.interlace = P.same_lines ? J.outs[0].interlace : 0u;
-    ph::ChanArgs one{};  // the layers, as the channel kernel's entries check them (their texts); what the job reads
-    int n_ops = 0;
-    if (const int bad = chan_ops(J.n, J.layers, out_w, out_h, one.op, one.plane_u, one.plane_v, one.cm_op, &one.planar, &n_ops)) return bad;
-    for (int i = 0; i < n_ops; ++i) {
-      const ph::ChanSrc &src = one.op[i].src;
-      P.reads.push_back(ChanSpan{(const char *)src.ptr, (size_t)src.pitch * src.h, -1, 0u});
-      // a planar frame's chroma planes, sized as the kernel sizes them (ph_kernels_chan.hip planes_of)
-      const bool v420 = src.kind == ph::kChanP8x420 || src.kind == ph::kChanNv12 || src.kind == ph::kChanP10x420 || src.kind == ph::kChanP010;
-      const bool cbcr = src.kind == ph::kChanNv12 || src.kind == ph::kChanP010;
-      const size_t chroma = (size_t)(cbcr ? src.pitch : src.pitch >> 1) * (v420 ? (src.h + 1u) >> 1 : src.h);
-      if (one.plane_u[i]) P.reads.push_back(ChanSpan{(const char *)one.plane_u[i], chroma, -1, 0u});
-      if (one.plane_v[i]) P.reads.push_back(ChanSpan{(const char *)one.plane_v[i], chroma, -1, 0u});
-    }
-  }
+  std::vector<ChanJobPlan> plan((size_t)n_jobs);
+  for (int j = 0; j < n_jobs; ++j)
+    if (const int bad = chan_job_check(fn, j, jobs[j], ph::kMaxUpOuts, /*tables: below, once there is a context*/ nullptr, out_w, out_h, plan[(size_t)j])) return bad;
   if (!ctx) return fail(PH_E_INVALID, "%s: ctx is NULL", fn);
   if (n_jobs == 1)  // a group of one job is that call
     return ph_clip_compose_multi(ctx, queue, jobs[0].n, jobs[0].layers, jobs[0].n_out, jobs[0].outs, out_w, out_h, rd_cm, rd_lut, rd_gm);
@@ -2963,45 +2861,6 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
       if (!lds_view(ctx, jobs[j].outs[k].wr_gamma_lut).found)
         return fail(PH_E_INVALID, "%s: job %d: output %d: the writer gamma LUT has no LDS form (ph_lut_register it, or run the separate kernels)", fn, j, k);
   const uint32_t num_cus = (uint32_t)ctx->props.multiProcessorCount;
-  // one job's launch arguments as ph_clip_compose_multi makes them for its one-launch route (false: the job is not for that route as a whole)
-  auto clip_args = [&](int j, ph::ClipUpMultiArgs &c, bool &alpha) {
-    const ph_chan_job_out &J = jobs[j];
-    const ClipOutJob &P = plan[(size_t)j];
-    if (ctx->chan_enlarged != 1 || J.n != 1) return false;
-    if (J.n_out == 1 && J.outs[0].format == PH_FMT_V210) return false;  // (ph_chan_compose, under its names)
-    const ph_chan_source &S = J.layers[0].src;
-    const int fmt = fmt_of_src(S.format);
-    if (fmt < 0 || (fmt_v420(fmt) && (S.height & 1))) return false;
-    for (int k = 0; k < J.n_out; ++k)
-      if (J.outs[k].wr_gamma_lut != J.outs[0].wr_gamma_lut || (J.outs[k].format == PH_FMT_V210 && out_w % 48)) return false;  // (several launches there)
-    if (!chan_layers_enlarged(1, J.layers, out_w, out_h, P.interlace, /*v210_fill*/ true)) return false;
-    c = ph::ClipUpMultiArgs{};
-    ph::UpArgs &a = c.clip.up;
-    a.n = 1, a.jobs = 1;
-    a.layer[0].w = (uint32_t)S.width, a.layer[0].h = (uint32_t)S.height, a.layer[0].pitch = (uint32_t)S.width * 16u;
-    for (int k = 0; k < 6; ++k) a.layer[0].m[k] = S.matrix9_host[k];
-    compose_up_lines(a, out_w, out_h, P.interlace);
-    if (!ph::compose_up_eligible(a) || !a.lines) return false;
-    a.wr = lds_view(ctx, J.outs[0].wr_gamma_lut).view;
-    alpha = fmt_rgb8(fmt);
-    c.n_out = (uint32_t)J.n_out;
-    for (int k = 0; k < J.n_out; ++k) {
-      const ph_chan_output &o = J.outs[k];
-      ph::UpOut &d = c.out[k];
-      d.fmt = (uint32_t)o.format;
-      d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48)
-      d.wr_cm = (const float *)o.wr_col_matrix12;
-      for (int i = 0; i < 3; ++i) d.plane[0][i] = o.planes[i];
-      d.takes = P.same_lines || !o.interlace ? 0u : o.interlace == 1 ? 1u : 2u;
-      d.line_end = o.interlace ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as ph_chan_compose writes it)
-      d.field = o.interlace ? 1u : 0u;
-    }
-    c.clip.rd = rref.view, c.clip.rd_gm = (const float *)rd_gm;
-    c.clip.src[0] = ph::ClipSrc{S.data, S.data_u, S.data_v, (const float *)(S.col_matrix12 ? S.col_matrix12 : rd_cm), (uint32_t)fmt,
-                                fmt == PH_FMT_V210 ? ph_v210_pitch_bytes((uint32_t)S.width) / 16u : ph::pack_pitch(fmt, (uint32_t)S.width)};
-    ph::ClipUpArgs probe = c.clip;
-    return ph::clip_up_plan(probe, !alpha, num_cus, /*v210_tails*/ false) != 0;
-  };
   // the plan: the steps of the call, in the jobs' order
   std::vector<ClipBatchStep> steps;
   ClipBatchStep cur;  // the launch being collected
@@ -3022,10 +2881,10 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
   };
   for (int j = 0; j < n_jobs; ++j) {
     const ph_chan_job_out &J = jobs[j];
-    const ClipOutJob &P = plan[(size_t)j];
+    const ChanJobPlan &P = plan[(size_t)j];
     ph::ClipUpMultiArgs c;
     bool alpha = false;
-    if (!clip_args(j, c, alpha)) {  // in its turn, on its own
+    if (!clip_job_args(ctx, J, P, out_w, out_h, rd_cm, rd_gm, rref.view, c, alpha)) {  // in its turn, on its own
       flush();
       ClipBatchStep own;
       own.first = j;
@@ -3042,15 +2901,8 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
         const ph_chan_output &o = J.outs[k], &o0 = J0.outs[k];
         apart = o.format != o0.format || o.interlace != o0.interlace || o.wr_col_matrix12 != o0.wr_col_matrix12 || o.wr_gamma_lut != o0.wr_gamma_lut;
       }
-      for (int i = cur.first; i < cur.first + (int)a.jobs && !apart; ++i) {
-        const ClipOutJob &Q = plan[(size_t)i];
-        for (const ChanSpan &w : P.writes) {
-          for (const ChanSpan &r : Q.reads) apart = apart || spans_meet(w, r);
-          for (const ChanSpan &v : Q.writes) apart = apart || spans_meet(w, v);
-        }
-        for (const ChanSpan &r : P.reads)
-          for (const ChanSpan &v : Q.writes) apart = apart || spans_meet(r, v);
-      }
+      // (no exception for the two fields of one frame: they are two launches here)
+      for (int i = cur.first; i < cur.first + (int)a.jobs && !apart; ++i) apart = clashes(P.print, plan[(size_t)i].print, kAllHazards, /*fields_interleave*/ false);
       if (apart) flush();
     }
     if (!cur.shared) {
@@ -3072,15 +2924,11 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
       if ((rc = ph_clip_compose_multi(ctx, queue, J.n, J.layers, J.n_out, J.outs, out_w, out_h, rd_cm, rd_lut, rd_gm))) return rc;
       continue;
     }
-    std::lock_guard<std::mutex> scratch(ctx->chan_scratch_mu[queue]);  // until the launch is enqueued
-    {
-      std::lock_guard<std::mutex> lock(ctx->mu);
-      rc = chan_index_reserve(ctx, queue, (size_t)s.m.clip.wg_bytes * s.grid + 4096u);
-      if (rc) return rc;
-      s.m.clip.scratch = (char *)ctx->chan_index[queue];
-    }
-    const hipError_t e = ph::launch_clip_up_multi(stream_of(ctx, queue), s.m, !s.alpha, s.grid);
-    if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    rc = with_scratch(fn, ctx, queue, (size_t)s.m.clip.wg_bytes * s.grid + 4096u, [&](hipStream_t st, void *area) {
+      s.m.clip.scratch = (char *)area;
+      return ph::launch_clip_up_multi(st, s.m, !s.alpha, s.grid);
+    });
+    if (rc) return rc;
   }
   return PH_OK;
 }

@@ -1,5 +1,6 @@
 // ph_internal.h - what the library's two host translation units share: ph_api.cpp (context, buffers, queues, the typed entry
 // points) and ph_run.cpp (programs and their by-name jobs).  Nothing here is exported: the C ABI is include/phaneron_hip.h.
+// Both plan shared launches - which jobs may sit in one - with ph_spans.h: a job's byte ranges and the one hazard test on them.
 #pragma once
 #include <atomic>
 #include <cstdlib>
@@ -11,6 +12,11 @@
 #include "../../include/phaneron_hip.h"
 #include "ph_kernels.h"
 #include "ph_program.h"
+#include "ph_spans.h"
+
+static_assert(ph::kSpanLayers == ph::kMaxLayers && ph::kSpanOuts >= ph::kMaxChanOuts && ph::kSpanOuts >= ph::kMaxFusedOuts && ph::kSpanOuts >= ph::kMaxUpOuts,
+              "a Footprint holds any job's ranges: ph_spans.h sizes it by these limits without seeing ph_kernels.h");
+static_assert(ph::kMaxChanOps <= ph::kSpanLayers * 3, "a channel job's op list is at most three sources per layer");
 
 // sets the calling thread's ph_last_error text; returns code
 #pragma GCC visibility push(hidden)

@@ -943,6 +943,37 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
 namespace {
 thread_local int g_programs_done = 0;  // jobs of the calling thread's last ph_run_programs call whose launches were made
 }
+// What a job of each grouped kind reads and writes (ph_spans.h), by byte range.
+// fused_v210_combine_<n>: every layer and the frame are frame_bytes long
+static void fused_footprint(const FusedCall &f, Footprint &fp) {
+  for (int l = 0; l < f.n; ++l) span_read(fp, f.layers[l], f.frame_bytes);
+  span_write(fp, f.out, f.frame_bytes);
+}
+// fused_v210_combine_multi_<n>: a layer is any v210_bytes, a plane what its format gives it at the height rounded up to even
+static void fused_multi_footprint(const FusedMultiCall &m, Footprint &fp) {
+  const size_t frame_bytes = v210_bytes(m.width, m.height);
+  for (int l = 0; l < m.n; ++l) span_read(fp, m.layers[l], frame_bytes);
+  // (a format without plane sizes is one the typed call refuses: the job goes down alone and is answered there)
+  for (int o = 0; o < m.n_out; ++o) span_write_output(fp, m.outs[o], m.width, m.height + (m.height & 1u), frame_bytes);
+}
+// compose_up_write_v210_<n>: a layer image - either field's - is any buffer of w * h * 16 bytes (packedRgb: 12), a frame any buffer of
+// v210_bytes; a pair writes two
+static void up_footprint(const UpCall &u, Footprint &fp) {
+  const size_t frame_bytes = v210_bytes(u.width, u.height);
+  for (int l = 0; l < u.n; ++l) {
+    const size_t bytes = (size_t)u.layers[l].width * (size_t)u.layers[l].height * (u.rgb ? 12u : 16u);
+    span_read(fp, u.layers[l].data, bytes);
+    if (u.pair) span_read(fp, u.layers2[l].data, bytes);
+  }
+  span_write(fp, u.o->dptr, frame_bytes);
+  if (u.pair) span_write(fp, u.o2->dptr, frame_bytes);
+}
+// chan_compose_v210_<n>: the sources by their formats, a plane of no bytes widened to one; the frame pitch * height
+static void chan_footprint(const ChanCall &c, Footprint &fp) {
+  for (int l = 0; l < c.n_layers; ++l)
+    for (const ph_chan_source *s : {&c.layers[l].src, &c.layers[l].incoming, &c.layers[l].mask}) span_read_source(fp, *s, 1);
+  span_write(fp, c.out_planes[0], (size_t)ph_v210_pitch_bytes(c.width) * c.height);
+}
 int ph_run_programs_progress(int *jobs_done) {
   if (!jobs_done) return fail(PH_E_INVALID, "ph_run_programs_progress: NULL argument");
   *jobs_done = g_programs_done;
@@ -963,6 +994,15 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
   // (option "chan_batch_outs"), 5: fused_v210_combine_multi (option "fused_multi_batch"), 6: clip_compose_multi (option "clip_batch"),
   // 0: whatever else, launched as it is
   std::vector<char> kind((size_t)n_jobs, 0);
+  // the footprints of the group being collected, the candidate's last: does it keep clear of every job already in the group?
+  // (the calling thread's, kept from call to call: a call allocates none)
+  static thread_local std::vector<Footprint> kept;
+  std::vector<Footprint> &prints = kept;
+  auto joins = [&](unsigned hazards) {
+    for (size_t e = 0; e + 1 < prints.size(); ++e)
+      if (clashes(prints.back(), prints[e], hazards, false)) return false;
+    return true;
+  };
   for (int j = 0; j < n_jobs; ++j) {  // every job is checked before anything is launched: a bad one refuses the call as a whole
     if (!progs[j] || (n_args[j] > 0 && !args[j])) return fail(PH_E_INVALID, "ph_run_programs: job %d: NULL argument", j);
     if ((rc = flush_dirty_args(ctx, args[j], n_args[j], queue))) return rc;
@@ -1005,19 +1045,12 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       const FusedCall &f0 = fused[(size_t)j];
       std::vector<const void *> layers;
       std::vector<void *> outs;
-      auto overlap = [&](const void *p, const void *q) {
-        const char *a0 = (const char *)p, *b0 = (const char *)q;
-        return a0 < b0 + f0.frame_bytes && b0 < a0 + f0.frame_bytes;
-      };
+      prints.clear();
       for (; k < n_jobs && kind[(size_t)k] == 2 && k - j < ph::kMaxBatch; ++k) {
         const FusedCall &f = fused[(size_t)k];
         if (f.n != f0.n || f.width != f0.width || f.height != f0.height || !(f.r == f0.r)) break;
-        bool clash = false;
-        for (size_t e = 0; e < outs.size() && !clash; ++e) {
-          clash = overlap(f.out, outs[e]);
-          for (int l = 0; l < f.n && !clash; ++l) clash = overlap(f.layers[l], outs[e]) || overlap(f.out, layers[e * (size_t)f0.n + (size_t)l]);
-        }
-        if (clash) break;
+        fused_footprint(f, prints.emplace_back());
+        if (!joins(kAllHazards)) break;
         layers.insert(layers.end(), f.layers, f.layers + f.n);
         outs.push_back(f.out);
       }
@@ -1034,36 +1067,9 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       // layer an earlier job reads or a plane it writes, starts the next launch: call order is kept.  By byte range, as the headline
       // kernel's groups: a layer is any v210_bytes, a plane what its format gives it.
       const FusedMultiCall &m0 = multis[(size_t)j];
-      const size_t frame_bytes = v210_bytes(m0.width, m0.height);
-      auto overlap = [](const void *p, size_t p_bytes, const void *q, size_t q_bytes) {
-        const char *a0 = (const char *)p, *b0 = (const char *)q;
-        return a0 < b0 + q_bytes && b0 < a0 + p_bytes;
-      };
-      size_t plane_bytes[ph::kMaxFusedOuts][3];
-      for (int o = 0; o < m0.n_out; ++o) {
-        plane_bytes[o][0] = plane_bytes[o][1] = plane_bytes[o][2] = 0;
-        // (a format without plane sizes is one the typed call refuses: the job goes down alone and is answered there)
-        if (pack_plane_bytes(m0.outs[o].format, m0.width, m0.height + (m0.height & 1u), plane_bytes[o]) < 0) plane_bytes[o][0] = frame_bytes;
-      }
-      // does a plane of u overlap a plane (planes_too) or a layer of e; or a layer of u a plane of e?
-      auto clashes = [&](const FusedMultiCall &u, const FusedMultiCall &e) {
-        for (int o = 0; o < m0.n_out; ++o)
-          for (int p = 0; p < 3; ++p) {
-            if (u.outs[o].planes[p] && plane_bytes[o][p]) {
-              for (int l = 0; l < e.n; ++l)
-                if (overlap(u.outs[o].planes[p], plane_bytes[o][p], e.layers[l], frame_bytes)) return true;
-              for (int o2 = 0; o2 < m0.n_out; ++o2)
-                for (int p2 = 0; p2 < 3; ++p2)
-                  if (e.outs[o2].planes[p2] && plane_bytes[o2][p2] && overlap(u.outs[o].planes[p], plane_bytes[o][p], e.outs[o2].planes[p2], plane_bytes[o2][p2])) return true;
-            }
-            if (e.outs[o].planes[p] && plane_bytes[o][p])
-              for (int l = 0; l < u.n; ++l)
-                if (overlap(u.layers[l], frame_bytes, e.outs[o].planes[p], plane_bytes[o][p])) return true;
-          }
-        return false;
-      };
       std::vector<const void *> layers;
       std::vector<ph_chan_output> outs;
+      prints.clear();
       for (; k < n_jobs && kind[(size_t)k] == 5 && k - j < ph::kMaxBatch; ++k) {
         const FusedMultiCall &m = multis[(size_t)k];
         bool same = m.n == m0.n && m.width == m0.width && m.height == m0.height && m.n_out == m0.n_out && m.r.rd_cm == m0.r.rd_cm && m.r.rd_lut == m0.r.rd_lut &&
@@ -1072,9 +1078,8 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
           same = m.outs[o].format == m0.outs[o].format && m.outs[o].interlace == m0.outs[o].interlace && m.outs[o].wr_col_matrix12 == m0.outs[o].wr_col_matrix12 &&
                  m.outs[o].wr_gamma_lut == m0.outs[o].wr_gamma_lut;
         if (!same) break;
-        bool clash = false;
-        for (int e = j; e < k && !clash; ++e) clash = clashes(m, multis[(size_t)e]);
-        if (clash) break;
+        fused_multi_footprint(m, prints.emplace_back());
+        if (!joins(kAllHazards)) break;
         layers.insert(layers.end(), m.layers, m.layers + m.n);
         outs.insert(outs.end(), m.outs, m.outs + m.n_out);
       }
@@ -1095,18 +1100,7 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       const ph_image_layer *sets[ph::kMaxUpJobs];
       void *outs[ph::kMaxUpJobs];
       int frames = 0;
-      const size_t frame_bytes = v210_bytes(u0.width, u0.height);
-      auto overlap = [](const void *p, size_t p_bytes, const void *q, size_t q_bytes) {
-        const char *a0 = (const char *)p, *b0 = (const char *)q;
-        return a0 < b0 + q_bytes && b0 < a0 + p_bytes;
-      };
-      auto reads = [&](const UpCall &u, const void *frame) {  // does a layer image of u - either field's - overlap the frame at `frame`?
-        for (int l = 0; l < u.n; ++l) {
-          const size_t bytes = (size_t)u.layers[l].width * (size_t)u.layers[l].height * (u.rgb ? 12u : 16u);
-          if (overlap(u.layers[l].data, bytes, frame, frame_bytes) || (u.pair && overlap(u.layers2[l].data, bytes, frame, frame_bytes))) return true;
-        }
-        return false;
-      };
+      prints.clear();
       for (; k < n_jobs && kind[(size_t)k] == 3; ++k) {
         const UpCall &u = ups[(size_t)k];
         bool same = u.n == u0.n && u.rgb == u0.rgb && u.width == u0.width && u.height == u0.height && u.interlace == u0.interlace && u.r == u0.r;
@@ -1115,12 +1109,10 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
           for (int e = 0; e < 9 && same; ++e) same = u.layers[l].matrix9_host[e] == u0.layers[l].matrix9_host[e];
         }
         if (!same || frames + (u.pair ? 2 : 1) > ph::kMaxUpJobs) break;
-        bool clash = u.pair && overlap(u.o->dptr, frame_bytes, u.o2->dptr, frame_bytes);
-        for (int f = 0; f < frames && !clash; ++f)  // written twice, or read here after it is written there
-          clash = overlap(outs[f], frame_bytes, u.o->dptr, frame_bytes) || (u.pair && overlap(outs[f], frame_bytes, u.o2->dptr, frame_bytes)) || reads(u, outs[f]);
-        for (int e = j; e < k && !clash; ++e)  // written here after it is read there
-          clash = reads(ups[(size_t)e], u.o->dptr) || (u.pair && reads(ups[(size_t)e], u.o2->dptr));
-        if (clash) break;
+        Footprint &fp = prints.emplace_back();
+        up_footprint(u, fp);
+        // written twice - by the job's own pair, or by an earlier job -, read here after it is written there, or written here after it is read there
+        if ((fp.n_writes == 2 && spans_meet(fp.writes[0], fp.writes[1])) || !joins(kAllHazards)) break;
         sets[frames] = u.layers, outs[frames++] = u.o->dptr;
         if (u.pair) sets[frames] = u.layers2, outs[frames++] = u.o2->dptr;
       }
@@ -1157,33 +1149,13 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
     std::vector<ph_chan_job> batch;
     // a frame that reads what an earlier frame of the group writes (a channel routed into another), or writes what one reads, starts the next
     // call of ph_chan_compose_batch: the jobs of one such call may share launches, and call order has to hold
-    const size_t out_bytes = (size_t)ph_v210_pitch_bytes(c0.width) * c0.height;
-    auto touches = [&](const void *p, size_t bytes, const void *out) {
-      const char *a0 = (const char *)p, *b0 = (const char *)out;
-      return p && a0 < b0 + out_bytes && b0 < a0 + (bytes ? bytes : 1);
-    };
-    // (the bytes a source's planes hold: an f32 image 16 per pixel, a wire-format frame what its format's planes take - a range taken
-    // wider than that runs into whatever buffer lies behind the plane, and where the launches of a call end would depend on where its
-    // buffers were allocated)
-    auto reads = [&](const ChanCall &c, const void *out) {  // does a source of c overlap the frame at `out`?
-      for (int l = 0; l < c.n_layers; ++l)
-        for (const ph_chan_source *s2 : {&c.layers[l].src, &c.layers[l].incoming, &c.layers[l].mask}) {
-          if (!s2->data) continue;
-          size_t pb[3];
-          const int fmt = fmt_of_src(s2->format);
-          // an f32 image (or a frame whose planes have no size of their own - odd 4:2:0 dims, which the launch refuses: the widest any format takes)
-          if (fmt < 0 || ((s2->width | s2->height) & 1) || pack_plane_bytes(fmt, (uint32_t)s2->width, (uint32_t)s2->height, pb) < 0)
-            pb[0] = (size_t)s2->width * s2->height * 16u, pb[1] = pb[2] = (size_t)s2->width * s2->height * 2u;
-          if (touches(s2->data, pb[0], out) || touches(s2->data_u, pb[1], out) || touches(s2->data_v, pb[2], out)) return true;
-        }
-      return false;
-    };
+    prints.clear();
     for (; k < n_jobs && kind[(size_t)k] == 1; ++k) {
       const ChanCall &c = calls[(size_t)k];
       if (c.width != c0.width || c.height != c0.height || !(c.r == c0.r)) break;
-      bool clash = false;
-      for (int e = j; e < k && !clash; ++e) clash = reads(c, calls[(size_t)e].out_planes[0]) || reads(calls[(size_t)e], c.out_planes[0]);
-      if (clash) break;
+      chan_footprint(c, prints.emplace_back());
+      // (WAW is not asked here: ph_chan_compose_batch sees to the jobs that name one frame, and keeps the two fields of a frame in one launch)
+      if (!joins(kRAW | kWAR)) break;
       batch.push_back(ph_chan_job{c.n_layers, c.layers, c.out_planes[0], c.interlace});
     }
     rc = ph_chan_compose_batch(ctx, queue, (int)batch.size(), batch.data(), c0.width, c0.height, c0.r.rd_cm->dptr, c0.r.rd_lut->dptr, c0.r.rd_gm->dptr,

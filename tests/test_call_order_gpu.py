@@ -221,6 +221,29 @@ def test_a_job_with_a_hazard_against_the_job_before_it_keeps_out_of_its_launch(r
             assert np.array_equal(one[i], want[i]), "%s: buffer %d differs from the oracle's chain (%d words)" % (name, i, int(np.count_nonzero(one[i] != want[i])))
 
 
+def test_the_two_fields_of_one_frame_from_the_channel_kernel_stay_in_one_launch(rig, contents):
+    """chan_compose_v210_<n> jobs that write the same frame are not parted by ph_run_programs - the upper and the lower field of buffer 4,
+    from two sources, are one launch (ph_chan_compose_batch keeps the two fields of a frame together) - while the same field written
+    twice is two, the later job's lines standing: every buffer equals the jobs posted one by one"""
+    upper, lower = co.job("chan", 1, [0], 4, small=[True]), co.job("chan", 1, [6], 4, small=[True])
+
+    class Fields(Rig):  # the rig's jobs, each with the field named in its spec
+        def __init__(self):
+            self.__dict__.update(rig.__dict__)
+
+        def job(self, j, pool):
+            prog, params = Rig.job(self, j, pool)
+            return prog, dict(params, interlace=j["field"])
+    fields = Fields()
+    for (fa, fb), launches in (((1, 3), 1), ((3, 1), 1), ((1, 1), 2), ((3, 3), 2)):
+        spec = [dict(upper, field=fa), dict(lower, field=fb)]
+        one, each, traced = run_both(fields, spec, contents, traced=True)
+        for i, (a, b) in enumerate(zip(one, each)):
+            assert np.array_equal(a, b), "fields %d, %d: buffer %d of the one call differs from the separate calls" % (fa, fb, i)
+        assert not np.array_equal(one[4], contents[4])
+        assert traced == launches and dry_launches(fields, spec, contents) == launches, "fields %d, %d: %d launches" % (fa, fb, traced)
+
+
 def test_random_calls_of_every_kind_of_job_equal_the_jobs_posted_one_by_one(rig, contents):
     """seeded random calls (PH_FUZZ_SEED, PH_FUZZ_CASES; 25 cases of 2 - 8 jobs by default, tests/test_call_order_cpu.py says what they
     hold) of headline, channel and compositor jobs - RGBA and packed images, one field and two - whose arguments are each other's frames:

@@ -222,6 +222,21 @@ def test_a_job_reading_an_earlier_jobs_output():
     assert launches(route) == [(2, 4), (2, 4)], route
 
 
+def test_a_job_writing_what_an_earlier_job_reads():
+    """the second job's rgba8 frame is the graphic the first job places over its clip: the first job has read it before the second writes
+    it - the second job starts the next launch, with the third"""
+    w, h = 384, 54
+    v = variants(w, h)
+    uploaded = device_layers(v[3])
+
+    def reader(planes):
+        return uploaded + [dict(src=(planes["screen"][0], w, h, m(w, h, **PIP[1]), "rgba8"))]
+    jobs = [(reader, [out("yuv422p8"), out("rgba8")]), (v[0], [dict(out("rgba8"), slot="screen"), out("v210")]), (v[1], [out("v210"), out("bgra8")])]
+    route, _, _ = run_both(jobs, w, h, "a job that writes what the first job reads")
+    # (three jobs without a hazard are one launch - test_an_odd_height_field_beside_a_frame; here the first is alone: ph_chan_compose_multi's)
+    assert launches(route) == [(2, 4)] and re.match(r"chan_compose_multi<\d>x2\+chan_compose_batch_out<", route), route
+
+
 def test_a_second_writer_table_in_the_middle_runs_in_its_turn():
     w, h = 384, 54
     v = variants(w, h)

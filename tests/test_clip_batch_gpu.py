@@ -30,8 +30,9 @@ class Reads:
     def device(self, planes):
         return [dict(src=(planes[self.slot][0], self.w, self.h, m(self.w, self.h), "rgba8"))]
 
-    def oracle(self, host):
-        return [dict(src=Src([host[self.slot][0]], self.w, self.h, m(self.w, self.h), fmt="rgba8"))]
+    def oracle(self, host):  # (a frame nobody has written yet holds the poison)
+        frame = host[self.slot] if self.slot in host else poisoned("rgba8", self.w, self.h)
+        return [dict(src=Src([frame[0]], self.w, self.h, m(self.w, self.h), fmt="rgba8"))]
 
 
 def check_batch(jobs, w, h, what, specs=("709", "709")):
@@ -96,7 +97,14 @@ def check_batch(jobs, w, h, what, specs=("709", "709")):
         comp = composite(layers.oracle(host) if isinstance(layers, Reads) else layers, w, h, rd_o)
         for i, o in enumerate(outs):
             rc = writer(o["fmt"], o["spec"], o["own_table"])
-            host[o.get("slot", (j, i))] = oracle_frame(o["fmt"], comp, w, h, o["interlace"], rc[0], rc[1])
+            slot, frame = o.get("slot", (j, i)), oracle_frame(o["fmt"], comp, w, h, o["interlace"], rc[0], rc[1])
+            if o["interlace"] and slot in host:  # a field into a frame an earlier job wrote (a format with a row per line in every plane): its lines over that frame's
+                lines = slice(1 if o["interlace"] == 3 else 0, None, 2)
+                merged = [p.copy() for p in host[slot]]
+                for mp, fp in zip(merged, frame):
+                    mp.reshape(h, -1)[lines] = fp.reshape(h, -1)[lines]
+                frame = merged
+            host[slot] = frame
     for slot, planes in host.items():
         for pl, wnt in enumerate(planes):
             bad = np.flatnonzero(got[slot][pl] != wnt)
@@ -223,6 +231,25 @@ def test_a_job_that_writes_what_an_earlier_job_writes_starts_the_next_launch():
     route = check_batch([(layers, [dict(out("nv12"), slot="encoder") if j in (0, 2) else out("nv12"), out("rgba8")]) for j, layers in enumerate(clips(4, seed=3612))], W, H,
                         "the third job writes the first job's frame")
     assert route == "clip_up_multi<rgb>x2j2+clip_up_multi<rgb>x2j2", route
+
+
+def test_a_job_that_writes_what_an_earlier_job_reads_starts_the_next_launch():
+    """job 0's clip IS the rgba8 frame job 1 writes: two launches in order, job 0's frames made from what the buffer held before"""
+    second = clips(1, ("rgba8",), 3620, sw=W, sh=H)[0]
+    outs0 = [out("rgba8"), out("nv12")]
+    outs1 = [dict(out("rgba8"), slot="screen"), out("nv12")]
+    route = check_batch([(Reads("screen", W, H), outs0), (second, outs1)], W, H, "job 1 writes the frame job 0 reads")
+    assert route == "clip_up_multi<rgba>x2+clip_up_multi<rgba>x2", route
+
+
+def test_the_two_fields_of_one_frame_are_two_launches():
+    """no launch of this kernel holds two field modes: the upper and the lower field of one yuv422p8 frame, from two clips, in their turn"""
+    field = lambda il: [dict(out("yuv422p8", il), slot="frame"), out("rgba8", il)]
+    jobs = [small_clip(3630 + j, "yuv420p") for j in range(2)]  # (enlarged per written row of a field too)
+    route = check_batch([(jobs[0], field(1)), (jobs[1], field(3))], W, H, "two fields of one frame")
+    assert route == "clip_up_multi<rgb>x2+clip_up_multi<rgb>x2", route
+    route = check_batch([(jobs[0], field(3)), (jobs[1], field(3))], W, H, "one field twice")
+    assert route == "clip_up_multi<rgb>x2+clip_up_multi<rgb>x2", route
 
 
 def batch_args(jobs, w, h):

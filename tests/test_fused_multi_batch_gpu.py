@@ -324,6 +324,44 @@ def test_by_name_a_job_that_reads_an_earlier_output_splits_the_group(by_name):
     prog.destroy()
 
 
+def test_by_name_a_job_that_writes_an_earlier_layer_splits_the_group(by_name):
+    """job 2's v210 frame is written over job 0's layer 0: jobs 0 and 1 share a launch - job 0 has read its layer by then - and job 2
+    starts the next with job 3"""
+    b, w, h = by_name, by_name.w, by_name.h
+    prog = b.ctx.create_program("phaneron:fused", "fused_v210_combine_multi_2", [w, h])
+    jobs, outs, want = four_jobs(b, prog)
+    layer = jobs[0][1]["l0In"]
+    jobs[2][1]["output"] = layer
+    outs[2] = ([layer],) + tuple(outs[2][1:])
+    b.ctx.set_option("fused_multi_batch", 1)
+    with b.capi.trace(dry_run=True) as dry:
+        b.ctx.run_programs(jobs)
+    with b.capi.trace() as t:
+        b.ctx.run_programs(jobs)
+    b.ctx.wait()
+    assert t.kernels == dry.kernels == [SHARED % (3, 2), SHARED % (3, 2)], t.route
+    expect_bytes(b, outs, want, "a write after a read")
+    prog.destroy()
+
+
+def test_by_name_a_job_that_writes_an_earlier_output_splits_the_group(by_name):
+    """job 2's yuv422p8 chroma plane U is job 0's - no first plane, which the typed call would refuse: jobs 0 and 1 share a launch, job 2
+    starts the next with job 3, and its chroma stands"""
+    b, w, h = by_name, by_name.w, by_name.h
+    prog = b.ctx.create_program("phaneron:fused", "fused_v210_combine_multi_2", [w, h])
+    jobs, outs, want = four_jobs(b, prog)
+    jobs[2][1]["output1U"] = outs[0][1][1]
+    outs[2] = (outs[2][0], [outs[2][1][0], outs[0][1][1], outs[2][1][2]], outs[2][2])
+    want[0][1] = [want[0][1][0], want[2][1][1], want[0][1][2]]
+    b.ctx.set_option("fused_multi_batch", 1)
+    with b.capi.trace() as t:
+        b.ctx.run_programs(jobs)
+    b.ctx.wait()
+    assert t.kernels == [SHARED % (3, 2), SHARED % (3, 2)], t.route
+    expect_bytes(b, outs, want, "a write after a write")
+    prog.destroy()
+
+
 def test_by_name_another_output_list_splits_the_group(by_name):
     b = by_name
     prog = b.ctx.create_program("phaneron:fused", "fused_v210_combine_multi_2", [b.w, b.h])
