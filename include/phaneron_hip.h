@@ -54,7 +54,8 @@ extern "C" {
  *    (tests): which store policy the next launch would be given.  ph_clip_compose_multi: file playback - enlarged clips, decoders' frames
  *    under the default fill - for up to four consumers of any format the channel kernel writes, read once per source pixel; program
  *    "clip_compose_multi_<n>".  ph_clip_compose_batch_out (ph_chan_job_out): several channels' such frames in one launch; context
- *    option "clip_batch" */
+ *    option "clip_batch".  ph_clip_compose_transition_multi: file playback through a MIX or WIPE - a layer's src, incoming and mask clips
+ *    each read once per source pixel; program "clip_compose_trans_<n>" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -274,6 +275,8 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * output<k> (output<k>U / V / C), out<k>ColMatrix, out<k>GammaLut, interlace<k>: ph_chan_compose_multi - runs in its turn as a launch of its own.
  * So does a clip_compose_multi_<n> job: the same arguments, name for name, through ph_clip_compose_multi (grouped across jobs only with the
  * context option "clip_batch" = 1: consecutive such jobs of one geometry and Loader recipe in one ph_clip_compose_batch_out call).
+ * So does a clip_compose_trans_<n> job (ph_clip_compose_transition_multi: the same arguments, the transition's l<i>Transition, l<i>Mix,
+ * l<i>Incoming... and l<i>Mask... included), which no option groups.
  * So does a compose_up_multi_<n> job (ph_compose_up_write_multi): compose_up_write_v210_<n>'s layers (l<i>In, l<i>Matrix, packedRgb,
  * l<i>Width / l<i>Height) and chan_compose_multi_<n>'s outputs.  Its twin - the other field of a de-interlaced frame - is announced by
  * l0In2 (l<i>In2: its images), and its planes carry the first job's names behind the word twin: twinOutput (twinOutputU / V / C),
@@ -607,6 +610,27 @@ int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
 int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs,
                           uint32_t out_width, uint32_t out_height, const void *rd_col_matrix12, const void *rd_gamma_lut,
                           const void *rd_gamut9);
+/* FILE PLAYBACK THROUGH A MIX OR WIPE: a playlist's transition from one clip to the next (LOADBG ... MIX 25, transitioner.ts:165-176) on the
+ * read-once routes.  ph_clip_compose_multi's signature and contract: exactly, bit for bit and in order, the `n_out` calls of
+ * ph_chan_compose with each output's format, planes, interlace, matrix and table - the chain ph_pack_read / ph_v210_read of every present
+ * image -> ph_transform of each with its own matrix -> ph_transition_dissolve / ph_transition_wipe -> ph_combine -> ph_pack_write.  It takes
+ * everything ph_chan_compose_multi takes and answers its errors (yuv420p10 / p010 outputs included); every check of the arguments is made
+ * before the context is looked at, and a refused call writes nothing.  out_height == 0 is PH_OK.
+ * Routes, decided in this order.  (1) Every layer PH_TRANSITION_CUT: IS ph_clip_compose_multi, same routes, same trace names.  (2) The
+ * lines composed are the field every output wants, else the whole frame.  (3) Every PRESENT image - each layer's src, a dissolve's or
+ * wipe's incoming, a wipe's mask - must qualify as a src does for ph_clip_compose_multi on the composed lines (enlarged by 1 % or more
+ * without rotation or mirroring, or of the channel's size under the default fill on a frame write; a wire format or PH_SRC_RGBA_F32), the
+ * reader's and every output's table must have an LDS form, planar outputs need out_width % 8 == 0, and "chan_enlarged" must not be 0:
+ * else the call runs ph_chan_compose_multi on the same arguments, under that call's trace name.  (4) The outputs are grouped by registered
+ * writer table, in the order the tables first appear; a v210 output at out_width % 48 != 0 is made by a ph_chan_compose call of its own.
+ * (5) A group is ONE launch ("clip_up_trans<rgb|rgba>x<outputs>" in a trace: up to three rectangles per workgroup tile - src, incoming, mask,
+ * each converted once per source pixel by its own format's reader - then the transition and every output's writer) where n == 1, every
+ * present image is in a wire format (a 4:2:0 one of an even height) and "chan_enlarged" = 1; <rgb> where none of the images is rgba8 /
+ * bgra8.  (6) Otherwise two stages: every wire-format image through its format's reader into the queue's scratch images (finished f32
+ * images are taken as they are), then "compose_up_trans<rgba>x<outputs>j1" per table (the scratch images are f32 RGBA whatever the clips). */
+int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs,
+                                     uint32_t out_width, uint32_t out_height, const void *rd_col_matrix12, const void *rd_gamma_lut,
+                                     const void *rd_gamut9);
 /* Several CHANNELS' frames for any consumers in one launch: ph_chan_compose_batch's sharing (the tables loaded once, the wave steps of
  * all jobs in front of one barrier) with ph_chan_compose_multi's outputs - an encoder's yuv422p8 / yuv420p / nv12 frame, the screen's
  * rgba8 beside SDI's v210.  Exactly, in order, `n_jobs` calls of ph_chan_compose_multi (a job with n_out == 1: ph_chan_compose), bit for

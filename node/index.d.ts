@@ -144,7 +144,11 @@ export class clContext {
 	/** extension: `name` may be `clip_compose_multi_<n>` (n = layers): `chan_compose_multi_<n>`'s arguments, name for name, through
 	 * ph_clip_compose_multi - file playback (an enlarged clip, a decoder's frame under the default fill) for up to four consumers with the clip
 	 * read once per source pixel; same bytes as `chan_compose_multi_<n>`.  Reached by name only: the recording context (defer.js) does not plan it
-	 * (`clipBatch` lets the jobs of a tick share launches). */
+	 * (`clipBatch` lets the jobs of a tick share launches).
+	 * `name` may also be `clip_compose_trans_<n>`: the same arguments with the transition's (`l<i>Transition` 1 dissolve / 2 wipe, `l<i>Mix`,
+	 * `l<i>Incoming...`, `l<i>Mask...`) through ph_clip_compose_transition_multi - file playback through a MIX or WIPE, every clip of the
+	 * transition read once per source pixel; same bytes as `chan_compose_multi_<n>`.  Reached by name only: defer.js does not plan it and
+	 * `clipBatch` does not group it - every job is a launch of its own in its turn. */
 	createProgram(kernel: string, options: { name: string; globalWorkItems?: number | Uint32Array | number[]; workItemsPerGroup?: number }): Promise<OpenCLProgram>
 	runProgram(program: OpenCLProgram, params: KernelParams, queue?: number): Promise<RunTimings>
 	/** Recording contexts only: runProgram without the promise (node/jobs.js uses it per job of a batch).  null = not a recording

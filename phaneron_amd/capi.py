@@ -44,6 +44,7 @@ EXPORTS = [
     "ph_debug_image_nt",
     "ph_clip_compose_multi",
     "ph_clip_compose_batch_out",
+    "ph_clip_compose_transition_multi",
 ]
 
 
@@ -228,6 +229,7 @@ def lib():
         "ph_chan_compose_batch": (ci, [vp, ci, ci, C.POINTER(PhChanJob), cu, cu, vp, vp, vp, vp, vp]),
         "ph_chan_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_clip_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
+        "ph_clip_compose_transition_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_compose_up_write_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_compose_up_transition_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageTransLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_pack_write_multi": (ci, [vp, ci, vp, ci, C.POINTER(PhChanOutput), cu, cu]),
@@ -878,6 +880,20 @@ class Context:
         outs = self._chan_outputs(outputs)
         args = (self.h, queue, len(layers), arr, len(outputs), outs, out_w, out_h, _ptr(rd_cm), _ptr(rd_lut), _ptr(rd_gm))
         fn, h = lib().ph_clip_compose_multi, self.h
+        if prepare_only:
+
+            def job(_keep=(keep, layers, outputs, outs)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
+
+    def clip_compose_transition_multi(self, layers, outputs, out_w, out_h, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
+        """File playback through a MIX or WIPE for 1..4 consumers (ph_clip_compose_transition_multi): clip_compose_multi's arguments and
+        frames, with layers in a transition on the read-once routes too - one launch per writer table for one layer of wire-format clips."""
+        arr, keep = self._chan_layers(layers)
+        outs = self._chan_outputs(outputs)
+        args = (self.h, queue, len(layers), arr, len(outputs), outs, out_w, out_h, _ptr(rd_cm), _ptr(rd_lut), _ptr(rd_gm))
+        fn, h = lib().ph_clip_compose_transition_multi, self.h
         if prepare_only:
 
             def job(_keep=(keep, layers, outputs, outs)):

@@ -1528,26 +1528,28 @@ static int chan_ops(int n, const ph_chan_layer *layers, uint32_t out_w, uint32_t
 // Context option "chan_enlarged" = 0 (or PH_CHAN_ENLARGED=0): such frames through the channel kernel like any other (A/B runs, tests of that path).
 // v210_fill: v210 frames under the default fill count too - only worth it when several channels' frames of one shape share the launches
 // (one alone: 22.3 us by the channel kernel against 23.5; four to a call 18.7 against 15.6): ph_chan_compose_batch asks that way
+// one image - a layer's src, or a transition's incoming image or mask (ph_clip_compose_transition_multi asks per image)
+static bool chan_image_enlarged(const ph_chan_source &S, uint32_t out_w, uint32_t out_h, uint32_t interlace, bool v210_fill) {
+  const float *m = S.matrix9_host;
+  // (v210 frames, a file decoder's planar frames, packed 8-bit RGB: whatever has a reader of its own - ph_v210_read, ph_pack_read)
+  // - and finished f32 images, which the compositor takes as they are
+  const int fmt = fmt_of_src(S.format);
+  if ((fmt < 0 && S.format != PH_SRC_RGBA_F32) || !m || S.width <= 0 || S.height <= 0 || ((S.width & 1) && !fmt_rgb8(fmt) && S.format != PH_SRC_RGBA_F32))
+    return false;
+  if (m[1] != 0.0f || m[3] != 0.0f || !(m[0] > 0.0f) || !(m[4] > 0.0f)) return false;                      // (ph_kernels_up.hip compose_up_eligible)
+  // ... or a decoder's frame of the channel's size under the Mixer's default fill (the compositor takes exactly that placement beside the
+  // enlargements: compose_up_eligible): a 1080p yuv420p clip 26.1 -> 22.6 us, under a bgra8 graphic 45.2 -> 40.2.  Not v210 frames: the channel
+  // kernel's shared taps serve those better (22.3 against 23.2 us)
+  const bool fill = (v210_fill || S.format != PH_SRC_V210) && !interlace && (uint32_t)S.width == out_w && (uint32_t)S.height == out_h && m[0] == 1.0f && m[4] == 1.0f &&
+                    m[2] == 0.0f && m[5] == 0.0f;
+  if (!fill && ((double)m[0] * S.width > 0.99 * out_w || (double)m[4] * S.height * (interlace ? 2 : 1) > 0.99 * out_h)) return false;
+  if ((uint64_t)S.width * 16u * (uint64_t)S.height >= (1ull << 30) || S.width >= (1 << 22)) return false;
+  return true;
+}
 static bool chan_layers_enlarged(int n, const ph_chan_layer *layers, uint32_t out_w, uint32_t out_h, uint32_t interlace, bool v210_fill = false) {
   if (out_w % 2u) return false;
-  for (int i = 0; i < n; ++i) {
-    const ph_chan_layer &L = layers[i];
-    const float *m = L.src.matrix9_host;
-    // (v210 frames, a file decoder's planar frames, packed 8-bit RGB: whatever has a reader of its own - ph_v210_read, ph_pack_read)
-    // - and finished f32 images, which the compositor takes as they are
-    const int fmt = fmt_of_src(L.src.format);
-    if (L.transition != PH_TRANSITION_CUT || (fmt < 0 && L.src.format != PH_SRC_RGBA_F32) || !m || L.src.width <= 0 || L.src.height <= 0 ||
-        ((L.src.width & 1) && !fmt_rgb8(fmt) && L.src.format != PH_SRC_RGBA_F32))
-      return false;
-    if (m[1] != 0.0f || m[3] != 0.0f || !(m[0] > 0.0f) || !(m[4] > 0.0f)) return false;                      // (ph_kernels_up.hip compose_up_eligible)
-    // ... or a decoder's frame of the channel's size under the Mixer's default fill (the compositor takes exactly that placement beside the
-    // enlargements: compose_up_eligible): a 1080p yuv420p clip 26.1 -> 22.6 us, under a bgra8 graphic 45.2 -> 40.2.  Not v210 frames: the channel
-    // kernel's shared taps serve those better (22.3 against 23.2 us)
-    const bool fill = (v210_fill || L.src.format != PH_SRC_V210) && !interlace && (uint32_t)L.src.width == out_w && (uint32_t)L.src.height == out_h && m[0] == 1.0f && m[4] == 1.0f &&
-                      m[2] == 0.0f && m[5] == 0.0f;
-    if (!fill && ((double)m[0] * L.src.width > 0.99 * out_w || (double)m[4] * L.src.height * (interlace ? 2 : 1) > 0.99 * out_h)) return false;
-    if ((uint64_t)L.src.width * 16u * (uint64_t)L.src.height >= (1ull << 30) || L.src.width >= (1 << 22)) return false;
-  }
+  for (int i = 0; i < n; ++i)
+    if (layers[i].transition != PH_TRANSITION_CUT || !chan_image_enlarged(layers[i].src, out_w, out_h, interlace, v210_fill)) return false;
   return true;
 }
 // two such frames of one shape (layer count, clip sizes, placements): one launch of the compositor can make both
@@ -1560,17 +1562,19 @@ static bool chan_enlarged_same_shape(int n, const ph_chan_layer *a, const ph_cha
   return true;
 }
 // The reading half of the two-stage route, for `jobs` frames of one shape: every clip through its format's reader - as few launches as
-// their sizes allow - into the queue's scratch images (finished f32 images are taken as they are); il / sets: the images as the 2 x 2-block
-// compositor's entries take them.  The caller holds ctx->chan_scratch_mu[queue], and keeps it until its compositor launch is enqueued.
-static int chan_enlarged_read(ph_ctx *ctx, int queue, int jobs, int n, const ph_chan_layer *const *layers, const void *rd_cm, const void *rd_lut, const void *rd_gm,
-                              ph_image_layer (*il)[ph::kMaxLayers], const ph_image_layer **sets) {
+// their sizes allow - into the queue's scratch images (finished f32 images are taken as they are).  The caller holds
+// ctx->chan_scratch_mu[queue], and keeps it until its compositor launch is enqueued.
+// The images are given as a flat list, srcs[j * n + i]: image i of job j (n: up to kMaxUpJobs * kMaxLayers / jobs - a frame in a transition
+// brings its partners as further images); imgs[j * n + i]: where the compositor finds it.
+static int chan_images_read(ph_ctx *ctx, int queue, int jobs, int n, const ph_chan_source *const *srcs, const void *rd_cm, const void *rd_lut, const void *rd_gm,
+                            void **imgs) {
   // the images live in the channel compositor's scratch area of the queue (launches on one queue are in order)
-  size_t off[ph::kMaxLayers], per_job = 0;
+  size_t off[ph::kMaxUpJobs * ph::kMaxLayers], per_job = 0;
   bool one_size = true;
   for (int i = 0; i < n; ++i) {
     off[i] = per_job;
-    per_job += ((size_t)layers[0][i].src.width * layers[0][i].src.height * 16u + 255u) & ~(size_t)255u;
-    one_size = one_size && layers[0][i].src.width == layers[0][0].src.width && layers[0][i].src.height == layers[0][0].src.height;
+    per_job += ((size_t)srcs[i]->width * srcs[i]->height * 16u + 255u) & ~(size_t)255u;
+    one_size = one_size && srcs[i]->width == srcs[0]->width && srcs[i]->height == srcs[0]->height;
   }
   const size_t total = per_job * (size_t)jobs;
   // Three sets of images taken in turn: a frame's read kernel overwriting the very lines the previous frame's compositor has just read
@@ -1586,37 +1590,34 @@ static int chan_enlarged_read(ph_ctx *ctx, int queue, int jobs, int n, const ph_
     base = (char *)ctx->chan_index[queue] + total * (ctx->chan_scratch_turn[queue]++ % kTurns);
   }
   const void *ins[ph::kMaxUpJobs * ph::kMaxLayers];
-  void *imgs[ph::kMaxUpJobs * ph::kMaxLayers];
   for (int j = 0; j < jobs; ++j) {
     for (int i = 0; i < n; ++i) {
-      const ph_chan_source &S = layers[j][i].src;
+      const ph_chan_source &S = *srcs[j * n + i];
       ins[j * n + i] = S.data, imgs[j * n + i] = S.format == PH_SRC_RGBA_F32 ? const_cast<void *>(S.data) : base + per_job * (size_t)j + off[i];
-      il[j][i] = ph_image_layer{imgs[j * n + i], PH_IMG_RGBA_F32, S.width, S.height, S.matrix9_host};
     }
-    sets[j] = il[j];
   }
   int rc = PH_OK;
   const int frames = jobs * n;
   bool all_v210 = true;
-  for (int f = 0; f < frames; ++f) all_v210 = all_v210 && layers[f / n][f % n].src.format == PH_SRC_V210;
+  for (int f = 0; f < frames; ++f) all_v210 = all_v210 && srcs[f]->format == PH_SRC_V210;
   bool one_reader = !all_v210 && one_size && frames > 1;  // every frame a decoder's frame of ONE format, size and Loader matrix: one launch reads them all
   for (int f = 0; f < frames && one_reader; ++f) {
-    const ph_chan_source &S = layers[f / n][f % n].src, &S0 = layers[0][0].src;
+    const ph_chan_source &S = *srcs[f], &S0 = *srcs[0];
     one_reader = S.format == S0.format && fmt_of_src(S.format) > PH_FMT_V210 && S.col_matrix12 == S0.col_matrix12;
   }
   if (one_reader) {
     const void *planes[ph::kMaxUpJobs * ph::kMaxLayers][3];
     for (int f = 0; f < frames; ++f) {
-      const ph_chan_source &S = layers[f / n][f % n].src;
+      const ph_chan_source &S = *srcs[f];
       planes[f][0] = S.data, planes[f][1] = S.data_u, planes[f][2] = S.data_v;
     }
-    const ph_chan_source &S0 = layers[0][0].src;
+    const ph_chan_source &S0 = *srcs[0];
     for (int f = 0; f < frames && rc == PH_OK; f += ph::kMaxLayers)
       rc = ph_pack_read_batch(ctx, queue, fmt_of_src(S0.format), frames - f < ph::kMaxLayers ? frames - f : ph::kMaxLayers, planes + f, imgs + f,
                               (uint32_t)S0.width, (uint32_t)S0.height, S0.col_matrix12 ? S0.col_matrix12 : rd_cm, rd_lut, rd_gm);
   } else if (!all_v210) {  // each clip through the reader of its format (a source with code ranges of its own brings its Loader matrix)
     for (int f = 0; f < frames && rc == PH_OK; ++f) {
-      const ph_chan_source &S = layers[f / n][f % n].src;
+      const ph_chan_source &S = *srcs[f];
       if (S.format == PH_SRC_RGBA_F32) continue;  // an image: nothing to read
       if (S.format == PH_SRC_V210) {
         rc = ph_v210_read(ctx, queue, S.data, imgs[f], (uint32_t)S.width, (uint32_t)S.height, rd_cm, rd_lut, rd_gm);
@@ -1628,13 +1629,31 @@ static int chan_enlarged_read(ph_ctx *ctx, int queue, int jobs, int n, const ph_
     }
   } else if (one_size && frames > 1) {
     for (int f = 0; f < frames && rc == PH_OK; f += ph::kMaxLayers)
-      rc = ph_v210_read_batch(ctx, queue, frames - f < ph::kMaxLayers ? frames - f : ph::kMaxLayers, ins + f, imgs + f, (uint32_t)layers[0][0].src.width,
-                              (uint32_t)layers[0][0].src.height, rd_cm, rd_lut, rd_gm);
+      rc = ph_v210_read_batch(ctx, queue, frames - f < ph::kMaxLayers ? frames - f : ph::kMaxLayers, ins + f, imgs + f, (uint32_t)srcs[0]->width,
+                              (uint32_t)srcs[0]->height, rd_cm, rd_lut, rd_gm);
   } else {
     for (int f = 0; f < frames && rc == PH_OK; ++f)
-      rc = ph_v210_read(ctx, queue, ins[f], imgs[f], (uint32_t)layers[f / n][f % n].src.width, (uint32_t)layers[f / n][f % n].src.height, rd_cm, rd_lut, rd_gm);
+      rc = ph_v210_read(ctx, queue, ins[f], imgs[f], (uint32_t)srcs[f]->width, (uint32_t)srcs[f]->height, rd_cm, rd_lut, rd_gm);
   }
   return rc;
+}
+// every layer's src of `jobs` frames of one shape; il / sets: the images as the 2 x 2-block compositor's entries take them
+static int chan_enlarged_read(ph_ctx *ctx, int queue, int jobs, int n, const ph_chan_layer *const *layers, const void *rd_cm, const void *rd_lut, const void *rd_gm,
+                              ph_image_layer (*il)[ph::kMaxLayers], const ph_image_layer **sets) {
+  const ph_chan_source *srcs[ph::kMaxUpJobs * ph::kMaxLayers];
+  void *imgs[ph::kMaxUpJobs * ph::kMaxLayers];
+  for (int j = 0; j < jobs; ++j)
+    for (int i = 0; i < n; ++i) srcs[j * n + i] = &layers[j][i].src;
+  const int rc = chan_images_read(ctx, queue, jobs, n, srcs, rd_cm, rd_lut, rd_gm, imgs);
+  if (rc) return rc;
+  for (int j = 0; j < jobs; ++j) {
+    for (int i = 0; i < n; ++i) {
+      const ph_chan_source &S = layers[j][i].src;
+      il[j][i] = ph_image_layer{imgs[j * n + i], PH_IMG_RGBA_F32, S.width, S.height, S.matrix9_host};
+    }
+    sets[j] = il[j];
+  }
+  return PH_OK;
 }
 // `jobs` frames of one shape and field mode (1 .. kMaxUpJobs, different outputs): the clips read - as few launches as their sizes allow -
 // and ONE compositor launch (ph_compose_up_write_v210_batch)
@@ -2796,6 +2815,153 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
     }
     for (int i = 0; i < n; ++i) m.up.layer[i].ptr = il[0][i].data;
     const hipError_t e = ph::launch_compose_up_multi(stream_of(ctx, queue), m, false, (uint32_t)ctx->props.multiProcessorCount);
+    if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  }
+  return PH_OK;
+}
+
+static bool chan_sources_same_shape(const ph_chan_source &a, const ph_chan_source &b) {
+  if (a.width != b.width || a.height != b.height) return false;
+  for (int k = 0; k < 9; ++k)
+    if (a.matrix9_host[k] != b.matrix9_host[k]) return false;
+  return true;
+}
+
+/* File playback through a MIX or WIPE, for up to four consumers: see include/phaneron_hip.h.  ph_clip_compose_multi's signature and contract -
+ * exactly the n_out calls of ph_chan_compose in order, bit for bit; every check is made before the context is looked at, a refused call
+ * writes nothing - with layers in a transition taken by the read-once routes too: every present image (a layer's src, a transition's
+ * incoming image, a wipe's mask) must qualify as a src does for ph_clip_compose_multi.  One layer whose images are all wire-format clips:
+ * one launch of clip_up_trans_kernel per writer table; else the format readers into the queue's scratch images (f32 RGBA, whatever the
+ * clips' formats: the launch is the <rgba> one) and one compose_up_trans launch per table.  What these routes do not take runs
+ * ph_chan_compose_multi on the same arguments inside the call. */
+int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w,
+                                     uint32_t out_h, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  const char *const fn = "ph_clip_compose_transition_multi";
+  if (!layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n_out < 1 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  if (const int bad = fused_multi_outputs_check(fn, queue, n_out, outs, out_w, out_h)) return bad;
+  {  // the layers and their transitions, as the channel kernel's entries check them (their texts)
+    ph::ChanArgs probe{};
+    int n_ops = 0;
+    if (const int bad = chan_ops(n, layers, out_w, out_h, probe.op, probe.plane_u, probe.plane_v, probe.cm_op, &probe.planar, &n_ops)) return bad;
+  }
+  if (!ctx) return fail(PH_E_INVALID, "%s: ctx is NULL", fn);
+  // 1. no transition: ph_clip_compose_multi, its routes under its names
+  bool any = false;
+  for (int i = 0; i < n; ++i) any = any || layers[i].transition != PH_TRANSITION_CUT;
+  if (!any) return ph_clip_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm);
+  // 2. the lines composed: the field every output wants, or the whole frame (a field output then takes the rows of its parity)
+  bool same_lines = true;
+  for (int k = 1; k < n_out; ++k) same_lines = same_lines && outs[k].interlace == outs[0].interlace;
+  const uint32_t interlace = same_lines ? outs[0].interlace : 0u;
+  // 3. every present image, in the order layer by layer: src, incoming, mask
+  const ph_chan_source *img[ph::kMaxLayers * 3];
+  int first_img[ph::kMaxLayers], n_img = 0;
+  for (int i = 0; i < n; ++i) {
+    first_img[i] = n_img;
+    img[n_img++] = &layers[i].src;
+    if (layers[i].transition != PH_TRANSITION_CUT) img[n_img++] = &layers[i].incoming;
+    if (layers[i].transition == PH_TRANSITION_WIPE) img[n_img++] = &layers[i].mask;
+  }
+  const LutRef rref = lds_view(ctx, rd_lut);
+  LutRef wref[ph::kMaxUpOuts];
+  bool takes = ctx->chan_enlarged != 0 && rref.get() && out_w % 2u == 0;
+  for (int k = 0; k < n_out && takes; ++k) {
+    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
+    takes = wref[k].get() && !(fmt_planar(outs[k].format) && out_w % 8);
+  }
+  ph::UpArgs base{};
+  base.n = n, base.jobs = 1;
+  compose_up_lines(base, out_w, out_h, interlace);
+  bool wire = true, alpha = false;  // every image in a wire format the clip kernel reads; an image that carries alpha
+  for (int f = 0; f < n_img && takes; ++f) {
+    const ph_chan_source &S = *img[f];
+    takes = chan_image_enlarged(S, out_w, out_h, interlace, /*v210_fill*/ true);  // (it has a placement then)
+    if (!takes) break;
+    ph::UpArgs one = base;
+    one.n = 1, one.layer[0] = up_layer_of(S);
+    takes = ph::compose_up_eligible(one);
+    const int fmt = fmt_of_src(S.format);
+    wire = wire && fmt >= 0 && !(fmt_v420(fmt) && (S.height & 1));
+    alpha = alpha || fmt < 0 || fmt_rgb8(fmt);
+  }
+  if (!takes) return ph_chan_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm);
+  if (!base.lines) return PH_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  const bool one_launch = ctx->chan_enlarged == 1 && n == 1 && wire;
+  // 4. the outputs by writer table, in the order the tables first appear; a v210 output whose lines end in a tail quad through
+  // ph_chan_compose, alone (ph_clip_compose_multi's route 4; the scratch area's lock as there)
+  void *image[ph::kMaxLayers * 3];
+  std::unique_lock<std::mutex> images;
+  for (int k = 0; k < n_out; ++k) {
+    bool seen = false;
+    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    if (seen) continue;
+    ph::UpMultiArgs m{};
+    m.up = base, m.up.wr = *wref[k].get();
+    for (int i = 0; i < n; ++i) m.up.layer[i] = up_layer_of(layers[i].src);
+    for (int j = k; j < n_out; ++j) {
+      const ph_chan_output &o = outs[j];
+      if (o.wr_gamma_lut != outs[k].wr_gamma_lut) continue;
+      if (o.format == PH_FMT_V210 && out_w % 48) {
+        if (images.owns_lock()) images.unlock();
+        rc = ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, o.planes, out_w, out_h, o.interlace, rd_cm, rd_lut, rd_gm, o.wr_col_matrix12, o.wr_gamma_lut);
+        if (rc) return rc;
+        continue;
+      }
+      m.out[m.n_out++] = up_out_of(o, same_lines, out_w, out_h);
+    }
+    if (!m.n_out) continue;
+    // 5. the group's one launch: a single layer, every image a clip in its wire format
+    if (one_launch) {
+      const ph_chan_layer &L = layers[0];
+      ph::ClipUpTransArgs t{};
+      ph::ClipUpMultiArgs &c = t.multi;
+      c.clip.up = m.up, c.n_out = m.n_out;
+      for (uint32_t i = 0; i < m.n_out; ++i) c.out[i] = m.out[i];
+      c.clip.rd = *rref.get(), c.clip.rd_gm = (const float *)rd_gm;
+      c.clip.src[0] = clip_src_of(L.src, fmt_of_src(L.src.format), rd_cm);
+      t.kind = (uint32_t)L.transition, t.mix = L.mix;
+      const ph_chan_source *const theirs[2] = {&L.incoming, &L.mask};
+      for (int w = 0; w < (L.transition == PH_TRANSITION_WIPE ? 2 : 1); ++w) {
+        t.partner[w] = up_layer_of(*theirs[w]);
+        t.partner_src[w] = clip_src_of(*theirs[w], fmt_of_src(theirs[w]->format), rd_cm);
+        t.same |= chan_sources_same_shape(*theirs[w], L.src) ? 1u << w : 0u;
+      }
+      const uint32_t grid = ph::clip_up_trans_plan(t, !alpha, (uint32_t)ctx->props.multiProcessorCount);
+      if (grid) {
+        if (images.owns_lock()) images.unlock();
+        rc = with_scratch(fn, ctx, queue, (size_t)c.clip.wg_bytes * grid + 4096u, [&](hipStream_t s, void *area) {
+          c.clip.scratch = (char *)area;
+          return ph::launch_clip_up_trans(s, t, !alpha, grid);
+        });
+        if (rc) return rc;
+        continue;
+      }
+    }
+    // 6. the two stages: every wire-format image through its format's reader into the queue's scratch images (finished f32 images as they
+    // are), then the transition compositor's launch
+    if (!images.owns_lock()) {
+      images = std::unique_lock<std::mutex>(ctx->chan_scratch_mu[queue]);
+      rc = chan_images_read(ctx, queue, 1, n_img, img, rd_cm, rd_lut, rd_gm, image);
+      if (rc) return rc;
+    }
+    ph::UpTransArgs t{};
+    t.multi = m;
+    for (int i = 0; i < n; ++i) {
+      const ph_chan_layer &L = layers[i];
+      t.multi.up.layer[i].ptr = image[first_img[i]];
+      t.kind[i] = (uint32_t)L.transition, t.mix[0][i] = L.mix;
+      const ph_chan_source *const theirs[2] = {&L.incoming, &L.mask};
+      for (int w = 0; w < (L.transition == PH_TRANSITION_WIPE ? 2 : L.transition == PH_TRANSITION_CUT ? 0 : 1); ++w) {
+        t.partner[i][w] = up_layer_of(*theirs[w]);
+        t.partner[i][w].ptr = image[first_img[i] + 1 + w];
+        t.same[i] |= chan_sources_same_shape(*theirs[w], L.src) ? 1u << w : 0u;
+      }
+    }
+    const hipError_t e = ph::launch_compose_up_trans(stream_of(ctx, queue), t, false, (uint32_t)ctx->props.multiProcessorCount);
     if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   }
   return PH_OK;

@@ -450,6 +450,25 @@ static_assert(sizeof(ClipUpMultiArgs) < 4096, "kernel arguments are limited to 4
 // grid: clip_up_plan(clip, rgb12, num_cus, false); named clip_up_multi<rgb|rgba>x<outputs> in a route trace, with several jobs
 // clip_up_multi<rgb|rgba>x<outputs>j<jobs>
 hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rgb12, uint32_t grid);
+// ONE wire-format clip in a TRANSITION for any consumer (ph_clip_compose_transition_multi, clip_up_trans_kernel): a playlist's MIX or WIPE
+// from one file to the next.  multi is the frame as for clip_up_multi_kernel with a single layer and a single job - multi.clip.up.layer[0]
+// and multi.clip.src[0] are the layer's `src` - and the transition brings the incoming clip (dissolve, wipe) and the mask clip (wipe), each
+// with a size and a placement of its own.  A workgroup converts up to three rectangles per tile: slot 0 src, slot 1 incoming, slot 2 mask;
+// multi.clip.rect_off / rect_cap are indexed by slot.
+struct ClipUpTransArgs {
+  ClipUpMultiArgs multi;
+  UpLayer partner[2];        // [0: incoming, 1: mask]: size and placement (ptr / pitch are the kernel's)
+  ClipSrc partner_src[2];
+  uint32_t kind;             // PH_TRANSITION_DISSOLVE or PH_TRANSITION_WIPE
+  uint32_t same;             // bit 0: the incoming clip has the layer's size and placement, bit 1: the mask has
+  float mix;                 // dissolve
+};
+static_assert(sizeof(ClipUpTransArgs) < 4096, "kernel arguments are limited to 4 KiB");
+// plans the launch as a clip of three "layers" (clip_up_plan: tiling, a rectangle bound per slot from that image's own size and placement);
+// returns the number of workgroups (0: not for this kernel)
+uint32_t clip_up_trans_plan(ClipUpTransArgs &t, bool rgb12, uint32_t num_cus);
+// named clip_up_trans<rgb|rgba>x<outputs> in a route trace.  Refuses what launch_clip_up_multi refuses, several jobs or layers, and a cut
+hipError_t launch_clip_up_trans(hipStream_t s, const ClipUpTransArgs &t, bool rgb12, uint32_t grid);
 // The same with layers in a transition (ph_compose_up_transition_multi, compose_up_trans_kernel): a layer may bring an incoming image
 // (dissolve, wipe) and a mask (wipe), each with a size and a placement of its own.  multi.up.layer[l] is the layer's `src`; job j > 0
 // differs in the images' data, the outputs' planes and the mix values.  multi.up.shared is not used: geometry is per layer, and a

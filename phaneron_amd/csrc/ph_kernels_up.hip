@@ -810,7 +810,8 @@ struct ClipRect {  // uniform: the source rectangle of a tile, inside the image 
 // FIRST: the launch's first rectangle.  Its first round of samples is requested BEFORE the reader's table is loaded (the table load and the
 // samples' trip to HBM overlap), and the table load + barrier happen in here.  Within a rectangle a round's samples are requested before
 // the round before it is converted.
-template <int FMT, bool RGB12, bool FIRST>
+// BLOCK: the lanes of the kernel's workgroup (clip_up_trans_kernel is built with fewer too)
+template <int FMT, bool RGB12, bool FIRST, int BLOCK = kUpBlock>
 __device__ __forceinline__ void clip_convert(const ClipSrc &S, const UpLayer &L, const ClipRect &R, char *dst, uint32_t ppitch, const float *rd_gm, const LutK &rlk,
                                              const LutView &rd_view) {
   // the rectangle's pixels row by row over all the workgroup's lanes, kClipRound of them per lane and round
@@ -824,7 +825,7 @@ __device__ __forceinline__ void clip_convert(const ClipSrc &S, const UpLayer &L,
   auto request = [&](uint32_t base, Round &q) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < kClipRound; ++i) {
-      const uint32_t idx = base + (uint32_t)i * kUpBlock < total ? base + (uint32_t)i * kUpBlock : total - 1u;  // (lanes past the end redo the last pixel)
+      const uint32_t idx = base + (uint32_t)i * BLOCK < total ? base + (uint32_t)i * BLOCK : total - 1u;  // (lanes past the end redo the last pixel)
       uint32_t r = (uint32_t)((float)idx * inv_w);  // idx / R.w, off by one at most
       r -= r * R.w > idx ? 1u : 0u;
       r += (r + 1u) * R.w <= idx ? 1u : 0u;
@@ -835,7 +836,7 @@ __device__ __forceinline__ void clip_convert(const ClipSrc &S, const UpLayer &L,
   Round cur;
   if (total) request(threadIdx.x, cur);  // (uniform)
   if (FIRST) {
-    lds_lut_load<kUpBlock>(rd_view);
+    lds_lut_load<BLOCK>(rd_view);
     __syncthreads();
   }
   ReadK k;
@@ -845,9 +846,9 @@ __device__ __forceinline__ void clip_convert(const ClipSrc &S, const UpLayer &L,
   } else {
     k = load_read_k(S.cm, rd_gm);
   }
-  for (uint32_t base = threadIdx.x; base < total; base += kClipRound * kUpBlock) {
+  for (uint32_t base = threadIdx.x; base < total; base += kClipRound * BLOCK) {
     Round nxt = cur;
-    const uint32_t next_base = base + kClipRound * kUpBlock;
+    const uint32_t next_base = base + kClipRound * BLOCK;
     if (next_base - threadIdx.x < total) request(next_base < total ? next_base : total - 1u, nxt);  // (uniform test: the whole workgroup takes the round or not)
 #pragma unroll
     for (int i = 0; i < kClipRound; ++i) {
@@ -1165,6 +1166,186 @@ __global__ __launch_bounds__(kUpBlock) void clip_up_multi_kernel(ClipUpMultiArgs
   }
 }
 
+// ---- ONE clip in a TRANSITION, for any consumer: a playlist's MIX or WIPE from one file to the next -------------------------------------
+// The Transitioner's frame of file playback (transitioner.ts:165-176): one layer whose `src` clip dissolves or wipes into an `incoming` clip,
+// a wipe through a mask clip - two or three decoders' frames, each with a size and a placement of its own.  Phase 1 is clip_up_multi_kernel's
+// with up to three rectangles per tile - slot 0 src, slot 1 incoming, slot 2 the mask - each bounded by its own image's taps and converted by
+// its own format's reader, all in front of the one table swap; phase 2 is up_trans_layer's arithmetic (compose_up_trans_kernel) on patches
+// taken from the rectangles, then compose_up_multi_kernel's twelve table reads and every output's up_write_out.  This is a THIRD copy of
+// those texts, kept in step by hand: the kernels it copies from are pinned (profiles/clip_multi_resources.txt, profiles/up_trans_resources.txt)
+// and are not rebuilt around shared functions.
+// A frame of one layer: what the transition leaves IS the frame, and no writer reads its alpha - the alpha arithmetic of up_values and of the
+// mixes below is written out as transition.ts has it and dropped by the compiler.
+//
+// Lanes.  compose_up_trans_kernel runs 768 lanes because a transitioning layer's sixteen values spill at 1024; here only twelve are alive
+// (no alpha) and neither 1024 lanes (119 vector registers of 128) nor 768 (125 of 168) spills one or uses scratch
+// (profiles/clip_trans_resources.txt).  Timed on the one-launch route, 1024 against 768 lanes: two 1080p yuv420p files dissolving on a
+// 1080p channel -> nv12 33.4 / 36.3 us, -> v210 + rgba8 35.2 / 38.6; a 720p file into a 1080p one 30.3 / 34.3; two 1080p p010 files on
+// 2160p -> yuv422p10 65.8 / 76.7; a wipe through a 960 x 540 v210 mask 40.6 / 43.6 (profiles/clip_transition_lanes.jsonl; spreads up to
+// 1.2 us): 1024 lanes it is, the clip kernels' kUpBlock - clip_up_plan's tiling counts rounds of sixteen waves.
+#ifndef PH_CLIP_TRANS_BLOCK
+#define PH_CLIP_TRANS_BLOCK 1024
+#endif
+constexpr int kClipTransBlock = PH_CLIP_TRANS_BLOCK;
+static_assert(kMaxLayers >= 3, "clip_up_trans_plan plans the three slots as three layers");
+template <bool RGB12>
+__global__ __launch_bounds__(kClipTransBlock) void clip_up_trans_kernel(ClipUpTransArgs tr) {
+  const ClipUpMultiArgs &cm = tr.multi;
+  const ClipUpArgs &c = cm.clip;
+  const UpArgs &a = c.up;
+  constexpr uint32_t kTexel = RGB12 ? 12u : 16u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  // the tile
+  const uint32_t upr = (a.cover_w + kUpCols - 1u) / kUpCols, rps = (a.lines + 1u) / 2u;
+  const uint32_t ty = blockIdx.x / c.gx, tx = blockIdx.x - ty * c.gx;
+  const uint32_t cu0 = tx * c.tcu, rp0 = ty * c.trp;
+  const uint32_t ncu = cu0 + c.tcu <= upr ? c.tcu : upr - cu0, nrp = rp0 + c.trp <= rps ? c.trp : rps - rp0;
+  char *const mine = c.scratch + (size_t)blockIdx.x * c.wg_bytes;
+  const int slots = tr.kind == (uint32_t)PH_TRANSITION_WIPE ? 3 : 2;  // uniform
+  // ---- phase 1: the reader's table; every present image's rectangle converted
+  const LutK rlk = make_lut_k(c.rd);
+  uint4 *const info = reinterpret_cast<uint4 *>(g_lds + c.info_off);
+#pragma unroll 1
+  for (int s = 0; s < slots; ++s) {
+    const UpLayer L = s ? tr.partner[s - 1] : a.layer[0];
+    const ClipSrc S = s ? tr.partner_src[s - 1] : c.src[0];
+    const uint32_t x_first = cu0 * kUpCols, x_end = (cu0 + ncu) * kUpCols < a.out_w ? (cu0 + ncu) * kUpCols : a.out_w;
+    const uint32_t li_last = 2u * (rp0 + nrp) < a.lines ? 2u * (rp0 + nrp) - 1u : a.lines - 1u;
+    ClipRect R{0, 0, 0, 0};
+    if (x_first < x_end) {
+      int c_lo = clip_tap_col(L, x_first, a.out_w), c_hi = clip_tap_col(L, x_end - 1u, a.out_w) + 2;
+      int r_lo = clip_tap_row(L, a.first_line + 2u * rp0 * a.line_step, a.out_h), r_hi = clip_tap_row(L, a.first_line + li_last * a.line_step, a.out_h) + 2;
+      c_lo = c_lo < 0 ? 0 : c_lo, r_lo = r_lo < 0 ? 0 : r_lo;
+      c_hi = c_hi >= (int)L.w ? (int)L.w - 1 : c_hi, r_hi = r_hi >= (int)L.h ? (int)L.h - 1 : r_hi;
+      if (c_hi >= c_lo && r_hi >= r_lo) R = ClipRect{(uint32_t)c_lo, (uint32_t)r_lo, (uint32_t)(c_hi - c_lo + 1), (uint32_t)(r_hi - r_lo + 1)};
+    }
+    R.c0 = __builtin_amdgcn_readfirstlane(R.c0), R.r0 = __builtin_amdgcn_readfirstlane(R.r0);
+    R.w = __builtin_amdgcn_readfirstlane(R.w), R.h = __builtin_amdgcn_readfirstlane(R.h);
+    const uint32_t ppitch = R.w * kTexel;
+    if (ppitch && R.h * ppitch > c.rect_cap[s]) R.h = c.rect_cap[s] / ppitch;  // (the launcher's bound holds: never taken)
+    char *const dst = mine + c.rect_off[s];
+#define PH_CLIP_CASE(F)                                                                                                   \
+  case F:                                                                                                                  \
+    if (s == 0) clip_convert<F, RGB12, true, kClipTransBlock>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);                   \
+    else clip_convert<F, RGB12, false, kClipTransBlock>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);                         \
+    break;
+    switch (S.fmt) {  // uniform
+      PH_CLIP_CASE(PH_FMT_V210)
+      PH_CLIP_CASE(PH_FMT_YUV422P10)
+      PH_CLIP_CASE(PH_FMT_YUV422P8)
+      PH_CLIP_CASE(PH_FMT_YUV420P)
+      PH_CLIP_CASE(PH_FMT_NV12)
+      PH_CLIP_CASE(PH_FMT_YUV420P10)
+      PH_CLIP_CASE(PH_FMT_P010)
+      PH_CLIP_CASE(PH_FMT_RGBA8)
+      default:
+        if (s == 0) clip_convert<PH_FMT_BGRA8, RGB12, true, kClipTransBlock>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);
+        else clip_convert<PH_FMT_BGRA8, RGB12, false, kClipTransBlock>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd);
+        break;
+    }
+#undef PH_CLIP_CASE
+    if (threadIdx.x == 0) {  // the image as phase 2 sees it (clip_up_write_v210_kernel)
+      const uint64_t base = (uint64_t)(uintptr_t)dst - ((uint64_t)R.r0 * ppitch + (uint64_t)R.c0 * kTexel);
+      info[s] = make_uint4((uint32_t)base, (uint32_t)(base >> 32), ppitch ? ppitch : kTexel, 0u);
+    }
+  }
+  // ---- the swap: every wave's rectangle rows are in L2, the writer's table comes in
+  __threadfence_block();
+  __syncthreads();
+  const LutK lk = make_lut_k(a.wr);
+  lds_lut_load<kClipTransBlock>(a.wr);
+  __syncthreads();
+  // ---- phase 2: the layer's four block pixels after transform and transition, every output's writer behind them
+  const uint32_t role = lane - 3u * (lane / 3u);
+  auto image_of = [&](int s) __attribute__((always_inline)) {
+    UpLayer L = s ? tr.partner[s - 1] : a.layer[0];
+    const uint4 d = info[s];  // uniform address: one broadcast read
+    const uint64_t base = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)d.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)d.y) << 32;
+    L.ptr = reinterpret_cast<const void *>((uintptr_t)base);
+    L.pitch = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.z);
+    L.pad = kUpOutside - 16u;
+    return L;
+  };
+  const uint32_t kind = tr.kind, same = tr.same;  // uniform
+  const uint32_t units = ncu * nrp;
+  for (uint32_t u = wave; u < units; u += kClipTransBlock / 64) {
+    const uint32_t rp_in = ncu == 1u ? u : u / ncu, cu_in = u - rp_in * ncu;
+    UpStep st;
+    clip_step(a, 0u, cu0 + cu_in, rp0 + rp_in, lane, st);
+    // (up_trans_layer, on the rectangles)
+    UpTexel v[2][2];
+    UpGeo geo;
+    {
+      const UpLayer L = image_of(0);
+      geo = up_geo<RGB12>(L, st);
+      UpPatch p;
+      up_fetch<RGB12>(L, geo, p);
+      up_values<RGB12>(p, geo, [&](int dy, int dx, const UpTexel &t) __attribute__((always_inline)) { v[dy][dx] = t; });
+    }
+    // a partner of the layer's size and placement has a rectangle of the layer's shape (its base aside) and is filtered with the layer's
+    // geometry; any other brings its own, which takes the layer's place - and is replaced in its turn if the next partner is like the layer again
+    bool geo_is_layers = true;
+    auto partner = [&](int which, auto each) __attribute__((always_inline)) {
+      const UpLayer P = image_of(1 + which);
+      const bool like_layer = (same >> which) & 1u;
+      if (!(like_layer && geo_is_layers)) geo = up_geo<RGB12>(P, st);  // uniform
+      geo_is_layers = like_layer;
+      UpPatch p;
+      up_fetch<RGB12>(P, geo, p);
+      up_values<RGB12>(p, geo, each);
+    };
+    if (kind == (uint32_t)PH_TRANSITION_WIPE) {  // the mask before the incoming image, as up_trans_layer
+      float mr[2][2];
+      partner(1, [&](int dy, int dx, const UpTexel &t) __attribute__((always_inline)) {
+        const float mk = t.r, rm = 1.0f - mk;
+        UpTexel &s = v[dy][dx];
+        mr[dy][dx] = mk, s.r = s.r * rm, s.g = s.g * rm, s.b = s.b * rm, s.a = s.a * rm;
+      });
+      partner(0, [&](int dy, int dx, const UpTexel &t) __attribute__((always_inline)) {
+        const float mk = mr[dy][dx];
+        UpTexel &s = v[dy][dx];
+        s.r = fma_rn(t.r, mk, s.r), s.g = fma_rn(t.g, mk, s.g), s.b = fma_rn(t.b, mk, s.b), s.a = fma_rn(t.a, mk, s.a);
+      });
+    } else {
+      const float mix = tr.mix, rmix = 1.0f - mix;  // uniform
+      partner(0, [&](int dy, int dx, const UpTexel &t) __attribute__((always_inline)) {
+        UpTexel &s = v[dy][dx];
+        s.r = fma_rn(s.r, mix, t.r * rmix), s.g = fma_rn(s.g, mix, t.g * rmix), s.b = fma_rn(s.b, mix, t.b * rmix), s.a = fma_rn(s.a, mix, t.a * rmix);
+      });
+    }
+    // the twelve table reads of the block's four pixels, started together - once for all outputs (compose_up_multi_kernel)
+    float t[2][2][3];
+    {
+      PxPending pend[2][2];
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx)
+          pend[dy][dx] = write_px_issue(lds_lut_index_unit(v[dy][dx].r), lds_lut_index_unit(v[dy][dx].g), lds_lut_index_unit(v[dy][dx].b), lk);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx)
+          t[dy][dx][0] = lds_lut_finish(pend[dy][dx].r), t[dy][dx][1] = lds_lut_finish(pend[dy][dx].g), t[dy][dx][2] = lds_lut_finish(pend[dy][dx].b);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kMaxUpOuts; ++k) {
+      if (k >= cm.n_out) break;  // uniform
+      const UpOut &o = cm.out[k];
+      switch (o.fmt) {  // uniform
+        case PH_FMT_V210: up_write_out<PH_FMT_V210>(o, st, t, role); break;
+        case PH_FMT_YUV422P10: up_write_out<PH_FMT_YUV422P10>(o, st, t, role); break;
+        case PH_FMT_YUV422P8: up_write_out<PH_FMT_YUV422P8>(o, st, t, role); break;
+        case PH_FMT_YUV420P: up_write_out<PH_FMT_YUV420P>(o, st, t, role); break;
+        case PH_FMT_NV12: up_write_out<PH_FMT_NV12>(o, st, t, role); break;
+        case PH_FMT_RGBA8: up_write_out<PH_FMT_RGBA8>(o, st, t, role); break;
+        case PH_FMT_BGRA8: up_write_out<PH_FMT_BGRA8>(o, st, t, role); break;
+      }
+    }
+  }
+}
+
 // The tiling: tiles of tcu wave-step columns x trp row pairs, one per workgroup, as even as the frame allows (a workgroup's sixteen waves
 // share its tile's wave steps); then every layer's rectangle bound - the taps of (tcu * 126) columns x (2 * trp) written rows span that
 // many source texels times the magnification, + the patch's third column / row, + one for the rounding of the coordinates.
@@ -1258,6 +1439,46 @@ hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rg
   };
   if (multi) return rgb12 ? go(clip_up_multi_kernel<true, true>) : go(clip_up_multi_kernel<false, true>);
   return rgb12 ? go(clip_up_multi_kernel<true>) : go(clip_up_multi_kernel<false>);
+}
+
+// One clip in a transition: the launch planned as a clip of three "layers" - src, incoming, mask (a dissolve: two) - so that clip_up_plan's
+// tiling, its rectangle bound per slot (from that image's OWN size and placement: a partner placed differently from the layer gets the
+// bound of its own taps) and its scratch size hold as they are.  The composition itself stays one layer.
+uint32_t clip_up_trans_plan(ClipUpTransArgs &t, bool rgb12, uint32_t num_cus) {
+  ClipUpArgs &c = t.multi.clip;
+  if (c.up.n != 1 || c.up.jobs > 1u || (t.kind != (uint32_t)PH_TRANSITION_DISSOLVE && t.kind != (uint32_t)PH_TRANSITION_WIPE)) return 0;
+  const int slots = t.kind == (uint32_t)PH_TRANSITION_WIPE ? 3 : 2;
+  ClipUpArgs p = c;
+  p.up.n = slots;
+  for (int s = 1; s < slots; ++s) p.up.layer[s] = t.partner[s - 1];
+  const uint32_t grid = clip_up_plan(p, rgb12, num_cus, false);
+  if (!grid || p.info_off + 16u * 3u > (uint32_t)kMaxDynamicLds) return 0;  // (the launch reserves three descriptors, a dissolve's third unused)
+  c.up.jobs = 1, c.up.out_qpitch = p.up.out_qpitch, c.up.cover_w = p.up.cover_w, c.up.shared = 0;
+  c.tcu = p.tcu, c.trp = p.trp, c.gx = p.gx, c.gy = p.gy, c.wg_bytes = p.wg_bytes, c.info_off = p.info_off;
+  for (int s = 0; s < slots; ++s) c.rect_off[s] = p.rect_off[s], c.rect_cap[s] = p.rect_cap[s];
+  return grid;
+}
+
+hipError_t launch_clip_up_trans(hipStream_t s, const ClipUpTransArgs &t, bool rgb12, uint32_t grid) {
+  const ClipUpMultiArgs &m = t.multi;
+  const UpArgs &a = m.clip.up;
+  if (!grid || m.n_out < 1 || m.n_out > (uint32_t)kMaxUpOuts || a.jobs != 1u || a.n != 1 || a.cover_w != a.out_w || grid != m.clip.gx * m.clip.gy)
+    return hipErrorInvalidValue;
+  if (t.kind != (uint32_t)PH_TRANSITION_DISSOLVE && t.kind != (uint32_t)PH_TRANSITION_WIPE) return hipErrorInvalidValue;
+  for (uint32_t k = 0; k < m.n_out; ++k)
+    if (!fmt_chan_out((int)m.out[k].fmt) || (m.out[k].fmt == PH_FMT_V210 && a.out_w % 48u)) return hipErrorInvalidValue;
+  char name[48];
+  snprintf(name, sizeof name, "clip_up_trans<%s>x%u", rgb12 ? "rgb" : "rgba", m.n_out);
+  if (trace_launch(name)) return hipSuccess;
+  const uint32_t lds = m.clip.info_off + 16u * 3u;
+  if (lds > (uint32_t)kMaxDynamicLds) return hipErrorInvalidValue;
+  auto go = [&](auto kernel) -> hipError_t {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
+    if (e != hipSuccess) return e;
+    kernel<<<grid, kClipTransBlock, lds, s>>>(t);
+    return hipGetLastError();
+  };
+  return rgb12 ? go(clip_up_trans_kernel<true>) : go(clip_up_trans_kernel<false>);
 }
 
 // Does the 2 x 2 block scheme apply?  Unrotated, unmirrored, MAGNIFIED in both directions (then the first taps of the two

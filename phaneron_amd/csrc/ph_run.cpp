@@ -237,6 +237,7 @@ struct ChanCall {
   // chan_compose_multi_<n>: every output as ph_chan_compose_multi takes it (outs[0]: the one above)
   bool multi;  // the program is chan_compose_multi_<n> - or clip_compose_multi_<n>, which names its arguments the same
   bool clip;   // the program is clip_compose_multi_<n>: ph_clip_compose_multi, a launch of its own in its turn (option "clip_batch": grouped, ph_clip_compose_batch_out)
+  bool clip_trans;  // the program is clip_compose_trans_<n>: ph_clip_compose_transition_multi, always a launch of its own in its turn
   int n_out;
   ph_chan_output outs[ph::kMaxChanOuts];
 };
@@ -322,7 +323,8 @@ static int chan_call_parse(Args &a, ChanCall *call) {
   chan_output_parse(a, 0, width, height, &call->outs[0], &call->r.wr_cm, &call->r.wr_lut, &call->r);
   call->n_out = 1;
   call->clip = a.prog->kernel.compare(0, 19, "clip_compose_multi_") == 0;
-  call->multi = call->clip || a.prog->kernel.compare(0, 19, "chan_compose_multi_") == 0;
+  call->clip_trans = a.prog->kernel.compare(0, 19, "clip_compose_trans_") == 0;
+  call->multi = call->clip || call->clip_trans || a.prog->kernel.compare(0, 19, "chan_compose_multi_") == 0;
   if (call->multi) {  // the outputs named, in turn
     ph_buf *wr_cm, *wr_lut;
     for (int k = 1; k < ph::kMaxChanOuts && !a.rc && a.has("output%d", k); ++k) chan_output_parse(a, k, width, height, &call->outs[call->n_out++], &wr_cm, &wr_lut);
@@ -753,6 +755,9 @@ static int dispatch_compose(Args &a, int queue) {
       if (call.clip)  // clip_compose_multi_<n>: chan_compose_multi_<n>'s arguments, name for name
         return ph_clip_compose_multi(ctx, queue, call.n_layers, call.layers, call.n_out, call.outs, call.width, call.height, call.r.rd_cm->dptr, call.r.rd_lut->dptr,
                                      call.r.rd_gm->dptr);
+      if (call.clip_trans)  // clip_compose_trans_<n>: the same arguments, the transition's included
+        return ph_clip_compose_transition_multi(ctx, queue, call.n_layers, call.layers, call.n_out, call.outs, call.width, call.height, call.r.rd_cm->dptr,
+                                                call.r.rd_lut->dptr, call.r.rd_gm->dptr);
       if (call.multi)  // chan_compose_multi_<n>: chan_compose_v210_<n>'s arguments (output 0) and up to three more outputs (chan_output_parse)
         return ph_chan_compose_multi(ctx, queue, call.n_layers, call.layers, call.n_out, call.outs, call.width, call.height, call.r.rd_cm->dptr, call.r.rd_lut->dptr,
                                      call.r.rd_gm->dptr);
@@ -1013,7 +1018,8 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
       // "chan_batch_outs" lets such jobs share launches too: ph_chan_compose_batch_out)
       // (a clip_compose_multi_<n> job: a launch of its own, in its turn - unless the context option "clip_batch" lets such jobs share
       // launches: ph_clip_compose_batch_out)
-      kind[(size_t)j] = calls[(size_t)j].clip ? (ctx->clip_batch ? 6 : 0) : calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
+      // (a clip_compose_trans_<n> job: a launch of its own, in its turn - never grouped)
+      kind[(size_t)j] = calls[(size_t)j].clip_trans ? 0 : calls[(size_t)j].clip ? (ctx->clip_batch ? 6 : 0) : calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
     } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j]) && !fused_is_trans(progs[j]) && !fused_is_route(progs[j])) {
       if ((rc = fused_call_parse(job, &fused[(size_t)j]))) return rc;
       kind[(size_t)j] = 2;
