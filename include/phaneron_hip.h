@@ -55,7 +55,8 @@ extern "C" {
  *    under the default fill - for up to four consumers of any format the channel kernel writes, read once per source pixel; program
  *    "clip_compose_multi_<n>".  ph_clip_compose_batch_out (ph_chan_job_out): several channels' such frames in one launch; context
  *    option "clip_batch".  ph_clip_compose_transition_multi: file playback through a MIX or WIPE - a layer's src, incoming and mask clips
- *    each read once per source pixel; program "clip_compose_trans_<n>" */
+ *    each read once per source pixel; program "clip_compose_trans_<n>".  ph_clip_compose_route_multi: a routed channel's file playback -
+ *    ph_clip_compose_multi's frames and the combined f32 RGBA image itself from the read-once launches; program "clip_compose_route_<n>" */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -277,6 +278,9 @@ int ph_check_program(ph_ctx *ctx, ph_program *prog, const ph_arg *args, int n_ar
  * context option "clip_batch" = 1: consecutive such jobs of one geometry and Loader recipe in one ph_clip_compose_batch_out call).
  * So does a clip_compose_trans_<n> job (ph_clip_compose_transition_multi: the same arguments, the transition's l<i>Transition, l<i>Mix,
  * l<i>Incoming... and l<i>Mask... included), which no option groups.
+ * So does a clip_compose_route_<n> job (ph_clip_compose_route_multi: clip_compose_multi_<n>'s arguments and the optional buffer imageOut, the
+ * combined f32 RGBA image; `output` may be absent only where imageOut is there), which no option groups either: no shared launch reaches
+ * across it, so the image it writes is there for the next job and everything before it has been read or written.
  * So does a compose_up_multi_<n> job (ph_compose_up_write_multi): compose_up_write_v210_<n>'s layers (l<i>In, l<i>Matrix, packedRgb,
  * l<i>Width / l<i>Height) and chan_compose_multi_<n>'s outputs.  Its twin - the other field of a de-interlaced frame - is announced by
  * l0In2 (l<i>In2: its images), and its planes carry the first job's names behind the word twin: twinOutput (twinOutputU / V / C),
@@ -631,6 +635,35 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
 int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs,
                                      uint32_t out_width, uint32_t out_height, const void *rd_col_matrix12, const void *rd_gamma_lut,
                                      const void *rd_gamut9);
+/* A ROUTED CHANNEL'S FILE PLAYBACK: a ROUTE (routeProducer.ts:63-126, combiner.ts:219-254) hands another channel this channel's combined
+ * image - an f32 RGBA frame of the channel's size, which arrives there as a PH_SRC_RGBA_F32 layer.  ph_clip_compose_multi's arguments and
+ * `image_out` (f32 RGBA, out_width x out_height, rows unpadded, or NULL), `n_out` 0..4.
+ * With image_out == NULL and n_out >= 1 the call IS ph_clip_compose_multi: same routes, trace names and errors.
+ * With image_out the image is built in this order, bit for bit: the format's reader of every wire-format layer (ph_pack_read /
+ * ph_v210_read; a PH_SRC_RGBA_F32 layer is taken as it is), ph_transform of each with its own matrix to the output size, ph_combine in
+ * layer order into image_out (n == 1: the Combiner's passthrough, the one transformed image).  Every output is
+ * ph_pack_write(image_out, ...) with its format, planes, interlace, matrix and table: ph_clip_compose_multi's frames on the same
+ * arguments.  The whole frame is always composed; a field output takes the rows of its parity.  The arithmetic is ph_combine's, as
+ * ph_fused_v210_route_multi states it: the bottom layer as it is (its -0 and its alpha included), above it k = 1 - l.a,
+ * rgb = fma(acc, k, l), a = fma(acc.a, 0, l.a); a layer's filtered alpha is computed as a value,
+ * ((w00 a00 + w10 a10) + w01 a01) + w11 a11, with 1 inside a clip that has no alpha and the border's 0 outside; only a NaN's payload is
+ * unpinned.  image_out is stored under the context's store policy (option "stream_images"), as ph_combine stores its image.
+ * Routes, decided in this order.  (1) The outputs are grouped by registered writer table as ph_clip_compose_multi groups them; the first
+ * group's launch - or a launch with no output - also writes the image, further groups run ph_clip_compose_multi's launches; a v210
+ * output at out_width % 48 != 0 is a ph_chan_compose call of its own; a lone v210 output belongs to the image's launch.  (2) ONE launch,
+ * "clip_up_route<rgb|rgba>x<outputs>" in a trace, where n == 1, the clip is in a wire format (a 4:2:0 one of an even height) and
+ * "chan_enlarged" = 1; <rgba> where the clip is rgba8 / bgra8.  (3) Otherwise two stages: every wire-format clip through its reader into
+ * the queue's scratch images, then one "compose_up_route<rgba>x<outputs>j1" launch.  (4) With n_out == 0 no writer table is loaded or
+ * looked at.  (5) PH_E_INVALID, naming the chain to run instead (ph_pack_read, ph_transform, ph_combine, ph_pack_write_multi), where the
+ * call does not qualify for (2) / (3): a layer neither enlarged by 1 % or more without rotation or mirroring nor of the channel's size
+ * under the default fill, a layer in a transition, "chan_enlarged" = 0, a table without an LDS form, a planar output at
+ * out_width % 8 != 0: nothing else makes the image in one call, and the entry runs no chain of its own.  (6) Also refused: everything
+ * ph_clip_compose_multi refuses (yuv420p10 / p010 outputs with the channel kernel's message), n_out outside 0..4, n_out == 0 with
+ * image_out == NULL, image_out overlapping by byte range any source plane, f32 layer image or output plane.  Everything decidable from
+ * the arguments is decided before the context is looked at; a refused call writes nothing; out_height == 0 is PH_OK. */
+int ph_clip_compose_route_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, void *image_out, int n_out,
+                                const ph_chan_output *outs, uint32_t out_width, uint32_t out_height, const void *rd_col_matrix12,
+                                const void *rd_gamma_lut, const void *rd_gamut9);
 /* Several CHANNELS' frames for any consumers in one launch: ph_chan_compose_batch's sharing (the tables loaded once, the wave steps of
  * all jobs in front of one barrier) with ph_chan_compose_multi's outputs - an encoder's yuv422p8 / yuv420p / nv12 frame, the screen's
  * rgba8 beside SDI's v210.  Exactly, in order, `n_jobs` calls of ph_chan_compose_multi (a job with n_out == 1: ph_chan_compose), bit for

@@ -148,7 +148,12 @@ export class clContext {
 	 * `name` may also be `clip_compose_trans_<n>`: the same arguments with the transition's (`l<i>Transition` 1 dissolve / 2 wipe, `l<i>Mix`,
 	 * `l<i>Incoming...`, `l<i>Mask...`) through ph_clip_compose_transition_multi - file playback through a MIX or WIPE, every clip of the
 	 * transition read once per source pixel; same bytes as `chan_compose_multi_<n>`.  Reached by name only: defer.js does not plan it and
-	 * `clipBatch` does not group it - every job is a launch of its own in its turn. */
+	 * `clipBatch` does not group it - every job is a launch of its own in its turn.
+	 * `name` may also be `clip_compose_route_<n>`: `clip_compose_multi_<n>`'s arguments and the optional image buffer `imageOut` through
+	 * ph_clip_compose_route_multi - a routed channel's file playback: the consumers' frames (same bytes as `clip_compose_multi_<n>`) and the combined f32
+	 * RGBA image another channel takes as a layer, from the same read-once launch; `output` may be absent only where `imageOut` is there (the image
+	 * alone).  A frame the read-once routes do not take is REFUSED (post `read`, `transform`, `combine_<n>` and the writers instead).  Reached by name only:
+	 * defer.js does not plan it and `clipBatch` does not group it - every job is a launch of its own in its turn. */
 	createProgram(kernel: string, options: { name: string; globalWorkItems?: number | Uint32Array | number[]; workItemsPerGroup?: number }): Promise<OpenCLProgram>
 	runProgram(program: OpenCLProgram, params: KernelParams, queue?: number): Promise<RunTimings>
 	/** Recording contexts only: runProgram without the promise (node/jobs.js uses it per job of a batch).  null = not a recording

@@ -45,6 +45,7 @@ EXPORTS = [
     "ph_clip_compose_multi",
     "ph_clip_compose_batch_out",
     "ph_clip_compose_transition_multi",
+    "ph_clip_compose_route_multi",
 ]
 
 
@@ -230,6 +231,7 @@ def lib():
         "ph_chan_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_clip_compose_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_clip_compose_transition_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
+        "ph_clip_compose_route_multi": (ci, [vp, ci, ci, C.POINTER(PhChanLayer), vp, ci, C.POINTER(PhChanOutput), cu, cu, vp, vp, vp]),
         "ph_compose_up_write_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_compose_up_transition_multi": (ci, [vp, ci, ci, ci, C.POINTER(C.POINTER(PhImageTransLayer)), ci, C.POINTER(PhChanOutput), cu, cu]),
         "ph_pack_write_multi": (ci, [vp, ci, vp, ci, C.POINTER(PhChanOutput), cu, cu]),
@@ -897,6 +899,21 @@ class Context:
         if prepare_only:
 
             def job(_keep=(keep, layers, outputs, outs)):
+                check(fn(*args), h)
+            return job
+        check(fn(*args), h)
+
+    def clip_compose_route_multi(self, layers, image_out, outputs, out_w, out_h, rd_cm, rd_lut, rd_gm, queue=QUEUE_PROCESS, prepare_only=False):
+        """A routed channel's file playback (ph_clip_compose_route_multi): clip_compose_multi's arguments and frames for 0..4 consumers, and
+        image_out - an f32 RGBA tensor of the channel's size, or None - receives the combined image from the same read-once launch."""
+        arr, keep = self._chan_layers(layers)
+        outs = self._chan_outputs(outputs)
+        args = (self.h, queue, len(layers), arr, None if image_out is None else _ptr(image_out), len(outputs), outs, out_w, out_h) + tuple(
+            None if t is None else _ptr(t) for t in (rd_cm, rd_lut, rd_gm))
+        fn, h = lib().ph_clip_compose_route_multi, self.h
+        if prepare_only:
+
+            def job(_keep=(keep, layers, image_out, outputs, outs)):
                 check(fn(*args), h)
             return job
         check(fn(*args), h)

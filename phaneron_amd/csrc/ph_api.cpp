@@ -2967,6 +2967,172 @@ int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_cha
   return PH_OK;
 }
 
+/* A ROUTED channel's file playback: ph_clip_compose_multi's frames and the combined image itself, made inside the read-once launches: see
+ * include/phaneron_hip.h.  With image_out == NULL the call IS ph_clip_compose_multi.  With it the whole frame is composed, the first
+ * writer table's launch (or a launch without outputs) stores the image, and what the read-once routes do not take is refused - the
+ * entry runs no fallback chain.  Everything the arguments decide is decided before the context is looked at; a refused call writes nothing. */
+// Everything the call refuses with image_out set, in the entry's order - the arguments first, the context last - and what the launches
+// need of it: the composition's geometry and the tables' LDS forms.  Launches nothing.
+static int clip_route_checked(const char *fn, ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, void *image_out, int n_out, const ph_chan_output *outs,
+                              uint32_t out_w, uint32_t out_h, const void *rd_cm, const void *rd_lut, const void *rd_gm, ph::UpArgs &base, LutRef &rref,
+                              LutRef (&wref)[ph::kMaxUpOuts], bool args_only = false) {
+  if (!layers || (n_out && !outs) || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  if (const int bad = fused_multi_outputs_check(fn, queue, n_out, outs, out_w, out_h)) return bad;
+  {  // the layers, as the channel kernel's entries check them (their texts)
+    ph::ChanArgs probe{};
+    int n_ops = 0;
+    if (const int bad = chan_ops(n, layers, out_w, out_h, probe.op, probe.plane_u, probe.plane_v, probe.cm_op, &probe.planar, &n_ops)) return bad;
+  }
+  const char *const chain = "nothing else makes image_out in one call: run ph_pack_read, ph_transform, ph_combine and ph_pack_write_multi";
+  // what the read-once routes take, as far as the arguments say: every layer a cut, enlarged or of the channel's size under the default fill
+  base = ph::UpArgs{};
+  base.n = n, base.jobs = 1;
+  compose_up_lines(base, out_w, out_h, 0);  // the whole frame: a field output takes the rows of its parity
+  if (out_w % 2u) return fail(PH_E_INVALID, "%s: width %u is odd; %s", fn, out_w, chain);
+  for (int i = 0; i < n; ++i) {
+    if (layers[i].transition != PH_TRANSITION_CUT) return fail(PH_E_INVALID, "%s: layer %d is in a transition; %s", fn, i, chain);
+    if (!out_h) continue;  // (an empty frame has no placement to judge: PH_OK below)
+    bool takes = chan_image_enlarged(layers[i].src, out_w, out_h, 0, /*v210_fill*/ true);
+    if (takes) {
+      ph::UpArgs one = base;
+      one.n = 1, one.layer[0] = up_layer_of(layers[i].src);
+      takes = ph::compose_up_eligible(one);
+    }
+    if (!takes)
+      return fail(PH_E_INVALID,
+                  "%s: layer %d is neither enlarged by 1 %% or more without rotation or mirroring nor of the channel's size under the default fill; %s", fn, i,
+                  chain);
+    base.layer[i] = up_layer_of(layers[i].src);
+  }
+  {  // image_out against everything the call reads or writes, by byte range
+    ph::Footprint fp;
+    for (int i = 0; i < n; ++i) ph::span_read_source(fp, layers[i].src, 0);
+    for (int k = 0; k < n_out; ++k) ph::span_write_output(fp, outs[k], out_w, out_h);
+    const ph::Span image{(const char *)image_out, (size_t)out_w * out_h * 16u, -1, 0u};
+    for (int r = 0; r < fp.n_reads; ++r)
+      if (ph::spans_meet(image, fp.reads[r])) return fail(PH_E_INVALID, "%s: image_out overlaps a layer's source (range %d of the call's reads)", fn, r);
+    for (int w = 0; w < fp.n_writes; ++w)
+      if (ph::spans_meet(image, fp.writes[w])) return fail(PH_E_INVALID, "%s: image_out overlaps an output's plane (range %d of the call's writes)", fn, w);
+  }
+  if (args_only) return PH_OK;
+  if (!ctx) return fail(PH_E_INVALID, "%s: ctx is NULL", fn);
+  if (ctx->chan_enlarged == 0) return fail(PH_E_INVALID, "%s: the read-once routes are switched off (\"chan_enlarged\" = 0); %s", fn, chain);
+  rref = lds_view(ctx, rd_lut);
+  if (!rref.get()) return fail(PH_E_INVALID, "%s: the reader's table has no LDS form; %s", fn, chain);
+  for (int k = 0; k < n_out; ++k) {  // (no output: no writer table is looked at)
+    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
+    if (!wref[k].get()) return fail(PH_E_INVALID, "%s: output %d: the writer's table has no LDS form; %s", fn, k, chain);
+  }
+  return PH_OK;
+}
+static const char *const kClipRouteFn = "ph_clip_compose_route_multi";
+// what both forms of the call refuse before anything else
+static int clip_route_counts(int n_out, const void *image_out) {
+  if (n_out < 0 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 0..%d outputs (%d)", kClipRouteFn, ph::kMaxUpOuts, n_out);
+  if (!n_out && !image_out) return fail(PH_E_INVALID, "%s: nothing to make: no output and image_out is NULL", kClipRouteFn);
+  return PH_OK;
+}
+// (ph_internal.h: a by-name job's check answers as its launch does)
+extern "C++" int clip_compose_route_check(int queue, int n, const ph_chan_layer *layers, void *image_out, int n_out, const ph_chan_output *outs, uint32_t out_w,
+                             uint32_t out_h, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  if (const int bad = clip_route_counts(n_out, image_out)) return bad;
+  if (!image_out) return PH_OK;  // (ph_clip_compose_multi's job: checked as clip_compose_multi_<n> is)
+  ph::UpArgs base;
+  LutRef rref, wref[ph::kMaxUpOuts];
+  // (the arguments' part: a job's tables get their LDS forms when the job is launched, so what the context decides is answered there)
+  return clip_route_checked(kClipRouteFn, nullptr, queue, n, layers, image_out, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, base, rref, wref, /*args_only*/ true);
+}
+
+int ph_clip_compose_route_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, void *image_out, int n_out, const ph_chan_output *outs,
+                                uint32_t out_w, uint32_t out_h, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  const char *const fn = kClipRouteFn;
+  if (const int bad = clip_route_counts(n_out, image_out)) return bad;
+  if (!image_out) return ph_clip_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm);
+  ph::UpArgs base;
+  LutRef rref, wref[ph::kMaxUpOuts];
+  if (const int bad = clip_route_checked(fn, ctx, queue, n, layers, image_out, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, base, rref, wref)) return bad;
+  if (!base.lines) return PH_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  // one launch?  A single clip in a wire format (v210 included), a 4:2:0 one of an even height
+  bool one_launch = ctx->chan_enlarged == 1 && n == 1, alpha = false;
+  if (one_launch) {
+    const ph_chan_source &S = layers[0].src;
+    const int fmt = fmt_of_src(S.format);
+    one_launch = fmt >= 0 && !(fmt_v420(fmt) && (S.height & 1));
+    alpha = fmt_rgb8(fmt);
+  }
+  ph_image_layer il[1][ph::kMaxLayers];
+  const ph_image_layer *sets[1];
+  std::unique_lock<std::mutex> images;
+  bool image_made = false;
+  // a group's launch (m.n_out == 0: the image alone); the first one made stores the image, the others are ph_clip_compose_multi's
+  auto launch = [&](ph::UpMultiArgs &m) -> int {
+    const bool with_image = !image_made;
+    image_made = true;
+    if (one_launch) {
+      ph::ClipUpRouteArgs r{};
+      ph::ClipUpMultiArgs &c = r.multi;
+      c.clip.up = m.up, c.n_out = m.n_out;
+      for (uint32_t i = 0; i < m.n_out; ++i) c.out[i] = m.out[i];
+      c.clip.rd = *rref.get(), c.clip.rd_gm = (const float *)rd_gm;
+      c.clip.src[0] = clip_src_of(layers[0].src, fmt_of_src(layers[0].src.format), rd_cm);
+      r.image = image_out;
+      const uint32_t grid = ph::clip_up_plan(c.clip, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ false);
+      if (grid) {
+        if (images.owns_lock()) images.unlock();
+        return with_scratch(fn, ctx, queue, (size_t)c.clip.wg_bytes * grid + 4096u, [&](hipStream_t s, void *area) {
+          c.clip.scratch = (char *)area;
+          return with_image ? ph::launch_clip_up_route(s, r, !alpha, grid) : ph::launch_clip_up_multi(s, c, !alpha, grid);
+        });
+      }
+    }
+    // the two stages: every clip through its format's reader into the queue's scratch images, then the 2 x 2-block compositor's launch
+    if (!images.owns_lock()) {
+      images = std::unique_lock<std::mutex>(ctx->chan_scratch_mu[queue]);
+      if (const int bad = chan_enlarged_read(ctx, queue, 1, n, &layers, rd_cm, rd_lut, rd_gm, il, sets)) return bad;
+    }
+    for (int i = 0; i < n; ++i) m.up.layer[i].ptr = il[0][i].data;
+    hipError_t e;
+    if (with_image) {
+      ph::UpRouteArgs r{};
+      r.multi = m, r.image = image_out;
+      e = ph::launch_compose_up_route(stream_of(ctx, queue), r, (uint32_t)ctx->props.multiProcessorCount);
+    } else {
+      e = ph::launch_compose_up_multi(stream_of(ctx, queue), m, false, (uint32_t)ctx->props.multiProcessorCount);
+    }
+    return e == hipSuccess ? PH_OK : fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  };
+  // the outputs by writer table, in the order the tables first appear; a v210 output whose lines end in a tail quad through ph_chan_compose, alone
+  for (int k = 0; k < n_out; ++k) {
+    bool seen = false;
+    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    if (seen) continue;
+    ph::UpMultiArgs m{};
+    m.up = base, m.up.wr = *wref[k].get();
+    for (int j = k; j < n_out; ++j) {
+      const ph_chan_output &o = outs[j];
+      if (o.wr_gamma_lut != outs[k].wr_gamma_lut) continue;
+      if (o.format == PH_FMT_V210 && out_w % 48) {
+        if (images.owns_lock()) images.unlock();
+        rc = ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, o.planes, out_w, out_h, o.interlace, rd_cm, rd_lut, rd_gm, o.wr_col_matrix12, o.wr_gamma_lut);
+        if (rc) return rc;
+        continue;
+      }
+      m.out[m.n_out++] = up_out_of(o, /*same_lines*/ false, out_w, out_h);
+    }
+    if (!m.n_out) continue;
+    if ((rc = launch(m))) return rc;
+  }
+  if (!image_made) {  // no output, or every output split off: the image alone, without a table
+    ph::UpMultiArgs m{};
+    m.up = base;
+    if ((rc = launch(m))) return rc;
+  }
+  return PH_OK;
+}
+
 namespace {
 struct ClipBatchStep {  // what the call does in its turn: a shared launch of jobs [first, first + m.clip.up.jobs), or job `first` handed on
   int first = 0;

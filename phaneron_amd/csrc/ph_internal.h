@@ -127,6 +127,10 @@ int closed_error(const char *fn);
 void refresh_buf_lut(ph_ctx *ctx, ph_buf *b);  // a ph_buf used as `gammaLut`: (re)compress from its host mirror if new data went in
 void mirror_mark(ph_buf *b, hipStream_t s);    // an asynchronous copy into or out of b's mirror has just been enqueued on `s`
 int chan_out_refused(const char *fn, int fmt);  // a format the channel kernel does not write: one answer from ph_chan_compose and from a program's outPacking
+// everything ph_clip_compose_route_multi decides from its arguments alone - all it refuses before it looks at the context - with its texts,
+// and nothing launched (a clip_compose_route_<n> job's check)
+int clip_compose_route_check(int queue, int n, const ph_chan_layer *layers, void *image_out, int n_out, const ph_chan_output *outs, uint32_t out_w,
+                             uint32_t out_h, const void *rd_cm, const void *rd_lut, const void *rd_gm);
 bool inject_failure(ph_ctx *ctx);              // the "fail_launches" fault injection: does this launch fail?
 
 inline bool queue_ok(int queue) { return queue >= 0 && queue < 3; }

@@ -484,6 +484,26 @@ struct UpTransArgs {
 };
 static_assert(sizeof(UpTransArgs) < 4096, "kernel arguments are limited to 4 KiB: kMaxUpJobs jobs of kMaxLayers layers with two partners each must fit");
 hipError_t launch_compose_up_trans(hipStream_t s, const UpTransArgs &t, bool rgb12, uint32_t num_cus);
+// A ROUTED channel's file playback (ph_clip_compose_route_multi): the frames as above and the COMBINED IMAGE itself - f32 RGBA, out_w x
+// out_h, rows unpadded - which another channel takes as a layer.  The whole frame is composed (up.first_line 0, line_step 1, lines out_h);
+// the block's four pixels are made as values with their filtered alpha (ph_combine's arithmetic, alpha included) and stored before the
+// writers' table reads.  n_out may be 0: the image alone, no writer table loaded (up.wr is not looked at).  One job.
+struct ClipUpRouteArgs {  // clip_up_route_kernel: ONE clip in its wire format, one launch
+  ClipUpMultiArgs multi;
+  void *image;
+  uint32_t nt;            // launcher: the image's store policy (image_nt)
+};
+static_assert(sizeof(ClipUpRouteArgs) < 4096, "kernel arguments are limited to 4 KiB");
+// grid: clip_up_plan(multi.clip, rgb12, num_cus, false); named clip_up_route<rgb|rgba>x<outputs> in a route trace
+hipError_t launch_clip_up_route(hipStream_t s, const ClipUpRouteArgs &r, bool rgb12, uint32_t grid);
+struct UpRouteArgs {  // compose_up_route_kernel: f32 RGBA images (the readers' scratch images, routed images), any number of layers
+  UpMultiArgs multi;
+  void *image;
+  uint32_t nt;
+};
+static_assert(sizeof(UpRouteArgs) < 4096, "kernel arguments are limited to 4 KiB");
+// named compose_up_route<rgba>x<outputs>j1 in a route trace
+hipError_t launch_compose_up_route(hipStream_t s, const UpRouteArgs &r, uint32_t num_cus);
 
 struct DeintArgs {  // ph_kernels_deint.hip
   const uint4 *prev[kMaxLayers], *cur[kMaxLayers], *next[kMaxLayers];  // v210 frames, width x height

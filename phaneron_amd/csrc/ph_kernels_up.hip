@@ -1346,6 +1346,183 @@ __global__ __launch_bounds__(kClipTransBlock) void clip_up_trans_kernel(ClipUpTr
   }
 }
 
+// ---- a ROUTED channel's file playback: the combined IMAGE beside (or instead of) the consumers' frames ------------------------------------
+// A ROUTE (routeProducer.ts:63-126, combiner.ts:219-254) hands another channel this channel's combined image - f32 RGBA, the channel's
+// size.  The read-once kernels above hold the block's four combined pixels in registers right before the writers' table reads; the two
+// kernels below are their texts again (clip_up_multi_kernel's phase 1 and table swap, compose_up_multi_kernel's front: both pinned,
+// profiles/clip_route_resources.txt) with a phase 2 that makes every layer's four pixels as VALUES (up_values: the filtered alpha computed
+// - 1 inside a clip without alpha, the border's 0 outside - never taken from the geometry), carries four alpha accumulators through
+// ph_combine's arithmetic (combine_kernel: the bottom layer as it is, above it k = 1 - l.a, rgb = fma(acc, k, l), a = fma(acc.a, 0, l.a)),
+// stores the block - two rows of two pixels, 32 bytes each, streamed or cached by `nt` as ph_combine stores its image - and then runs the
+// twelve table reads and every output's writer on the very values it stored.  With no output there is no table: the image alone.
+// one layer over the block's accumulators (FIRST: the bottom layer - or the Combiner's passthrough of a single one)
+template <bool RGB12, bool FIRST>
+__device__ __forceinline__ void up_route_layer(const UpLayer &L, const UpGeo &geo, UpTexel (&v)[2][2]) {
+  UpPatch p;
+  up_fetch<RGB12>(L, geo, p);
+  up_values<RGB12>(p, geo, [&](int dy, int dx, const UpTexel &t) __attribute__((always_inline)) {
+    UpTexel &s = v[dy][dx];
+    if (FIRST) {
+      s = t;
+    } else {  // combine.ts:45-65, as combine_kernel has it
+      const float k = 1.0f - t.a;
+      s.r = fma_rn(s.r, k, t.r), s.g = fma_rn(s.g, k, t.g), s.b = fma_rn(s.b, k, t.b), s.a = fma_rn(s.a, 0.0f, t.a);
+    }
+  });
+}
+// the block into the image, then - where the launch has outputs - compose_up_multi_kernel's tail
+__device__ __forceinline__ void up_route_tail(void *image, uint32_t nt, uint32_t out_w, const UpStep &st, const UpTexel (&v)[2][2], uint32_t n_out,
+                                              const UpOut (&out)[kMaxUpOuts], uint32_t role, const LutK &lk) {
+#pragma unroll
+  for (int dy = 0; dy < 2; ++dy) {
+    if (!(st.live && (dy == 0 || st.li[1] != st.li[0]))) continue;  // (x0 is even and so is out_w: both pixels of a live lane are inside)
+    float4 *const at = static_cast<float4 *>(image) + (size_t)st.line[dy] * out_w + st.x0;
+    store_image(at, make_float4(v[dy][0].r, v[dy][0].g, v[dy][0].b, v[dy][0].a), nt);
+    store_image(at + 1, make_float4(v[dy][1].r, v[dy][1].g, v[dy][1].b, v[dy][1].a), nt);
+  }
+  if (!n_out) return;  // uniform
+  float t[2][2][3];
+  {
+    PxPending pend[2][2];
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx)
+        pend[dy][dx] = write_px_issue(lds_lut_index_unit(v[dy][dx].r), lds_lut_index_unit(v[dy][dx].g), lds_lut_index_unit(v[dy][dx].b), lk);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx)
+        t[dy][dx][0] = lds_lut_finish(pend[dy][dx].r), t[dy][dx][1] = lds_lut_finish(pend[dy][dx].g), t[dy][dx][2] = lds_lut_finish(pend[dy][dx].b);
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < (uint32_t)kMaxUpOuts; ++k) {
+    if (k >= n_out) break;  // uniform
+    const UpOut &o = out[k];
+    switch (o.fmt) {  // uniform
+      case PH_FMT_V210: up_write_out<PH_FMT_V210>(o, st, t, role); break;
+      case PH_FMT_YUV422P10: up_write_out<PH_FMT_YUV422P10>(o, st, t, role); break;
+      case PH_FMT_YUV422P8: up_write_out<PH_FMT_YUV422P8>(o, st, t, role); break;
+      case PH_FMT_YUV420P: up_write_out<PH_FMT_YUV420P>(o, st, t, role); break;
+      case PH_FMT_NV12: up_write_out<PH_FMT_NV12>(o, st, t, role); break;
+      case PH_FMT_RGBA8: up_write_out<PH_FMT_RGBA8>(o, st, t, role); break;
+      case PH_FMT_BGRA8: up_write_out<PH_FMT_BGRA8>(o, st, t, role); break;
+    }
+  }
+}
+
+// ONE clip in its wire format: phase 1 and the swap are clip_up_multi_kernel's (one frame, one layer: the launcher refuses the rest)
+template <bool RGB12>
+__global__ __launch_bounds__(kUpBlock) void clip_up_route_kernel(ClipUpRouteArgs rt) {
+  const ClipUpMultiArgs &cm = rt.multi;
+  const ClipUpArgs &c = cm.clip;
+  const UpArgs &a = c.up;
+  constexpr uint32_t kTexel = RGB12 ? 12u : 16u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  // the tile
+  const uint32_t upr = (a.cover_w + kUpCols - 1u) / kUpCols, rps = (a.lines + 1u) / 2u;
+  const uint32_t ty = blockIdx.x / c.gx, tx = blockIdx.x - ty * c.gx;
+  const uint32_t cu0 = tx * c.tcu, rp0 = ty * c.trp;
+  const uint32_t ncu = cu0 + c.tcu <= upr ? c.tcu : upr - cu0, nrp = rp0 + c.trp <= rps ? c.trp : rps - rp0;
+  char *const mine = c.scratch + (size_t)blockIdx.x * c.wg_bytes;
+  // ---- phase 1: the reader's table; the clip's rectangle converted
+  const LutK rlk = make_lut_k(c.rd);
+  uint4 *const info = reinterpret_cast<uint4 *>(g_lds + c.info_off);
+  {
+    const UpLayer L = a.layer[0];
+    const ClipSrc S = c.src[0];
+    const uint32_t x_first = cu0 * kUpCols, x_end = (cu0 + ncu) * kUpCols < a.out_w ? (cu0 + ncu) * kUpCols : a.out_w;
+    const uint32_t li_last = 2u * (rp0 + nrp) < a.lines ? 2u * (rp0 + nrp) - 1u : a.lines - 1u;
+    ClipRect R{0, 0, 0, 0};
+    if (x_first < x_end) {
+      int c_lo = clip_tap_col(L, x_first, a.out_w), c_hi = clip_tap_col(L, x_end - 1u, a.out_w) + 2;
+      int r_lo = clip_tap_row(L, a.first_line + 2u * rp0 * a.line_step, a.out_h), r_hi = clip_tap_row(L, a.first_line + li_last * a.line_step, a.out_h) + 2;
+      c_lo = c_lo < 0 ? 0 : c_lo, r_lo = r_lo < 0 ? 0 : r_lo;
+      c_hi = c_hi >= (int)L.w ? (int)L.w - 1 : c_hi, r_hi = r_hi >= (int)L.h ? (int)L.h - 1 : r_hi;
+      if (c_hi >= c_lo && r_hi >= r_lo) R = ClipRect{(uint32_t)c_lo, (uint32_t)r_lo, (uint32_t)(c_hi - c_lo + 1), (uint32_t)(r_hi - r_lo + 1)};
+    }
+    R.c0 = __builtin_amdgcn_readfirstlane(R.c0), R.r0 = __builtin_amdgcn_readfirstlane(R.r0);
+    R.w = __builtin_amdgcn_readfirstlane(R.w), R.h = __builtin_amdgcn_readfirstlane(R.h);
+    const uint32_t ppitch = R.w * kTexel;
+    if (ppitch && R.h * ppitch > c.rect_cap[0]) R.h = c.rect_cap[0] / ppitch;  // (the launcher's bound holds: never taken)
+    char *const dst = mine + c.rect_off[0];
+#define PH_CLIP_CASE(F)                                                                 \
+  case F: clip_convert<F, RGB12, true>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd); break;
+    switch (S.fmt) {  // uniform
+      PH_CLIP_CASE(PH_FMT_V210)
+      PH_CLIP_CASE(PH_FMT_YUV422P10)
+      PH_CLIP_CASE(PH_FMT_YUV422P8)
+      PH_CLIP_CASE(PH_FMT_YUV420P)
+      PH_CLIP_CASE(PH_FMT_NV12)
+      PH_CLIP_CASE(PH_FMT_YUV420P10)
+      PH_CLIP_CASE(PH_FMT_P010)
+      PH_CLIP_CASE(PH_FMT_RGBA8)
+      default: clip_convert<PH_FMT_BGRA8, RGB12, true>(S, L, R, dst, ppitch, c.rd_gm, rlk, c.rd); break;
+    }
+#undef PH_CLIP_CASE
+    if (threadIdx.x == 0) {  // the layer as phase 2 sees it (clip_up_write_v210_kernel)
+      const uint64_t base = (uint64_t)(uintptr_t)dst - ((uint64_t)R.r0 * ppitch + (uint64_t)R.c0 * kTexel);
+      info[0] = make_uint4((uint32_t)base, (uint32_t)(base >> 32), ppitch ? ppitch : kTexel, 0u);
+    }
+  }
+  // ---- the swap: every wave's rectangle rows are in L2; the writer's table comes in where there is an output
+  __threadfence_block();
+  __syncthreads();
+  const LutK lk = make_lut_k(a.wr);
+  if (cm.n_out) {  // uniform
+    lds_lut_load<kUpBlock>(a.wr);
+    __syncthreads();
+  }
+  // ---- phase 2: the transformed clip as values - the image -, every output's writer behind it
+  const uint32_t role = lane - 3u * (lane / 3u);
+  UpLayer L = a.layer[0];
+  {
+    const uint4 d = info[0];  // uniform address: one broadcast read
+    const uint64_t base = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)d.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)d.y) << 32;
+    L.ptr = reinterpret_cast<const void *>((uintptr_t)base);
+    L.pitch = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.z);
+    L.pad = kUpOutside - 16u;
+  }
+  const uint32_t units = ncu * nrp;
+  for (uint32_t u = wave; u < units; u += kUpBlock / 64) {
+    const uint32_t rp_in = ncu == 1u ? u : u / ncu, cu_in = u - rp_in * ncu;
+    UpStep st;
+    clip_step(a, 0u, cu0 + cu_in, rp0 + rp_in, lane, st);
+    UpTexel v[2][2];
+    up_route_layer<RGB12, true>(L, up_geo<RGB12>(L, st), v);
+    up_route_tail(rt.image, rt.nt, a.out_w, st, v, cm.n_out, cm.out, role, lk);
+  }
+}
+
+// f32 RGBA images, any number of layers: compose_up_multi_kernel's front (COLS: 126 with a v210 output, else 128)
+template <uint32_t COLS>
+__global__ __launch_bounds__(kUpBlock) void compose_up_route_kernel(UpRouteArgs rt) {
+  const UpMultiArgs &m = rt.multi;
+  const UpArgs &a = m.up;
+  const LutK lk = make_lut_k(a.wr);
+  if (m.n_out) {  // uniform
+    lds_lut_load<kUpBlock>(a.wr);
+    __syncthreads();
+  }
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const UpShare sh = up_share<COLS>(a);
+  const uint32_t role = lane - 3u * (lane / 3u);
+  UpStep st;
+  for (uint32_t base = 0; up_step<COLS>(a, sh, base, wave, lane, st);) {
+    UpTexel v[2][2];
+    UpGeo geo = up_geo<false>(a.layer[0], st);
+    up_route_layer<false, true>(a.layer[0], geo, v);
+#pragma unroll 1
+    for (int l = 1; l < a.n; ++l) {
+      const UpLayer L = a.layer[l];
+      if (!a.shared) geo = up_geo<false>(L, st);  // uniform
+      up_route_layer<false, false>(L, geo, v);
+    }
+    up_route_tail(rt.image, rt.nt, a.out_w, st, v, m.n_out, m.out, role, lk);
+  }
+}
+
 // The tiling: tiles of tcu wave-step columns x trp row pairs, one per workgroup, as even as the frame allows (a workgroup's sixteen waves
 // share its tile's wave steps); then every layer's rectangle bound - the taps of (tcu * 126) columns x (2 * trp) written rows span that
 // many source texels times the magnification, + the patch's third column / row, + one for the rounding of the coordinates.
@@ -1593,6 +1770,60 @@ hipError_t launch_compose_up_trans(hipStream_t s, const UpTransArgs &t, bool rgb
   };
   if (!v210) return rgb12 ? go(compose_up_trans_kernel<true, 128u>) : go(compose_up_trans_kernel<false, 128u>);
   return rgb12 ? go(compose_up_trans_kernel<true, kUpCols>) : go(compose_up_trans_kernel<false, kUpCols>);
+}
+
+// what both route launches refuse: no image, more than one job, lines other than the whole frame, an output the writers do not make
+static bool up_route_refused(const UpArgs &a, const void *image, uint32_t n_out, const UpOut *out) {
+  if (!image || n_out > (uint32_t)kMaxUpOuts || a.jobs > 1u || a.n < 1 || a.n > kMaxLayers) return true;
+  if (a.out_w % 2u || a.first_line != 0u || a.line_step != 1u || a.lines != a.out_h) return true;  // (the image is the whole frame)
+  for (uint32_t k = 0; k < n_out; ++k)
+    if (!fmt_chan_out((int)out[k].fmt) || (out[k].fmt == PH_FMT_V210 && a.out_w % 48u)) return true;
+  return false;
+}
+
+// One clip, the image and its frames: named clip_up_route<rgb|rgba>x<outputs> in a route trace.  grid: clip_up_plan's, asked with
+// v210_tails == false
+hipError_t launch_clip_up_route(hipStream_t s, const ClipUpRouteArgs &r, bool rgb12, uint32_t grid) {
+  const ClipUpMultiArgs &m = r.multi;
+  const UpArgs &a = m.clip.up;
+  if (!grid || up_route_refused(a, r.image, m.n_out, m.out) || a.n != 1 || a.cover_w != a.out_w || grid != m.clip.gx * m.clip.gy) return hipErrorInvalidValue;
+  char name[48];
+  snprintf(name, sizeof name, "clip_up_route<%s>x%u", rgb12 ? "rgb" : "rgba", m.n_out);
+  if (trace_launch(name)) return hipSuccess;
+  const uint32_t lds = m.clip.info_off + 16u;
+  if (lds > (uint32_t)kMaxDynamicLds) return hipErrorInvalidValue;
+  ClipUpRouteArgs b = r;
+  b.nt = image_nt((size_t)a.out_w * a.out_h * 16u);
+  auto go = [&](auto kernel) -> hipError_t {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
+    if (e != hipSuccess) return e;
+    kernel<<<grid, kUpBlock, lds, s>>>(b);
+    return hipGetLastError();
+  };
+  return rgb12 ? go(clip_up_route_kernel<true>) : go(clip_up_route_kernel<false>);
+}
+
+// f32 RGBA images, the image and its frames: named compose_up_route<rgba>x<outputs>j1 in a route trace
+hipError_t launch_compose_up_route(hipStream_t s, const UpRouteArgs &r, uint32_t num_cus) {
+  const UpMultiArgs &m = r.multi;
+  if (!m.up.lines) return hipSuccess;
+  if (up_route_refused(m.up, r.image, m.n_out, m.out)) return hipErrorInvalidValue;
+  char name[48];
+  snprintf(name, sizeof name, "compose_up_route<rgba>x%uj1", m.n_out);
+  if (trace_launch(name)) return hipSuccess;
+  bool v210 = false;
+  for (uint32_t k = 0; k < m.n_out; ++k) v210 = v210 || m.out[k].fmt == PH_FMT_V210;
+  UpRouteArgs b = r;
+  b.multi.up.jobs = 1;
+  const uint32_t grid = up_plan(b.multi.up, false, num_cus, v210 ? kUpCols : 128u);
+  b.nt = image_nt((size_t)m.up.out_w * m.up.out_h * 16u);
+  auto go = [&](auto kernel) -> hipError_t {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
+    if (e != hipSuccess) return e;
+    kernel<<<grid, kUpBlock, m.n_out ? b.multi.up.wr.bytes : 0u, s>>>(b);
+    return hipGetLastError();
+  };
+  return v210 ? go(compose_up_route_kernel<kUpCols>) : go(compose_up_route_kernel<128u>);
 }
 
 }  // namespace ph

@@ -200,6 +200,7 @@ int resolve_program(const char *src, const char *name, ProgramChoice &c, std::st
   if (0 == strncmp(name, "chan_compose_multi_", 19)) return layers("chan_compose_multi_", 1, K_CHAN_COMPOSE);  // (the same program with more outputs: told apart by name, ph_run.cpp)
   if (0 == strncmp(name, "clip_compose_multi_", 19)) return layers("clip_compose_multi_", 1, K_CHAN_COMPOSE);  // (chan_compose_multi_<n>'s arguments through ph_clip_compose_multi: told apart by name, ph_run.cpp)
   if (0 == strncmp(name, "clip_compose_trans_", 19)) return layers("clip_compose_trans_", 1, K_CHAN_COMPOSE);  // (the same arguments through ph_clip_compose_transition_multi - file playback through a MIX or WIPE: told apart by name, ph_run.cpp)
+  if (0 == strncmp(name, "clip_compose_route_", 19)) return layers("clip_compose_route_", 1, K_CHAN_COMPOSE);  // (the same arguments and imageOut through ph_clip_compose_route_multi - a routed channel's file playback: told apart by name, ph_run.cpp)
   if (0 == strncmp(name, "compose_up_write_v210_", 22)) return layers("compose_up_write_v210_", 1, K_COMPOSE_UP);
   if (0 == strncmp(name, "compose_up_multi_", 17)) return layers("compose_up_multi_", 1, K_COMPOSE_UP);  // (the same program with any writer and more outputs: told apart by name, ph_run.cpp)
   if (0 == strncmp(name, "compose_up_trans_", 17)) return layers("compose_up_trans_", 1, K_COMPOSE_UP);  // (compose_up_multi_<n> with layers in a transition, ph_compose_up_transition_multi: told apart by name, ph_run.cpp)

@@ -238,6 +238,10 @@ struct ChanCall {
   bool multi;  // the program is chan_compose_multi_<n> - or clip_compose_multi_<n>, which names its arguments the same
   bool clip;   // the program is clip_compose_multi_<n>: ph_clip_compose_multi, a launch of its own in its turn (option "clip_batch": grouped, ph_clip_compose_batch_out)
   bool clip_trans;  // the program is clip_compose_trans_<n>: ph_clip_compose_transition_multi, always a launch of its own in its turn
+  // the program is clip_compose_route_<n>: ph_clip_compose_route_multi, always a launch of its own in its turn.  image_out: the optional
+  // buffer imageOut, the combined f32 RGBA image; `output` may be absent only where imageOut is there (n_out == 0: the image alone)
+  bool clip_route;
+  void *image_out;
   int n_out;
   ph_chan_output outs[ph::kMaxChanOuts];
 };
@@ -320,12 +324,22 @@ static int chan_call_parse(Args &a, ChanCall *call) {
     if (l.transition == PH_TRANSITION_WIPE) chan_source_parse(a, i, "Mask", width, height, &l.mask);
   }
   call->r = Recipe();
-  chan_output_parse(a, 0, width, height, &call->outs[0], &call->r.wr_cm, &call->r.wr_lut, &call->r);
-  call->n_out = 1;
   call->clip = a.prog->kernel.compare(0, 19, "clip_compose_multi_") == 0;
   call->clip_trans = a.prog->kernel.compare(0, 19, "clip_compose_trans_") == 0;
-  call->multi = call->clip || call->clip_trans || a.prog->kernel.compare(0, 19, "chan_compose_multi_") == 0;
-  if (call->multi) {  // the outputs named, in turn
+  call->clip_route = a.prog->kernel.compare(0, 19, "clip_compose_route_") == 0;
+  call->multi = call->clip || call->clip_trans || call->clip_route || a.prog->kernel.compare(0, 19, "chan_compose_multi_") == 0;
+  call->image_out = nullptr;
+  if (call->clip_route)
+    if (const ph_buf *image = a.buf_or_null(image_bytes(width, height), "imageOut")) call->image_out = image->dptr;
+  if (call->image_out && !a.has("output")) {  // the image alone: no packed frame at all
+    call->outs[0] = ph_chan_output{};
+    call->n_out = 0;
+    a.loader(&call->r);
+  } else {
+    chan_output_parse(a, 0, width, height, &call->outs[0], &call->r.wr_cm, &call->r.wr_lut, &call->r);
+    call->n_out = 1;
+  }
+  if (call->multi && call->n_out) {  // the outputs named, in turn
     ph_buf *wr_cm, *wr_lut;
     for (int k = 1; k < ph::kMaxChanOuts && !a.rc && a.has("output%d", k); ++k) chan_output_parse(a, k, width, height, &call->outs[call->n_out++], &wr_cm, &wr_lut);
   }
@@ -751,6 +765,9 @@ static int dispatch_compose(Args &a, int queue) {
     case K_CHAN_COMPOSE: {
       ChanCall call;
       chan_call_parse(a, &call);
+      if (call.clip_route && !a.rc && a.check_only)  // (a check answers as the launch does: the typed call's own refusals)
+        return clip_compose_route_check(queue, call.n_layers, call.layers, call.image_out, call.n_out, call.outs, call.width, call.height, call.r.rd_cm->dptr,
+                                        call.r.rd_lut->dptr, call.r.rd_gm->dptr);
       if (a.done()) return a.rc;
       if (call.clip)  // clip_compose_multi_<n>: chan_compose_multi_<n>'s arguments, name for name
         return ph_clip_compose_multi(ctx, queue, call.n_layers, call.layers, call.n_out, call.outs, call.width, call.height, call.r.rd_cm->dptr, call.r.rd_lut->dptr,
@@ -758,6 +775,9 @@ static int dispatch_compose(Args &a, int queue) {
       if (call.clip_trans)  // clip_compose_trans_<n>: the same arguments, the transition's included
         return ph_clip_compose_transition_multi(ctx, queue, call.n_layers, call.layers, call.n_out, call.outs, call.width, call.height, call.r.rd_cm->dptr,
                                                 call.r.rd_lut->dptr, call.r.rd_gm->dptr);
+      if (call.clip_route)  // clip_compose_route_<n>: the same arguments and the optional imageOut
+        return ph_clip_compose_route_multi(ctx, queue, call.n_layers, call.layers, call.image_out, call.n_out, call.outs, call.width, call.height,
+                                           call.r.rd_cm->dptr, call.r.rd_lut->dptr, call.r.rd_gm->dptr);
       if (call.multi)  // chan_compose_multi_<n>: chan_compose_v210_<n>'s arguments (output 0) and up to three more outputs (chan_output_parse)
         return ph_chan_compose_multi(ctx, queue, call.n_layers, call.layers, call.n_out, call.outs, call.width, call.height, call.r.rd_cm->dptr, call.r.rd_lut->dptr,
                                      call.r.rd_gm->dptr);
@@ -1014,12 +1034,17 @@ int ph_run_programs(ph_ctx *ctx, int n_jobs, ph_program *const *progs, const ph_
     Args job{ctx, progs[j], args[j], n_args[j], false};
     if (progs[j]->id == K_CHAN_COMPOSE) {
       if ((rc = chan_call_parse(job, &calls[(size_t)j]))) return rc;
+      if (const ChanCall &c = calls[(size_t)j]; c.clip_route && (rc = clip_compose_route_check(queue, c.n_layers, c.layers, c.image_out, c.n_out, c.outs, c.width, c.height,
+                                                                                            c.r.rd_cm->dptr, c.r.rd_lut->dptr, c.r.rd_gm->dptr)))
+        return rc;
       // (a frame for another consumer, or a chan_compose_multi_<n> job: a launch of its own, in its turn - unless the context option
       // "chan_batch_outs" lets such jobs share launches too: ph_chan_compose_batch_out)
       // (a clip_compose_multi_<n> job: a launch of its own, in its turn - unless the context option "clip_batch" lets such jobs share
       // launches: ph_clip_compose_batch_out)
-      // (a clip_compose_trans_<n> job: a launch of its own, in its turn - never grouped)
-      kind[(size_t)j] = calls[(size_t)j].clip_trans ? 0 : calls[(size_t)j].clip ? (ctx->clip_batch ? 6 : 0) : calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
+      // (a clip_compose_trans_<n> job: a launch of its own, in its turn - never grouped.  So is a clip_compose_route_<n> job: no group
+      // reaches across it, so the image it writes - which the entry itself holds against the job's own sources and planes by byte range,
+      // ph_spans.h - is written before any later job of the call reads it, and after every earlier job has read or written its bytes)
+      kind[(size_t)j] = calls[(size_t)j].clip_trans || calls[(size_t)j].clip_route ? 0 : calls[(size_t)j].clip ? (ctx->clip_batch ? 6 : 0) : calls[(size_t)j].out_format == PH_FMT_V210 && !calls[(size_t)j].multi ? 1 : ctx->chan_batch_outs ? 4 : 0;
     } else if (progs[j]->id == K_FUSED_V210 && !fused_is_multi(progs[j]) && !fused_is_trans(progs[j]) && !fused_is_route(progs[j])) {
       if ((rc = fused_call_parse(job, &fused[(size_t)j]))) return rc;
       kind[(size_t)j] = 2;
