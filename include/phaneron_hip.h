@@ -610,7 +610,10 @@ int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
  * reader into an L2-resident rectangle per workgroup tile, the writer's table swapped in, the 2 x 2-block compositor, every output's
  * writer) where the frame is a single clip in a wire format - any PH_SRC_* but PH_SRC_RGBA_F32; a 4:2:0 one of an even height - and
  * "chan_enlarged" = 1; else two stages: each clip through its format's reader into the queue's scratch images (finished f32 images are
- * taken as they are), then "compose_up_multi<rgba>x<outputs>j1".  out_height == 0 is PH_OK. */
+ * taken as they are), then "compose_up_multi<rgba>x<outputs>j1".  out_height == 0 is PH_OK.
+ * With the context option "up_v210_tails" = 1 route (4)'s split is not made for a group of two or more outputs: the v210 output stays in
+ * the group, whose launch is "clip_up_multi_t<rgb|rgba>x<outputs>" (two stages: "compose_up_multi_t<rgba>x<outputs>j1"); a group whose
+ * only member is that v210 output, and n_out == 1, keep the routes above. */
 int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs,
                           uint32_t out_width, uint32_t out_height, const void *rd_col_matrix12, const void *rd_gamma_lut,
                           const void *rd_gamut9);
@@ -694,7 +697,9 @@ int ph_chan_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
  * job.  A launch holds up to 4 jobs of up to 4 outputs; longer runs are split.  The entry point itself sees to it that no job of a
  * launch reads or writes what another job of it writes, or writes what one reads (by byte range): such a job starts the next launch.
  * Every other job - several layers, f32 images, the two-stage shapes, several writer tables, a lone v210 output, a v210 tail width - and
- * a group of one job run in their turn through ph_clip_compose_multi, under that call's trace names. */
+ * a group of one job run in their turn through ph_clip_compose_multi, under that call's trace names.
+ * With the context option "up_v210_tails" = 1 the condition "no v210 output at out_width % 48 != 0" is dropped - such jobs share
+ * "clip_up_multi_t<rgb|rgba>x<outputs>j<jobs>" - while "not a lone v210 output" stays. */
 int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_job_out *jobs, uint32_t out_width, uint32_t out_height,
                               const void *rd_col_matrix12, const void *rd_gamma_lut, const void *rd_gamut9);
 /* Several consumers' frames of one ENLARGED composition in one launch: the 2 x 2-block compositor (ph_compose_up_write_v210) with any
@@ -716,7 +721,9 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
  * PH_E_INVALID: a placement that does not qualify; a format the channel kernel does not write (yuv420p10, p010); an odd width, a
  * planar output whose width is not a multiple of 8, a 4:2:0 output with an odd height; n_out outside 1..4, jobs outside 1..4; two
  * outputs, of any job, naming the same first plane; a writer table that is not registered; layers of different image formats.
- * A refused call writes nothing. */
+ * A refused call writes nothing.
+ * With the context option "up_v210_tails" = 1 a v210 output at width % 48 != 0 that shares its table with at least one other output
+ * stays in that table's launch ("compose_up_multi_t<rgb|rgba>x<outputs>j<jobs>" in a trace); alone with its table it is today's kernel's. */
 int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, int n_out,
                               const ph_chan_output *outs, uint32_t out_width, uint32_t out_height);
 /* The same with layers in a TRANSITION (transitioner.ts:165-176): a layer may bring the transition's second source and, for a wipe, its
@@ -920,7 +927,15 @@ int ph_lut_layout_of(const float *host_lut65536, ph_lut_layout *layout, void *ld
  *          either way.  Any other value is PH_E_INVALID;
  *          "clip_batch" (default 0): 1 lets ph_run_programs put consecutive clip_compose_multi_<n> jobs of one geometry and Loader recipe
  *          into one ph_clip_compose_batch_out call, which shares launches among those of one clip shape and output list; 0: each such
- *          job a launch of its own, in its turn.  The same bits either way.  Any other value is PH_E_INVALID. */
+ *          job a launch of its own, in its turn.  The same bits either way.  Any other value is PH_E_INVALID;
+ *          "up_v210_tails" (default 0): 1 keeps a v210 output whose lines end in a tail quad (out_width % 48 != 0 - 1280 x 720, SDI's
+ *          720p frame) inside its writer table's launch of the 2 x 2-block compositor's several-outputs kernels - ph_compose_up_write_multi,
+ *          ph_clip_compose_multi, ph_clip_compose_batch_out, each of which says how, and by name compose_up_multi_<n>, clip_compose_multi_<n>
+ *          and ph_run_programs with "clip_batch" - where the tail quad's lanes look the writer's table up a second time with truncated
+ *          indices; 0: that output is made on its own, the composition a second time.  The same bits either way.  It leaves alone: the
+ *          transition and route entries (ph_compose_up_transition_multi still refuses such an output beside a transition and, with every
+ *          layer a cut, splits it off as with 0; ph_clip_compose_transition_multi and ph_clip_compose_route_multi split it off as
+ *          ever), the ph_fused_v210_* family and the channel kernel.  Any other value is PH_E_INVALID. */
 int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value);
 /* TESTS: the store policy a launch issued next on the calling thread for `ctx` would be given for an f32 RGBA image of `bytes` bytes -
  * 0 through the caches, 1 streamed - from "stream_images" and "stream_threshold_mb" (2: 1 for bytes > threshold << 20, strictly).

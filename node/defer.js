@@ -141,6 +141,12 @@ class Deferral {
 		// shape and output list share a launch).  `clipBatch: true` on the context; off unless asked for - with it off every such job is
 		// launched as posted, in its turn.
 		this.clipBatch = ctx.clipBatch === true
+		// A 720p channel (1280 wide: every v210 line ends in a tail quad) with SDI beside other consumers: the library's context option
+		// "up_v210_tails" keeps the v210 frame inside the several-outputs launches of the 2 x 2-block compositor (compose_up_multi_<n>,
+		// clip_compose_multi_<n>) instead of a launch of its own.  `upTails: true` on the context; off unless asked for.  Nothing is planned
+		// differently - v210 siblings of any width are handed to compose_up_multi_<n> as ever: the option is set once, in front of the first launch.
+		this.upTails = ctx.upTails === true
+		this.upTailsSet = false
 		this.batchOutsSet = false
 		this.fusedBatchSet = false
 		this.clipBatchSet = false
@@ -411,6 +417,7 @@ class Deferral {
 			progs.push(n.program._handle), names.push(nm), values.push(vs)
 		}
 		if (!this.clipBatchSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'clip_batch', 1); this.clipBatchSet = true }
+		this._upTails()
 		let made = jobs.length
 		let failure = null
 		try {
@@ -546,6 +553,7 @@ class Deferral {
 		const queue = plans[0].node.queue
 		if (plans[0].fusedOuts && !this.fusedBatchSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'fused_multi_batch', 1); this.fusedBatchSet = true }
 		if (plans[0].outs && !this.batchOutsSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'chan_batch_outs', 1); this.batchOutsSet = true }
+		this._upTails()
 		try {
 			this.ctx._native.runPrograms(this.ctx._ctx, progs, names, values, queue)
 		} catch (e) {
@@ -586,7 +594,14 @@ class Deferral {
 		}
 		this.stats.launched++
 		this.launchedOn.set(queue, (this.launchedOn.get(queue) || 0) + 1)
+		this._upTails()
 		return this.ctx._native.runProgram(this.ctx._ctx, program._handle, names, values, queue, false)
+	}
+	// upTails: the library's option, once, in front of the context's first launch
+	_upTails() {
+		if (!this.upTails || this.upTailsSet || !this.ctx._native.setOption) return
+		this.ctx._native.setOption(this.ctx._ctx, 'up_v210_tails', 1)
+		this.upTailsSet = true
 	}
 	// a fused launch that may be refused (a shape the kernel does not take): false = nothing was launched
 	_try(program, params, queue) {

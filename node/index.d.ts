@@ -117,6 +117,10 @@ export class clContext {
 	 * of consumers share ONE launch (ph_clip_compose_batch_out, `clip_up_multi<rgb|rgba>x<outputs>j<jobs>` in a trace; counted under
 	 * `deferredStats().batched`); `false`: a launch per job, in its turn.  The same bytes either way.  No route is planned for it: the programs
 	 * are those the caller names.
+	 * `upTails` (default false; PHANERON_UP_TAILS=1): on a channel whose v210 lines end in a tail quad (width % 48 != 0 - 1280 x 720) SDI's v210
+	 * frame stays inside the launch that makes the other consumers' frames (`compose_up_multi_<n>`, `clip_compose_multi_<n>`:
+	 * `compose_up_multi_t<..>` / `clip_up_multi_t<..>` in a trace) instead of a launch of its own - the library's context option
+	 * `up_v210_tails`, set once in front of the context's first launch.  The same bytes either way; nothing is planned differently.
 	 * `imageWriters` (default false; PHANERON_IMAGE_WRITERS=1): wire-format `write` jobs that are launched as posted (no fused plan, or every fused
 	 * candidate refused) take the pending writes of the other consumers of the same image - any of the nine formats, yuv420p10 / p010 included -
 	 * with them as ONE `pack_write_multi_<n>` launch (ph_pack_write_multi: the image read and looked up once); `false`: a launch per write.
@@ -136,7 +140,7 @@ export class clContext {
 	 * `strictHandles` (default false; PHANERON_STRICT_HANDLES=1): a fresh object per takeover, so that a reference kept past release()
 	 * is refused ('... released buffer') instead of aliasing the next owner's buffer - for running an application under test. */
 	constructor(params?: { platformIndex?: number; deviceIndex?: number; overlapping?: boolean; profile?: boolean; spinWaitMicros?: number; deferred?: boolean;
-		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; upTransitions?: boolean; fusedTransitions?: boolean; batchOuts?: boolean; clipBatch?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
+		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; upTransitions?: boolean; fusedTransitions?: boolean; batchOuts?: boolean; clipBatch?: boolean; upTails?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
 	readonly queue: { load: number; process: number; unload: number }
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo

@@ -174,6 +174,10 @@ class clContext {
 		// several channels' file playback of a tick - clip_compose_multi_<n> jobs posted by name - in one runPrograms call with the library's
 		// "clip_batch" set (node/defer.js clipBatch): off unless asked for (clipBatch: true, or PHANERON_CLIP_BATCH=1)
 		this.clipBatch = params.clipBatch === undefined ? process.env.PHANERON_CLIP_BATCH === '1' : !!params.clipBatch
+		// a 720p channel's SDI frame (1280 wide: v210 lines that end in a tail quad) inside the several-outputs launches of the 2 x 2-block
+		// compositor - the library's "up_v210_tails", set once in front of the first launch (node/defer.js upTails): off unless asked for
+		// (upTails: true, or PHANERON_UP_TAILS=1)
+		this.upTails = params.upTails === undefined ? process.env.PHANERON_UP_TAILS === '1' : !!params.upTails
 		// wire-format writes of one image that are launched as posted - a routed channel's image, a frame whose fused launch was refused, the 10-bit
 		// 4:2:0 consumers - as ONE pack_write_multi_<n> launch (node/defer.js imageWriters): off unless asked for (DESIGN.md 5.1: v210 + rgba8 alone measured slower)
 		this.imageWriters = params.imageWriters === undefined ? process.env.PHANERON_IMAGE_WRITERS === '1' : !!params.imageWriters

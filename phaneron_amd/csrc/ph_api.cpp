@@ -975,6 +975,10 @@ int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value) {
     if (value != 0 && value != 1) return fail(PH_E_INVALID, "clip_batch: 0 (a launch per such job) or 1 (shared launches)");
     return ctx->clip_batch = value, PH_OK;
   }
+  if (0 == strcmp(name, "up_v210_tails")) {
+    if (value != 0 && value != 1) return fail(PH_E_INVALID, "up_v210_tails: 0 (a v210 output at width %% 48 != 0 is made on its own) or 1 (it stays in its table's launch)");
+    return ctx->up_v210_tails = value, PH_OK;
+  }
   if (0 == strcmp(name, "fused_multi_wgs")) {
     if (value < 0) return fail(PH_E_INVALID, "fused_multi_wgs: a number of workgroups, or 0 for no cap");
     return ctx->fused_multi_wgs = value, PH_OK;
@@ -2603,9 +2607,10 @@ struct UpLaunch {
 };
 // the launches of such a call: per writer table, in the order the tables first appear, a v210 output that cannot share (its lines end in a tail quad,
 // or nobody else names its table) through the one-output kernel, then the rest as one several-outputs launch.  split_v210 == false (layers in a
-// transition, which the one-output kernel does not have): every output of a table stays in the table's launch
+// transition, which the one-output kernel does not have): every output of a table stays in the table's launch.  keep_tails (context option
+// "up_v210_tails"): a v210 output whose lines end in a tail quad stays with the others of its table - alone with its table it is split off as ever
 static void compose_up_launches(const ph::UpArgs &base, int jobs, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h,
-                                bool split_v210, std::vector<UpLaunch> &launches) {
+                                bool split_v210, std::vector<UpLaunch> &launches, bool keep_tails = false) {
   for (int k = 0; k < n_out; ++k) {
     bool seen = false;
     for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
@@ -2618,7 +2623,7 @@ static void compose_up_launches(const ph::UpArgs &base, int jobs, int n_out, con
     shared.solo = false, shared.table = k, shared.m.up = base;
     for (int g = 0; g < members; ++g) {
       const ph_chan_output &o = outs[group[g]];
-      if (split_v210 && o.format == PH_FMT_V210 && (out_w % 48 || members == 1)) {
+      if (split_v210 && o.format == PH_FMT_V210 && ((out_w % 48 && !keep_tails) || members == 1)) {
         UpLaunch own{};
         own.solo = true, own.table = k, own.m.up = base, own.m.up.wr_cm = (const float *)o.wr_col_matrix12;
         own.m.up.out = o.planes[0];
@@ -2629,7 +2634,7 @@ static void compose_up_launches(const ph::UpArgs &base, int jobs, int n_out, con
       }
       ph::UpOut &d = shared.m.out[shared.m.n_out];
       d.fmt = (uint32_t)o.format;
-      d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48)
+      d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48 - or the launcher's to set)
       d.wr_cm = (const float *)o.wr_col_matrix12;
       for (int j = 0; j < jobs; ++j)
         for (int i = 0; i < 3; ++i) d.plane[j][i] = outs[j * n_out + group[g]].planes[i];
@@ -2647,8 +2652,9 @@ static void compose_up_launches(const ph::UpArgs &base, int jobs, int n_out, con
 
 /* Several consumers' frames of one enlarged composition: see include/phaneron_hip.h.  Every check is made, and every launch of the call
  * is planned, before anything is launched. */
-int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, int n_out, const ph_chan_output *outs,
-                              uint32_t out_w, uint32_t out_h) {
+// keep_tails: the context option "up_v210_tails" as this call sees it - the transition entry's all-cuts call passes false, whatever the option says
+static int compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, int n_out, const ph_chan_output *outs,
+                                  uint32_t out_w, uint32_t out_h, bool keep_tails) {
   const char *const fn = "ph_compose_up_write_multi";
   if (!ctx || !layer_sets || !outs) return fail(PH_E_INVALID, "%s: NULL argument", fn);
   if (n_out < 1 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
@@ -2668,7 +2674,7 @@ int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_
   rc = compose_up_layers(fn, jobs, n, layer_sets, base, &fmt);
   if (rc) return rc;
   std::vector<UpLaunch> launches;
-  compose_up_launches(base, jobs, n_out, outs, out_w, out_h, true, launches);
+  compose_up_launches(base, jobs, n_out, outs, out_w, out_h, true, launches, keep_tails);
   for (UpLaunch &l : launches) {
     l.m.up.wr = *wref[l.table].get();
     if (!ph::compose_up_eligible(l.m.up)) return compose_up_not_eligible(fn);
@@ -2678,12 +2684,16 @@ int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_
   for (const UpLaunch &l : launches) {
     if (!l.m.up.lines) continue;
     hipError_t e = hipSuccess;
-    if (!l.solo) e = ph::launch_compose_up_multi(stream_of(ctx, queue), l.m, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount);
+    if (!l.solo) e = ph::launch_compose_up_multi(stream_of(ctx, queue), l.m, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount, keep_tails);
     else if (!ph::trace_launch("compose_up_write_v210"))
       e = ph::launch_compose_up_write_v210(stream_of(ctx, queue), l.m.up, fmt == PH_IMG_RGB_F32, (uint32_t)ctx->props.multiProcessorCount);
     if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   }
   return PH_OK;
+}
+int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_image_layer *const *layer_sets, int n_out, const ph_chan_output *outs,
+                              uint32_t out_w, uint32_t out_h) {
+  return compose_up_write_multi(ctx, queue, jobs, n, layer_sets, n_out, outs, out_w, out_h, ctx && ctx->up_v210_tails);
 }
 
 // What ph_clip_compose_multi's one-launch route and ph_clip_compose_batch_out's planner make of a clip and of an output: a clip's size and
@@ -2716,8 +2726,15 @@ static ph::ClipSrc clip_src_of(const ph_chan_source &S, int fmt, const void *rd_
  * per writer table where the frame is a single wire-format clip, else the format readers into the queue's scratch images and one
  * compose_up_multi launch per table (n > 1: measured for v210 frames only - chan_compose_enlarged - tools/clip_multi_bench.py records
  * n = 2 both ways).  Whatever these routes do not take runs ph_chan_compose_multi on the same arguments inside the call. */
+static int clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h,
+                              const void *rd_cm, const void *rd_lut, const void *rd_gm, bool keep_tails);
 int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h,
                           const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+  return clip_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, ctx && ctx->up_v210_tails);
+}
+// keep_tails: the context option "up_v210_tails" as this call sees it - the transition and route entries' calls pass false, whatever the option says
+static int clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h,
+                              const void *rd_cm, const void *rd_lut, const void *rd_gm, bool keep_tails) {
   const char *const fn = "ph_clip_compose_multi";
   if (!layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
   if (n_out < 1 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
@@ -2765,7 +2782,8 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
     alpha = fmt_rgb8(fmt);
   }
   // 4. the outputs by writer table, in the order the tables first appear; a v210 output whose lines end in a tail quad truncates its table
-  // indices there where the other writers round: through ph_chan_compose, alone
+  // indices there where the other writers round: through ph_chan_compose, alone - unless keep_tails and another output names its table: then
+  // it stays in the group, whose launch is the kernels' TAILS form (clip_up_multi_t / compose_up_multi_t)
   // (the two stages: the clips are read once for all the call's tables; the queue's scratch area is held until the last compositor launch
   // that takes the images is enqueued - and given up in front of a ph_chan_compose call, which takes the area itself)
   ph_image_layer il[1][ph::kMaxLayers];
@@ -2777,14 +2795,20 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
     if (seen) continue;
     ph::UpMultiArgs m{};
     m.up = base, m.up.wr = *wref[k].get();
+    int members = 0;
+    for (int j = k; j < n_out; ++j) members += outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    bool tails = false;  // the group's launch has a v210 output whose lines end in a tail quad
     for (int j = k; j < n_out; ++j) {
       const ph_chan_output &o = outs[j];
       if (o.wr_gamma_lut != outs[k].wr_gamma_lut) continue;
       if (o.format == PH_FMT_V210 && out_w % 48) {
-        if (images.owns_lock()) images.unlock();
-        rc = ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, o.planes, out_w, out_h, o.interlace, rd_cm, rd_lut, rd_gm, o.wr_col_matrix12, o.wr_gamma_lut);
-        if (rc) return rc;
-        continue;
+        if (!(keep_tails && members >= 2)) {
+          if (images.owns_lock()) images.unlock();
+          rc = ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, o.planes, out_w, out_h, o.interlace, rd_cm, rd_lut, rd_gm, o.wr_col_matrix12, o.wr_gamma_lut);
+          if (rc) return rc;
+          continue;
+        }
+        tails = true;
       }
       m.out[m.n_out++] = up_out_of(o, same_lines, out_w, out_h);
     }
@@ -2796,12 +2820,12 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
       for (uint32_t i = 0; i < m.n_out; ++i) c.out[i] = m.out[i];
       c.clip.rd = *rref.get(), c.clip.rd_gm = (const float *)rd_gm;
       c.clip.src[0] = clip_src_of(layers[0].src, fmt_of_src(layers[0].src.format), rd_cm);
-      const uint32_t grid = ph::clip_up_plan(c.clip, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ false);
+      const uint32_t grid = ph::clip_up_plan(c.clip, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ tails);
       if (grid) {
         if (images.owns_lock()) images.unlock();
         rc = with_scratch(fn, ctx, queue, (size_t)c.clip.wg_bytes * grid + 4096u, [&](hipStream_t s, void *area) {
           c.clip.scratch = (char *)area;
-          return ph::launch_clip_up_multi(s, c, !alpha, grid);
+          return ph::launch_clip_up_multi(s, c, !alpha, grid, tails);
         });
         if (rc) return rc;
         continue;
@@ -2814,7 +2838,7 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
       if (rc) return rc;
     }
     for (int i = 0; i < n; ++i) m.up.layer[i].ptr = il[0][i].data;
-    const hipError_t e = ph::launch_compose_up_multi(stream_of(ctx, queue), m, false, (uint32_t)ctx->props.multiProcessorCount);
+    const hipError_t e = ph::launch_compose_up_multi(stream_of(ctx, queue), m, false, (uint32_t)ctx->props.multiProcessorCount, tails);
     if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   }
   return PH_OK;
@@ -2850,7 +2874,7 @@ int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_cha
   // 1. no transition: ph_clip_compose_multi, its routes under its names
   bool any = false;
   for (int i = 0; i < n; ++i) any = any || layers[i].transition != PH_TRANSITION_CUT;
-  if (!any) return ph_clip_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm);
+  if (!any) return clip_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, /*keep_tails*/ false);
   // 2. the lines composed: the field every output wants, or the whole frame (a field output then takes the rows of its parity)
   bool same_lines = true;
   for (int k = 1; k < n_out; ++k) same_lines = same_lines && outs[k].interlace == outs[0].interlace;
@@ -3048,7 +3072,7 @@ int ph_clip_compose_route_multi(ph_ctx *ctx, int queue, int n, const ph_chan_lay
                                 uint32_t out_w, uint32_t out_h, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
   const char *const fn = kClipRouteFn;
   if (const int bad = clip_route_counts(n_out, image_out)) return bad;
-  if (!image_out) return ph_clip_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm);
+  if (!image_out) return clip_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, /*keep_tails*/ false);
   ph::UpArgs base;
   LutRef rref, wref[ph::kMaxUpOuts];
   if (const int bad = clip_route_checked(fn, ctx, queue, n, layers, image_out, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, base, rref, wref)) return bad;
@@ -3137,20 +3161,25 @@ namespace {
 struct ClipBatchStep {  // what the call does in its turn: a shared launch of jobs [first, first + m.clip.up.jobs), or job `first` handed on
   int first = 0;
   bool shared = false, alpha = false;
+  bool tails = false;  // option "up_v210_tails": the launch has a v210 output whose lines end in a tail quad (the same for every job: one output list)
   uint32_t grid = 0;
   ph::ClipUpMultiArgs m{};
 };
 }  // namespace
 // one job's launch arguments as ph_clip_compose_multi makes them for its one-launch route (false: the job is not for that route as a whole)
 static bool clip_job_args(ph_ctx *ctx, const ph_chan_job_out &J, const ChanJobPlan &P, uint32_t out_w, uint32_t out_h, const void *rd_cm, const void *rd_gm,
-                          const ph::LutView &rd, ph::ClipUpMultiArgs &c, bool &alpha) {
+                          const ph::LutView &rd, ph::ClipUpMultiArgs &c, bool &alpha, bool &tails) {
   if (ctx->chan_enlarged != 1 || J.n != 1) return false;
   if (J.n_out == 1 && J.outs[0].format == PH_FMT_V210) return false;  // (ph_chan_compose, under its names)
   const ph_chan_source &S = J.layers[0].src;
   const int fmt = fmt_of_src(S.format);
   if (fmt < 0 || (fmt_v420(fmt) && (S.height & 1))) return false;
-  for (int k = 0; k < J.n_out; ++k)
-    if (J.outs[k].wr_gamma_lut != J.outs[0].wr_gamma_lut || (J.outs[k].format == PH_FMT_V210 && out_w % 48)) return false;  // (several launches there)
+  tails = false;
+  for (int k = 0; k < J.n_out; ++k) {
+    const bool tail = J.outs[k].format == PH_FMT_V210 && out_w % 48;
+    if (J.outs[k].wr_gamma_lut != J.outs[0].wr_gamma_lut || (tail && !ctx->up_v210_tails)) return false;  // (several launches there)
+    tails = tails || tail;
+  }
   if (!chan_layers_enlarged(1, J.layers, out_w, out_h, P.interlace, /*v210_fill*/ true)) return false;
   c = ph::ClipUpMultiArgs{};
   ph::UpArgs &a = c.clip.up;
@@ -3164,7 +3193,7 @@ static bool clip_job_args(ph_ctx *ctx, const ph_chan_job_out &J, const ChanJobPl
   c.clip.rd = rd, c.clip.rd_gm = (const float *)rd_gm;
   c.clip.src[0] = clip_src_of(S, fmt, rd_cm);
   ph::ClipUpArgs probe = c.clip;
-  return ph::clip_up_plan(probe, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ false) != 0;
+  return ph::clip_up_plan(probe, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ tails) != 0;
 }
 
 /* Several CHANNELS' file playback for any consumers in one launch: see include/phaneron_hip.h.  Exactly, in order and bit for bit, the
@@ -3199,7 +3228,7 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
   auto flush = [&]() {
     if (!cur.shared) return;
     ph::ClipUpArgs &c = cur.m.clip;
-    if (c.up.jobs > 1u) cur.grid = ph::clip_up_plan(c, !cur.alpha, num_cus, /*v210_tails*/ false);
+    if (c.up.jobs > 1u) cur.grid = ph::clip_up_plan(c, !cur.alpha, num_cus, /*v210_tails*/ cur.tails);
     if (c.up.jobs > 1u && cur.grid) {
       steps.push_back(cur);
     } else {  // a group of one job (or a tiling the kernel does not take): ph_clip_compose_multi, job by job
@@ -3215,8 +3244,8 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
     const ph_chan_job_out &J = jobs[j];
     const ChanJobPlan &P = plan[(size_t)j];
     ph::ClipUpMultiArgs c;
-    bool alpha = false;
-    if (!clip_job_args(ctx, J, P, out_w, out_h, rd_cm, rd_gm, rref.view, c, alpha)) {  // in its turn, on its own
+    bool alpha = false, tails = false;
+    if (!clip_job_args(ctx, J, P, out_w, out_h, rd_cm, rd_gm, rref.view, c, alpha, tails)) {  // in its turn, on its own
       flush();
       ClipBatchStep own;
       own.first = j;
@@ -3238,7 +3267,7 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
       if (apart) flush();
     }
     if (!cur.shared) {
-      cur.shared = true, cur.first = j, cur.alpha = alpha, cur.m = c;
+      cur.shared = true, cur.first = j, cur.alpha = alpha, cur.tails = tails, cur.m = c;
       continue;
     }
     const uint32_t at = cur.m.clip.up.jobs++;
@@ -3258,7 +3287,7 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
     }
     rc = with_scratch(fn, ctx, queue, (size_t)s.m.clip.wg_bytes * s.grid + 4096u, [&](hipStream_t st, void *area) {
       s.m.clip.scratch = (char *)area;
-      return ph::launch_clip_up_multi(st, s.m, !s.alpha, s.grid);
+      return ph::launch_clip_up_multi(st, s.m, !s.alpha, s.grid, s.tails);
     });
     if (rc) return rc;
   }
@@ -3309,7 +3338,7 @@ int ph_compose_up_transition_multi(ph_ctx *ctx, int queue, int jobs, int n, cons
       for (int i = 0; i < n; ++i) flat[(size_t)j * n + i] = layer_sets[j][i].src;
       sets[j] = &flat[(size_t)j * n];
     }
-    return ph_compose_up_write_multi(ctx, queue, jobs, n, sets, n_out, outs, out_w, out_h);
+    return compose_up_write_multi(ctx, queue, jobs, n, sets, n_out, outs, out_w, out_h, /*keep_tails*/ false);
   }
   int rc = compose_up_outputs(fn, jobs, n_out, outs, out_w, out_h);
   if (rc) return rc;

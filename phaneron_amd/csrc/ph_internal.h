@@ -72,6 +72,9 @@ struct ph_ctx {
   int chan_batch_outs = 0;
   // option "clip_batch" (default 0): ph_run_programs puts consecutive clip_compose_multi_<n> jobs into shared launches (ph_clip_compose_batch_out)
   int clip_batch = 0;
+  // option "up_v210_tails" (default 0): a v210 output whose lines end in a tail quad (width % 48 != 0: 1280) stays in its writer table's launch of
+  // the several-outputs kernels (ph_compose_up_write_multi, ph_clip_compose_multi, ph_clip_compose_batch_out) instead of being made on its own
+  int up_v210_tails = 0;
   // option "fused_multi_wgs" (default 0 = no cap): the most workgroups a ph_fused_v210_combine_multi launch may have (tests, A/B runs)
   int fused_multi_wgs = 0;
   // option "fused_multi_batch" (default 0): ph_run_programs puts consecutive fused_v210_combine_multi_<n> jobs into shared launches (ph_fused_v210_combine_multi_batch)

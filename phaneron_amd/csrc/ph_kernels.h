@@ -435,7 +435,8 @@ struct UpMultiArgs {
   UpOut out[kMaxUpOuts];
 };
 static_assert(sizeof(UpMultiArgs) < 4096, "kernel arguments are limited to 4 KiB");
-hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb12, uint32_t num_cus);
+// v210_tails (context option "up_v210_tails"): a v210 output whose lines end in a tail quad stays in the launch - compose_up_multi_t<..>
+hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb12, uint32_t num_cus, bool v210_tails = false);
 // Clips straight from their wire formats for ANY consumer, up to kMaxUpOuts per launch (ph_clip_compose_multi, clip_up_multi_kernel):
 // clip describes the composition as for clip_up_write_v210_kernel - clip.up.out / more_out / wr_cm are unused, clip.up.wr is the ONE
 // writer table of the launch - and every output brings its format, its planes per job and its writer matrix, as in UpMultiArgs.  A v210
@@ -449,7 +450,9 @@ struct ClipUpMultiArgs {
 static_assert(sizeof(ClipUpMultiArgs) < 4096, "kernel arguments are limited to 4 KiB");
 // grid: clip_up_plan(clip, rgb12, num_cus, false); named clip_up_multi<rgb|rgba>x<outputs> in a route trace, with several jobs
 // clip_up_multi<rgb|rgba>x<outputs>j<jobs>
-hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rgb12, uint32_t grid);
+// v210_tails (context option "up_v210_tails"): a v210 output whose lines end in a tail quad stays in the launch - grid is then
+// clip_up_plan(clip, rgb12, num_cus, true), the name clip_up_multi_t<..>
+hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rgb12, uint32_t grid, bool v210_tails = false);
 // ONE wire-format clip in a TRANSITION for any consumer (ph_clip_compose_transition_multi, clip_up_trans_kernel): a playlist's MIX or WIPE
 // from one file to the next.  multi is the frame as for clip_up_multi_kernel with a single layer and a single job - multi.clip.up.layer[0]
 // and multi.clip.src[0] are the layer's `src` - and the transition brings the incoming clip (dissolve, wipe) and the mask clip (wipe), each

@@ -419,7 +419,8 @@ __global__ __launch_bounds__(kUpBlock) void compose_up_write_v210_kernel(UpArgs 
 // are made once, then every output packs the same twelve values with its own matrix.  A block with even x and y is one 4:2:0 chroma site.
 // Every output of a launch names the launch's ONE table (the kernel is persistent and single-phase: no point at which all waves could
 // swap it), and rounds its indices - a v210 output whose lines end in a tail quad, which truncates them there, is launched on its own
-// by the caller (compose_up_write_v210_kernel<RGB12, true>).
+// by the caller (compose_up_write_v210_kernel<RGB12, true>) - or, with the context option "up_v210_tails", stays in the kernels' TAILS
+// form (up_write_outs_tails below).
 //
 // Stores.  rgba8 / bgra8 store 8 bytes per lane and row - a wave's row segment without a gap, as the v210 halves; the planar writers
 // store the lane's two luma samples (2 or 4 bytes) and its one chroma site per plane (1 or 2 bytes), again contiguous over the wave's
@@ -481,8 +482,13 @@ __device__ __forceinline__ void up_layers(const UpArgs &a, const UpStep &st, UpA
   }
 }
 
-template <int OUT>
-__device__ __forceinline__ void up_write_out(const UpOut &o, const UpStep &st, const float (&t)[2][2][3], uint32_t role) {
+// TAILS (a v210 output of a launch whose lines end in a tail quad and cleared slots - the TAILS forms of the several-outputs kernels, whose
+// wave steps cover the pitch): up_write<true>'s line ends.  `t` holds the tail quad's lanes' values from TRUNCATED indices (the caller's
+// second set); their codes go through round() and the truncating convert, a lane beyond the line's pixels contributes zero code values, and
+// lanes A and C of every quad slot of the pitch store (o.pitch: the pitch in quad slots).  The other writers of such a launch are called as
+// ever: a lane beyond the line is not live and stores nothing for them.
+template <int OUT, bool TAILS = false>
+__device__ __forceinline__ void up_write_out(const UpOut &o, const UpStep &st, const float (&t)[2][2][3], uint32_t role, uint32_t out_w = 0) {
   constexpr bool WIDE = fmt_wide(OUT), V420 = fmt_v420(OUT), NV12 = fmt_cbcr(OUT);
   char *const p0 = static_cast<char *>(o.plane[st.job][0]);
   WriteK wk;
@@ -496,6 +502,20 @@ __device__ __forceinline__ void up_write_out(const UpOut &o, const UpStep &st, c
       typedef uint32_t ph_u2v __attribute__((ext_vector_type(2)));
       const ph_u2v px{rgb8_pack<OUT>(e[0], e[1], e[2]), rgb8_pack<OUT>(d[0], d[1], d[2])};
       if (st.live) __builtin_nontemporal_store(px, reinterpret_cast<ph_u2v *>(p0 + ((size_t)line * o.pitch + st.x0) * 4u));
+      continue;
+    }
+    if (TAILS && OUT == PH_FMT_V210) {  // up_write<true>: the tail quad's codes, zeros beyond the line, every quad slot of the pitch stored
+      typedef uint32_t ph_u2v __attribute__((ext_vector_type(2)));
+      const uint32_t quad = st.x0 / 6u;
+      const bool in_tail = quad == out_w / 6u, beyond = st.x0 >= out_w;
+      auto code = [&](const float *px, const float4 row) __attribute__((always_inline)) {
+        const float v = dot4(px[0], px[1], px[2], 1.0f, row);
+        const uint32_t c = in_tail ? sat_u16_trunc(__builtin_roundf(v)) : sat_u16_rte(v);
+        return beyond ? 0u : c;
+      };
+      const uint2 half = up_v210_half(code(e, wk.y), code(e, wk.u), code(e, wk.v), code(d, wk.y), role);
+      ph_u2v *dst = reinterpret_cast<ph_u2v *>(reinterpret_cast<uint4 *>(p0) + (size_t)line * o.pitch + quad) + (role == 2u ? 1 : 0);
+      if ((threadIdx.x & 63u) < 63u && quad < o.pitch && role != 1u) __builtin_nontemporal_store(ph_u2v{half.x, half.y}, dst);
       continue;
     }
     // chroma from the even pixel (v210.ts:145-162 and every planar writer)
@@ -527,7 +547,72 @@ __device__ __forceinline__ void up_write_out(const UpOut &o, const UpStep &st, c
   }
 }
 
-template <bool RGB12, uint32_t COLS>
+// The writers of a wave step in the TAILS forms of compose_up_multi_kernel and clip_up_multi_kernel (context option "up_v210_tails"): a v210
+// output whose lines end in a tail quad (out_w % 48 != 0; 1280: src/config.ts:43-54) beside the rounding writers of its table.  The twelve
+// table reads are made once for all outputs as ever.  In the ONE wave step of a row pair that holds the tail quad's pixels (a wave-uniform
+// test: every other step runs the reads above and nothing more) twelve more reads give the v210 outputs their second set - the tail quad's
+// lanes from truncated indices (v210.ts:176-178), every other lane its rounded values again.  (The channel kernel's way - the rounded index
+// is the truncated one plus 0 or 1, ph_kernels_chan.hip - saves those reads in a kernel that waits for the LDS; this one does not, and the
+// step is one of ten or more per row pair.)
+__device__ __forceinline__ void up_write_outs_tails(uint32_t out_w, const UpStep &st, const UpAcc (&acc)[2][2], uint32_t n_out, const UpOut *out, uint32_t role,
+                                                    const LutK &lk) {
+  float t[2][2][3], tv[2][2][3];
+  {
+    PxPending pend[2][2];
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx)
+        pend[dy][dx] = write_px_issue(lds_lut_index_unit(acc[dy][dx].r), lds_lut_index_unit(acc[dy][dx].g), lds_lut_index_unit(acc[dy][dx].b), lk);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx)
+        t[dy][dx][0] = lds_lut_finish(pend[dy][dx].r), t[dy][dx][1] = lds_lut_finish(pend[dy][dx].g), t[dy][dx][2] = lds_lut_finish(pend[dy][dx].b);
+  }
+#pragma unroll
+  for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx)
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) tv[dy][dx][ch] = t[dy][dx][ch];
+  const bool in_tail = st.x0 / 6u == out_w / 6u && st.x0 < out_w;  // the lane's block belongs to the tail quad (none where out_w % 6 == 0)
+  if (__builtin_amdgcn_ballot_w64(in_tail) != 0) {  // uniform: the step that holds the tail quad
+    PxPending pend[2][2];
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx)
+        pend[dy][dx] = write_px_issue(lds_lut_index_unit_tail(acc[dy][dx].r, in_tail), lds_lut_index_unit_tail(acc[dy][dx].g, in_tail),
+                                      lds_lut_index_unit_tail(acc[dy][dx].b, in_tail), lk);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx)
+        tv[dy][dx][0] = lds_lut_finish(pend[dy][dx].r), tv[dy][dx][1] = lds_lut_finish(pend[dy][dx].g), tv[dy][dx][2] = lds_lut_finish(pend[dy][dx].b);
+  }
+  // (left to the compiler whether to unroll: with the pragma of the kernels' own copies of this loop it answers "loop not unrolled" here)
+  for (uint32_t k = 0; k < (uint32_t)kMaxUpOuts; ++k) {
+    if (k >= n_out) break;  // uniform
+    const UpOut &o = out[k];
+    switch (o.fmt) {  // uniform
+      case PH_FMT_V210: up_write_out<PH_FMT_V210, true>(o, st, tv, role, out_w); break;
+      case PH_FMT_YUV422P10: up_write_out<PH_FMT_YUV422P10>(o, st, t, role); break;
+      case PH_FMT_YUV422P8: up_write_out<PH_FMT_YUV422P8>(o, st, t, role); break;
+      case PH_FMT_YUV420P: up_write_out<PH_FMT_YUV420P>(o, st, t, role); break;
+      case PH_FMT_NV12: up_write_out<PH_FMT_NV12>(o, st, t, role); break;
+      case PH_FMT_RGBA8: up_write_out<PH_FMT_RGBA8>(o, st, t, role); break;
+      case PH_FMT_BGRA8: up_write_out<PH_FMT_BGRA8>(o, st, t, role); break;
+    }
+  }
+}
+
+// TAILS: a v210 output's lines end in a tail quad and cleared slots (an instantiation of its own, 126 columns: the existing forms keep
+// their text and their registers, profiles/up_tails_resources.txt).  The wave steps cover the pitch (up_plan), a lane beyond the line's
+// pixels composes whatever its taps give (loads are bounded by the buffer's records) and up_write_outs_tails lets none of it out.
+template <bool RGB12, uint32_t COLS, bool TAILS = false>
 __global__ __launch_bounds__(kUpBlock) void compose_up_multi_kernel(UpMultiArgs m) {
   const UpArgs &a = m.up;
   const LutK lk = make_lut_k(a.wr);
@@ -544,6 +629,10 @@ __global__ __launch_bounds__(kUpBlock) void compose_up_multi_kernel(UpMultiArgs 
 #pragma unroll
       for (int dx = 0; dx < 2; ++dx) acc[dy][dx] = UpAcc{0.0f, 0.0f, 0.0f};
     up_layers<RGB12>(a, st, acc, lk);
+    if (TAILS) {
+      up_write_outs_tails(a.out_w, st, acc, m.n_out, m.out, role, lk);
+      continue;
+    }
     // the twelve table reads of the block's four pixels, started together - once for all outputs
     float t[2][2][3];
     {
@@ -1016,11 +1105,15 @@ __global__ __launch_bounds__(kUpBlock) void clip_up_write_v210_kernel(ClipUpArgs
 // (their code is pinned: profiles/up_out_resources.txt, profiles/clip_multi_resources.txt), so the two halves are copies kept in step by
 // hand.  One frame per launch unless MULTI (job 0's planes of every output: clip_step's job is 0); the wave step is the clip kernel's 126 columns for
 // every launch, a v210 output or not, so the tiling and the rectangle bounds of clip_up_plan hold as they are.  A v210 output's lines end
-// on a 48-pixel block here (the caller sends the others through the one-output routes: their tail quads truncate table indices).
+// on a 48-pixel block here (the caller sends the others through the one-output routes: their tail quads truncate table indices) -
+// unless TAILS.
 // MULTI: several frames of one shape in the launch, as clip_up_write_v210_kernel's MULTI - rows of tiles job after job, job j's clip in
 // src[j], its planes o.plane[j] of every output (an instantiation of its own: the one-frame forms keep their text and their registers,
 // profiles/clip_multi_batch_resources.txt)
-template <bool RGB12, bool MULTI = false>
+// TAILS: a v210 output's lines end in a tail quad and cleared slots (instantiations of their own, as compose_up_multi_kernel's): the tiles
+// cover the pitch (clip_up_plan with v210_tails), the rectangle bounds clamp to the line's pixels as clip_up_write_v210_kernel<.., TAILS>'s
+// do, and up_write_outs_tails is the writer.
+template <bool RGB12, bool MULTI = false, bool TAILS = false>
 __global__ __launch_bounds__(kUpBlock) void clip_up_multi_kernel(ClipUpMultiArgs cm) {
   const ClipUpArgs &c = cm.clip;
   const UpArgs &a = c.up;
@@ -1132,6 +1225,10 @@ __global__ __launch_bounds__(kUpBlock) void clip_up_multi_kernel(ClipUpMultiArgs
       else layers(std::false_type{}, std::true_type{});
     } else {
       layers(std::false_type{}, std::false_type{});
+    }
+    if (TAILS) {
+      up_write_outs_tails(a.out_w, st, acc, cm.n_out, cm.out, role, lk);
+      continue;
     }
     // the twelve table reads of the block's four pixels, started together - once for all outputs (compose_up_multi_kernel)
     float t[2][2][3];
@@ -1595,17 +1692,21 @@ hipError_t launch_clip_up_write_v210(hipStream_t s, const ClipUpArgs &c, bool rg
 // Several outputs of one clip composition: named clip_up_multi<rgb|rgba>x<outputs> in a route trace.  grid: clip_up_plan's, asked with
 // v210_tails == false.  Refuses what launch_compose_up_multi refuses.  Several jobs (single-layer frames of one shape, job j's clip in
 // clip.src[j] and its planes in out[k].plane[j]): named clip_up_multi<rgb|rgba>x<outputs>j<jobs>, the MULTI instantiation.
-hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rgb12, uint32_t grid) {
+// v210_tails (context option "up_v210_tails"): a v210 output whose lines end in a tail quad is taken - grid is then clip_up_plan's asked
+// with v210_tails == true (the tiles cover the pitch), the launch is named clip_up_multi_t<..> and runs the TAILS instantiations.
+hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rgb12, uint32_t grid, bool v210_tails) {
   const UpArgs &a = m.clip.up;
-  if (!grid || m.n_out < 1 || m.n_out > (uint32_t)kMaxUpOuts || a.jobs < 1u || a.jobs > (uint32_t)kMaxUpJobs || a.n < 1 || a.n > kMaxLayers || a.cover_w != a.out_w)
-    return hipErrorInvalidValue;
+  if (!grid || m.n_out < 1 || m.n_out > (uint32_t)kMaxUpOuts || a.jobs < 1u || a.jobs > (uint32_t)kMaxUpJobs || a.n < 1 || a.n > kMaxLayers) return hipErrorInvalidValue;
+  bool tails = false;
+  for (uint32_t k = 0; k < m.n_out; ++k) tails = tails || (v210_tails && m.out[k].fmt == PH_FMT_V210 && a.out_w % 48u);
+  if (a.cover_w != (tails ? a.out_qpitch * 6u : a.out_w)) return hipErrorInvalidValue;
   const bool multi = a.jobs > 1u;
   if (multi && (a.n != 1 || !m.clip.gy || grid != m.clip.gx * m.clip.gy * a.jobs)) return hipErrorInvalidValue;  // (a tile's job is its row of tiles / gy: within jobs)
   for (uint32_t k = 0; k < m.n_out; ++k)
-    if (!fmt_chan_out((int)m.out[k].fmt) || (m.out[k].fmt == PH_FMT_V210 && a.out_w % 48u)) return hipErrorInvalidValue;
+    if (!fmt_chan_out((int)m.out[k].fmt) || (m.out[k].fmt == PH_FMT_V210 && a.out_w % 48u && !tails)) return hipErrorInvalidValue;
   char name[48];
-  if (multi) snprintf(name, sizeof name, "clip_up_multi<%s>x%uj%u", rgb12 ? "rgb" : "rgba", m.n_out, a.jobs);
-  else snprintf(name, sizeof name, "clip_up_multi<%s>x%u", rgb12 ? "rgb" : "rgba", m.n_out);
+  if (multi) snprintf(name, sizeof name, "clip_up_multi%s<%s>x%uj%u", tails ? "_t" : "", rgb12 ? "rgb" : "rgba", m.n_out, a.jobs);
+  else snprintf(name, sizeof name, "clip_up_multi%s<%s>x%u", tails ? "_t" : "", rgb12 ? "rgb" : "rgba", m.n_out);
   if (trace_launch(name)) return hipSuccess;
   const uint32_t lds = m.clip.info_off + 16u * (uint32_t)a.n;
   auto go = [&](auto kernel) -> hipError_t {
@@ -1614,6 +1715,19 @@ hipError_t launch_clip_up_multi(hipStream_t s, const ClipUpMultiArgs &m, bool rg
     kernel<<<grid, kUpBlock, lds, s>>>(m);
     return hipGetLastError();
   };
+  if (tails) {  // a v210 output's line pitch: every quad slot of it is written
+    ClipUpMultiArgs b = m;
+    for (uint32_t k = 0; k < b.n_out; ++k)
+      if (b.out[k].fmt == PH_FMT_V210) b.out[k].pitch = a.out_qpitch;
+    auto go_tails = [&](auto kernel) -> hipError_t {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
+      if (e != hipSuccess) return e;
+      kernel<<<grid, kUpBlock, lds, s>>>(b);
+      return hipGetLastError();
+    };
+    if (multi) return rgb12 ? go_tails(clip_up_multi_kernel<true, true, true>) : go_tails(clip_up_multi_kernel<false, true, true>);
+    return rgb12 ? go_tails(clip_up_multi_kernel<true, false, true>) : go_tails(clip_up_multi_kernel<false, false, true>);
+  }
   if (multi) return rgb12 ? go(clip_up_multi_kernel<true, true>) : go(clip_up_multi_kernel<false, true>);
   return rgb12 ? go(clip_up_multi_kernel<true>) : go(clip_up_multi_kernel<false>);
 }
@@ -1718,13 +1832,17 @@ hipError_t launch_compose_up_write_v210(hipStream_t s, const UpArgs &a, bool rgb
 }
 
 // Several outputs of one composition: named compose_up_multi<rgb|rgba>x<outputs>j<jobs> in a route trace
-hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb12, uint32_t num_cus) {
+// v210_tails (context option "up_v210_tails"): a v210 output whose lines end in a tail quad is taken - the launch is named
+// compose_up_multi_t<..> and runs the TAILS instantiation, its wave steps over the pitch.
+hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb12, uint32_t num_cus, bool v210_tails) {
   if (!m.up.lines) return hipSuccess;
   if (m.n_out < 1 || m.n_out > (uint32_t)kMaxUpOuts || m.up.jobs < 1 || m.up.jobs > (uint32_t)kMaxUpJobs) return hipErrorInvalidValue;
+  bool tails = false;
+  for (uint32_t k = 0; k < m.n_out; ++k) tails = tails || (v210_tails && m.out[k].fmt == PH_FMT_V210 && m.up.out_w % 48u);
   for (uint32_t k = 0; k < m.n_out; ++k)
-    if (!fmt_chan_out((int)m.out[k].fmt) || (m.out[k].fmt == PH_FMT_V210 && m.up.out_w % 48u)) return hipErrorInvalidValue;
+    if (!fmt_chan_out((int)m.out[k].fmt) || (m.out[k].fmt == PH_FMT_V210 && m.up.out_w % 48u && !tails)) return hipErrorInvalidValue;
   char name[48];
-  snprintf(name, sizeof name, "compose_up_multi<%s>x%uj%u", rgb12 ? "rgb" : "rgba", m.n_out, m.up.jobs);
+  snprintf(name, sizeof name, "compose_up_multi%s<%s>x%uj%u", tails ? "_t" : "", rgb12 ? "rgb" : "rgba", m.n_out, m.up.jobs);
   if (trace_launch(name)) return hipSuccess;
   // the wave step: 126 columns with a v210 output (its quads), else 128 - every store instruction of a wave then covers whole 32-byte
   // sectors of its row where the pitch allows (see compose_up_multi_kernel).  PH_UP_OUT_STEP=126 in the environment keeps 126 for every
@@ -1734,13 +1852,18 @@ hipError_t launch_compose_up_multi(hipStream_t s, const UpMultiArgs &m, bool rgb
   for (uint32_t k = 0; k < m.n_out; ++k) v210 = v210 || m.out[k].fmt == PH_FMT_V210;
   const bool wide = !v210 && !narrow_always;
   UpMultiArgs b = m;
-  const uint32_t grid = up_plan(b.up, false, num_cus, wide ? 128u : kUpCols);
+  const uint32_t grid = up_plan(b.up, tails, num_cus, wide ? 128u : kUpCols);
   auto go = [&](auto kernel) -> hipError_t {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
     if (e != hipSuccess) return e;
     kernel<<<grid, kUpBlock, b.up.wr.bytes, s>>>(b);
     return hipGetLastError();
   };
+  if (tails) {  // (a v210 output: 126 columns) - its line pitch, every quad slot of which is written
+    for (uint32_t k = 0; k < b.n_out; ++k)
+      if (b.out[k].fmt == PH_FMT_V210) b.out[k].pitch = b.up.out_qpitch;
+    return rgb12 ? go(compose_up_multi_kernel<true, kUpCols, true>) : go(compose_up_multi_kernel<false, kUpCols, true>);
+  }
   if (wide) return rgb12 ? go(compose_up_multi_kernel<true, 128u>) : go(compose_up_multi_kernel<false, 128u>);
   return rgb12 ? go(compose_up_multi_kernel<true, kUpCols>) : go(compose_up_multi_kernel<false, kUpCols>);
 }
