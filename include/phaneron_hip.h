@@ -56,7 +56,9 @@ extern "C" {
  *    "clip_compose_multi_<n>".  ph_clip_compose_batch_out (ph_chan_job_out): several channels' such frames in one launch; context
  *    option "clip_batch".  ph_clip_compose_transition_multi: file playback through a MIX or WIPE - a layer's src, incoming and mask clips
  *    each read once per source pixel; program "clip_compose_trans_<n>".  ph_clip_compose_route_multi: a routed channel's file playback -
- *    ph_clip_compose_multi's frames and the combined f32 RGBA image itself from the read-once launches; program "clip_compose_route_<n>" */
+ *    ph_clip_compose_multi's frames and the combined f32 RGBA image itself from the read-once launches; program "clip_compose_route_<n>".
+ *    Context option "fused_fields": ph_fused_v210_combine_multi and its batch compose only the field where every output takes the same
+ *    one; ph_debug_fused_field_quad (tests): a field quad's place in the frame, as those launches' kernels make it */
 #define PH_ABI_VERSION 8
 
 enum {
@@ -779,7 +781,14 @@ int ph_pack_write_multi(ph_ctx *ctx, int queue, const void *in, int n_out, const
  * several-outputs form ("fused_v210_combine_multi x<outputs>" in a trace): its phase 1 is the headline kernel's; between the phases a quad
  * is its 18 writer-table indices in registers, and the writer's phase runs once per distinct writer table among the outputs - the 18
  * table reads made once, every output of that table packing the same 18 values with its own writer matrix.  No second composition
- * and no index frame in memory.  The whole frame is always composed; a field output (interlace 1 / 3) stores the quads of its lines.
+ * and no index frame in memory.  By default the whole frame is composed; a field output (interlace 1 / 3) stores the quads of its lines.
+ * Context option "fused_fields" (default 0) = 1: where EVERY output is a field output of the same field (all interlace 1, or all 3 - a
+ * 1080i channel's consumers; a lone v210 field, SDI's call, included) and the call qualifies for the shared launch, only that field is
+ * composed: height / 2 lines from line 0 (interlace 1) or line 1 (interlace 3) are read, combined and looked up, in one launch
+ * ("fused_v210_field_multi x<outputs>f<interlace>" in a trace) whose workgroups divide the FIELD's quads; height < 2 is PH_OK with nothing
+ * launched.  The same bytes as with 0: the other parity's lines and, at an odd height, the last line are not touched; a 4:2:0 field
+ * output's chroma row comes from the written line of the pair.  Outputs of mixed field modes, or any frame output among them, keep the
+ * whole-frame launch and its name, with either value.
  * The shared launch needs width % 48 == 0, the reader's table and every writer's table registered, and the context option "lds_lut"
  * = 1; a call that does not qualify runs ph_chan_compose_multi on the equivalent layers inside the call, under that call's trace name,
  * so the entry takes everything ph_chan_compose_multi takes and answers its errors.
@@ -798,7 +807,10 @@ int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const
  * Routes: jobs == 1 IS ph_fused_v210_combine_multi, same route.  Every job one v210 frame (n_out == 1, PH_FMT_V210, interlace == 0) IS
  * ph_fused_v210_combine_batch, same route.  Otherwise one launch ("fused_v210_combine_multi x<outputs>j<jobs>" in a trace): max(1, CUs /
  * jobs) workgroups per job - never more than a job's slices, "fused_multi_wgs" caps them per job - each owning an equal contiguous quad
- * range of its job; arithmetic and order within a job are ph_fused_v210_combine_multi's.  A call the shared launch does not take
+ * range of its job; arithmetic and order within a job are ph_fused_v210_combine_multi's.  With the context option "fused_fields" = 1 and
+ * every output a field output of the same field, the launch composes that field only, as ph_fused_v210_combine_multi says
+ * ("fused_v210_field_multi x<outputs>j<jobs>f<interlace>"; the workgroups per job never more than the FIELD's slices); the same bytes.
+ * A call the shared launch does not take
  * (width % 48 != 0, a table without its LDS form, "lds_lut" = 0, a frame too large for the kernel's division by reciprocal) runs
  * ph_fused_v210_combine_multi per job, in order, inside the call, under those calls' trace names.
  * PH_E_INVALID, decided before anything is launched (a refused call writes nothing): jobs outside 1..8; everything
@@ -925,6 +937,13 @@ int ph_lut_layout_of(const float *host_lut65536, ph_lut_layout *layout, void *ld
  *          layer count, Loader recipe and output list (formats, field modes, writer matrices and tables, in order) into shared launches,
  *          up to 8 jobs each (ph_fused_v210_combine_multi_batch); 0: each such job a launch of its own, in its turn.  The same bits
  *          either way.  Any other value is PH_E_INVALID;
+ *          "fused_fields" (default 0): 1 lets ph_fused_v210_combine_multi and ph_fused_v210_combine_multi_batch - and what reaches them:
+ *          ph_fused_v210_transition_multi with every layer a cut, ph_fused_v210_route_multi without an image layer or image_out, the
+ *          programs fused_v210_combine_multi_<n> and their shared launches - compose only the field where every output takes the same one
+ *          (all interlace 1 or all 3) and the call qualifies for the shared launch: half the lines read, combined and looked up
+ *          ("fused_v210_field_multi ..." in a trace); 0: the whole frame, a field output storing the quads of its lines.  The same bytes
+ *          either way.  Still whole-frame with 1: outputs of mixed field modes or with a frame among them, a layer in a transition, an
+ *          image layer or image_out.  Any other value is PH_E_INVALID;
  *          "clip_batch" (default 0): 1 lets ph_run_programs put consecutive clip_compose_multi_<n> jobs of one geometry and Loader recipe
  *          into one ph_clip_compose_batch_out call, which shares launches among those of one clip shape and output list; 0: each such
  *          job a launch of its own, in its turn.  The same bits either way.  Any other value is PH_E_INVALID;
@@ -941,6 +960,11 @@ int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value);
  * 0 through the caches, 1 streamed - from "stream_images" and "stream_threshold_mb" (2: 1 for bytes > threshold << 20, strictly).
  * Selects the context's device as a launch does; negative on error (a NULL or destroyed context). */
 int ph_debug_image_nt(ph_ctx *ctx, size_t bytes);
+/* TESTS: where the field launches ("fused_fields") put field quad g of a width x height frame - the mapping their kernels use, run on the
+ * host.  The field (interlace 1: the even lines, 3: the odd ones) is height / 2 lines of width / 6 quads, g counts them in raster order;
+ * *f: the frame's flat quad (line * (width / 6) + col), *line: the frame line, *col: the quad's place in it (each may be NULL).
+ * PH_E_INVALID: width % 48 != 0, interlace not 1 or 3, g outside the field, a frame beyond the kernels' division by reciprocal. */
+int ph_debug_fused_field_quad(uint32_t width, uint32_t height, int interlace, uint32_t g, uint32_t *f, uint32_t *line, uint32_t *col);
 
 /* ---- host colour maths (src/process/colourMaths.ts, run by Loader/Saver constructors
  *      loadSave.ts:50-63,139-149): outputs are HOST arrays the caller uploads. ------------------ */

@@ -147,6 +147,12 @@ class Deferral {
 		// differently - v210 siblings of any width are handed to compose_up_multi_<n> as ever: the option is set once, in front of the first launch.
 		this.upTails = ctx.upTails === true
 		this.upTailsSet = false
+		// A 1080i channel: every consumer takes one field of the composed frame.  The library's context option "fused_fields" lets the
+		// fused_v210_combine_multi_<n> launches (fusedWriters, fusedBatch, or posted by name) compose that field only - half the lines.
+		// `fusedFields: true` on the context; off unless asked for.  Nothing is planned differently: the option is set once, in front of the
+		// first launch.
+		this.fusedFields = ctx.fusedFields === true
+		this.fusedFieldsSet = false
 		this.batchOutsSet = false
 		this.fusedBatchSet = false
 		this.clipBatchSet = false
@@ -418,6 +424,7 @@ class Deferral {
 		}
 		if (!this.clipBatchSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'clip_batch', 1); this.clipBatchSet = true }
 		this._upTails()
+		this._fusedFields()
 		let made = jobs.length
 		let failure = null
 		try {
@@ -554,6 +561,7 @@ class Deferral {
 		if (plans[0].fusedOuts && !this.fusedBatchSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'fused_multi_batch', 1); this.fusedBatchSet = true }
 		if (plans[0].outs && !this.batchOutsSet && this.ctx._native.setOption) { this.ctx._native.setOption(this.ctx._ctx, 'chan_batch_outs', 1); this.batchOutsSet = true }
 		this._upTails()
+		this._fusedFields()
 		try {
 			this.ctx._native.runPrograms(this.ctx._ctx, progs, names, values, queue)
 		} catch (e) {
@@ -595,6 +603,7 @@ class Deferral {
 		this.stats.launched++
 		this.launchedOn.set(queue, (this.launchedOn.get(queue) || 0) + 1)
 		this._upTails()
+		this._fusedFields()
 		return this.ctx._native.runProgram(this.ctx._ctx, program._handle, names, values, queue, false)
 	}
 	// upTails: the library's option, once, in front of the context's first launch
@@ -602,6 +611,12 @@ class Deferral {
 		if (!this.upTails || this.upTailsSet || !this.ctx._native.setOption) return
 		this.ctx._native.setOption(this.ctx._ctx, 'up_v210_tails', 1)
 		this.upTailsSet = true
+	}
+	// fusedFields: the library's option, once, in front of the context's first launch
+	_fusedFields() {
+		if (!this.fusedFields || this.fusedFieldsSet || !this.ctx._native.setOption) return
+		this.ctx._native.setOption(this.ctx._ctx, 'fused_fields', 1)
+		this.fusedFieldsSet = true
 	}
 	// a fused launch that may be refused (a shape the kernel does not take): false = nothing was launched
 	_try(program, params, queue) {

@@ -135,12 +135,17 @@ export class clContext {
 	 * launch per channel, in its turn.  The same bytes either way.  Measured through the library, not through node (DESIGN.md 5.1), per call: four 1080p
 	 * channels' yuv422p8 frames 75.5 -> 53.7 us, SDI + the screen 89.7 -> 69.4, eight nv12 channels 149.7 -> 102.5, two channels with three consumers
 	 * 47.5 -> 40.7; two 2160p channels 106.4 -> 103.6 - a win, and the smallest.  No shape lost.
+	 * `fusedFields` (default false; PHANERON_FUSED_FIELDS=1): where every consumer of a `fused_v210_combine_multi_<n>` frame takes the same field
+	 * (a 1080i channel: `interlace` 1 or 3 on every output) only that field's lines are composed - half the reads, combines and table look-ups
+	 * (`fused_v210_field_multi ...` in a trace) - the library's context option `fused_fields`, set once in front of the context's first launch.
+	 * The same bytes either way; nothing is planned differently.  Frames with a layer in a transition, routed frames and consumers of mixed field
+	 * modes are composed whole as before.
 	 * `recycleBuffers` (default true; PHANERON_RECYCLE=0): released frames / images are parked for the next createBuffer of their shape,
 	 * up to `parkMb` MiB (default 4096) or the most that was ever in use at once.  A parked buffer is taken over as the same JS object;
 	 * `strictHandles` (default false; PHANERON_STRICT_HANDLES=1): a fresh object per takeover, so that a reference kept past release()
 	 * is refused ('... released buffer') instead of aliasing the next owner's buffer - for running an application under test. */
 	constructor(params?: { platformIndex?: number; deviceIndex?: number; overlapping?: boolean; profile?: boolean; spinWaitMicros?: number; deferred?: boolean;
-		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; upTransitions?: boolean; fusedTransitions?: boolean; batchOuts?: boolean; clipBatch?: boolean; upTails?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
+		earlyLaunch?: boolean; multiWriter?: boolean; upWriters?: boolean; upTransitions?: boolean; fusedTransitions?: boolean; batchOuts?: boolean; clipBatch?: boolean; upTails?: boolean; imageWriters?: boolean; fusedWriters?: boolean; fusedBatch?: boolean; fusedFields?: boolean; recycleBuffers?: boolean; parkMb?: number; strictHandles?: boolean })
 	readonly queue: { load: number; process: number; unload: number }
 	initialise(): Promise<void>
 	getPlatformInfo(): PlatformInfo

@@ -178,6 +178,10 @@ class clContext {
 		// compositor - the library's "up_v210_tails", set once in front of the first launch (node/defer.js upTails): off unless asked for
 		// (upTails: true, or PHANERON_UP_TAILS=1)
 		this.upTails = params.upTails === undefined ? process.env.PHANERON_UP_TAILS === '1' : !!params.upTails
+		// an interlaced channel's fused_v210_combine_multi_<n> frames - every consumer one and the same field - composed for that field's lines
+		// only: the library's "fused_fields", set once in front of the first launch (node/defer.js fusedFields): off unless asked for
+		// (fusedFields: true, or PHANERON_FUSED_FIELDS=1)
+		this.fusedFields = params.fusedFields === undefined ? process.env.PHANERON_FUSED_FIELDS === '1' : !!params.fusedFields
 		// wire-format writes of one image that are launched as posted - a routed channel's image, a frame whose fused launch was refused, the 10-bit
 		// 4:2:0 consumers - as ONE pack_write_multi_<n> launch (node/defer.js imageWriters): off unless asked for (DESIGN.md 5.1: v210 + rgba8 alone measured slower)
 		this.imageWriters = params.imageWriters === undefined ? process.env.PHANERON_IMAGE_WRITERS === '1' : !!params.imageWriters

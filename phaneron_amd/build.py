@@ -15,8 +15,8 @@ LIB = os.path.join(LIB_DIR, "libphaneron_hip.so")
 VARIANT_DIR = os.path.normpath(os.path.join(HERE, "..", "tools", "_variants"))
 ARCH = "gfx950"
 
-SOURCES = ["ph_kernels.hip", "ph_kernels_lds.hip", "ph_kernels_fused_multi.hip", "ph_kernels_fused_trans.hip", "ph_kernels_fused_route.hip", "ph_kernels_fmt.hip", "ph_kernels_deint.hip", "ph_kernels_chan.hip", "ph_kernels_up.hip", "ph_api.cpp", "ph_run.cpp", "ph_program.cpp", "ph_colour.cpp", "ph_lut.cpp"]
-HEADERS = ["ph_device.h", "ph_formats.h", "ph_internal.h", "ph_kernels.h", "ph_kernels_fused_multi_body.h", "ph_kernels_fused_out.h", "ph_lut.h", "ph_lut_host.h", "ph_ldslut.h", "ph_program.h", "ph_spans.h", "ph_yadif.h", os.path.join("..", "..", "include", "phaneron_hip.h")]
+SOURCES = ["ph_kernels.hip", "ph_kernels_lds.hip", "ph_kernels_fused_multi.hip", "ph_kernels_fused_trans.hip", "ph_kernels_fused_route.hip", "ph_kernels_fused_field.hip", "ph_kernels_fmt.hip", "ph_kernels_deint.hip", "ph_kernels_chan.hip", "ph_kernels_up.hip", "ph_api.cpp", "ph_run.cpp", "ph_program.cpp", "ph_colour.cpp", "ph_lut.cpp"]
+HEADERS = ["ph_device.h", "ph_formats.h", "ph_fused_field.h", "ph_internal.h", "ph_kernels.h", "ph_kernels_fused_multi_body.h", "ph_kernels_fused_out.h", "ph_lut.h", "ph_lut_host.h", "ph_ldslut.h", "ph_program.h", "ph_spans.h", "ph_yadif.h", os.path.join("..", "..", "include", "phaneron_hip.h")]
 # -ffp-contract=off: every fused multiply-add in the kernels is explicit (parity with the
 # reference's OpenCL arithmetic); no fast-math anywhere.
 # -fno-slp-vectorize: the SLP vectoriser pairs independent f32 operations into v_pk_add / v_pk_fma_f32.  On gfx950 a
@@ -32,9 +32,10 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "
 # Flags of one source.  ph_kernels_fused_trans.hip: the shared body's slice loop must be unrolled in full (the tile's packed indices
 # st[p][9] are registers only then), and with a transition layer's code inside it the loop is larger than the size up to which
 # "#pragma unroll" is obeyed - left rolled, st goes to scratch (224 bytes per lane).  ph_kernels_fused_route.hip: the same body with an image
-# layer's code inside the loop.
+# layer's code inside the loop.  ph_kernels_fused_field.hip: the same body with a field quad's place in the frame made inside the loop.
 PER_SOURCE = {"ph_kernels_fused_trans.hip": ["-mllvm", "-pragma-unroll-threshold=100000"],
-              "ph_kernels_fused_route.hip": ["-mllvm", "-pragma-unroll-threshold=100000"]}
+              "ph_kernels_fused_route.hip": ["-mllvm", "-pragma-unroll-threshold=100000"],
+              "ph_kernels_fused_field.hip": ["-mllvm", "-pragma-unroll-threshold=100000"]}
 
 
 def hipcc():

@@ -42,6 +42,7 @@ EXPORTS = [
     "ph_fused_v210_transition_multi",
     "ph_fused_v210_route_multi",
     "ph_debug_image_nt",
+    "ph_debug_fused_field_quad",
     "ph_clip_compose_multi",
     "ph_clip_compose_batch_out",
     "ph_clip_compose_transition_multi",
@@ -263,6 +264,7 @@ def lib():
         "ph_trace_begin": (ci, [ci]),
         "ph_trace_end": (ci, [C.c_char_p, cs]),
         "ph_debug_image_nt": (ci, [vp, cs]),
+        "ph_debug_fused_field_quad": (ci, [cu, cu, ci, cu, C.POINTER(cu), C.POINTER(cu), C.POINTER(cu)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(l, name)  # AttributeError here = the header and the library disagree
@@ -299,6 +301,14 @@ class trace:
     @property
     def kernels(self):
         return self.route.split("+") if self.route else []
+
+
+def debug_fused_field_quad(width, height, interlace, g):
+    """(f, line, col): where the field launches ("fused_fields") put field quad g of a width x height frame - the kernels' own mapping,
+    run on the host (ph_debug_fused_field_quad; needs no device).  Raises PhaneronError where the entry refuses."""
+    f, line, col = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().ph_debug_fused_field_quad(int(width), int(height), int(interlace), int(g), C.byref(f), C.byref(line), C.byref(col)))
+    return f.value, line.value, col.value
 
 
 # ---- host colour maths (pure host code in the library; no device needed) ---------------------

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/phaneron_hip.h"
+#include "ph_fused_field.h"
 #include "ph_internal.h"
 #include "ph_kernels.h"
 #include "ph_lut_host.h"
@@ -935,6 +936,20 @@ int ph_debug_fused_lut_k(const float *host, uint32_t k5[5]) {
 uint32_t ph_debug_fused_job_of(uint32_t wg_per_job, uint32_t block) {
   return wg_per_job ? ph::fused_job_of(block, ph::fused_wg_magic(wg_per_job)) : 0;
 }
+// Field quad g's place in the frame as the field launches' kernels make it (ph_fused_field.h, the function they inline), under the bounds
+// the entries and launchers ask of a frame before those kernels see it
+int ph_debug_fused_field_quad(uint32_t width, uint32_t height, int interlace, uint32_t g, uint32_t *f, uint32_t *line, uint32_t *col) {
+  if (!width || width % 48) return fail(PH_E_INVALID, "ph_debug_fused_field_quad: width %u (the field launches take width %% 48 == 0)", width);
+  if (interlace != 1 && interlace != 3) return fail(PH_E_INVALID, "ph_debug_fused_field_quad: interlace %d (a field: 1 or 3)", interlace);
+  const uint32_t qpl = width / 6;
+  if ((uint64_t)qpl * height * qpl >= (1ull << 32)) return fail(PH_E_INVALID, "ph_debug_fused_field_quad: %u x %u is beyond the kernels' division by reciprocal", width, height);
+  if (g >= qpl * (height / 2u)) return fail(PH_E_INVALID, "ph_debug_fused_field_quad: quad %u is outside the field (%u quads)", g, qpl * (height / 2u));
+  const ph::FieldQuad q = ph::fused_field_quad(g, qpl, (uint32_t)(((1ull << 32) + qpl - 1) / qpl), interlace == 3 ? 1u : 0u);
+  if (f) *f = q.f;
+  if (line) *line = q.line;
+  if (col) *col = q.col;
+  return PH_OK;
+}
 // The store policy (ph_kernels.h image_nt) a launch issued next on the calling thread for `ctx` would be given for an image of `bytes`
 // bytes: the context's "stream_images" / "stream_threshold_mb" as set_device hands them to the launchers.  0 cached, 1 streamed.
 int ph_debug_image_nt(ph_ctx *ctx, size_t bytes) {
@@ -986,6 +1001,10 @@ int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value) {
   if (0 == strcmp(name, "fused_multi_batch")) {
     if (value != 0 && value != 1) return fail(PH_E_INVALID, "fused_multi_batch: 0 (a launch per such job) or 1 (shared launches)");
     return ctx->fused_multi_batch = value, PH_OK;
+  }
+  if (0 == strcmp(name, "fused_fields")) {
+    if (value != 0 && value != 1) return fail(PH_E_INVALID, "fused_fields: 0 (the plain-layer launches compose the whole frame) or 1 (only the field, where every output takes the same one)");
+    return ctx->fused_fields = value, PH_OK;
   }
   if (0 == strcmp(name, "host_pool_mb")) {
     if (value < 0) return fail(PH_E_INVALID, "host_pool_mb: a size in MiB");
@@ -1881,6 +1900,14 @@ int ph_chan_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
   });
 }
 
+// The field (interlace 1 or 3) of which alone ph_fused_v210_combine_multi and its batch compose the lines: every output takes it and the context
+// asks for it (option "fused_fields") - or 0: the whole frame is composed.  (A field of a frame of height h is h / 2 lines: out_lines.)
+static uint32_t fused_field_of(const ph_ctx *ctx, int n_out, const ph_chan_output *outs) {
+  if (!ctx->fused_fields) return 0;
+  for (int k = 0; k < n_out; ++k)
+    if (!outs[k].interlace || outs[k].interlace != outs[0].interlace) return 0;
+  return (uint32_t)outs[0].interlace;
+}
 // What ph_fused_v210_combine_multi and ph_fused_v210_transition_multi refuse about their outputs and geometry - everything but the layers and
 // the context, which each entry sees to itself
 static int fused_multi_outputs_check(const char *fn, int queue, int n_out, const ph_chan_output *outs, uint32_t width, uint32_t height) {
@@ -1896,8 +1923,9 @@ static int fused_multi_outputs_check(const char *fn, int queue, int n_out, const
 // The shared launch's arguments but for the layers - or false: the call does not qualify.  It needs lines of whole 48-pixel blocks, every
 // table in its LDS form (none is with the option "lds_lut" = 0), a frame small enough for the kernel's quad -> line division by reciprocal.
 // order (kMaxFusedOuts entries, or NULL): m.out[i] is outs[order[i]]
+// field (fused_field_of): 0, or the field every output takes - the arguments are then the field launch's: its quads, every composed line every output's
 static bool fused_multi_shared(ph_ctx *ctx, int n_out, const ph_chan_output *outs, uint32_t width, uint32_t height, const void *rd_cm, const void *rd_lut,
-                               const void *rd_gm, ph::FusedMultiArgs &m, int *order = nullptr) {
+                               const void *rd_gm, ph::FusedMultiArgs &m, int *order = nullptr, uint32_t field = 0) {
   const LutRef rref = lds_view(ctx, rd_lut);
   LutRef wref[ph::kMaxFusedOuts];
   bool shared = width % 48 == 0 && rref.get() && (uint64_t)(width / 6) * height * (width / 6) < (1ull << 32);
@@ -1906,7 +1934,7 @@ static bool fused_multi_shared(ph_ctx *ctx, int n_out, const ph_chan_output *out
     shared = wref[k].get() != nullptr;
   }
   if (!shared) return false;
-  m.quads_per_line = width / 6, m.total_quads = m.quads_per_line * height;
+  m.quads_per_line = width / 6, m.total_quads = m.quads_per_line * (field ? height / 2u : height);
   m.rd_cm = (const float *)rd_cm, m.rd_gm = (const float *)rd_gm, m.rd = *rref.get();
   int own[ph::kMaxFusedOuts];
   if (!order) order = own;
@@ -1916,7 +1944,7 @@ static bool fused_multi_shared(ph_ctx *ctx, int n_out, const ph_chan_output *out
     const ph_chan_output &o = outs[order[i]];
     ph::FusedOut &d = m.out[i];
     d.fmt = (uint32_t)o.format;
-    out_lines(o, /*same_lines*/ false, height, d);  // the whole frame is composed: a field output takes the lines of its parity
+    out_lines(o, /*same_lines*/ field != 0, height, d);  // the whole frame is composed: a field output takes the lines of its parity - or only the field all take
     d.wr_cm = (const float *)(o.wr_col_matrix12 ? o.wr_col_matrix12 : rd_cm);
     d.plane[0] = o.planes[0], d.plane[1] = o.planes[1], d.plane[2] = o.planes[2];
     d.wr = *wref[order[i]].get();
@@ -1939,8 +1967,10 @@ int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const
   // one v210 frame: the headline kernel itself, same route
   if (n_out == 1 && outs[0].format == PH_FMT_V210 && outs[0].interlace == 0)
     return ph_fused_v210_combine(ctx, queue, n, layers, outs[0].planes[0], width, height, rd_cm, rd_lut, rd_gm, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
-  ph::FusedMultiArgs m{};
-  if (!fused_multi_shared(ctx, n_out, outs, width, height, rd_cm, rd_lut, rd_gm, m)) {
+  const uint32_t field = fused_field_of(ctx, n_out, outs);
+  ph::FusedFieldArgs fa{};  // (the whole-frame launch takes its m alone)
+  ph::FusedMultiArgs &m = fa.m;
+  if (!fused_multi_shared(ctx, n_out, outs, width, height, rd_cm, rd_lut, rd_gm, m, nullptr, field)) {
     ph_chan_layer cl[ph::kMaxLayers];
     memset(cl, 0, sizeof cl);
     for (int i = 0; i < n; ++i) {
@@ -1949,11 +1979,14 @@ int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const
     }
     return ph_chan_compose_multi(ctx, queue, n, cl, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
   }
-  if (!height) return PH_OK;
+  if (!m.total_quads) return PH_OK;  // height 0 - or a field of a frame of one line
   for (int i = 0; i < n; ++i) m.layers[i] = layers[i];
   const int rc = set_device(ctx);
   if (rc) return rc;
-  const hipError_t e = ph::launch_fused_v210_combine_multi(stream_of(ctx, queue), n, m, (uint32_t)ctx->props.multiProcessorCount, (uint32_t)ctx->fused_multi_wgs);
+  fa.first_line = field == 3 ? 1u : 0u;
+  const uint32_t cus = (uint32_t)ctx->props.multiProcessorCount, cap = (uint32_t)ctx->fused_multi_wgs;
+  const hipError_t e = field ? ph::launch_fused_v210_field_multi(stream_of(ctx, queue), n, fa, field, cus, cap)
+                             : ph::launch_fused_v210_combine_multi(stream_of(ctx, queue), n, m, cus, cap);
   if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   return PH_OK;
 }
@@ -2109,14 +2142,16 @@ int ph_fused_v210_combine_multi_batch(ph_ctx *ctx, int queue, int jobs, int n, c
     return ph_fused_v210_combine_batch(ctx, queue, jobs, n, layers, frames, width, height, rd_cm, rd_lut, rd_gm, outs[0].wr_col_matrix12, outs[0].wr_gamma_lut);
   }
   // the shared launch: what ph_fused_v210_combine_multi's own asks for, with its arguments (every job's output list is job 0's: one order for all)
-  ph::FusedMultiBatchArgs b{};
+  const uint32_t field = fused_field_of(ctx, n_out, outs);
+  ph::FusedFieldBatchArgs fb{};  // (the whole-frame launch takes its b alone)
+  ph::FusedMultiBatchArgs &b = fb.b;
   int order[ph::kMaxFusedOuts];
-  if (!fused_multi_shared(ctx, n_out, outs, width, height, rd_cm, rd_lut, rd_gm, b.m, order)) {
+  if (!fused_multi_shared(ctx, n_out, outs, width, height, rd_cm, rd_lut, rd_gm, b.m, order, field)) {
     for (int j = 0; j < jobs; ++j)
       if (const int rc = ph_fused_v210_combine_multi(ctx, queue, n, layers + (size_t)j * n, n_out, outs + (size_t)j * n_out, width, height, rd_cm, rd_lut, rd_gm)) return rc;
     return PH_OK;
   }
-  if (!height) return PH_OK;
+  if (!b.m.total_quads) return PH_OK;  // height 0 - or a field of a frame of one line
   for (int j = 0; j < jobs; ++j) {  // (b.m.out[i].plane, job 0's, is not read: each job's planes are b.plane's)
     for (int i = 0; i < n; ++i) b.layers[j][i] = layers[(size_t)j * n + i];
     for (int i = 0; i < n_out; ++i)
@@ -2124,7 +2159,10 @@ int ph_fused_v210_combine_multi_batch(ph_ctx *ctx, int queue, int jobs, int n, c
   }
   const int rc = set_device(ctx);
   if (rc) return rc;
-  const hipError_t e = ph::launch_fused_v210_combine_multi_batch(stream_of(ctx, queue), n, (uint32_t)jobs, b, (uint32_t)ctx->props.multiProcessorCount, (uint32_t)ctx->fused_multi_wgs);
+  fb.first_line = field == 3 ? 1u : 0u;
+  const uint32_t cus = (uint32_t)ctx->props.multiProcessorCount, cap = (uint32_t)ctx->fused_multi_wgs;
+  const hipError_t e = field ? ph::launch_fused_v210_field_multi_batch(stream_of(ctx, queue), n, (uint32_t)jobs, fb, field, cus, cap)
+                             : ph::launch_fused_v210_combine_multi_batch(stream_of(ctx, queue), n, (uint32_t)jobs, b, cus, cap);
   if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
   return PH_OK;
 }

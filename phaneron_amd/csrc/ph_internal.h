@@ -79,6 +79,9 @@ struct ph_ctx {
   int fused_multi_wgs = 0;
   // option "fused_multi_batch" (default 0): ph_run_programs puts consecutive fused_v210_combine_multi_<n> jobs into shared launches (ph_fused_v210_combine_multi_batch)
   int fused_multi_batch = 0;
+  // option "fused_fields" (default 0): ph_fused_v210_combine_multi and ph_fused_v210_combine_multi_batch compose only the field when every output
+  // takes the same one (launch_fused_v210_field_multi / _batch); 0: the whole frame, a field output taking the lines of its parity
+  int fused_fields = 0;
   std::atomic<int> fail_launches{0};  // option "fail_launches" (a TEST hook): > 0 every launch through ph_run_program(s) fails; -k: the next k go through, then every one fails
   int host_pool_mb = 4096;
   size_t host_live_bytes = 0, host_peak_bytes = 0;  // mirrors attached to buffers now / at most

@@ -107,7 +107,8 @@ FusedLdsArgs fused_lds_args(const FusedArgs &f, const LutView &rd, const LutView
 // Several consumers' frames of ONE plain-layer composite in one launch (ph_fused_v210_combine_multi; ph_kernels_fused_multi.hip): the
 // headline kernel's phase 1, then the writer's phase once per distinct writer table - the quad's 18 table reads made once, every
 // output of that table packing them with its own writer matrix.  width % 48 == 0 only: a line is quads_per_line whole quads, a planar
-// pitch is the width.  The whole frame is composed; a field output stores the quads whose line has its parity.
+// pitch is the width.  The whole frame is composed; a field output stores the quads whose line has its parity (the field alone:
+// launch_fused_v210_field_multi below).
 // The launcher expects the outputs grouped by writer table.
 constexpr int kMaxFusedOuts = 4;
 struct FusedOut {
@@ -171,6 +172,23 @@ struct FusedRouteArgs {
 };
 // named "fused_v210_route_multi x<outputs>i<0|1>" (i1: the image is written); workgroups as launch_fused_v210_combine_multi
 hipError_t launch_fused_v210_route_multi(hipStream_t s, int n, const FusedRouteArgs &a, uint32_t num_cus, uint32_t max_wgs);
+// The single frame's and the batched launch for outputs that all take the SAME FIELD (context option "fused_fields";
+// ph_kernels_fused_field.hip): only that field's lines are composed - first_line, first_line + 2, ... - and the workgroups' ranges,
+// tiles and tails are counted in field quads (ph_fused_field.h).  m / b: as the whole-frame launchers take them, but total_quads is the
+// FIELD's (quads_per_line * (height / 2)) and every output's takes is 0; their kernarg layout is the existing kernels', so the first
+// line stands behind them.  interlace: the outputs' (1 or 3), for the trace name.
+struct FusedFieldArgs {
+  FusedMultiArgs m;
+  uint32_t first_line;  // 0 (interlace 1) or 1 (interlace 3)
+};
+struct FusedFieldBatchArgs {
+  FusedMultiBatchArgs b;
+  uint32_t first_line;
+};
+// named "fused_v210_field_multi x<outputs>f<interlace>"; workgroups as launch_fused_v210_combine_multi, never more than the field's slices
+hipError_t launch_fused_v210_field_multi(hipStream_t s, int n, const FusedFieldArgs &a, uint32_t interlace, uint32_t num_cus, uint32_t max_wgs);
+// named "fused_v210_field_multi x<outputs>j<jobs>f<interlace>"; workgroups as launch_fused_v210_combine_multi_batch, of the field's slices
+hipError_t launch_fused_v210_field_multi_batch(hipStream_t s, int n, uint32_t jobs, const FusedFieldBatchArgs &a, uint32_t interlace, uint32_t num_cus, uint32_t max_wgs);
 
 struct ComposeArgs {
   const void *layers[kMaxLayers];

@@ -12,6 +12,10 @@
 // layers that may be f32 RGBA images - such a layer leaves the plain path for fm_route_image_layer - and the combined image as an output
 // (karg->image_out, stored at the end of phase 1).  There the combine is ph_combine's to the bit: the bottom layer is assigned, and with
 // IMG the six alphas are carried.  n_out may be 0: no phase 2.
+// PH_FM_FIELD 1 (ph_kernels_fused_field.hip; `a`: FusedFieldArgs::m or FusedFieldBatchArgs::b.m - both begin with the whole-frame kernel's
+// arguments, which is what the kernarg pointers below are cast to; first_line: the kernel's own): the outputs all take the same field and
+// only its lines are composed.  a.total_quads, the ranges, the tiles, the wave skipping and the tail lanes are the field's; a field quad's
+// place in the frame (ph_fused_field.h) is made where a slice loads (quad_of) and where it stores (phase 2).
 #if PH_FM_ROUTE
   constexpr int P = PH_FM_ROUTE_P, BS = kLdsBlock;
 #else
@@ -63,10 +67,21 @@
     // registers through it for a next tile that a frame-sized share does not have)
     uint32_t last_quad = wg_end - 1;
     asm volatile("" : "+s"(last_quad));
+#if PH_FM_FIELD
+    // the range, the tile and the tail are the FIELD's; what a slice loads at is that quad's place in the frame, made where the slice
+    // asks for it from a pinned copy of the lane (left alone, all six slices' are made in front of the loop and kept through it)
+    auto quad_of = [&](int p) {
+      uint32_t lane = threadIdx.x;
+      asm volatile("" : "+v"(lane));
+      const uint32_t g = tile_begin + p * BS + lane;
+      return fused_field_quad(g < wg_end ? g : last_quad, a.quads_per_line, a.magic_qpl, first_line).f;
+    };
+#else
     auto quad_of = [&](int p) {
       const uint32_t f = tile_begin + p * BS + threadIdx.x;  // width % 48 == 0: flat index == offset
       return f < wg_end ? f : last_quad;                      // tail lanes recompute the last quad
     };
+#endif
     // one-deep prefetch through layers and slices; the very first word is requested before the table load
 #if PH_FM_ROUTE
     // (an image layer's slot in the chain stays empty: its v210 word is not loaded, its texels are fm_route_image_layer's)
@@ -197,6 +212,17 @@
             // two pixels' twelve LDS reads in flight at a time: all thirty-six at once would want registers this kernel does not have
             if (i % 3 == 2) __builtin_amdgcn_sched_barrier(0);
           }
+#if PH_FM_FIELD
+          if (f < wg_end) {  // (f: the FIELD quad; the outputs' takes are 0 - every line composed is theirs)
+            const FieldQuad at = fused_field_quad(f, a.quads_per_line, a.magic_qpl, first_line);
+#pragma unroll 1
+#if PH_FM_BATCH
+            for (uint32_t k = k0; k < k1; ++k) fused_out_store(outs[k], karg->plane[blockIdx.y][k], g, at.f, at.line, at.col);
+#else
+            for (uint32_t k = k0; k < k1; ++k) fused_out_store(outs[k], outs[k].plane, g, at.f, at.line, at.col);
+#endif
+          }
+#else
           if (f < wg_end) {
             uint32_t line = 0, col = 0;
             if (a.need_line) {  // uniform: some output is a field or 4:2:0
@@ -210,6 +236,7 @@
             for (uint32_t k = k0; k < k1; ++k) fused_out_store(outs[k], outs[k].plane, g, f, line, col);
 #endif
           }
+#endif
         }
       }
       k0 = k1;
