@@ -895,6 +895,7 @@ int ph_lut_register(ph_ctx *ctx, const void *dev, const float *host) {
     PH_HIP(hipMalloc(&e.blob_dev, blob_bytes));
     PH_HIP(hipMemcpy(e.blob_dev, blob.data(), blob_bytes, hipMemcpyHostToDevice));
     e.view = ph::lut_view(info, e.blob_dev);
+    e.max_finite = ph::lut_max_finite(host);
   }
   {
     std::lock_guard<std::mutex> lock(ctx->mu);
@@ -931,6 +932,16 @@ int ph_debug_fused_lut_k(const float *host, uint32_t k5[5]) {
   const ph::FusedLutK k = ph::fused_lut_k(ph::lut_view(info, nullptr));
   memcpy(k5, &k, 5 * sizeof(uint32_t));
   return (int)info.bytes;
+}
+// The fused kernel's witness guard as a launch gets it, device-free (tests/test_fused_witness_cpu.py): lmax = what ph_lut_register
+// keeps of the reader table and fused_lds_args passes on, holds = the kernel's own expression (ph_kernels.h fused_witness_holds)
+// of lmax and the nine gamut coefficients.
+int ph_debug_fused_witness(const float *host, const float *gm9, float *lmax, int *holds) {
+  if (!host || !gm9 || !lmax || !holds) return fail(PH_E_INVALID, "ph_debug_fused_witness: NULL argument");
+  const ph::FusedLdsArgs a = ph::fused_lds_args(ph::FusedArgs{}, ph::LutView{}, ph::LutView{}, ph::lut_max_finite(host));
+  *lmax = a.rd_lmax;
+  *holds = ph::fused_witness_holds(a.rd_lmax, gm9) ? 1 : 0;
+  return PH_OK;
 }
 // block / wg_per_job as the kernel takes it: the high word of (2 * block + 1) * magic
 uint32_t ph_debug_fused_job_of(uint32_t wg_per_job, uint32_t block) {
@@ -1035,6 +1046,7 @@ int ph_ctx_set_option(ph_ctx *ctx, const char *name, int value) {
 struct LutRef {
   ph::LutView view{};
   bool found = false;
+  float max_finite = __builtin_inff();  // (LutEntry's)
   const ph::LutView *get() const { return found ? &view : nullptr; }
 };
 static LutRef lds_view(ph_ctx *ctx, const void *dev) {
@@ -1043,7 +1055,7 @@ static LutRef lds_view(ph_ctx *ctx, const void *dev) {
   std::lock_guard<std::mutex> lock(ctx->mu);
   auto it = ctx->luts.find(dev);
   if (it == ctx->luts.end() || !it->second.view.bytes) return r;
-  r.view = it->second.view, r.found = true;
+  r.view = it->second.view, r.max_finite = it->second.max_finite, r.found = true;
   return r;
 }
 
@@ -1160,7 +1172,7 @@ int ph_fused_v210_combine(ph_ctx *ctx, int queue, int n, const void *const *laye
     const LutRef rref = lds_view(ctx, rd_lut), wref = lds_view(ctx, wr_lut);
     const ph::LutView *rv = rref.get(), *wv = wref.get();
     if (rv && wv) {
-      const ph::FusedLdsArgs la = ph::fused_lds_args(a, *rv, *wv);
+      const ph::FusedLdsArgs la = ph::fused_lds_args(a, *rv, *wv, rref.max_finite);
       PH_LAUNCH(ph::launch_fused_v210_combine_lds(stream_of(ctx, queue), n, la, (uint32_t)ctx->props.multiProcessorCount));
     }
   }
@@ -1205,7 +1217,7 @@ int ph_fused_v210_combine_batch(ph_ctx *ctx, int queue, int jobs, int n, const v
   f.total_quads = f.quads_per_line_used * height;
   f.rd_cm = (const float *)rd_cm, f.rd_lut = (const float *)rd_lut, f.rd_gm = (const float *)rd_gm;
   f.wr_cm = (const float *)wr_cm, f.wr_lut = (const float *)wr_lut;
-  ph::FusedLdsArgs la = ph::fused_lds_args(f, *rv, *wv);
+  ph::FusedLdsArgs la = ph::fused_lds_args(f, *rv, *wv, rref.max_finite);
   la.jobs = (uint32_t)jobs;
   for (int j = 1; j < jobs; ++j) {
     for (int l = 0; l < n; ++l) la.more_layers[j - 1][l] = layers[(size_t)j * n + l];

@@ -32,6 +32,7 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 struct LutEntry {
   ph::LutView view{};  // bytes == 0: a plain table
   void *blob_dev = nullptr;
+  float max_finite = __builtin_inff();  // ph::lut_max_finite of the host copy (Inf: not known, the fused kernel's witness guard fails)
 };
 
 // Lifetime: buffers, programs, events and graphs each hold a reference on their context, so the storage a

@@ -86,6 +86,9 @@ struct alignas(64) FusedLdsArgs {
   uint32_t quads_per_line_pitch;    // pitch bytes / 16
   // widths that are not a multiple of 48 (the TAIL instantiation only): see FusedArgs
   uint32_t tail_px, magic_qpp;
+  // max |entry| over the reader table's finite entries (ph_lut_host.h lut_max_finite; the registry keeps it): what the kernel's
+  // witness guard starts from (fused_witness_holds below).  Asked for behind the table DMA, like the colour coefficients.
+  float rd_lmax;
   const void *more_layers[kMaxBatch - 1][kMaxLayers];
   void *more_out[kMaxBatch - 1];
 };
@@ -101,8 +104,24 @@ static_assert(offsetof(FusedLdsArgs, rd_k) == 128 && offsetof(FusedLdsArgs, wr_k
               offsetof(FusedLdsArgs, quads_per_line_used) == 188 && offsetof(FusedLdsArgs, quads_per_line_pitch) == kFusedHeadBytes,
               "line 2 of the fused kernel's head");
 static_assert(offsetof(FusedLdsArgs, more_layers) >= kFusedHeadBytes, "the batch arrays lie behind the head");
-// the arguments of one frame (or of job 0 and what all jobs share) from the plain kernel's and the two tables
-FusedLdsArgs fused_lds_args(const FusedArgs &f, const LutView &rd, const LutView &wr);  // ph_kernels_lds.hip
+// The fused kernel's witness guard (ph_kernels_lds.hip fused_layer_combine), uniform per launch: with every finite table entry
+// at most lmax in magnitude, no product and no partial sum of a gamut row gm[3i .. 3i+2] . (r, g, b) of finite r, g, b exceeds
+// lmax * (|g0| + |g1| + |g2|), so below 2^126 (a factor four under the largest float, for the roundings of the sums) nothing
+// overflows and a lower layer's value is non-finite exactly where one of its three table entries is.  Every comparison is false
+// for a NaN, and an Inf in gm makes a product Inf or (lmax = 0) NaN: any of them fails the guard.
+static inline __host__ __device__ bool fused_witness_holds(float lmax, const float *gm) {
+  const float bound = 8.5070591730234616e37f, half = 4.2535295865117308e37f;  // 2^126, 2^125
+  bool ok = lmax < half;
+  for (int i = 0; i < 3; ++i) {
+    const float row = (__builtin_fabsf(gm[3 * i]) + __builtin_fabsf(gm[3 * i + 1])) + __builtin_fabsf(gm[3 * i + 2]);
+    ok = ok & (lmax * row < bound);
+  }
+  return ok;
+}
+static_assert(offsetof(FusedLdsArgs, rd_lmax) == 204 && offsetof(FusedLdsArgs, more_layers) == 208, "rd_lmax fills a gap behind the head: no other field moves");
+// the arguments of one frame (or of job 0 and what all jobs share) from the plain kernel's and the two tables; rd_lmax: the
+// reader table's lut_max_finite
+FusedLdsArgs fused_lds_args(const FusedArgs &f, const LutView &rd, const LutView &wr, float rd_lmax);  // ph_kernels_lds.hip
 
 // Several consumers' frames of ONE plain-layer composite in one launch (ph_fused_v210_combine_multi; ph_kernels_fused_multi.hip): the
 // headline kernel's phase 1, then the writer's phase once per distinct writer table - the quad's 18 table reads made once, every

@@ -166,19 +166,26 @@ __device__ __forceinline__ FusedHead fused_head_load() {
   return h;
 }
 
-// One layer of one quad in phase 1 of the shipped fused kernel: decode the word, reader table, gamut, and the combine into the
-// quad's eighteen accumulators (combine.ts:45-65).  The layer's place in the stack is a compile-time property, so that neither
-// end of the stack pays for what only the middle needs:
-//  - the FIRST layer has nothing below it: acc = t, no zero to start from and no fma.  That is fma(0, kk, t) for every t, Inf
-//    and NaN included, except that t = -0 stays -0 where the fma gives +0 - and the sign of a zero can never reach the packed
-//    output: the clamp and x 65535 + M behind the last layer map both zeros to index 0;
-//  - a MIDDLE layer is acc = fma(acc, kk, t), written as the three-operand v_fma_f32 with acc as destination.  Left to itself
-//    LLVM picks v_fmac (d = a*b + d, so the result lands in t's register) and pays for it with a v_mov per accumulator per
-//    layer to get the loop-carried value back;
-//  - the LAST layer is the same instruction with the clamp modifier: the writer's clamp to [0, 1] (v210.ts:148-150) rides on
-//    it for nothing, where a v_max_f32 ... clamp per accumulator used to follow the loop.  Only here: on a lower layer the
-//    clamp would turn an Inf or NaN of the stack below into a number, and the layers above would hide that it was ever there.
-// A one-layer stack is first and last at once: its clamp goes on the value itself.
+// One layer of one quad in phase 1 of the shipped fused kernel: decode the word, reader table, and what the layer's place in
+// the stack asks for (combine.ts:45-65) - a compile-time property.
+// A v210 reader emits alpha = 1, so the combine's factor kk = 1 - alpha is the constant 0 and every combine is
+// acc = fma(acc, 0, t): t exactly where acc is finite (the sign of a zero can never reach the packed output: the clamp and
+// x 65535 + M behind the last layer map both zeros to index 0), NaN where acc is +-Inf or NaN.  A layer below the top therefore
+// reaches the picture through one bit per pixel - whether any of its values is non-finite - and that bit is all it keeps, in a
+// WITNESS register per pixel that is NaN if so and +-0 if not:
+//  - the FIRST layer: W = r * 0, W = fma(g, 0, W), W = fma(b, 0, W) of the pixel's three table entries r, g, b;
+//  - a MIDDLE layer: the same three fma onto the W it finds (NaN stays NaN), no gamut matrix and no accumulators;
+//  - the LAST layer: gamut matrix, then acc = fma(W, 0, t) with the clamp modifier - the instruction the combine always was,
+//    with W in place of the accumulator below.  The writer's clamp to [0, 1] (v210.ts:148-150) rides on it for nothing.  Only
+//    here: on a lower layer the clamp would turn a NaN of the stack below into a number.
+// Why W stands for the accumulator: t = gm . (r, g, b).  If one of r, g, b is non-finite, so are all three channels of t for a
+// finite gm (Inf * c is +-Inf, or NaN for c = 0; a sum with NaN is NaN; Inf - Inf is NaN), and the accumulators above it are NaN
+// in all three from the next combine on.  If all three are finite and nothing overflows on the way, t is finite.  "Nothing
+// overflows" and "gm is finite" are the caller's to check, once per launch (ph_kernels.h fused_witness_holds); where they do not
+// hold the kernel runs the rolled phase1_slice below, which keeps the eighteen accumulators through every layer.
+// The witness statements are asm volatile like the combine: the compiler can neither fold x * 0 nor move a pixel's lookups
+// across them, so the lookups stay one pixel deep (all eighteen at once run a lane out of registers).
+// A one-layer stack is first and last at once: no combine, its clamp goes on the value itself.
 constexpr int kLayerFirst = 1, kLayerLast = 2;
 // f(0) ... f(COUNT - 1) with the index a compile-time constant: straight-line code whatever its size
 template <int... I, typename F>
@@ -190,33 +197,33 @@ __device__ __forceinline__ void static_for(F &&f) {
   static_for_each(std::make_integer_sequence<int, COUNT>{}, f);
 }
 template <int PLACE, bool STD>
-__device__ __forceinline__ void fused_layer_combine(float (&acc)[18], const uint4 w, const ReadK &rk, const LutK &rlut, float last) {
+__device__ __forceinline__ void fused_layer_combine(float (&acc)[18], float (&wit)[6], const uint4 w, const ReadK &rk, const LutK &rlut, float last) {
   // A layer is scheduled on its own, as an iteration of the rolled loop was: nothing of the next layer's decode moves up into
-  // this one's.  Within the layer the asm statements (the first layer has an empty one per pixel) keep the pixels in order;
+  // this one's.  Within the layer the asm statements (a one-layer stack has an empty one per pixel) keep the pixels in order;
   // without that order the eighteen lookups of a quad are all started at once and a lane runs out of registers (spills).
   __builtin_amdgcn_sched_barrier(0);
   const Yuv6 q = unpack_quad(w);
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
-    const float4 t = read_px_lds<STD>(q.y[j], q.cb[j >> 1], q.cr[j >> 1], rk, rlut, last);
-    if (PLACE & kLayerFirst) {
-      acc[3 * j] = t.x, acc[3 * j + 1] = t.y, acc[3 * j + 2] = t.z;
-      if (PLACE & kLayerLast) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[3 * j + c] = __builtin_fminf(__builtin_fmaxf(acc[3 * j + c], 0.0f), 1.0f);
-      }
-      // (no instruction: the place in the pixel order that the combine's asm statement holds in the other layers)
+    if constexpr (PLACE == (kLayerFirst | kLayerLast)) {
+      const float4 t = read_px_lds<STD>(q.y[j], q.cb[j >> 1], q.cr[j >> 1], rk, rlut, last);
+      acc[3 * j] = __builtin_fminf(__builtin_fmaxf(t.x, 0.0f), 1.0f);
+      acc[3 * j + 1] = __builtin_fminf(__builtin_fmaxf(t.y, 0.0f), 1.0f);
+      acc[3 * j + 2] = __builtin_fminf(__builtin_fmaxf(t.z, 0.0f), 1.0f);
+      // (no instruction: the place in the pixel order that the asm statements hold in the other layers)
       asm volatile("" : "+v"(acc[3 * j]), "+v"(acc[3 * j + 1]), "+v"(acc[3 * j + 2]));
+    } else if constexpr (PLACE == kLayerLast) {
+      const float4 t = read_px_lds<STD>(q.y[j], q.cb[j >> 1], q.cr[j >> 1], rk, rlut, last);
+      // (one statement per channel: an output may then take the register of the t it replaces)
+      asm volatile("v_fma_f32 %0, %1, 0, %2 clamp" : "=v"(acc[3 * j]) : "v"(wit[j]), "v"(t.x));
+      asm volatile("v_fma_f32 %0, %1, 0, %2 clamp" : "=v"(acc[3 * j + 1]) : "v"(wit[j]), "v"(t.y));
+      asm volatile("v_fma_f32 %0, %1, 0, %2 clamp" : "=v"(acc[3 * j + 2]) : "v"(wit[j]), "v"(t.z));
     } else {
-      const float kk = 1.0f - t.w;
-      if (PLACE & kLayerLast)
-        asm volatile("v_fma_f32 %0, %0, %3, %4 clamp\n\tv_fma_f32 %1, %1, %3, %5 clamp\n\tv_fma_f32 %2, %2, %3, %6 clamp"
-                     : "+v"(acc[3 * j]), "+v"(acc[3 * j + 1]), "+v"(acc[3 * j + 2])
-                     : "v"(kk), "v"(t.x), "v"(t.y), "v"(t.z));
+      const Rgb1 e = read_px_lds_rgb<STD>(q.y[j], q.cb[j >> 1], q.cr[j >> 1], rk, rlut, last);
+      if constexpr (PLACE == kLayerFirst)
+        asm volatile("v_mul_f32 %0, 0, %1\n\tv_fma_f32 %0, %2, 0, %0\n\tv_fma_f32 %0, %3, 0, %0" : "=&v"(wit[j]) : "v"(e.r), "v"(e.g), "v"(e.b));
       else
-        asm volatile("v_fma_f32 %0, %0, %3, %4\n\tv_fma_f32 %1, %1, %3, %5\n\tv_fma_f32 %2, %2, %3, %6"
-                     : "+v"(acc[3 * j]), "+v"(acc[3 * j + 1]), "+v"(acc[3 * j + 2])
-                     : "v"(kk), "v"(t.x), "v"(t.y), "v"(t.z));
+        asm volatile("v_fma_f32 %0, %1, 0, %0\n\tv_fma_f32 %0, %2, 0, %0\n\tv_fma_f32 %0, %3, 0, %0" : "+v"(wit[j]) : "v"(e.r), "v"(e.g), "v"(e.b));
     }
   }
 }
@@ -315,6 +322,14 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
   const uint32_t wr_bytes = head.word(offsetof(FusedLdsArgs, wr_bytes)), wr_hole = head.word(offsetof(FusedLdsArgs, wr_hole));
   uint4 *const out_ptr = reinterpret_cast<uint4 *>(job ? a.more_out[job - 1] : a.out);
   const bool std_matrix = ycbcr_matrix_is_standard(rk);  // uniform
+  // The witness guard (ph_kernels.h fused_witness_holds), uniform: the layers below the last may carry a witness only where no
+  // finite table entry can overflow on its way through the gamut matrix.  The table's bound lies behind the head and is one
+  // more scalar load under the DMA.
+  bool witness = false;
+  if (kSplitLayers && N > 1) {
+    const float rd_lmax = ((const_f32_ptr)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(FusedLdsArgs, rd_lmax) / 4];
+    witness = fused_witness_holds(rd_lmax, rk.gm);
+  }
   for (uint32_t tile_begin = wg_begin; tile_begin < wg_end; tile_begin += tile_quads) {
     uint32_t st[P][9];
     auto quad_of = [&](int p) { return quad_at(tile_begin, p); };
@@ -331,7 +346,8 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
       const uint32_t g = f - __umulhi(f, a.magic_qpp) * a.quads_per_line_pitch;
       return g < a.quads_per_line_used ? 0u : (g == a.quads_per_line_used && a.tail_px) ? 1u : 2u;
     };
-    auto phase1_slice = [&](auto tag, uint4 w, uint32_t f, uint32_t f_next, bool more, uint32_t(&st)[9]) -> uint4 {
+    // (inlined by order, like the split form below: the shipped kernel has it twelve times, as what runs where the witness guard fails)
+    auto phase1_slice = [&](auto tag, uint4 w, uint32_t f, uint32_t f_next, bool more, uint32_t(&st)[9]) __attribute__((always_inline)) -> uint4 {
       const bool in_tail = TAIL && slot_kind(f) == 1u;
       const float last = TAIL ? (in_tail ? 0.0f : 1.0f) : 1.0f;
       float acc[18];
@@ -373,7 +389,9 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
       return w;
     };
     // The same slice in the shipped form (PIPE off, MODE 0), with the layer loop split by a layer's place in the stack
-    // (fused_layer_combine): first, middle, last.  The prefetch chain is the one above - while a layer is decoded the word
+    // (fused_layer_combine): first, middle, last - the layers below the last carry a witness per pixel, not accumulators, which
+    // takes the launch's witness guard (`witness` below; the rolled slice above runs where it fails, and in every other form of
+    // the kernel).  The prefetch chain is the one above - while a layer is decoded the word
     // behind it is in flight - but the words are named, not copied: straight-line code for up to two middle layers, and a loop
     // of PAIRS beyond that (N > 4) in which the two word registers take turns, so no `w = nxt` is left in it.  One copy
     // remains per slice: the `nxt = w` in front of the last layer, for a wave's last slice, where nothing is prefetched (four
@@ -383,10 +401,10 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
       constexpr int MID = N > 2 ? N - 2 : 0;  // layers 1 .. N-2
       const bool in_tail = TAIL && slot_kind(f) == 1u;
       const float last = TAIL ? (in_tail ? 0.0f : 1.0f) : 1.0f;
-      float acc[18];
+      float acc[18], wit[6];  // (the accumulators: written by the last layer only; the witnesses: six registers below it)
       constexpr bool STD = decltype(tag)::value;
       auto combine = [&](auto place, const uint4 word) __attribute__((always_inline)) {
-        fused_layer_combine<decltype(place)::value, STD>(acc, word, rk, rlut, last);
+        fused_layer_combine<decltype(place)::value, STD>(acc, wit, word, rk, rlut, last);
       };
       constexpr std::integral_constant<int, N == 1 ? (kLayerFirst | kLayerLast) : kLayerFirst> first_layer{};
       constexpr std::integral_constant<int, 0> middle_layer{};
@@ -574,8 +592,14 @@ __global__ __launch_bounds__(BS) void fused_v210_combine_lds_kernel(FusedLdsArgs
           PH_BALANCE(p);
           const bool more = (p + 1 < P) && ((p + 1) * BS + wave_first < wg_end - tile_begin);  // uniform per wave
           const uint32_t f_next = more ? quad_of(p + 1) : f;
-          if (std_matrix) w = phase1_slice_split(std::true_type{}, w, f, f_next, more, st[p]);
-          else w = phase1_slice_split(std::false_type{}, w, f, f_next, more, st[p]);
+          // (both choices per slice: made per tile or per layer the copies' registers do not come apart, and the kernel spills)
+          if (N == 1 || witness) {
+            if (std_matrix) w = phase1_slice_split(std::true_type{}, w, f, f_next, more, st[p]);
+            else w = phase1_slice_split(std::false_type{}, w, f, f_next, more, st[p]);
+          } else {
+            if (std_matrix) w = phase1_slice(std::true_type{}, w, f, f_next, more, st[p]);
+            else w = phase1_slice(std::false_type{}, w, f, f_next, more, st[p]);
+          }
         }
       });
     } else if (MODE != 2) {
@@ -1246,8 +1270,9 @@ FusedLutK fused_lut_k(const LutView &v) {
   return k;
 }
 
-FusedLdsArgs fused_lds_args(const FusedArgs &f, const LutView &rd, const LutView &wr) {
+FusedLdsArgs fused_lds_args(const FusedArgs &f, const LutView &rd, const LutView &wr, float rd_lmax) {
   FusedLdsArgs a{};
+  a.rd_lmax = rd_lmax;
   a.rd_blob = rd.blob, a.rd_bytes = rd.bytes, a.rd_hole = rd.hole;
   a.wr_blob = wr.blob, a.wr_bytes = wr.bytes, a.wr_hole = wr.hole;
   a.rd_k = fused_lut_k(rd), a.wr_k = fused_lut_k(wr);

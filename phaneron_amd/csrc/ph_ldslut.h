@@ -236,6 +236,27 @@ __device__ __forceinline__ bool ycbcr_matrix_is_standard(const ReadK &k) {
 // `last`: the fourth component of the reference's (Y, Cb, Cr, 1) vector.  It is 1 everywhere except in the tail of a line whose
 // width is not a multiple of 6, where the reference's reader builds its vectors with a 0 there (v210.ts:88-93) and so drops the
 // matrix's offset column; callers that serve such widths pass 0.0f / 1.0f per lane, everybody else the constant.
+// The reader up to and including its three table lookups: what read_px_lds hands to the gamut matrix.
+struct Rgb1 {
+  float r, g, b;
+};
+template <bool STD = false>
+__device__ __forceinline__ Rgb1 read_px_lds_rgb(float y, float cb, float cr, const ReadK &k, const LutK &lut, float last = 1.0f) {
+  float tr, tg, tb;
+  if (STD) {
+    const float ym = y * k.r.x;
+    tr = fma_rn(last, k.r.w, fma_rn(cr, k.r.z, ym));
+    tg = fma_rn(last, k.g.w, fma_rn(cr, k.g.z, fma_rn(cb, k.g.y, ym)));
+    tb = fma_rn(last, k.b.w, fma_rn(cb, k.b.y, ym));
+  } else {
+    tr = dot4(y, cb, cr, last, k.r), tg = dot4(y, cb, cr, last, k.g), tb = dot4(y, cb, cr, last, k.b);
+  }
+  Rgb1 o;
+  o.r = lds_lut_at_unit(lut, tr);
+  o.g = lds_lut_at_unit(lut, tg);
+  o.b = lds_lut_at_unit(lut, tb);
+  return o;
+}
 template <bool STD = false>
 __device__ __forceinline__ float4 read_px_lds(float y, float cb, float cr, const ReadK &k, const LutK &lut, float last = 1.0f) {
   float tr, tg, tb;

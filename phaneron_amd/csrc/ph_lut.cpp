@@ -34,6 +34,15 @@ LutView lut_view(const LutHostInfo &info, const void *blob_dev) {
   return v;
 }
 
+float lut_max_finite(const float *lut) {
+  uint32_t top = 0;  // the bit patterns of non-negative floats are ordered as the floats are
+  for (int i = 0; i < 65536; ++i) {
+    const uint32_t mag = f2u(lut[i]) & 0x7FFFFFFFu;
+    if (mag < 0x7F800000u && mag > top) top = mag;
+  }
+  return u2f(top);
+}
+
 bool lut_compress(const float *lut, uint32_t max_bytes, std::vector<uint32_t> &blob, LutHostInfo &info) {
   // per-call scratch: callers may compress tables from several threads (the node addon's libuv pool)
   std::vector<uint32_t> p(65536), blk(65536);

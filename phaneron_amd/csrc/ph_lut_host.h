@@ -19,5 +19,8 @@ constexpr uint32_t kLutMaxLdsBytes = 160 * 1024;
 bool lut_compress(const float *lut65536, uint32_t max_bytes, std::vector<uint32_t> &blob, LutHostInfo &info);
 // The kernel-side view of a compressed table whose blob lives at `blob_dev`.
 LutView lut_view(const LutHostInfo &info, const void *blob_dev);
+// max |entry| over the table's finite entries (0 if it has none): the bound the fused kernel's witness guard starts from
+// (ph_kernels.h fused_witness_holds).
+float lut_max_finite(const float *lut65536);
 
 }  // namespace ph
