@@ -1291,6 +1291,23 @@ int ph_pack_write(ph_ctx *ctx, int queue, int format, const void *in, void *cons
                                   lds_view(ctx, lut).get(), (uint32_t)ctx->props.multiProcessorCount));
 }
 
+// The outputs grouped by writer table, in the order the tables first appear - THE walk every several-outputs entry makes.  order (n_out
+// entries): the outputs' indices group by group, a group's members in the call's order; group g is order[start[g]] .. order[start[g + 1] - 1]
+// (start: n_out + 1 entries), and its first member is the first output that names its table.  Answers the number of groups
+static int writer_table_groups(int n_out, const ph_chan_output *outs, int *order, int *start) {
+  int placed = 0, groups = 0;
+  for (int k = 0; k < n_out; ++k) {
+    bool seen = false;
+    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
+    if (seen) continue;
+    start[groups++] = placed;
+    for (int j = k; j < n_out; ++j)
+      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) order[placed++] = j;
+  }
+  start[groups] = placed;
+  return groups;
+}
+
 /* One image packed for several consumers: see include/phaneron_hip.h.  Every check is ph_pack_write's, per output, and is made - and every
  * launch of the call planned - before anything is launched. */
 int ph_pack_write_multi(ph_ctx *ctx, int queue, const void *in, int n_out, const ph_chan_output *outs, uint32_t width, uint32_t height) {
@@ -1320,19 +1337,17 @@ int ph_pack_write_multi(ph_ctx *ctx, int queue, const void *in, int n_out, const
     ph::PackMultiArgs m;
   };
   std::vector<Launch> launches;
-  for (int k = 0; k < n_out; ++k) {
-    bool seen = false;
-    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
-    if (seen) continue;
-    const LutRef wref = lds_view(ctx, outs[k].wr_gamma_lut);
-    int group[ph::kMaxPackOuts], members = 0, share = 0;
+  int order[ph::kMaxPackOuts], start[ph::kMaxPackOuts + 1];
+  const int groups = writer_table_groups(n_out, outs, order, start);
+  for (int t = 0; t < groups; ++t) {
+    const int *const group = order + start[t], members = start[t + 1] - start[t];
+    const LutRef wref = lds_view(ctx, outs[group[0]].wr_gamma_lut);
+    int share = 0;
     bool shared_ok[ph::kMaxPackOuts];
-    for (int j = k; j < n_out; ++j) {
-      if (outs[j].wr_gamma_lut != outs[k].wr_gamma_lut) continue;
-      const int f = outs[j].format;
-      shared_ok[members] = wref.get() && !(f == PH_FMT_V210 && width % 48) && !(fmt_planar(f) && width % 8);
-      share += shared_ok[members] ? 1 : 0;
-      group[members++] = j;
+    for (int g = 0; g < members; ++g) {
+      const int f = outs[group[g]].format;
+      shared_ok[g] = wref.get() && !(f == PH_FMT_V210 && width % 48) && !(fmt_planar(f) && width % 8);
+      share += shared_ok[g] ? 1 : 0;
     }
     Launch shared{};
     shared.solo = -1;
@@ -1829,16 +1844,10 @@ static void out_lines(const ph_chan_output &o, bool same_lines, uint32_t out_h, 
   d.line_end = o.interlace ? 2u * (out_h / 2u) : out_h;  // (a field of an odd height: out_h / 2 lines, as ph_chan_compose writes it)
   d.field = o.interlace ? 1u : 0u;
 }
-// the outputs grouped by writer table, in the order the tables first appear
+// the outputs grouped by writer table (writer_table_groups): the order alone, for a launch that takes every group
 static void by_writer_table(int n_out, const ph_chan_output *outs, int *order) {
-  int placed = 0;
-  for (int k = 0; k < n_out; ++k) {
-    bool seen = false;
-    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
-    if (seen) continue;
-    for (int j = k; j < n_out; ++j)
-      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) order[placed++] = j;
-  }
+  int start[(ph::kMaxChanOuts > ph::kMaxFusedOuts ? ph::kMaxChanOuts : ph::kMaxFusedOuts) + 1];
+  writer_table_groups(n_out, outs, order, start);
 }
 
 /* Several consumers' frames of one composition in one launch: see include/phaneron_hip.h.  Every check is made before anything is
@@ -1963,6 +1972,14 @@ static bool fused_multi_shared(ph_ctx *ctx, int n_out, const ph_chan_output *out
   }
   return true;
 }
+// a frame of the channel's size taken 1:1, as a cut layer of ph_chan_compose_multi: what the fused entries hand a call on with
+static ph_chan_layer plain_chan_layer(const void *data, int format, uint32_t width, uint32_t height) {
+  ph_chan_layer c;
+  memset(&c, 0, sizeof c);
+  c.src.data = data, c.src.format = format, c.src.width = (int)width, c.src.height = (int)height;
+  c.transition = PH_TRANSITION_CUT;
+  return c;
+}
 
 /* The plain-layer composite for several consumers: see include/phaneron_hip.h.  The call IS the n_out calls of ph_chan_compose on the layers
  * taken 1:1; every check is made before anything is launched, with ph_chan_compose_multi's texts per output.  A call the shared kernel
@@ -1984,11 +2001,7 @@ int ph_fused_v210_combine_multi(ph_ctx *ctx, int queue, int n, const void *const
   ph::FusedMultiArgs &m = fa.m;
   if (!fused_multi_shared(ctx, n_out, outs, width, height, rd_cm, rd_lut, rd_gm, m, nullptr, field)) {
     ph_chan_layer cl[ph::kMaxLayers];
-    memset(cl, 0, sizeof cl);
-    for (int i = 0; i < n; ++i) {
-      cl[i].src.data = layers[i], cl[i].src.format = PH_SRC_V210, cl[i].src.width = (int)width, cl[i].src.height = (int)height;
-      cl[i].transition = PH_TRANSITION_CUT;
-    }
+    for (int i = 0; i < n; ++i) cl[i] = plain_chan_layer(layers[i], PH_SRC_V210, width, height);
     return ph_chan_compose_multi(ctx, queue, n, cl, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
   }
   if (!m.total_quads) return PH_OK;  // height 0 - or a field of a frame of one line
@@ -2035,14 +2048,12 @@ int ph_fused_v210_transition_multi(ph_ctx *ctx, int queue, int n, const ph_fused
   ph::FusedTransArgs t{};
   if (!fused_multi_shared(ctx, n_out, outs, width, height, rd_cm, rd_lut, rd_gm, t.m)) {
     ph_chan_layer cl[ph::kMaxLayers];
-    memset(cl, 0, sizeof cl);
-    auto source = [&](ph_chan_source &s, const void *data, int format) { s.data = data, s.format = format, s.width = (int)width, s.height = (int)height; };
     for (int i = 0; i < n; ++i) {
       const ph_fused_layer &L = layers[i];
-      source(cl[i].src, L.v210, PH_SRC_V210);
+      cl[i] = plain_chan_layer(L.v210, PH_SRC_V210, width, height);
       cl[i].transition = L.transition, cl[i].mix = L.mix;
-      if (L.transition != PH_TRANSITION_CUT) source(cl[i].incoming, L.incoming_v210, PH_SRC_V210);
-      if (L.transition == PH_TRANSITION_WIPE) source(cl[i].mask, L.mask, L.mask_format);
+      if (L.transition != PH_TRANSITION_CUT) cl[i].incoming = plain_chan_layer(L.incoming_v210, PH_SRC_V210, width, height).src;
+      if (L.transition == PH_TRANSITION_WIPE) cl[i].mask = plain_chan_layer(L.mask, L.mask_format, width, height).src;
     }
     return ph_chan_compose_multi(ctx, queue, n, cl, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
   }
@@ -2101,11 +2112,7 @@ int ph_fused_v210_route_multi(ph_ctx *ctx, int queue, int n, const ph_route_laye
                   "frame within the kernel's division by reciprocal) and nothing else makes image_out: run ph_v210_read, ph_combine and ph_pack_write_multi",
                   fn);
     ph_chan_layer cl[ph::kMaxLayers];
-    memset(cl, 0, sizeof cl);
-    for (int i = 0; i < n; ++i) {
-      cl[i].src.data = layers[i].data, cl[i].src.format = layers[i].format, cl[i].src.width = (int)width, cl[i].src.height = (int)height;
-      cl[i].transition = PH_TRANSITION_CUT;
-    }
+    for (int i = 0; i < n; ++i) cl[i] = plain_chan_layer(layers[i].data, layers[i].format, width, height);
     return ph_chan_compose_multi(ctx, queue, n, cl, n_out, outs, width, height, rd_cm, rd_lut, rd_gm);
   }
   if (!height) return PH_OK;
@@ -2650,6 +2657,17 @@ static int compose_up_tables(const char *fn, ph_ctx *ctx, int n_out, const ph_ch
   return PH_OK;
 }
 
+// an output of the several-outputs kernels' launches, job 0's planes (a further job's: the caller's to add)
+static ph::UpOut up_out_of(const ph_chan_output &o, bool same_lines, uint32_t out_w, uint32_t out_h) {
+  ph::UpOut d{};
+  d.fmt = (uint32_t)o.format;
+  d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48 - or the launcher's to set)
+  d.wr_cm = (const float *)o.wr_col_matrix12;
+  for (int i = 0; i < 3; ++i) d.plane[0][i] = o.planes[i];
+  out_lines(o, same_lines, out_h, d);
+  return d;
+}
+
 struct UpLaunch {
   bool solo;  // compose_up_write_v210_kernel: m.up alone
   int table;  // the first output that names the launch's writer table (m.up.wr: the caller's to fill)
@@ -2661,13 +2679,10 @@ struct UpLaunch {
 // "up_v210_tails"): a v210 output whose lines end in a tail quad stays with the others of its table - alone with its table it is split off as ever
 static void compose_up_launches(const ph::UpArgs &base, int jobs, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h,
                                 bool split_v210, std::vector<UpLaunch> &launches, bool keep_tails = false) {
-  for (int k = 0; k < n_out; ++k) {
-    bool seen = false;
-    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
-    if (seen) continue;
-    int group[ph::kMaxUpOuts], members = 0;
-    for (int j = k; j < n_out; ++j)
-      if (outs[j].wr_gamma_lut == outs[k].wr_gamma_lut) group[members++] = j;
+  int order[ph::kMaxUpOuts], start[ph::kMaxUpOuts + 1];
+  const int groups = writer_table_groups(n_out, outs, order, start);
+  for (int t = 0; t < groups; ++t) {
+    const int *const group = order + start[t], members = start[t + 1] - start[t], k = group[0];
     UpLaunch shared{};
     const ph_chan_output *stays[ph::kMaxUpOuts];  // the outputs of shared.m.out
     shared.solo = false, shared.table = k, shared.m.up = base;
@@ -2683,12 +2698,10 @@ static void compose_up_launches(const ph::UpArgs &base, int jobs, int n_out, con
         continue;
       }
       ph::UpOut &d = shared.m.out[shared.m.n_out];
-      d.fmt = (uint32_t)o.format;
-      d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48 - or the launcher's to set)
-      d.wr_cm = (const float *)o.wr_col_matrix12;
-      for (int j = 0; j < jobs; ++j)
+      d = up_out_of(o, true, out_w, out_h);  // (takes / line_end / field: settled below, once the launch's lines are known)
+      for (int j = 1; j < jobs; ++j)
         for (int i = 0; i < 3; ++i) d.plane[j][i] = outs[j * n_out + group[g]].planes[i];
-      stays[shared.m.n_out++] = &o;  // (takes / line_end / field: settled below, once the launch's lines are known)
+      stays[shared.m.n_out++] = &o;
     }
     if (!shared.m.n_out) continue;
     // a split-off v210 output does not count: the first output that stays decides what "the same" is
@@ -2746,28 +2759,161 @@ int ph_compose_up_write_multi(ph_ctx *ctx, int queue, int jobs, int n, const ph_
   return compose_up_write_multi(ctx, queue, jobs, n, layer_sets, n_out, outs, out_w, out_h, ctx && ctx->up_v210_tails);
 }
 
-// What ph_clip_compose_multi's one-launch route and ph_clip_compose_batch_out's planner make of a clip and of an output: a clip's size and
-// placement as a compositor layer (ptr: the launch's own), ...
+// What the clip entries and ph_clip_compose_batch_out's planner make of a clip (of an output: up_out_of, above): its size and placement as a
+// compositor layer (ptr: the launch's own), ...
 static ph::UpLayer up_layer_of(const ph_chan_source &S) {
   ph::UpLayer d{};
   d.w = (uint32_t)S.width, d.h = (uint32_t)S.height, d.pitch = (uint32_t)S.width * 16u;
   for (int k = 0; k < 6; ++k) d.m[k] = S.matrix9_host[k];
   return d;
 }
-// ... an output of a one-job launch of the several-outputs kernels, ...
-static ph::UpOut up_out_of(const ph_chan_output &o, bool same_lines, uint32_t out_w, uint32_t out_h) {
-  ph::UpOut d{};
-  d.fmt = (uint32_t)o.format;
-  d.pitch = o.format == PH_FMT_V210 ? out_w / 6u : out_w;  // (planar: a multiple of 8, no padding; v210 here: a multiple of 48)
-  d.wr_cm = (const float *)o.wr_col_matrix12;
-  for (int i = 0; i < 3; ++i) d.plane[0][i] = o.planes[i];
-  out_lines(o, same_lines, out_h, d);
-  return d;
-}
-// ... and a clip in its wire format fmt, as the clip kernel reads it
+// ... and the clip itself in its wire format fmt, as the clip kernel reads it
 static ph::ClipSrc clip_src_of(const ph_chan_source &S, int fmt, const void *rd_cm) {
   return ph::ClipSrc{S.data, S.data_u, S.data_v, (const float *)(S.col_matrix12 ? S.col_matrix12 : rd_cm), (uint32_t)fmt,
                      fmt == PH_FMT_V210 ? ph_v210_pitch_bytes((uint32_t)S.width) / 16u : ph::pack_pitch(fmt, (uint32_t)S.width)};
+}
+
+// ---- what the file playback entries share ------------------------------------------------------------------------------------------------
+// The argument checks of a clip call, in the entries' order and with their texts: NULLs, the counts, the outputs, then the layers as the
+// channel kernel's entries check them.  The context is not looked at.  route: ph_clip_compose_route_multi's form - clip_route_counts has
+// seen its counts, and a call without outputs need not name any
+static int clip_args_check(const char *fn, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h,
+                           const void *rd_cm, const void *rd_lut, const void *rd_gm, bool route = false) {
+  if (!layers || (!outs && !(route && !n_out)) || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
+  if (!route && (n_out < 1 || n_out > ph::kMaxUpOuts)) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
+  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
+  if (const int bad = fused_multi_outputs_check(fn, queue, n_out, outs, out_w, out_h)) return bad;
+  ph::ChanArgs probe{};
+  int n_ops = 0;
+  return chan_ops(n, layers, out_w, out_h, probe.op, probe.plane_u, probe.plane_v, probe.cm_op, &probe.planar, &n_ops);
+}
+// The lines a launch for several outputs composes: the field every output wants (*same_lines; the answer is its interlace value), or the
+// whole frame (0) - a field output then takes the rows of its parity
+static uint32_t lines_composed(int n_out, const ph_chan_output *outs, bool *same_lines) {
+  *same_lines = true;
+  for (int k = 1; k < n_out; ++k) *same_lines = *same_lines && outs[k].interlace == outs[0].interlace;
+  return *same_lines ? (uint32_t)outs[0].interlace : 0u;
+}
+// Is the image a clip in a wire format the clip kernel reads (v210 included; a 4:2:0 one needs an even height)?  *alpha: it carries alpha
+static bool clip_wire(const ph_chan_source &S, bool *alpha) {
+  const int fmt = fmt_of_src(S.format);
+  *alpha = fmt_rgb8(fmt);
+  return fmt >= 0 && !(fmt_v420(fmt) && (S.height & 1));
+}
+// Do the read-once routes take the outputs?  Each writer table in its LDS form into wref[k]; a planar frame's width must be a multiple of 8
+static bool clip_tables_take(ph_ctx *ctx, int n_out, const ph_chan_output *outs, uint32_t out_w, LutRef *wref) {
+  for (int k = 0; k < n_out; ++k) {
+    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
+    if (!wref[k].get() || (fmt_planar(outs[k].format) && out_w % 8)) return false;
+  }
+  return true;
+}
+// A clip kernel launch's arguments (c: zeroed) from a writer table's group m, the reader's table and the frame's one clip S - as every
+// clip entry and the batch planner make them (clip.scratch and the tiling: clip_up_plan's and the launch's)
+static void clip_multi_fill(ph::ClipUpMultiArgs &c, const ph::UpMultiArgs &m, const ph::LutView &rd, const void *rd_gm, const ph_chan_source &S, const void *rd_cm) {
+  c.clip.up = m.up, c.n_out = m.n_out;
+  for (uint32_t i = 0; i < m.n_out; ++i) c.out[i] = m.out[i];
+  c.clip.rd = rd, c.clip.rd_gm = (const float *)rd_gm;
+  c.clip.src[0] = clip_src_of(S, fmt_of_src(S.format), rd_cm);
+}
+
+// The queue's scratch area through the launches of one clip call.  `images` is ctx->chan_scratch_mu[queue], held from the read of the
+// clips into the queue's scratch images until the last compositor launch that takes them is enqueued - and never across ph_chan_compose
+// or with_scratch, which take the area (and the lock) themselves: the images are given up in front of those.  RELEASED MEANS GONE: the
+// next group that needs the images reads them again.
+extern "C++" {
+struct ClipScratch {
+  const char *fn;
+  ph_ctx *ctx;
+  int queue;
+  std::unique_lock<std::mutex> images;
+  void *image[ph::kMaxLayers * 3];  // where the compositor finds the images read last
+  void release() {
+    if (images.owns_lock()) images.unlock();
+  }
+  // one launch of a clip kernel, planned with `grid` workgroups (clip_up_plan): launch(stream) enqueues it, clip.scratch set
+  template <class Launch>
+  int one_launch(ph::ClipUpArgs &clip, uint32_t grid, Launch launch) {
+    release();
+    return with_scratch(fn, ctx, queue, (size_t)clip.wg_bytes * grid + 4096u, [&](hipStream_t s, void *area) {
+      clip.scratch = (char *)area;
+      return launch(s);
+    });
+  }
+  // the first of the two stages: every image through its format's reader into the queue's scratch images (image[f]: srcs[f]'s) - unless
+  // they are still held from an earlier group of the call
+  int images_for_two_stages(int n_img, const ph_chan_source *const *srcs, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
+    if (images.owns_lock()) return PH_OK;
+    images = std::unique_lock<std::mutex>(ctx->chan_scratch_mu[queue]);
+    return chan_images_read(ctx, queue, 1, n_img, srcs, rd_cm, rd_lut, rd_gm, image);
+  }
+};
+}
+// The outputs of a clip call by writer table, in the order the tables first appear: group(m, tails) makes a table's launch(es) - m.up is
+// base with the table, m.out the outputs that stay.  A v210 output whose lines end in a tail quad truncates its table indices there where
+// the other writers round: through ph_chan_compose, alone, in its turn - unless keep_tails and another output names its table: then it
+// stays in the group, whose launch is the kernels' TAILS form (tails; clip_up_multi_t / compose_up_multi_t).  wref[k]: output k's table
+extern "C++" template <class Group>
+static int clip_groups(ClipScratch &scratch, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h,
+                       const void *rd_cm, const void *rd_lut, const void *rd_gm, const ph::UpArgs &base, const LutRef *wref, bool same_lines, bool keep_tails,
+                       Group group) {
+  ph_ctx *const ctx = scratch.ctx;
+  const int queue = scratch.queue;
+  int order[ph::kMaxUpOuts], start[ph::kMaxUpOuts + 1];
+  const int groups = writer_table_groups(n_out, outs, order, start);
+  for (int g = 0; g < groups; ++g) {
+    ph::UpMultiArgs m{};
+    m.up = base, m.up.wr = *wref[order[start[g]]].get();
+    bool tails = false;  // the group's launch has a v210 output whose lines end in a tail quad
+    for (int i = start[g]; i < start[g + 1]; ++i) {
+      const ph_chan_output &o = outs[order[i]];
+      if (o.format == PH_FMT_V210 && out_w % 48) {
+        if (!(keep_tails && start[g + 1] - start[g] >= 2)) {
+          scratch.release();
+          const int rc = ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, o.planes, out_w, out_h, o.interlace, rd_cm, rd_lut, rd_gm, o.wr_col_matrix12, o.wr_gamma_lut);
+          if (rc) return rc;
+          continue;
+        }
+        tails = true;
+      }
+      m.out[m.n_out++] = up_out_of(o, same_lines, out_w, out_h);
+    }
+    if (!m.n_out) continue;
+    if (const int rc = group(m, tails)) return rc;
+  }
+  return PH_OK;
+}
+// A group's launch by ph_clip_compose_multi's routes.  one_launch: the frame is a single clip in a wire format (alpha: one that carries
+// alpha) - one launch of the clip kernel, where it has a tiling; else the two stages: the clips into the queue's scratch images, then the
+// 2 x 2-block compositor's launch.  image_out (ph_clip_compose_route_multi's first launch): the launch stores the combined image too
+static int clip_group_launch(ClipScratch &scratch, bool one_launch, bool alpha, int n, const ph_chan_layer *layers, const void *rd_cm, const void *rd_lut,
+                             const void *rd_gm, const ph::LutView &rd, ph::UpMultiArgs &m, bool tails, void *image_out) {
+  ph_ctx *const ctx = scratch.ctx;
+  const uint32_t cus = (uint32_t)ctx->props.multiProcessorCount;
+  if (one_launch) {
+    ph::ClipUpRouteArgs r{};
+    ph::ClipUpMultiArgs &c = r.multi;
+    clip_multi_fill(c, m, rd, rd_gm, layers[0].src, rd_cm);
+    r.image = image_out;
+    const uint32_t grid = ph::clip_up_plan(c.clip, !alpha, cus, /*v210_tails*/ tails);
+    if (grid)
+      return scratch.one_launch(c.clip, grid, [&](hipStream_t s) {
+        return image_out ? ph::launch_clip_up_route(s, r, !alpha, grid) : ph::launch_clip_up_multi(s, c, !alpha, grid, tails);
+      });
+  }
+  const ph_chan_source *srcs[ph::kMaxLayers];
+  for (int i = 0; i < n; ++i) srcs[i] = &layers[i].src;
+  if (const int bad = scratch.images_for_two_stages(n, srcs, rd_cm, rd_lut, rd_gm)) return bad;
+  for (int i = 0; i < n; ++i) m.up.layer[i].ptr = scratch.image[i];
+  hipError_t e;
+  if (image_out) {
+    ph::UpRouteArgs r{};
+    r.multi = m, r.image = image_out;
+    e = ph::launch_compose_up_route(stream_of(ctx, scratch.queue), r, cus);
+  } else {
+    e = ph::launch_compose_up_multi(stream_of(ctx, scratch.queue), m, false, cus, tails);
+  }
+  return e == hipSuccess ? PH_OK : fail(PH_E_HIP, "%s: launch failed: %s", scratch.fn, hipGetErrorString(e));
 }
 
 /* File playback for any consumer, up to four per call: see include/phaneron_hip.h.  Exactly the n_out calls of ph_chan_compose in order,
@@ -2786,32 +2932,20 @@ int ph_clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *la
 static int clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w, uint32_t out_h,
                               const void *rd_cm, const void *rd_lut, const void *rd_gm, bool keep_tails) {
   const char *const fn = "ph_clip_compose_multi";
-  if (!layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
-  if (n_out < 1 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
-  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
-  if (const int bad = fused_multi_outputs_check(fn, queue, n_out, outs, out_w, out_h)) return bad;
-  {  // the layers, as the channel kernel's entries check them (their texts)
-    ph::ChanArgs probe{};
-    int n_ops = 0;
-    if (const int bad = chan_ops(n, layers, out_w, out_h, probe.op, probe.plane_u, probe.plane_v, probe.cm_op, &probe.planar, &n_ops)) return bad;
-  }
+  if (const int bad = clip_args_check(fn, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm)) return bad;
   if (!ctx) return fail(PH_E_INVALID, "%s: ctx is NULL", fn);
   // 1. a single v210 frame IS ph_chan_compose: today's routes under today's names
   if (n_out == 1 && outs[0].format == PH_FMT_V210)
     return ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, outs[0].planes, out_w, out_h, outs[0].interlace, rd_cm, rd_lut, rd_gm, outs[0].wr_col_matrix12,
                            outs[0].wr_gamma_lut);
-  // 2. the lines composed: the field every output wants, or the whole frame (a field output then takes the rows of its parity)
-  bool same_lines = true;
-  for (int k = 1; k < n_out; ++k) same_lines = same_lines && outs[k].interlace == outs[0].interlace;
-  const uint32_t interlace = same_lines ? outs[0].interlace : 0u;
+  // 2. the lines composed
+  bool same_lines;
+  const uint32_t interlace = lines_composed(n_out, outs, &same_lines);
   // 3. not for these routes: the channel kernel, under its own trace name
   const LutRef rref = lds_view(ctx, rd_lut);
   LutRef wref[ph::kMaxUpOuts];
-  bool takes = ctx->chan_enlarged != 0 && rref.get() && chan_layers_enlarged(n, layers, out_w, out_h, interlace, /*v210_fill*/ true);
-  for (int k = 0; k < n_out && takes; ++k) {
-    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
-    takes = wref[k].get() && !(fmt_planar(outs[k].format) && out_w % 8);
-  }
+  bool takes = ctx->chan_enlarged != 0 && rref.get() && chan_layers_enlarged(n, layers, out_w, out_h, interlace, /*v210_fill*/ true) &&
+               clip_tables_take(ctx, n_out, outs, out_w, wref);
   ph::UpArgs base{};
   if (takes) {
     base.n = n, base.jobs = 1;
@@ -2823,75 +2957,14 @@ static int clip_compose_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer
   if (!base.lines) return PH_OK;
   int rc = set_device(ctx);
   if (rc) return rc;
-  // one launch of the clip kernel per table?  A single clip in a wire format (v210 included), a 4:2:0 one of an even height
-  bool one_launch = ctx->chan_enlarged == 1 && n == 1, alpha = false;
-  if (one_launch) {
-    const ph_chan_source &S = layers[0].src;
-    const int fmt = fmt_of_src(S.format);
-    one_launch = fmt >= 0 && !(fmt_v420(fmt) && (S.height & 1));
-    alpha = fmt_rgb8(fmt);
-  }
-  // 4. the outputs by writer table, in the order the tables first appear; a v210 output whose lines end in a tail quad truncates its table
-  // indices there where the other writers round: through ph_chan_compose, alone - unless keep_tails and another output names its table: then
-  // it stays in the group, whose launch is the kernels' TAILS form (clip_up_multi_t / compose_up_multi_t)
-  // (the two stages: the clips are read once for all the call's tables; the queue's scratch area is held until the last compositor launch
-  // that takes the images is enqueued - and given up in front of a ph_chan_compose call, which takes the area itself)
-  ph_image_layer il[1][ph::kMaxLayers];
-  const ph_image_layer *sets[1];
-  std::unique_lock<std::mutex> images;
-  for (int k = 0; k < n_out; ++k) {
-    bool seen = false;
-    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
-    if (seen) continue;
-    ph::UpMultiArgs m{};
-    m.up = base, m.up.wr = *wref[k].get();
-    int members = 0;
-    for (int j = k; j < n_out; ++j) members += outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
-    bool tails = false;  // the group's launch has a v210 output whose lines end in a tail quad
-    for (int j = k; j < n_out; ++j) {
-      const ph_chan_output &o = outs[j];
-      if (o.wr_gamma_lut != outs[k].wr_gamma_lut) continue;
-      if (o.format == PH_FMT_V210 && out_w % 48) {
-        if (!(keep_tails && members >= 2)) {
-          if (images.owns_lock()) images.unlock();
-          rc = ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, o.planes, out_w, out_h, o.interlace, rd_cm, rd_lut, rd_gm, o.wr_col_matrix12, o.wr_gamma_lut);
-          if (rc) return rc;
-          continue;
-        }
-        tails = true;
-      }
-      m.out[m.n_out++] = up_out_of(o, same_lines, out_w, out_h);
-    }
-    if (!m.n_out) continue;
-    // 5. the group's launch
-    if (one_launch) {
-      ph::ClipUpMultiArgs c{};
-      c.clip.up = m.up, c.n_out = m.n_out;
-      for (uint32_t i = 0; i < m.n_out; ++i) c.out[i] = m.out[i];
-      c.clip.rd = *rref.get(), c.clip.rd_gm = (const float *)rd_gm;
-      c.clip.src[0] = clip_src_of(layers[0].src, fmt_of_src(layers[0].src.format), rd_cm);
-      const uint32_t grid = ph::clip_up_plan(c.clip, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ tails);
-      if (grid) {
-        if (images.owns_lock()) images.unlock();
-        rc = with_scratch(fn, ctx, queue, (size_t)c.clip.wg_bytes * grid + 4096u, [&](hipStream_t s, void *area) {
-          c.clip.scratch = (char *)area;
-          return ph::launch_clip_up_multi(s, c, !alpha, grid, tails);
-        });
-        if (rc) return rc;
-        continue;
-      }
-    }
-    // the two stages: every clip through its format's reader into the queue's scratch images, then the 2 x 2-block compositor's launch
-    if (!images.owns_lock()) {
-      images = std::unique_lock<std::mutex>(ctx->chan_scratch_mu[queue]);
-      rc = chan_enlarged_read(ctx, queue, 1, n, &layers, rd_cm, rd_lut, rd_gm, il, sets);
-      if (rc) return rc;
-    }
-    for (int i = 0; i < n; ++i) m.up.layer[i].ptr = il[0][i].data;
-    const hipError_t e = ph::launch_compose_up_multi(stream_of(ctx, queue), m, false, (uint32_t)ctx->props.multiProcessorCount, tails);
-    if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-  }
-  return PH_OK;
+  // one launch of the clip kernel per table?  A single clip in a wire format
+  bool alpha = false;
+  const bool one_launch = ctx->chan_enlarged == 1 && n == 1 && clip_wire(layers[0].src, &alpha);
+  // 4. the outputs by writer table, each group's launch in its turn (the clips are read once for all the call's two-stage groups)
+  ClipScratch scratch{fn, ctx, queue};
+  return clip_groups(scratch, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, base, wref, same_lines, keep_tails, [&](ph::UpMultiArgs &m, bool tails) {
+    return clip_group_launch(scratch, one_launch, alpha, n, layers, rd_cm, rd_lut, rd_gm, rref.view, m, tails, /*image_out*/ nullptr);
+  });
 }
 
 static bool chan_sources_same_shape(const ph_chan_source &a, const ph_chan_source &b) {
@@ -2911,24 +2984,15 @@ static bool chan_sources_same_shape(const ph_chan_source &a, const ph_chan_sourc
 int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, int n_out, const ph_chan_output *outs, uint32_t out_w,
                                      uint32_t out_h, const void *rd_cm, const void *rd_lut, const void *rd_gm) {
   const char *const fn = "ph_clip_compose_transition_multi";
-  if (!layers || !outs || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
-  if (n_out < 1 || n_out > ph::kMaxUpOuts) return fail(PH_E_INVALID, "%s: 1..%d outputs (%d)", fn, ph::kMaxUpOuts, n_out);
-  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
-  if (const int bad = fused_multi_outputs_check(fn, queue, n_out, outs, out_w, out_h)) return bad;
-  {  // the layers and their transitions, as the channel kernel's entries check them (their texts)
-    ph::ChanArgs probe{};
-    int n_ops = 0;
-    if (const int bad = chan_ops(n, layers, out_w, out_h, probe.op, probe.plane_u, probe.plane_v, probe.cm_op, &probe.planar, &n_ops)) return bad;
-  }
+  if (const int bad = clip_args_check(fn, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm)) return bad;
   if (!ctx) return fail(PH_E_INVALID, "%s: ctx is NULL", fn);
   // 1. no transition: ph_clip_compose_multi, its routes under its names
   bool any = false;
   for (int i = 0; i < n; ++i) any = any || layers[i].transition != PH_TRANSITION_CUT;
   if (!any) return clip_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, /*keep_tails*/ false);
-  // 2. the lines composed: the field every output wants, or the whole frame (a field output then takes the rows of its parity)
-  bool same_lines = true;
-  for (int k = 1; k < n_out; ++k) same_lines = same_lines && outs[k].interlace == outs[0].interlace;
-  const uint32_t interlace = same_lines ? outs[0].interlace : 0u;
+  // 2. the lines composed
+  bool same_lines;
+  const uint32_t interlace = lines_composed(n_out, outs, &same_lines);
   // 3. every present image, in the order layer by layer: src, incoming, mask
   const ph_chan_source *img[ph::kMaxLayers * 3];
   int first_img[ph::kMaxLayers], n_img = 0;
@@ -2940,15 +3004,11 @@ int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_cha
   }
   const LutRef rref = lds_view(ctx, rd_lut);
   LutRef wref[ph::kMaxUpOuts];
-  bool takes = ctx->chan_enlarged != 0 && rref.get() && out_w % 2u == 0;
-  for (int k = 0; k < n_out && takes; ++k) {
-    wref[k] = lds_view(ctx, outs[k].wr_gamma_lut);
-    takes = wref[k].get() && !(fmt_planar(outs[k].format) && out_w % 8);
-  }
+  bool takes = ctx->chan_enlarged != 0 && rref.get() && out_w % 2u == 0 && clip_tables_take(ctx, n_out, outs, out_w, wref);
   ph::UpArgs base{};
   base.n = n, base.jobs = 1;
   compose_up_lines(base, out_w, out_h, interlace);
-  bool wire = true, alpha = false;  // every image in a wire format the clip kernel reads; an image that carries alpha
+  bool wire = true, alpha = false;  // every image in a wire format the clip kernel reads; one of them carries alpha
   for (int f = 0; f < n_img && takes; ++f) {
     const ph_chan_source &S = *img[f];
     takes = chan_image_enlarged(S, out_w, out_h, interlace, /*v210_fill*/ true);  // (it has a placement then)
@@ -2956,47 +3016,26 @@ int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_cha
     ph::UpArgs one = base;
     one.n = 1, one.layer[0] = up_layer_of(S);
     takes = ph::compose_up_eligible(one);
-    const int fmt = fmt_of_src(S.format);
-    wire = wire && fmt >= 0 && !(fmt_v420(fmt) && (S.height & 1));
-    alpha = alpha || fmt < 0 || fmt_rgb8(fmt);
+    bool its_alpha;
+    wire = clip_wire(S, &its_alpha) && wire;
+    alpha = alpha || its_alpha;
   }
   if (!takes) return ph_chan_compose_multi(ctx, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm);
   if (!base.lines) return PH_OK;
   int rc = set_device(ctx);
   if (rc) return rc;
   const bool one_launch = ctx->chan_enlarged == 1 && n == 1 && wire;
-  // 4. the outputs by writer table, in the order the tables first appear; a v210 output whose lines end in a tail quad through
-  // ph_chan_compose, alone (ph_clip_compose_multi's route 4; the scratch area's lock as there)
-  void *image[ph::kMaxLayers * 3];
-  std::unique_lock<std::mutex> images;
-  for (int k = 0; k < n_out; ++k) {
-    bool seen = false;
-    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
-    if (seen) continue;
-    ph::UpMultiArgs m{};
-    m.up = base, m.up.wr = *wref[k].get();
-    for (int i = 0; i < n; ++i) m.up.layer[i] = up_layer_of(layers[i].src);
-    for (int j = k; j < n_out; ++j) {
-      const ph_chan_output &o = outs[j];
-      if (o.wr_gamma_lut != outs[k].wr_gamma_lut) continue;
-      if (o.format == PH_FMT_V210 && out_w % 48) {
-        if (images.owns_lock()) images.unlock();
-        rc = ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, o.planes, out_w, out_h, o.interlace, rd_cm, rd_lut, rd_gm, o.wr_col_matrix12, o.wr_gamma_lut);
-        if (rc) return rc;
-        continue;
-      }
-      m.out[m.n_out++] = up_out_of(o, same_lines, out_w, out_h);
-    }
-    if (!m.n_out) continue;
+  for (int i = 0; i < n; ++i) base.layer[i] = up_layer_of(layers[i].src);
+  const uint32_t cus = (uint32_t)ctx->props.multiProcessorCount;
+  // 4. the outputs by writer table, a v210 output whose lines end in a tail quad through ph_chan_compose, alone (ph_clip_compose_multi's route 4)
+  ClipScratch scratch{fn, ctx, queue};
+  return clip_groups(scratch, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, base, wref, same_lines, /*keep_tails*/ false, [&](ph::UpMultiArgs &m, bool) -> int {
     // 5. the group's one launch: a single layer, every image a clip in its wire format
     if (one_launch) {
       const ph_chan_layer &L = layers[0];
       ph::ClipUpTransArgs t{};
       ph::ClipUpMultiArgs &c = t.multi;
-      c.clip.up = m.up, c.n_out = m.n_out;
-      for (uint32_t i = 0; i < m.n_out; ++i) c.out[i] = m.out[i];
-      c.clip.rd = *rref.get(), c.clip.rd_gm = (const float *)rd_gm;
-      c.clip.src[0] = clip_src_of(L.src, fmt_of_src(L.src.format), rd_cm);
+      clip_multi_fill(c, m, rref.view, rd_gm, L.src, rd_cm);
       t.kind = (uint32_t)L.transition, t.mix = L.mix;
       const ph_chan_source *const theirs[2] = {&L.incoming, &L.mask};
       for (int w = 0; w < (L.transition == PH_TRANSITION_WIPE ? 2 : 1); ++w) {
@@ -3004,24 +3043,13 @@ int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_cha
         t.partner_src[w] = clip_src_of(*theirs[w], fmt_of_src(theirs[w]->format), rd_cm);
         t.same |= chan_sources_same_shape(*theirs[w], L.src) ? 1u << w : 0u;
       }
-      const uint32_t grid = ph::clip_up_trans_plan(t, !alpha, (uint32_t)ctx->props.multiProcessorCount);
-      if (grid) {
-        if (images.owns_lock()) images.unlock();
-        rc = with_scratch(fn, ctx, queue, (size_t)c.clip.wg_bytes * grid + 4096u, [&](hipStream_t s, void *area) {
-          c.clip.scratch = (char *)area;
-          return ph::launch_clip_up_trans(s, t, !alpha, grid);
-        });
-        if (rc) return rc;
-        continue;
-      }
+      const uint32_t grid = ph::clip_up_trans_plan(t, !alpha, cus);
+      if (grid) return scratch.one_launch(c.clip, grid, [&](hipStream_t s) { return ph::launch_clip_up_trans(s, t, !alpha, grid); });
     }
     // 6. the two stages: every wire-format image through its format's reader into the queue's scratch images (finished f32 images as they
     // are), then the transition compositor's launch
-    if (!images.owns_lock()) {
-      images = std::unique_lock<std::mutex>(ctx->chan_scratch_mu[queue]);
-      rc = chan_images_read(ctx, queue, 1, n_img, img, rd_cm, rd_lut, rd_gm, image);
-      if (rc) return rc;
-    }
+    if (const int bad = scratch.images_for_two_stages(n_img, img, rd_cm, rd_lut, rd_gm)) return bad;
+    void *const *const image = scratch.image;
     ph::UpTransArgs t{};
     t.multi = m;
     for (int i = 0; i < n; ++i) {
@@ -3035,10 +3063,9 @@ int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_cha
         t.same[i] |= chan_sources_same_shape(*theirs[w], L.src) ? 1u << w : 0u;
       }
     }
-    const hipError_t e = ph::launch_compose_up_trans(stream_of(ctx, queue), t, false, (uint32_t)ctx->props.multiProcessorCount);
-    if (e != hipSuccess) return fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-  }
-  return PH_OK;
+    const hipError_t e = ph::launch_compose_up_trans(stream_of(ctx, queue), t, false, cus);
+    return e == hipSuccess ? PH_OK : fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+  });
 }
 
 /* A ROUTED channel's file playback: ph_clip_compose_multi's frames and the combined image itself, made inside the read-once launches: see
@@ -3050,14 +3077,7 @@ int ph_clip_compose_transition_multi(ph_ctx *ctx, int queue, int n, const ph_cha
 static int clip_route_checked(const char *fn, ph_ctx *ctx, int queue, int n, const ph_chan_layer *layers, void *image_out, int n_out, const ph_chan_output *outs,
                               uint32_t out_w, uint32_t out_h, const void *rd_cm, const void *rd_lut, const void *rd_gm, ph::UpArgs &base, LutRef &rref,
                               LutRef (&wref)[ph::kMaxUpOuts], bool args_only = false) {
-  if (!layers || (n_out && !outs) || !rd_cm || !rd_lut || !rd_gm) return fail(PH_E_INVALID, "%s: NULL argument", fn);
-  if (n < 1 || n > ph::kMaxLayers) return fail(PH_E_INVALID, "%s: 1..%d layers", fn, ph::kMaxLayers);
-  if (const int bad = fused_multi_outputs_check(fn, queue, n_out, outs, out_w, out_h)) return bad;
-  {  // the layers, as the channel kernel's entries check them (their texts)
-    ph::ChanArgs probe{};
-    int n_ops = 0;
-    if (const int bad = chan_ops(n, layers, out_w, out_h, probe.op, probe.plane_u, probe.plane_v, probe.cm_op, &probe.planar, &n_ops)) return bad;
-  }
+  if (const int bad = clip_args_check(fn, queue, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, /*route*/ true)) return bad;
   const char *const chain = "nothing else makes image_out in one call: run ph_pack_read, ph_transform, ph_combine and ph_pack_write_multi";
   // what the read-once routes take, as far as the arguments say: every layer a cut, enlarged or of the channel's size under the default fill
   base = ph::UpArgs{};
@@ -3129,82 +3149,23 @@ int ph_clip_compose_route_multi(ph_ctx *ctx, int queue, int n, const ph_chan_lay
   if (!base.lines) return PH_OK;
   int rc = set_device(ctx);
   if (rc) return rc;
-  // one launch?  A single clip in a wire format (v210 included), a 4:2:0 one of an even height
-  bool one_launch = ctx->chan_enlarged == 1 && n == 1, alpha = false;
-  if (one_launch) {
-    const ph_chan_source &S = layers[0].src;
-    const int fmt = fmt_of_src(S.format);
-    one_launch = fmt >= 0 && !(fmt_v420(fmt) && (S.height & 1));
-    alpha = fmt_rgb8(fmt);
-  }
-  ph_image_layer il[1][ph::kMaxLayers];
-  const ph_image_layer *sets[1];
-  std::unique_lock<std::mutex> images;
+  bool alpha = false;
+  const bool one_launch = ctx->chan_enlarged == 1 && n == 1 && clip_wire(layers[0].src, &alpha);
+  ClipScratch scratch{fn, ctx, queue};
   bool image_made = false;
   // a group's launch (m.n_out == 0: the image alone); the first one made stores the image, the others are ph_clip_compose_multi's
-  auto launch = [&](ph::UpMultiArgs &m) -> int {
-    const bool with_image = !image_made;
+  auto launch = [&](ph::UpMultiArgs &m, bool) {
+    void *const image = image_made ? nullptr : image_out;
     image_made = true;
-    if (one_launch) {
-      ph::ClipUpRouteArgs r{};
-      ph::ClipUpMultiArgs &c = r.multi;
-      c.clip.up = m.up, c.n_out = m.n_out;
-      for (uint32_t i = 0; i < m.n_out; ++i) c.out[i] = m.out[i];
-      c.clip.rd = *rref.get(), c.clip.rd_gm = (const float *)rd_gm;
-      c.clip.src[0] = clip_src_of(layers[0].src, fmt_of_src(layers[0].src.format), rd_cm);
-      r.image = image_out;
-      const uint32_t grid = ph::clip_up_plan(c.clip, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ false);
-      if (grid) {
-        if (images.owns_lock()) images.unlock();
-        return with_scratch(fn, ctx, queue, (size_t)c.clip.wg_bytes * grid + 4096u, [&](hipStream_t s, void *area) {
-          c.clip.scratch = (char *)area;
-          return with_image ? ph::launch_clip_up_route(s, r, !alpha, grid) : ph::launch_clip_up_multi(s, c, !alpha, grid);
-        });
-      }
-    }
-    // the two stages: every clip through its format's reader into the queue's scratch images, then the 2 x 2-block compositor's launch
-    if (!images.owns_lock()) {
-      images = std::unique_lock<std::mutex>(ctx->chan_scratch_mu[queue]);
-      if (const int bad = chan_enlarged_read(ctx, queue, 1, n, &layers, rd_cm, rd_lut, rd_gm, il, sets)) return bad;
-    }
-    for (int i = 0; i < n; ++i) m.up.layer[i].ptr = il[0][i].data;
-    hipError_t e;
-    if (with_image) {
-      ph::UpRouteArgs r{};
-      r.multi = m, r.image = image_out;
-      e = ph::launch_compose_up_route(stream_of(ctx, queue), r, (uint32_t)ctx->props.multiProcessorCount);
-    } else {
-      e = ph::launch_compose_up_multi(stream_of(ctx, queue), m, false, (uint32_t)ctx->props.multiProcessorCount);
-    }
-    return e == hipSuccess ? PH_OK : fail(PH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    return clip_group_launch(scratch, one_launch, alpha, n, layers, rd_cm, rd_lut, rd_gm, rref.view, m, /*tails*/ false, image);
   };
-  // the outputs by writer table, in the order the tables first appear; a v210 output whose lines end in a tail quad through ph_chan_compose, alone
-  for (int k = 0; k < n_out; ++k) {
-    bool seen = false;
-    for (int j = 0; j < k; ++j) seen = seen || outs[j].wr_gamma_lut == outs[k].wr_gamma_lut;
-    if (seen) continue;
-    ph::UpMultiArgs m{};
-    m.up = base, m.up.wr = *wref[k].get();
-    for (int j = k; j < n_out; ++j) {
-      const ph_chan_output &o = outs[j];
-      if (o.wr_gamma_lut != outs[k].wr_gamma_lut) continue;
-      if (o.format == PH_FMT_V210 && out_w % 48) {
-        if (images.owns_lock()) images.unlock();
-        rc = ph_chan_compose(ctx, queue, n, layers, PH_FMT_V210, o.planes, out_w, out_h, o.interlace, rd_cm, rd_lut, rd_gm, o.wr_col_matrix12, o.wr_gamma_lut);
-        if (rc) return rc;
-        continue;
-      }
-      m.out[m.n_out++] = up_out_of(o, /*same_lines*/ false, out_w, out_h);
-    }
-    if (!m.n_out) continue;
-    if ((rc = launch(m))) return rc;
-  }
-  if (!image_made) {  // no output, or every output split off: the image alone, without a table
-    ph::UpMultiArgs m{};
-    m.up = base;
-    if ((rc = launch(m))) return rc;
-  }
-  return PH_OK;
+  // the outputs by writer table (the whole frame is composed: a field output takes the rows of its parity), a v210 output whose lines end in a
+  // tail quad through ph_chan_compose, alone
+  rc = clip_groups(scratch, n, layers, n_out, outs, out_w, out_h, rd_cm, rd_lut, rd_gm, base, wref, /*same_lines*/ false, /*keep_tails*/ false, launch);
+  if (rc || image_made) return rc;
+  ph::UpMultiArgs m{};  // no output, or every output split off: the image alone, without a table
+  m.up = base;
+  return launch(m, false);
 }
 
 namespace {
@@ -3222,8 +3183,7 @@ static bool clip_job_args(ph_ctx *ctx, const ph_chan_job_out &J, const ChanJobPl
   if (ctx->chan_enlarged != 1 || J.n != 1) return false;
   if (J.n_out == 1 && J.outs[0].format == PH_FMT_V210) return false;  // (ph_chan_compose, under its names)
   const ph_chan_source &S = J.layers[0].src;
-  const int fmt = fmt_of_src(S.format);
-  if (fmt < 0 || (fmt_v420(fmt) && (S.height & 1))) return false;
+  if (!clip_wire(S, &alpha)) return false;
   tails = false;
   for (int k = 0; k < J.n_out; ++k) {
     const bool tail = J.outs[k].format == PH_FMT_V210 && out_w % 48;
@@ -3231,17 +3191,16 @@ static bool clip_job_args(ph_ctx *ctx, const ph_chan_job_out &J, const ChanJobPl
     tails = tails || tail;
   }
   if (!chan_layers_enlarged(1, J.layers, out_w, out_h, P.interlace, /*v210_fill*/ true)) return false;
-  c = ph::ClipUpMultiArgs{};
-  ph::UpArgs &a = c.clip.up;
+  ph::UpMultiArgs m{};  // the job's one group, as clip_groups makes it
+  ph::UpArgs &a = m.up;
   a.n = 1, a.jobs = 1, a.layer[0] = up_layer_of(S);
   compose_up_lines(a, out_w, out_h, P.interlace);
   if (!ph::compose_up_eligible(a) || !a.lines) return false;
   a.wr = lds_view(ctx, J.outs[0].wr_gamma_lut).view;
-  alpha = fmt_rgb8(fmt);
-  c.n_out = (uint32_t)J.n_out;
-  for (int k = 0; k < J.n_out; ++k) c.out[k] = up_out_of(J.outs[k], P.same_lines, out_w, out_h);
-  c.clip.rd = rd, c.clip.rd_gm = (const float *)rd_gm;
-  c.clip.src[0] = clip_src_of(S, fmt, rd_cm);
+  m.n_out = (uint32_t)J.n_out;
+  for (int k = 0; k < J.n_out; ++k) m.out[k] = up_out_of(J.outs[k], P.same_lines, out_w, out_h);
+  c = ph::ClipUpMultiArgs{};
+  clip_multi_fill(c, m, rd, rd_gm, S, rd_cm);
   ph::ClipUpArgs probe = c.clip;
   return ph::clip_up_plan(probe, !alpha, (uint32_t)ctx->props.multiProcessorCount, /*v210_tails*/ tails) != 0;
 }
@@ -3329,16 +3288,14 @@ int ph_clip_compose_batch_out(ph_ctx *ctx, int queue, int n_jobs, const ph_chan_
   // the launches
   int rc = set_device(ctx);
   if (rc) return rc;
+  ClipScratch scratch{fn, ctx, queue};  // (holds no images: a job handed on takes the area itself)
   for (ClipBatchStep &s : steps) {
     if (!s.shared) {
       const ph_chan_job_out &J = jobs[s.first];
       if ((rc = ph_clip_compose_multi(ctx, queue, J.n, J.layers, J.n_out, J.outs, out_w, out_h, rd_cm, rd_lut, rd_gm))) return rc;
       continue;
     }
-    rc = with_scratch(fn, ctx, queue, (size_t)s.m.clip.wg_bytes * s.grid + 4096u, [&](hipStream_t st, void *area) {
-      s.m.clip.scratch = (char *)area;
-      return ph::launch_clip_up_multi(st, s.m, !s.alpha, s.grid, s.tails);
-    });
+    rc = scratch.one_launch(s.m.clip, s.grid, [&](hipStream_t st) { return ph::launch_clip_up_multi(st, s.m, !s.alpha, s.grid, s.tails); });
     if (rc) return rc;
   }
   return PH_OK;
